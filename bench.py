@@ -1,17 +1,20 @@
 #!/usr/bin/env python3
 """Headline benchmark: truncated-EM E-step throughput of Binary Sparse Coding on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path -- select_Hprimes + E_step (prosper/em/camodels/
 bsc_et.py:98-192) -- over one resident data shard of BASELINE config 2 per GPU:
 D=1024, H=256, H'=8, gamma=4 (K = 411 truncated states), N = 200 000 datapoints per GPU,
 synthetic BSC data generated on the device, float64 throughout.  Datapoints shard over ranks
-with no data-path collective, so scaling is weak (config 3 = 8 x 200k = 1.6 M).  The full
-EM iteration (CAModel.step incl. the one RCCL all-reduce and the H x H solve) is timed in a
-second region and reported as `em_iter_ms`.
+with no data-path collective, so scaling is weak (config 3 = 8 x 200k = 1.6 M).
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel -- bsc_estep_fused_kernel: scores GEMM,
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline
+(`value`, `ms_per_step`, the configuration, `per_rank`); `--dump-outputs DIR` also writes what the last timed step
+returned (dump_outputs).  Everything below is measured with `--full` only.
+
+The full EM iteration (CAModel.step incl. the one RCCL all-reduce and the H x H solve) is timed in a
+second region and reported as `em_iter_ms`.  `roofline` prices the dominant kernel -- bsc_estep_fused_kernel: scores GEMM,
 selection and E-step of 196 608 datapoints in one launch -- by its algorithmic flops / its average launch duration
 measured with HIP events on its stream inside the timed region, and reports the whole pass against the MFMA and HBM
 roofs beside it (`estep_mfma_frac`, `estep_hbm_frac`); `traffic` comes from committed PMC passes (`traffic_source`), the wave-instruction counts of the VALU-issue rooflines
@@ -40,6 +43,7 @@ sys.path.insert(0, ROOT)
 D, H, HP, GAMMA, N_PER_GPU = 1024, 256, 8, 4, 200_000
 MFMA_F64_PEAK_TFLOPS = 78.6   # MI355X dense f64 matrix peak (datasheet; = 32 flop/clk/SIMD)
 HBM_PEAK_GBS = 8000.0
+DUMP_ROWS = 16384             # rows of the --dump-outputs sample: 16384 x 411 log-joints in f64 = 54 MB
 
 
 def parse():
@@ -64,7 +68,17 @@ def parse():
                          "branch of this script end to end on the one-GPU box with it; never a SCALE measurement")
     ap.add_argument("--data", choices=("numpy", "device"), default="numpy",
                     help="numpy: SURVEY 8d's np.random.RandomState recipe (host draws, ~5 s); device: torch.Generator on the GPU")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel times and rooflines, the EM-iteration loops (flat and on "
+                         "the reference's schedule), the CPU baseline and parity, other models and shapes.  Without it the "
+                         "run sets up, warms up, times --steps passes and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed passes write what the last one returned to a caller as DIR/<name>.npy (rank 0): "
+                         "the log-joints `logpj` and the `candidates` of a fixed, seeded sample of %d rows" % DUMP_ROWS)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 VALU_COUNTS = "r06_valu_counts.json"
@@ -490,6 +504,21 @@ def parity_report(model_cls, anneal_cls):
             pass
 
 
+def dump_outputs(out_dir, data, result):
+    """--dump-outputs: what the last timed pass handed its caller -- ``data['candidates']`` from select_Hprimes and the
+    log-joints ``logpj`` from E_step -- on the rows of a fixed sample (RandomState(0), sorted), gathered on the device.
+    The inputs are seeded, so two builds run with the same arguments can be compared array for array."""
+    import numpy as np
+    import torch
+    logpj, cand = result["logpj"].tensor, data["candidates"].tensor
+    N = logpj.shape[0]
+    rows = np.sort(np.random.RandomState(0).choice(N, min(N, DUMP_ROWS), replace=False))
+    idx = torch.from_numpy(rows).to(logpj.device)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("logpj", logpj), ("candidates", cand)):
+        np.save(os.path.join(out_dir, name + ".npy"), t.index_select(0, idx).to(torch.float64).cpu().numpy())
+
+
 def cpu_baseline(args):
     """Oracle leg, run as a child process BEFORE this process touches the GPU."""
     cmd = [sys.executable, os.path.join(ROOT, "oracle", "cpu_baseline.py"), "--D", str(D), "--H", str(H),
@@ -508,6 +537,36 @@ def cpu_baseline(args):
         return {"value": None, "unit": "datapoints/s", "cores": 0, "kind": "port", "sample": "failed: %r" % (e,)}
 
 
+def gather_per_rank(mine, world, backend, comm):
+    """Every rank's record (a 1-D float64 tensor on its device) as rows of one array, on every rank."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    if world == 1:
+        return mine.cpu().numpy()[None, :]
+    if backend == "nccl":
+        allr = [torch.empty_like(mine) for _ in range(world)]
+        dist.all_gather(allr, mine)
+        return torch.stack(allr).cpu().numpy()
+    return np.stack(comm.allgather(mine.cpu().numpy()))
+
+
+def headline(args, world, N, elapsed, prewarm_ms):
+    """The keys of the result line that a plain run prints: the timed E-step passes (`elapsed`: the slowest rank's)."""
+    return {
+        "metric": "E-step datapoints/sec (+ EM-iter wall-clock) BSC D=1024 H=256 H'=8",
+        "value": world * N * args.steps / elapsed, "unit": "datapoints/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "prewarm_ms": prewarm_ms,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic" if args.data == "device" else "synthetic (np.random.RandomState recipe of SURVEY 8d: W_gt seed 0, rows of rank r seed r)",
+        "config": {"workload": "BSC_ET synthetic Gaussian D=1024 H=256 H'=8 gamma=4 (K=411 states), "
+                               "N=%d datapoints per GPU, select_Hprimes+E_step per step" % N,
+                   "global_datapoints": world * N, "parallelism": "dp%d" % world,
+                   "backend": ("rccl" if args.backend == "nccl" else "gloo (debug: ranks may share a device)")
+                              if world > 1 else None},
+    }
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -521,7 +580,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
 
     import numpy as np
@@ -628,20 +687,37 @@ def main():
     prewarm_ms = (time.perf_counter() - tw) * 1e3
     for _ in range(args.warmup):
         estep_pass()
-    # HIP events around the dominant kernel only (every 4th launch): an event pair costs ~10 us of stream time, so
-    # the other kernels are timed in a separate, untimed pass
+    # --full: HIP events around the dominant kernel only (every 4th launch): an event pair costs ~10 us of stream time,
+    # so the other kernels are timed in a separate, untimed pass
     fused = model._fused()
     dom = "estep_fused" if fused else "scores_gemm"
     chunks_per_step = 1 if fused else max(1, N // model._launch_rows(N))
-    timer = KernelTimer(only={dom}, stride=4 * chunks_per_step)
-    model.timer = timer
+    if args.full:
+        timer = KernelTimer(only={dom}, stride=4 * chunks_per_step)
+        model.timer = timer
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        estep_pass()
+        last = estep_pass()
     barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, data, last)
+    del last
+    if not args.full:
+        mine = torch.tensor([elapsed, float(data_seed), float(N)], dtype=torch.float64, device=dev)
+        per_rank = gather_per_rank(mine, world, args.backend, comm)
+        elapsed = float(per_rank[:, 0].max())                   # MAX over ranks
+        if rank == 0:
+            assert len({int(v) for v in per_rank[:, 1]}) == world and all(int(v) == N for v in per_rank[:, 2]), per_rank
+            out = headline(args, world, N, elapsed, prewarm_ms)
+            out["per_rank"] = [{"rank": r, "ms_per_step": per_rank[r, 0] / args.steps * 1e3, "data_seed": int(per_rank[r, 1]),
+                                "rows": int(per_rank[r, 2])} for r in range(world)]
+            print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     kern = timer.summary()
     model.timer = all_timer = KernelTimer()
     for _ in range(3):
@@ -719,15 +795,7 @@ def main():
     # per-rank record: what every rank generated and measured (a SCALE record stays attributable)
     mine = torch.tensor([elapsed, em_elapsed, allreduce_us, float(data_seed), float(N), em_steady], dtype=torch.float64,
                         device=dev)
-    if world > 1:
-        if args.backend == "nccl":
-            allr = [torch.empty_like(mine) for _ in range(world)]
-            dist.all_gather(allr, mine)
-            per_rank = torch.stack(allr).cpu().numpy()
-        else:
-            per_rank = np.stack(comm.allgather(mine.cpu().numpy()))
-    else:
-        per_rank = mine.cpu().numpy()[None, :]
+    per_rank = gather_per_rank(mine, world, args.backend, comm)
     elapsed, em_elapsed = float(per_rank[:, 0].max()), float(per_rank[:, 1].max())   # MAX over ranks
     em_steady = float(per_rank[:, 5].max())
 
@@ -775,17 +843,8 @@ def main():
         else:
             kname = "gemm_nt_f64_dma_kernel (scores A = Y.W^T)"
             alg_bytes = chunk * (D + H) * 8 + H * D * 8
-        out = {
-            "metric": "E-step datapoints/sec (+ EM-iter wall-clock) BSC D=1024 H=256 H'=8",
-            "value": value, "unit": "datapoints/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "prewarm_ms": prewarm_ms,
-            "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic" if args.data == "device" else "synthetic (np.random.RandomState recipe of SURVEY 8d: W_gt seed 0, rows of rank r seed r)",
-            "config": {"workload": "BSC_ET synthetic Gaussian D=1024 H=256 H'=8 gamma=4 (K=411 states), "
-                                   "N=%d datapoints per GPU, select_Hprimes+E_step per step" % N,
-                       "global_datapoints": world * N, "parallelism": "dp%d" % world,
-                       "backend": ("rccl" if args.backend == "nccl" else "gloo (debug: ranks may share a device)")
-                                  if world > 1 else None},
+        out = headline(args, world, N, elapsed, prewarm_ms)
+        out.update({
             "em_iter_ms": em_elapsed / args.em_steps * 1e3,
             "em_iter_steady_ms": em_steady / args.em_steps * 1e3,
             "em_iter_datapoints_per_s": world * N * args.em_steps / em_elapsed,
@@ -835,7 +894,7 @@ def main():
             "parity": parity,
             "other_models": others,
             "other_shapes": shapes,
-        }
+        })
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

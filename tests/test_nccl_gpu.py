@@ -74,7 +74,7 @@ def test_bench_multi_rank_branch_over_gloo(dev):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo",
                         "--n-per-gpu", "33000", "--steps", "2", "--warmup", "1", "--em-steps", "2", "--prewarm-ms", "5",
                         "--no-cpu-baseline", "--no-other-models"], env=env, capture_output=True, text=True, timeout=840)
     assert r.returncode == 0, r.stdout[-2000:] + "\n" + r.stderr[-4000:]
