@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's bars test (examples/barstests/bars-learning.py + param-bars-*.py) on the MI355X path.
 
-    python examples/bars_learning.py [bsc|mca|mmca|dsc|tsc|gsc] [--steps 50] [--N 2000] [--h5]
+    python examples/bars_learning.py [bsc|mca|mmca|dsc|tsc|gsc|mog|mop] [--steps 50] [--N 2000] [--h5]
 
 Generates bars data from ground-truth parameters, runs the annealed EM loop through the drop-in classes and
 reports how well the learned dictionary matches the bars (mean absolute error after the best permutation).
@@ -25,7 +25,8 @@ from prosper_amd.utils.datalog import dlog, StoreInMemory      # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("model", nargs="?", default="bsc", choices=["bsc", "mca", "mmca", "dsc", "tsc", "gsc"])
+    ap.add_argument("model", nargs="?", default="bsc", choices=["bsc", "mca", "mmca", "dsc", "tsc", "gsc", "mog",
+                                                                      "mop"])
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--N", type=int, default=2000)
     ap.add_argument("--size", type=int, default=5)
@@ -64,6 +65,14 @@ def main():
         from prosper_amd.em.camodels.tsc_et import TSC_ET as Model
         model = Model(D, H, Hprime, gamma, comm=comm)
         gt = {'W': bars, 'pi': 2. / H, 'sigma': 1.0}
+    elif a.model == "mog":     # examples/barstests/param-bars-mog.py of the reference: diagonal covariances
+        from prosper_amd.em.mixturemodels.MoG import MoG
+        model = MoG(D, H, sigmas_sq_type='diagonal', comm=comm)
+        gt = {'W': bars, 'pies': np.ones(H) / H, 'sigmas_sq': np.ones((H, D))}
+    elif a.model == "mop":     # param-bars-mop.py: A = nan (no normalisation)
+        from prosper_amd.em.mixturemodels.MoP import MoP
+        model = MoP(D, H, comm=comm)
+        gt = {'W': bars, 'pies': np.ones(H) / H}
     else:
         from prosper_amd.em.camodels.gsc_et import GSC as Model
         model = Model(D, H, Hprime, gamma, 'scalar', comm=comm)
@@ -84,8 +93,8 @@ def main():
         from prosper_amd.utils import create_output_path
         from prosper_amd.utils.datalog import StoreToH5
         out_dir = create_output_path("bars_learning_" + a.model, comm=comm)
-        store = dlog.set_handler(('W', 'pi', 'sigma', 'sigma_sq', 'mu', 'psi_sq', 'L', 'Q', 'N_use', 'T'), StoreToH5,
-                                 out_dir + "result.h5")
+        store = dlog.set_handler(('W', 'pi', 'sigma', 'sigma_sq', 'mu', 'psi_sq', 'pies', 'sigmas_sq', 'L', 'Q', 'N_use', 'T'),
+                                 StoreToH5, out_dir + "result.h5")
     em = EM(model=model, anneal=anneal, data={'y': my_data['y']}, lparams=init)
     em.run()
     if store is not None:

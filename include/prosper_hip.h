@@ -781,6 +781,48 @@ int pm_infer_topk_signed_f64(const double *logpj, int64_t ldl, const int32_t *ca
                              int64_t H, int64_t Hprime, int64_t S, int64_t topK, int rank, int32_t *top_idx, double *top_lpc,
                              double *top_post, int32_t *tie, int8_t *s_out, double *m_out, double *am_out, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Mixture models (prosper/em/mixturemodels/MoG.py, MoP.py; mixture_kernels.hip)
+ * ---------------------------------------------------------------------------------------
+ * Log-joints + posteriors, MoG.posterior / log_p_y (MoG.py:213-281) and MoP.posterior / log_p_y (MoP.py:176-232), which
+ * loop over components in batches of 100 / 500 datapoints:
+ *   logpj[n,h] = (S[n,h] + c[h]) * coef + lp[h]      (coef = -beta for MoG, +beta for MoP; lp = beta log pies)
+ *   Bq != NULL (MoG, diagonal): S = sum_d y^2 Bq[h,d] + y Bl[h,d]  (Bq = 1/sigma^2, Bl = -2 W^T/sigma^2, Y squared on the fly)
+ *   Bq == NULL (MoP):           S = sum_d (rowscale[n] y) Bl[h,d]   (Bl = log W^T; rowscale NULL = 1, else the scale of
+ *                               MoP.normalize, MoP.py:236-245 -- its "+1" belongs in c)
+ * and in the same kernel the posteriors (N, H): exp(logpj) with no max subtraction, NaN -> DBL_MIN, < DBL_MIN -> DBL_MIN,
+ * inf -> DBL_MAX / H, divided by the row sum (MoG.py:222-229).  H <= PM_MAX_H; logpj / post dense (N, H). */
+int pm_mix_scores_f64(const double *Y, int64_t ldy, const double *rowscale, const double *Bq, const double *Bl, int64_t ldb,
+                      const double *c, double coef, const double *lp, int64_t N, int64_t D, int64_t H, double *logpj,
+                      double *post, void *stream);
+/* Batched Cholesky of the H covariances S (H, D, D) of a full-covariance MoG, one workgroup per component, through global
+ * memory (any D): Linv (H, D, D) = L_h^-1 (lower triangular, zeros above), logdet[h] = log det S_h, status[h] = 0, or
+ * status[h] = 1 and logdet[h] = NaN for a component that is not positive definite (Linv_h undefined: the caller inverts it
+ * as the reference does, np.linalg.inv + slogdet(...)[1] at MoG.py:249-252).  L_work (H, D, D): scratch.  Replaces the per
+ * component inverse and log-determinant of MoG.log_p_y for every positive definite component. */
+int pm_mix_chol_f64(const double *S, int64_t D, int64_t H, double *L_work, double *Linv, double *logdet, int32_t *status,
+                    void *stream);
+/* The full-covariance term of MoG.log_p_y (MoG.py:262-268) for W (H, D) rows w_h, u = y_n - w_h, into S (N, lds >= H):
+ * mode[h] == 0 (or mode NULL): B_h = L_h^-1 from pm_mix_chol_f64, S[n,h] = |B_h u|^2; mode[h] == 1: B_h = the transpose of
+ * the host inverse Sinv_h, S[n,h] = u Sinv_h u^T.  B (H, D, D), mode (H) int32, both device. */
+int pm_mix_maha_f64(const double *Y, int64_t ldy, const double *W, const double *B, const int32_t *mode, int64_t N,
+                    int64_t D, int64_t H, double *S, int64_t lds, void *stream);
+/* The epilogue of pm_mix_scores_f64 on its own, from a given S (N, lds): logpj and posteriors (N, H) (MoG.py:213-229). */
+int pm_mix_posterior_f64(const double *S, int64_t lds, const double *c, double coef, const double *lp, int64_t N, int64_t H,
+                         double *logpj, double *post, void *stream);
+/* M-step statistics of MoG.M_step (MoG.py:142-202) and MoP.M_step (MoP.py:105-166), one shard, packed as
+ *   [colsum P (H) | Y^T P (D, H) | kind 1: (Y*Y)^T P (D, H) | kind 2: Y^T diag(P[:,h]) Y (H, D, D)]
+ * kind 0 (MoP): Y^T P with the rows of Y scaled by rowscale (NULL = 1; MoP's normalisation, whose "+1" adds colsum P);
+ * kind 1 (MoG diagonal), kind 2 (MoG full): rowscale must be NULL.  The datapoints are cut into pm_mix_stats_chunks fixed
+ * chunks whose partial statistics (the column sums of P formed by the workgroups that load P anyway) land in `work`
+ * (pm_mix_mstats_work_len doubles) and are added in chunk order: no atomics, the same bits on every run.
+ * pm_mix_stats_len: the packed length (-1 for a bad argument). */
+int64_t pm_mix_stats_len(int64_t D, int64_t H, int kind);
+int64_t pm_mix_stats_chunks(int64_t N, int64_t D, int64_t H, int kind);
+int64_t pm_mix_mstats_work_len(int64_t N, int64_t D, int64_t H, int kind);
+int pm_mix_mstats_f64(const double *Y, int64_t ldy, const double *P, int64_t ldp, const double *rowscale, int64_t N,
+                      int64_t D, int64_t H, int kind, double *work, double *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,15 @@ SIGNATURES = {
                                         c_dp, c_dp]),
     "pm_sort_row_list_i32": (C.c_int, [c_dp, c_dp, C.c_int64, c_dp, c_dp]),
     "pm_gsc_component_scores_f64": (C.c_int, [c_dp, i64, c_dp, c_dp, C.c_double, i64, i64, c_dp, i64, c_dp]),
+    "pm_mix_scores_f64": (C.c_int, [c_dp, i64, c_dp, c_dp, c_dp, i64, c_dp, C.c_double, c_dp, i64, i64, i64, c_dp, c_dp,
+                                    c_dp]),
+    "pm_mix_chol_f64": (C.c_int, [c_dp, i64, i64, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "pm_mix_maha_f64": (C.c_int, [c_dp, i64, c_dp, c_dp, c_dp, i64, i64, i64, c_dp, i64, c_dp]),
+    "pm_mix_posterior_f64": (C.c_int, [c_dp, i64, c_dp, C.c_double, c_dp, i64, i64, c_dp, c_dp, c_dp]),
+    "pm_mix_stats_len": (i64, [i64, i64, C.c_int]),
+    "pm_mix_stats_chunks": (i64, [i64, i64, i64, C.c_int]),
+    "pm_mix_mstats_work_len": (i64, [i64, i64, i64, C.c_int]),
+    "pm_mix_mstats_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, i64, i64, i64, C.c_int, c_dp, c_dp, c_dp]),
 }
 
 
@@ -173,7 +182,7 @@ class HipError(RuntimeError):
     pass
 
 
-MIN_VERSION = 1014
+MIN_VERSION = 1015
 _lib = None
 _lib_det = None
 LIB_PATH_DET = os.path.join(os.path.dirname(LIB_PATH), "libprosper_hip_det.so")

@@ -1,0 +1,99 @@
+"""Mixture-model base: restates prosper/em/mixturemodels/__init__.py (``MixtureModel`` :28-153).
+
+``MoG`` and ``MoP`` supply ``E_step`` / ``M_step``; in this package both run as HIP kernels on the MI355X
+(``_device``).  Host-side behaviour -- initialisation, data generation, row subsets, logging -- follows the reference
+draw for draw; where the reference cannot run as written the docstring says what is done instead.
+"""
+import numpy as np
+from scipy import stats
+
+from .. import Model
+from ...utils import parallel
+from ...utils import tracing
+from ...utils.datalog import dlog
+
+
+def _host(y):
+    """A data shard as a host float64 array (``DeviceArray`` handles and tensors download once)."""
+    if hasattr(y, "numpy") and not isinstance(y, np.ndarray):
+        y = y.numpy() if not hasattr(y, "detach") else y.detach().cpu().numpy()
+    return np.asarray(y, dtype=np.float64)
+
+
+class MixtureModel(Model):
+    """Abstract mixture model over H components of D-dimensional data."""
+
+    def __init__(self, D, H, to_learn=['W', 'pies'], comm=parallel.COMM_WORLD):
+        Model.__init__(self, comm)
+        self.to_learn = to_learn
+        self.D = D
+        self.H = H
+
+    @tracing.traced
+    def standard_init(self, data):
+        """W = the collective data mean + N(0, (sigma_init / 4)^2) noise, pies = 1/H (__init__.py:41-74).
+
+        The RNG order is the reference's: one ``np.random.normal(scale=noise, size=[D, H])``.  ``sigma_init`` is the
+        mean over dimensions of the square root of the collective per-dimension variance around that mean."""
+        comm = self.comm
+        H = self.H
+        my_y = _host(data['y'])
+        my_N, D = my_y.shape
+        assert D == self.D
+        W_mean = parallel.allmean(my_y, axis=0, comm=comm)
+        sigma_sq = parallel.allmean((my_y - W_mean) ** 2, axis=0, comm=comm)
+        sigma_init = np.sqrt(sigma_sq).sum() / D
+        noise = sigma_init / 4.
+        W_init = W_mean[:, None] + np.random.normal(scale=noise, size=[D, H])
+        model_params = {'W': W_init}
+        if 'pies' in self.to_learn:
+            model_params['pies'] = np.ones(H) * 1. / H
+        return model_params
+
+    def check_params(self, model_params):
+        raise NotImplementedError
+
+    @tracing.traced
+    def generate_data(self, model_params, my_N):
+        """Component labels from ``scipy.stats.rv_discrete(values=(arange(H), pies)).rvs(size=my_N)`` (the reference's
+        stream, __init__.py:85-98), then ``generate_from_hidden``."""
+        H = self.H
+        s = stats.rv_discrete(values=(np.arange(H), model_params['pies']), name='compProbDistr').rvs(size=my_N)
+        return self.generate_from_hidden(model_params, {'s': s})
+
+    @tracing.traced
+    def select_partial_data(self, anneal, data):
+        """A random subset of fraction ``anneal['partial']`` of the datapoints (0 or 1: all of them).
+
+        The reference (__init__.py:100-124) calls ``.shape`` on the data dict and cannot run; this does what it sets out
+        to do: ``sel = np.random.permutation(my_N)[:my_pN]`` (unsorted, as there) and every per-row entry of the dict
+        restricted to ``sel``."""
+        partial = anneal['partial']
+        if partial == 0 or partial == 1:
+            return data
+        my_N = data['y'].shape[0]
+        my_pN = int(np.ceil(my_N * partial))
+        if my_N == my_pN:
+            return data
+        sel = np.random.permutation(my_N)[:my_pN]
+        out = {}
+        for key, val in data.items():
+            out[key] = val[sel] if getattr(val, 'shape', None) and val.shape[0] == my_N else val
+        return out
+
+    @tracing.traced
+    def step(self, anneal, model_params, data):
+        """noisify -> check -> partial data -> E_step -> M_step, logging as __init__.py:126-149."""
+        model_params = self.noisify_params(model_params, anneal)
+        model_params = self.check_params(model_params)
+        pdata = self.select_partial_data(anneal, data)
+        post_comp_distr = self.E_step(anneal, model_params, pdata)
+        new_model_params = self.M_step(anneal, model_params, post_comp_distr, pdata)
+        dlog.append_all(new_model_params)
+        dlog.append_all(anneal.as_dict())
+        return new_model_params
+
+    @tracing.traced
+    def inference(self, anneal, model_params, my_data, no_maps=10):
+        """Not implemented, as in the reference (__init__.py:151-153)."""
+        raise NotImplementedError("MixtureModel.inference is not implemented (nor is it in the reference)")
