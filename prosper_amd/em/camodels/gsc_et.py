@@ -270,7 +270,8 @@ class GSC(DeviceCAModel):
         if self.sigma_sq_type not in ('scalar', 'diagonal', 'full'):
             raise _lib.HipError("GSC: unknown sigma_sq_type %r" % (self.sigma_sq_type,))
         if not _lib.load().pm_gsc_supported(self.H, self.Hprime, self.gamma):
-            raise _lib.HipError("GSC kernel range: H <= 512, gamma <= 8 (got H=%d Hprime=%d gamma=%d)"
+            raise _lib.HipError("GSC kernel range: H <= 512, gamma <= 8, and the E-step's 8 H + 16 (48 + 4 H'^2) + S / 4 doubles "
+                                "of LDS within 64 KB (H' = 8: H <= 408) (got H=%d Hprime=%d gamma=%d)"
                                 % (self.H, self.Hprime, self.gamma))
 
     def _masks(self):

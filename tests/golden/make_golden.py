@@ -19,6 +19,9 @@ Fixtures (all float64, bit-for-bit what the reference returned):
                         L, N_use, parameters (tests/golden/schedule_inputs.py holds the seeded inputs).  Slow: the
                         reference needs 9 minutes each for bsc_c2 and gsc_c4 -- `make_golden.py schedule` mints only
                         these, `make_golden.py schedule mca_c5,dsc` a subset
+  <model>_step_shipped*.npz   single steps at the reference's shipped H' / gamma (examples/barstests/param-bars-*.py) and at
+  shipped_traj_<model>.npz    gamma > 4; 30-step runs on the param files' own schedules from generate_data + standard_init.
+                        `make_golden.py shipped` mints only these
 """
 import os
 import sys
@@ -57,7 +60,7 @@ class Capture(DataHandler):
 dlog.set_handler(("L", "N", "N_use", "prior_mass"), Capture)
 
 
-def gsc_step_case(name, D, H, Hp, gamma, N, seed, T, full_psi=False, sigma_type="scalar", presteps=0):
+def gsc_step_case(name, D, H, Hp, gamma, N, seed, T, full_psi=False, sigma_type="scalar", presteps=0, bars=False):
     """select_Hprimes -> E_step -> M_step (+ compute_lpj) of GSC with scalar sigma_sq.  The reference
     returns its statistics in candidate-bucket order; they are mapped back to datapoint order here.
     ``presteps``: the fixture's INPUT parameters are what that many reference EM steps leave behind -- from the first
@@ -65,9 +68,11 @@ def gsc_step_case(name, D, H, Hp, gamma, N, seed, T, full_psi=False, sigma_type=
     its inverse and sum xpt_szsz (which gsc_et.py:625 inverts as it is)."""
     rng = np.random.RandomState(seed)
     W_gt = rng.normal(size=(D, H))
+    if bars:                # (param-bars-gsc.py: W = 10 bars, mu = 1; drawn after the normal W to keep the stream order)
+        W_gt = 10 * generate_bars_dict(H)
     pi_gt = np.full(H, min(0.4, 2.0 / H))
     psi_gt = np.eye(H)
-    mu_gt = np.ones(H) * 1.5
+    mu_gt = np.ones(H) * (1.0 if bars else 1.5)
     s = rng.random_sample((N, H)) <= pi_gt
     z = np.where(s, mu_gt[None, :] + rng.normal(size=(N, H)), 0.0)
     y = z @ W_gt.T + rng.normal(size=(N, D))
@@ -75,7 +80,8 @@ def gsc_step_case(name, D, H, Hp, gamma, N, seed, T, full_psi=False, sigma_type=
     if full_psi:
         Q = 0.08 * rng.normal(size=(H, H))
         psi0 = psi0 + Q @ Q.T
-    params = {"W": W_gt + 0.2 * rng.normal(size=(D, H)), "pi": np.clip(pi_gt * rng.uniform(0.7, 1.4, size=H), 0.02, 0.9),
+    params = {"W": W_gt + 0.2 * (10 if bars else 1) * rng.normal(size=(D, H)),
+              "pi": np.clip(pi_gt * rng.uniform(0.7, 1.4, size=H), 0.02, 0.9),
               "mu": mu_gt + 0.2 * rng.normal(size=H), "psi_sq": psi0, "sigma_sq": 1.3}
     if sigma_type == "diagonal":
         params["sigma_sq"] = rng.uniform(0.8, 1.8, size=D)
@@ -312,11 +318,13 @@ def mca_step_case(name, D, H, Hp, gamma, N, seed, T, Ncut, bars=False):
     print("mca_step_%s: N=%d K=%d Q=%.6f N_use=%d" % (name, N, ss["logpj"].shape[1], new["Q"], Capture.rows["N_use"][0]))
 
 
-def mmca_step_case(name, D, H, Hp, gamma, N, seed, T, Ncut):
+def mmca_step_case(name, D, H, Hp, gamma, N, seed, T, Ncut, bars=False):
     """One check_params -> select_Hprimes -> E_step -> M_step of MMCA_ET (signed max-magnitude causes)."""
     rng = np.random.RandomState(seed)
     W_gt = rng.normal(size=(D, H)) * 3.0
     pi_gt, sigma_gt = min(0.45, 2.0 / H), 1.0
+    if bars:                # (param-bars-mmca.py: W = 10 bars, pi = 1 / size, sigma = 2)
+        W_gt, pi_gt, sigma_gt = 10 * generate_bars_dict(H) + 0.5 * rng.normal(size=(D, H)), 2.0 / H, 2.0
     W0 = W_gt * (1.0 + 0.2 * rng.uniform(-1, 1, size=(D, H)))
     W0[rng.random_sample((D, H)) < 0.03] = 1e-6        # some entries below tol: check_params must lift them
     model = MMCA_ET(D, H, Hp, gamma)
@@ -341,7 +349,7 @@ def mmca_step_case(name, D, H, Hp, gamma, N, seed, T, Ncut):
     print("mmca_step_%s: N=%d K=%d Q=%.6f N_use=%d" % (name, N, ss["logpj"].shape[1], new["Q"], Capture.rows["N_use"][0]))
 
 
-def dsc_step_case(name, D, H, Hp, gamma, N, seed, T, Ncut, anneal_prior, states, pi_gt):
+def dsc_step_case(name, D, H, Hp, gamma, N, seed, T, Ncut, anneal_prior, states, pi_gt, bars=False):
     """One select_Hprimes -> E_step -> M_step of DSC_ET (K-ary latents) on seeded data."""
     import warnings
     warnings.simplefilter("ignore")
@@ -350,6 +358,8 @@ def dsc_step_case(name, D, H, Hp, gamma, N, seed, T, Ncut, anneal_prior, states,
     pi_gt = np.asarray(pi_gt, dtype=np.float64)
     W_gt = rng.normal(size=(D, H)) * 2.0
     sigma_gt = 1.0
+    if bars:                # (param-bars-dsc.py: W = 10 bars, sigma = 2)
+        W_gt, sigma_gt = 10 * generate_bars_dict(H), 2.0
     s = rng.choice(states, size=(N, H), replace=True, p=pi_gt)
     y = s @ W_gt.T + rng.normal(scale=sigma_gt, size=(N, D))
     model = DSC_ET(D, H, Hp, gamma, states=states)
@@ -415,13 +425,15 @@ def _make_tsc(D, H, Hp, gamma):
     return m
 
 
-def tsc_step_case(name, D, H, Hp, gamma, N, seed, T, Ncut, anneal_prior):
+def tsc_step_case(name, D, H, Hp, gamma, N, seed, T, Ncut, anneal_prior, bars=False):
     """One select_Hprimes -> E_step -> M_step of TSC_ET (ternary sparse coding, scalar pi)."""
     import warnings
     warnings.simplefilter("ignore")
     rng = np.random.RandomState(seed)
     W_gt = rng.normal(size=(D, H)) * 2.5
     pi_gt, sigma_gt = min(0.4, 2.5 / H), 1.0
+    if bars:                # (param-bars-tsc.py: W = 10 bars, pi = 1 / size, sigma = 2)
+        W_gt, pi_gt, sigma_gt = 10 * generate_bars_dict(H), 2.0 / H, 2.0
     s = rng.choice([-1., 0., 1.], size=(N, H), p=[pi_gt / 2, 1 - pi_gt, pi_gt / 2])
     y = s @ W_gt.T + rng.normal(scale=sigma_gt, size=(N, D))
     model = _make_tsc(D, H, Hp, gamma)
@@ -727,12 +739,137 @@ def generate_data_cases():
     print("generate_data_all:", sorted(out))
 
 
+# ----------------------------------------------------------------------------- the reference's shipped H' / gamma
+# examples/barstests/param-bars-{bsc,mca,mmca,dsc,tsc,gsc}.py and examples/simple-barstest.py: the truncation settings a script
+# moved over from the reference runs.  `make_golden.py shipped` mints only these.
+SHIPPED = {            # model: (H', gamma, LinearAnnealing T breakpoints) of the param file; Ncut_factor [(0, 0), (2/3, 1)] everywhere
+    "bsc": (8, 5, [(0, 5.), (.8, 1.)]),
+    "mca": (8, 5, [(0, 4.), (.8, 1.)]),
+    "mmca": (7, 5, [(0, 4.), (.8, 1.)]),
+    "dsc": (7, 5, [(0, 2.), (.7, 1.)]),
+    "tsc": (7, 5, [(0, 2.), (.7, 1.)]),
+    "gsc": (7, 4, [(0, 4.), (.8, 1.)]),
+}
+SHIPPED_DSC_STATES, SHIPPED_DSC_PI = [0., 1., 2.], [0.8, 0.15, 0.05]
+_MAKE = {}             # the step makers as main() found them (shipped_steps runs them under its own prefix)
+
+
+def shipped_steps():
+    """One step per model at the bars dimensions (D = 25, H = 10) and the shipped (H', gamma): without truncation, and with
+    Ncut_factor > 0 at T > 1; plus one case per model at larger dimensions with gamma = 5 (GSC: gamma = 5 on the G = 6 and
+    gamma = 8 on the G = 8 systems)."""
+    mk = _MAKE
+    Hp, g, _ = SHIPPED["bsc"]
+    mk["bsc_step_case"]("shipped", 25, 10, Hp, g, 64, seed=501, T=1.0, Ncut=0.0, anneal_prior=False, bars=True)
+    mk["bsc_step_case"]("shipped_cut", 25, 10, Hp, g, 53, seed=502, T=1.6, Ncut=0.7, anneal_prior=False, bars=True)
+    mk["bsc_step_case"]("shipped_simple", 25, 10, 6, 5, 80, seed=503, T=1.0, Ncut=0.5, anneal_prior=False, bars=True)
+    mk["bsc_step_case"]("shipped_g5", 64, 40, 8, 5, 100, seed=504, T=1.2, Ncut=0.0, anneal_prior=False)
+    Hp, g, _ = SHIPPED["mca"]
+    mk["mca_step_case"]("shipped", 25, 10, Hp, g, 64, seed=511, T=1.0, Ncut=0.0, bars=True)
+    mk["mca_step_case"]("shipped_cut", 25, 10, Hp, g, 53, seed=512, T=1.5, Ncut=0.6, bars=True)
+    mk["mca_step_case"]("shipped_g5", 64, 40, 8, 5, 40, seed=513, T=1.0, Ncut=0.0)
+    Hp, g, _ = SHIPPED["mmca"]
+    mk["mmca_step_case"]("shipped", 25, 10, Hp, g, 80, seed=521, T=1.0, Ncut=0.0, bars=True)
+    mk["mmca_step_case"]("shipped_cut", 25, 10, Hp, g, 65, seed=522, T=1.5, Ncut=0.6, bars=True)
+    mk["mmca_step_case"]("shipped_g5", 64, 40, 8, 5, 40, seed=523, T=1.0, Ncut=0.0)
+    Hp, g, _ = SHIPPED["dsc"]
+    mk["dsc_step_case"]("shipped", 25, 10, Hp, g, 20, seed=531, T=1.0, Ncut=0.0, anneal_prior=False,
+                        states=SHIPPED_DSC_STATES, pi_gt=SHIPPED_DSC_PI, bars=True)
+    mk["dsc_step_case"]("shipped_cut", 25, 10, Hp, g, 18, seed=532, T=1.4, Ncut=0.6, anneal_prior=False,
+                        states=SHIPPED_DSC_STATES, pi_gt=SHIPPED_DSC_PI, bars=True)
+    mk["dsc_step_case"]("shipped_g5", 40, 12, 7, 5, 30, seed=533, T=1.0, Ncut=0.0, anneal_prior=False,
+                        states=SHIPPED_DSC_STATES, pi_gt=[0.9, 0.07, 0.03])
+    Hp, g, _ = SHIPPED["tsc"]
+    mk["tsc_step_case"]("shipped", 25, 10, Hp, g, 20, seed=541, T=1.0, Ncut=0.0, anneal_prior=False, bars=True)
+    mk["tsc_step_case"]("shipped_cut", 25, 10, Hp, g, 18, seed=542, T=1.4, Ncut=0.6, anneal_prior=False, bars=True)
+    mk["tsc_step_case"]("shipped_g5", 64, 40, 7, 5, 16, seed=543, T=1.0, Ncut=0.0, anneal_prior=False)
+    Hp, g, _ = SHIPPED["gsc"]
+    mk["gsc_step_case"]("shipped", 25, 10, Hp, g, 100, seed=551, T=1.0, bars=True)
+    mk["gsc_step_case"]("shipped_T", 25, 10, Hp, g, 81, seed=552, T=1.8, bars=True)
+    mk["gsc_step_case"]("shipped_g5", 40, 24, 7, 5, 48, seed=553, T=1.0)
+    mk["gsc_step_case"]("shipped_g8", 30, 12, 8, 8, 50, seed=554, T=1.2)
+
+
+def _shipped_model(kind, D, H):
+    Hp, g, _ = SHIPPED[kind]
+    if kind == "gsc":
+        return GSC(D, H, Hp, g, "scalar")
+    if kind == "dsc":
+        return DSC_ET(D, H, Hp, g, states=np.array(SHIPPED_DSC_STATES))
+    if kind == "tsc":
+        return _make_tsc(D, H, Hp, g)
+    return {"bsc": BSC_ET, "mca": MCA_ET, "mmca": MMCA_ET}[kind](D, H, Hp, g)
+
+
+def _shipped_params_gt(kind, H):
+    """params_gt of the param file (bars W = 10 * bars; pi 1 / size = 2 / H; sigma 2)."""
+    W = 10 * generate_bars_dict(H)
+    if kind == "gsc":
+        return {"W": W, "pi": 2. / H * np.ones(H), "mu": np.ones(H), "psi_sq": np.eye(H), "sigma_sq": 1.0}
+    if kind == "dsc":
+        return {"W": W, "pi": np.array(SHIPPED_DSC_PI), "sigma": 2.0}
+    return {"W": W, "pi": 2. / H, "sigma": 2.0}
+
+
+def shipped_traj(kind, seed, steps=30, N=1000):
+    """The param file's own schedule (its T and Ncut_factor breakpoints on LinearAnnealing(steps)) from the reference's
+    generate_data (seed ``seed``) and standard_init (seed ``seed + 1``), every step recorded: N_use, L, the scalar / vector
+    parameters, W (and GSC's psi_sq).  y and the initial parameters are stored (data only)."""
+    import io, contextlib, time, warnings
+    warnings.simplefilter("ignore")
+    D, H = 25, 10
+    _, _, T_points = SHIPPED[kind]
+    model = _shipped_model(kind, D, H)
+    np.random.seed(seed)
+    data = model.generate_data(_shipped_params_gt(kind, H), N)
+    y = np.ascontiguousarray(data["y"])
+    np.random.seed(seed + 1)
+    with contextlib.redirect_stdout(io.StringIO()):
+        p0 = model.standard_init({"y": y.copy()})
+    p0 = {k: np.array(v, copy=True) for k, v in p0.items()}
+    anneal = LinearAnnealing(steps)
+    anneal["T"] = list(T_points)
+    anneal["Ncut_factor"] = [(0, 0.), (2. / 3, 1.)]
+    anneal["anneal_prior"] = False
+    Capture.rows.clear()
+    lparams = {k: np.array(v, copy=True) for k, v in p0.items()}
+    hist = {k: [] for k in p0}
+    t0 = time.time()
+    while not anneal.finished:                      # EM.run body (em/__init__.py:163-178)
+        new = model.step(anneal, lparams, {"y": y.copy()})
+        anneal.next(model.gain(lparams, new))
+        lparams = new
+        for k in hist:
+            hist[k].append(np.array(new[k], copy=True))
+    out = {"kind": kind, "D": D, "H": H, "Hprime": model.Hprime, "gamma": model.gamma, "N": N, "seed": seed, "steps": steps,
+           "T_points": np.array(T_points), "Ncut_points": np.array([(0, 0.), (2. / 3, 1.)]), "y": y,
+           "N_use": np.array(Capture.rows.get("N_use", [])), "L": np.array(Capture.rows.get("L", []))}
+    if kind == "dsc":
+        out["states"] = np.array(SHIPPED_DSC_STATES)
+    for k, v in p0.items():
+        out[k + "0"] = v
+    for k, v in hist.items():
+        out[k] = np.stack(v)
+    assert all(np.isfinite(out[k]).all() for k in hist), kind
+    np.savez_compressed(os.path.join(HERE, "shipped_traj_%s.npz" % kind), **out)
+    print("shipped_traj_%s: %d steps in %.0f s, L[0]=%.6f L[-1]=%.6f N_use %s" % (
+        kind, steps, time.time() - t0, out["L"][0] if len(out["L"]) else np.nan, out["L"][-1] if len(out["L"]) else np.nan,
+        out["N_use"][[0, -1]] if len(out["N_use"]) else "-"))
+
+
+def shipped_trajectories():
+    for i, kind in enumerate(("bsc", "mca", "mmca", "dsc", "tsc", "gsc")):
+        shipped_traj(kind, seed=601 + 10 * i)
+
+
 def main(only=None, cases=None):
     """``only``: regenerate just the fixtures whose maker's name starts with this prefix (e.g. ``mmca``);
     ``cases``: of those, just the named step cases (e.g. ``c2_plain,c2_cut``)."""
     want = lambda fn: only is None or fn.__name__.startswith(only)
     g = globals()
-    for _n in ("bsc_step_case", "gsc_step_case", "mca_step_case", "mmca_step_case", "dsc_step_case", "dsc_inference_case", "tsc_step_case", "tsc_inference_case", "bsc_inference_case",
+    step_makers = ("bsc_step_case", "gsc_step_case", "mca_step_case", "mmca_step_case", "dsc_step_case", "tsc_step_case")
+    _MAKE.update({n: g[n] for n in step_makers})
+    for _n in ("shipped_steps", "shipped_trajectories", "bsc_step_case", "gsc_step_case", "mca_step_case", "mmca_step_case", "dsc_step_case", "dsc_inference_case", "tsc_step_case", "tsc_inference_case", "bsc_inference_case",
                "mca_inference_case", "mmca_inference_case", "gsc_inference_case", "gsc_posterior_hprime_case", "bsc_trajectory",
                "bsc_init", "anneal_tracks", "schedule_trajectory", "inference_big_case", "noise_trajectory", "standard_init_cases", "generate_data_cases"):
         if not want(g[_n]):
@@ -741,6 +878,8 @@ def main(only=None, cases=None):
         for _n in ("bsc_step_case", "gsc_step_case", "mca_step_case", "mmca_step_case", "dsc_step_case", "tsc_step_case",
                    "schedule_trajectory", "noise_trajectory"):
             g[_n] = (lambda fn: (lambda name, *a, **k: fn(name, *a, **k) if name in cases else None))(g[_n])
+        for _n in step_makers:
+            _MAKE[_n] = (lambda fn: (lambda name, *a, **k: fn(name, *a, **k) if name in cases else None))(_MAKE[_n])
     # BASELINE config-1 dims (D=25 H=10 H'=5 gamma=3)
     bsc_step_case("c1_plain", 25, 10, 5, 3, 400, seed=1, T=1.0, Ncut=0.0, anneal_prior=False, bars=True)
     bsc_step_case("c1_anneal_cut", 25, 10, 5, 3, 333, seed=2, T=1.7, Ncut=0.6, anneal_prior=True, bars=True)
@@ -828,6 +967,9 @@ def main(only=None, cases=None):
                   states=[0., 1.], pi_gt=[0.8, 0.2])
     dsc_step_case("h64", 48, 64, 6, 3, 120, seed=65, T=1.0, Ncut=0.0, anneal_prior=False,
                   states=[-2., -1., 0., 1., 2.], pi_gt=[0.02, 0.03, 0.9, 0.03, 0.02])
+    # the reference's shipped truncation settings (gamma = 5; GSC 4, plus gamma = 5 and 8 at other dimensions)
+    shipped_steps()
+    shipped_trajectories()
 
 
 if __name__ == "__main__":

@@ -75,6 +75,10 @@ _CASES = {
     # of the 4-wavefront fused kernel; a shard smaller than one round at a large D (round-5 advisor finding: the slices'
     # atomics were quantised with another kernel family's bounds, or none: the deterministic build does not split there)
     "bsc_splitk": (_bsc, (256, 64, 6, 3, 40000)), "dsc_splitk": (_dsc, (512, 24, 5, 3, 900)),
+    # gamma = 5: the quanta's bounds grow with the number of states (the 4-wavefront one-kernel pass; scores GEMM + 16-lane row
+    # kernel above H = 256; MCA's 210 states; DSC's 1008 with four values; GSC's G = 6 systems)
+    "bsc_g5": (_bsc, (40, 30, 8, 5, 900)), "bsc_g5_two_kernel": (_bsc, (64, 300, 8, 5, 3000)),
+    "mca_g5": (_mca, (64, 40, 8, 5, 600)), "dsc_g5": (_dsc, (32, 24, 5, 5, 600)), "gsc_g5": (_gsc, (48, 40, 7, 5, 600)),
 }
 
 
@@ -124,7 +128,7 @@ def test_deterministic_mode_agrees_with_the_default_build_step_by_step(case):
         for k in keys:
             ref = np.asarray(qp[k], dtype=np.float64)
             got = np.asarray(qd[k], dtype=np.float64)
-            if case == "mca" and k == "W":
+            if case.startswith("mca") and k == "W":
                 # W_new = Wp / Wq element by element: where both are a few quanta the ratio is ill-determined in either build
                 # (a quantum is 2^-52 of the bound N on Wq: an element whose Wq is 1e-6 keeps seven digits)
                 rel = np.abs(got - ref) / (np.abs(ref) + 1e-300)
