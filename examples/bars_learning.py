@@ -32,6 +32,9 @@ def main():
     ap.add_argument("--size", type=int, default=5)
     ap.add_argument("--h5", action="store_true", help="store every parameter and the objective per EM step in "
                     "output/<script>.<date>/result.h5, as the reference's bars-learning.py does")
+    ap.add_argument("--heldout", type=int, default=0, metavar="N",
+                    help="also draw N held-out datapoints from the ground truth and print their log-likelihood per "
+                    "datapoint under the learned parameters and under the ground-truth ones (DESIGN 4.12)")
     a = ap.parse_args()
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         import torch
@@ -82,6 +85,10 @@ def main():
     first, last = parallel.stride_data(a.N, comm=comm)
     my_data = model.generate_data(gt, last - first)
     init = model.standard_init(my_data)
+    heldout = None
+    if a.heldout > 0:
+        hf, hl = parallel.stride_data(a.heldout, comm=comm)
+        heldout = {'y': model.generate_data(gt, hl - hf)['y']}
 
     anneal = LinearAnnealing(a.steps)
     anneal['T'] = [(0, 2.), (.7, 1.)]
@@ -111,6 +118,12 @@ def main():
         print("%s on %d bars datapoints (%d ranks), %d EM steps: bars recovered with mean abs error %.3f%s" % (
             a.model.upper(), a.N, comm.size, a.steps, mae,
             "; objective %.3f -> %.3f" % (float(trace[0]), float(trace[-1])) if len(trace) else ""))
+    if heldout is not None:
+        learned = model.log_likelihood(dict(em.lparams), heldout) / a.heldout      # (collective: every rank calls it)
+        truth = model.log_likelihood(dict(gt), heldout) / a.heldout
+        if comm.rank == 0:
+            print("held-out log-likelihood per datapoint (%d datapoints): learned %.4f, ground truth %.4f"
+                  % (a.heldout, learned, truth))
 
 
 if __name__ == "__main__":

@@ -823,6 +823,27 @@ int64_t pm_mix_mstats_work_len(int64_t N, int64_t D, int64_t H, int kind);
 int pm_mix_mstats_f64(const double *Y, int64_t ldy, const double *P, int64_t ldp, const double *rowscale, int64_t N,
                       int64_t D, int64_t H, int kind, double *work, double *stats, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Held-out log-likelihood (loglik_kernels.hip)
+ * ---------------------------------------------------------------------------------------
+ * Row log-sum-exp of log-joints X (N, ld >= S): v_n = m_n + log sum_s exp(a X[n,s] + o_s - m_n), m_n = max_s (a X[n,s] + o_s),
+ * o = col_offset (S values; NULL = 0).  A row that is all -inf gives -inf, a NaN entry gives NaN.  rows_out (N; NULL = not
+ * written) receives v, total[0] = sum_n v_n: workgroups add fixed row ranges in a fixed order into work
+ * (pm_rows_lse_work_len(N) doubles) and one workgroup adds those in index order -- no atomics, the same bits on every run
+ * and in both builds.  N == 0 writes total[0] = 0.  Any S.  The F(Theta; Y) of every component-analysis model's
+ * log_likelihood is this total plus N c(Theta). */
+int64_t pm_rows_lse_work_len(int64_t N);
+/* The log-likelihood mode of pm_mix_scores_f64 (mixture_kernels.hip), same scores and arguments, for MoG diagonal and MoP:
+ * rows[n] = log sum_h exp((S[n,h] + c[h]) coef + lp[h]) - (pmf ? sum_d lgamma(rowscale_n y_nd + yoff + 1) : 0), by a running
+ * maximum and sum per row across the 64-wide H blocks; neither logpj nor the posteriors are formed, and H has no bound.
+ * NaN in a row's terms gives NaN, all -inf gives -inf.  pmf (MoP's Poisson normaliser on the data the E-step sees: yoff = 1
+ * when rowscale normalises, else 0) needs Bq == NULL. */
+int pm_mix_loglik_f64(const double *Y, int64_t ldy, const double *rowscale, const double *Bq, const double *Bl, int64_t ldb,
+                      const double *c, double coef, const double *lp, int64_t N, int64_t D, int64_t H, int pmf, double yoff,
+                      double *rows, void *stream);
+int pm_rows_lse_f64(const double *logpj, int64_t ld, int64_t N, int64_t S, double a, const double *col_offset,
+                    double *rows_out, double *work, double *total, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

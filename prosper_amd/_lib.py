@@ -175,6 +175,10 @@ SIGNATURES = {
     "pm_mix_stats_chunks": (i64, [i64, i64, i64, C.c_int]),
     "pm_mix_mstats_work_len": (i64, [i64, i64, i64, C.c_int]),
     "pm_mix_mstats_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, i64, i64, i64, C.c_int, c_dp, c_dp, c_dp]),
+    "pm_rows_lse_work_len": (i64, [i64]),
+    "pm_rows_lse_f64": (C.c_int, [c_dp, i64, i64, i64, C.c_double, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "pm_mix_loglik_f64": (C.c_int, [c_dp, i64, c_dp, c_dp, c_dp, i64, c_dp, C.c_double, c_dp, i64, i64, i64, C.c_int,
+                                    C.c_double, c_dp, c_dp]),
 }
 
 
@@ -182,7 +186,7 @@ class HipError(RuntimeError):
     pass
 
 
-MIN_VERSION = 1015
+MIN_VERSION = 1016
 _lib = None
 _lib_det = None
 LIB_PATH_DET = os.path.join(os.path.dirname(LIB_PATH), "libprosper_hip_det.so")

@@ -72,16 +72,36 @@ __device__ __forceinline__ void posterior_row(const double *__restrict__ t, doub
 }
 
 // ---- scores + epilogue (MoG diagonal: Bq != null; MoP: Bq == null) --------------------------------------------------------
-template <bool SQ>
+// LL (log-likelihood mode, pm_mix_loglik_f64): neither logpj nor the posteriors are written.  Each 64 x 64 tile of
+// z = (S + c) coef + lp goes through LDS into a running maximum and sum per row (online log-sum-exp over the H blocks), and
+// `post` receives one value per row, log sum_h exp(z_nh) - (pmf ? sum_d lgamma(rs_n y_nd + yoff + 1) : 0); the row term is
+// formed from the operands the first H block loads anyway.  No H bound.
+template <bool SQ, bool LL = false>
 __global__ __launch_bounds__(256) void mix_scores_kernel(const double *__restrict__ Y, int64_t ldy,
                                                          const double *__restrict__ rs, const double *__restrict__ Bq,
                                                          const double *__restrict__ Bl, int64_t ldb,
                                                          const double *__restrict__ c, double coef,
                                                          const double *__restrict__ lp, int64_t N, int64_t D, int64_t H,
-                                                         double *__restrict__ logpj, double *__restrict__ post) {
+                                                         double *__restrict__ logpj, double *__restrict__ post,
+                                                         int pmf = 0, double yoff = 0.0) {
     __shared__ double As[BT * LDA];
     __shared__ double Bs[BT * LDA];
     __shared__ double Qs[SQ ? BT * LDA : 1];
+    __shared__ double Zs[LL ? BT * (BT + 1) : 1];
+    __shared__ double Rt[LL ? BT : 1];
+    // LL: running (max, sum, NaN seen, +inf seen) of the 16 rows r = wave + 4 i this wavefront finishes (all lanes alike)
+    double run_m[LL ? 16 : 1], run_s[LL ? 16 : 1];
+    int run_bad[LL ? 16 : 1], run_pinf[LL ? 16 : 1];
+    if constexpr (LL) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            run_m[i] = -INFINITY;
+            run_s[i] = 0.0;
+            run_bad[i] = 0;
+            run_pinf[i] = 0;
+        }
+    }
+    double lg = 0.0;     // LL, pmf: this thread's part of its tile row's sum of lgamma
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wr = wave >> 1, wc = wave & 1;
     const int64_t row0 = (int64_t)blockIdx.x * BT;
@@ -105,6 +125,7 @@ __global__ __launch_bounds__(256) void mix_scores_kernel(const double *__restric
                 ra[j] = in ? ya[k] * ascale : 0.0;
                 rb[j] = in ? bl[k] : 0.0;
                 if (SQ) rq[j] = in ? bq[k] : 0.0;
+                if (LL && pmf && in && h0 == 0) lg += lgamma(ra[j] + yoff + 1.0);
             }
         };
         pm_d4 acc[2][2];
@@ -142,6 +163,38 @@ __global__ __launch_bounds__(256) void mix_scores_kernel(const double *__restric
                     }
             }
         }
+        if constexpr (LL) {
+            // the tile into LDS (-inf past H), then each wavefront folds its 16 rows' 64 values into the running state
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int hl = wc * 32 + j * 16 + (lane & 15);
+                    const int64_t h = h0 + hl;
+                    const double ch = h < H ? c[h] : 0.0, lph = h < H ? lp[h] : 0.0;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int rl = wr * 32 + i * 16 + (lane >> 4) + 4 * r;
+                        Zs[rl * (BT + 1) + hl] = h < H ? (acc[i][j][r] + ch) * coef + lph : -INFINITY;
+                    }
+                }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const double z = Zs[(wave + 4 * i) * (BT + 1) + lane];
+                const int bad = __any(z != z), pinf = __any(z == INFINITY);
+                const double zz = (z != z || z == INFINITY) ? -INFINITY : z;
+                double bm = zz;
+                for (int o = 32; o >= 1; o >>= 1) bm = fmax(bm, __shfl_xor(bm, o, 64));
+                run_bad[i] |= bad;
+                run_pinf[i] |= pinf;
+                if (bm == -INFINITY) continue;            // (wave-uniform)
+                const double bs = wave_sum(exp(zz - bm));
+                const double m = fmax(run_m[i], bm);
+                run_s[i] = run_s[i] * exp(run_m[i] - m) + bs * exp(bm - m);
+                run_m[i] = m;
+            }
+        } else {
         // (S + c) * coef + lp into logpj
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -156,7 +209,28 @@ __global__ __launch_bounds__(256) void mix_scores_kernel(const double *__restric
                     if (n < N) logpj[n * H + h] = (acc[i][j][r] + ch) * coef + lph;
                 }
             }
+        }
     }
+    if constexpr (LL) {
+        // the lgamma row term: the 4 threads of a tile row (consecutive lanes) add their parts in a fixed order
+        lg += __shfl_xor(lg, 1, 64);
+        lg += __shfl_xor(lg, 2, 64);
+        if ((tid & 3) == 0) Rt[lr] = lg;
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int rl = wave + 4 * i;
+            const int64_t n = row0 + rl;
+            if (n >= N || lane != 0) continue;
+            double v;
+            if (run_bad[i]) v = NAN;
+            else if (run_pinf[i]) v = INFINITY;
+            else if (run_m[i] == -INFINITY) v = -INFINITY;
+            else v = run_m[i] + log(run_s[i]);
+            post[n] = pmf ? v - Rt[rl] : v;
+        }
+        return;
+    } else {
     __threadfence_block();
     __syncthreads();
     // the row epilogue: one wavefront per row, 16 rows per wavefront (rows written by this workgroup only)
@@ -164,6 +238,7 @@ __global__ __launch_bounds__(256) void mix_scores_kernel(const double *__restric
         const int64_t n = row0 + r;
         if (n >= N) break;
         posterior_row(logpj + n * H, post + n * H, (int)H, lane);
+    }
     }
 }
 
@@ -463,6 +538,22 @@ extern "C" int pm_mix_scores_f64(const double *Y, int64_t ldy, const double *row
         mix_scores_kernel<true><<<grid, 256, 0, st>>>(Y, ldy, nullptr, Bq, Bl, ldb, c, coef, lp, N, D, H, logpj, post);
     else
         mix_scores_kernel<false><<<grid, 256, 0, st>>>(Y, ldy, rowscale, nullptr, Bl, ldb, c, coef, lp, N, D, H, logpj, post);
+    return launched();
+}
+
+extern "C" int pm_mix_loglik_f64(const double *Y, int64_t ldy, const double *rowscale, const double *Bq, const double *Bl,
+                                 int64_t ldb, const double *c, double coef, const double *lp, int64_t N, int64_t D,
+                                 int64_t H, int pmf, double yoff, double *rows, void *stream) {
+    if (!Y || !Bl || !c || !lp || !rows || N <= 0 || D <= 0 || H <= 0 || ldy < D || ldb < D) return PM_EINVAL;
+    if (Bq && (rowscale || pmf)) return PM_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)cdiv(N, BT));
+    if (Bq)
+        mix_scores_kernel<true, true><<<grid, 256, 0, st>>>(Y, ldy, nullptr, Bq, Bl, ldb, c, coef, lp, N, D, H, nullptr, rows,
+                                                             0, 0.0);
+    else
+        mix_scores_kernel<false, true><<<grid, 256, 0, st>>>(Y, ldy, rowscale, nullptr, Bl, ldb, c, coef, lp, N, D, H, nullptr,
+                                                              rows, pmf, yoff);
     return launched();
 }
 

@@ -171,6 +171,17 @@ class _AnnealAt(object):
             a.cur_pos = old
 
 
+class LoglikPoint(dict):
+    """The annealing point ``log_likelihood`` evaluates at: T = 1, no prior annealing, no data truncation, all data and no
+    parameter noise (every other entry reads 0)."""
+
+    def __init__(self):
+        dict.__init__(self, T=1.0, anneal_prior=False, Ncut_factor=0.0, partial=0)
+
+    def __missing__(self, key):
+        return 0.0
+
+
 class KernelTimer(object):
     """HIP-event timing of individual kernel launches on the stream they are enqueued on
     (torch's current stream, which is the one handed to the C ABI).  bench.py attaches one
@@ -579,9 +590,11 @@ class DeviceCAModel(CAModel):
         return {'y': DeviceArray(y), 's': DeviceArray(s)}
 
     def invalidate_data(self):
-        """Forget the resident shard (call after modifying ``my_data['y']`` in place)."""
+        """Forget the resident shards, the training one and the one of ``log_likelihood`` (call after modifying
+        ``my_data['y']`` in place, or to release the held-out data's device memory and workspaces)."""
         self._data = {}
         self._par = {}
+        self.__dict__.pop("_eval_slot", None)
 
     def _gemm_nt(self, A, B, out, label="gemm_nt"):
         M, K = A.shape
@@ -1085,3 +1098,79 @@ class DeviceCAModel(CAModel):
         m_out = res_m if logprob else torch.exp(res_m)
         return {'s': res_s.cpu().numpy(), 'm': m_out.cpu().numpy(), 'p': res_p.cpu().numpy(),
                 'gamma': res_gamma.cpu().numpy(), 'Hprime': res_Hprime.cpu().numpy()}
+
+    # ---- held-out log-likelihood --------------------------------------------------------------------------
+    # What a log_likelihood call swaps out: the resident shard, the parameter products computed on it, the workspaces and
+    # the pinned staging buffers live in an evaluation slot of their own; the records the last M-step left for the next
+    # training step (seeded products, a speculative E-step pass, ranked candidates, next power tables) are hidden from it.
+    _EVAL_SLOT = ("_data", "_par", "_ws", "_pin", "_pin_out")
+    _EVAL_HIDDEN = ("_seed_rec", "_seed", "_spec", "_spec_estep", "_sel_seed", "_next_tabs", "_mstep_res", "_a0", "_nz")
+
+    def _eval_begin(self):
+        saved = dict(self.__dict__)
+        slot = saved.get("_eval_slot") or {k: {} for k in self._EVAL_SLOT}
+        for k in self._EVAL_SLOT:
+            setattr(self, k, slot[k])
+        for k in self._EVAL_HIDDEN:
+            if k in saved:
+                setattr(self, k, None)
+        self._in_step = False
+        self._loglik_eval = True         # (E-steps skip the M-step statistics they could fuse: nobody reads them)
+        return saved
+
+    def _eval_end(self, saved):
+        slot = {k: self.__dict__[k] for k in self._EVAL_SLOT}
+        gen = self.__dict__.get("_data_gen", 0)
+        self.__dict__.clear()
+        self.__dict__.update(saved)      # every attribute as the training loop left it
+        self._eval_slot = slot
+        self._data_gen = gen             # (shard keys stay unique across both slots)
+
+    def _loglik_terms(self, model_params, my_data):
+        """Per model: ``(logpj, a, c)`` -- the (N, K) device log-joints of the T = 1 E-step over exactly the states it scores
+        for each datapoint (any row stride), the scale a of the row log-sum-exp and the per-datapoint constant c(Theta) the
+        log-joints leave out, so that log sum_s p(s, y_n | Theta) = log sum_s exp(a logpj[n, s]) + c."""
+        raise NotImplementedError("%s has no log_likelihood" % type(self).__name__)
+
+    def _loglik_estep(self, model_params, my_data):
+        """select_Hprimes + E_step at ``LoglikPoint`` through the training kernels: the (N, K) device log-joints."""
+        data = self.select_Hprimes(model_params, my_data)
+        return self.E_step(LoglikPoint(), model_params, data)['logpj'].tensor
+
+    def log_likelihood(self, model_params, my_data, per_datapoint=False):
+        """Held-out log-likelihood F(Theta; Y) = sum_n log sum_{s in K_n} p(s, y_n | Theta) of ``my_data['y']`` (host
+        array, torch tensor or DeviceArray) under ``model_params``.
+
+        K_n is exactly the state set the model's E-step scores for y_n (the columns of its ``logpj``), p the model's full
+        generative joint (prior over all H units, no A_pi_gamma renormalisation), evaluated at T = 1 with no prior
+        annealing, data truncation, partial data or parameter noise.  Where K_n holds distinct states of the model, F is a
+        lower bound on log p(Y | Theta), exact when K_n holds every state (H' = gamma = H).  TSC is the exception: its
+        candidates may repeat a latent (tsc_et.py:142-213), and then K_n holds pseudo-states (a latent counted at two
+        positions) and neither the bound nor exactness holds for that row.  Each model's ``_loglik_terms`` derives its constant c(Theta).
+
+        Returns the sum over ALL ranks' datapoints as a float (a collective call: the per-rank sums are added in rank
+        order, so every rank returns the same bits), or with ``per_datapoint=True`` this rank's (my_N,) float64 values in
+        datapoint order (no collective).  ``model_params``, the training shard's residency, the records the last M-step
+        left for the next step and Hprime / gamma are left as they were: a call between two EM steps does not change the
+        training trajectory.  Runs the E-step kernels and pm_rows_lse_f64 on the device."""
+        saved = self._eval_begin()
+        try:
+            logpj, a, c = self._loglik_terms(dict(model_params), {'y': my_data['y']})
+            N, K = logpj.shape
+            lib = _lib.load(self.deterministic)
+            work = torch.empty(int(lib.pm_rows_lse_work_len(N)), dtype=torch.float64, device=self.device)
+            total = torch.empty(1, dtype=torch.float64, device=self.device)
+            rows = torch.empty(N, dtype=torch.float64, device=self.device) if per_datapoint else None
+            ld = logpj.stride(0) if N > 1 else max(int(logpj.stride(0)), K)
+            self._call("loglik_rows", "pm_rows_lse_f64", _ptr(logpj), ld, N, K, ctypes.c_double(a), None, _ptr(rows),
+                       _ptr(work), _ptr(total), self._stream())
+            if per_datapoint:
+                return rows.cpu().numpy() + c
+            local = float(total.cpu()[0]) + N * c
+        finally:
+            self._eval_end(saved)
+        parts = self.comm.allgather(local)
+        out = 0.0
+        for v in parts:
+            out += v
+        return out

@@ -606,6 +606,15 @@ class BSC_ET(DeviceCAModel):
         out.lse = lse
         return {'logpj': out}
 
+    def _loglik_terms(self, model_params, my_data):
+        """log_likelihood.  At T = 1 a column of ``logpj`` is pil_bar |s| - |y - mu - W s|^2 / (2 sigma^2)
+        (bsc_et.py:160-190), while log p(s, y) = |s| log pi + (H - |s|) log(1 - pi) - D/2 log(2 pi sigma^2) - |y - mu - W s|^2 /
+        (2 sigma^2): c = H log(1 - pi) - D/2 log(2 pi sigma^2), the reference's ``L`` (bsc_et.py:264-267) without its
+        - log A_pi_gamma, and a = 1."""
+        pies, sigma = float(model_params['pi']), float(model_params['sigma'])
+        c = self.H * np.log(1. - pies) - 0.5 * self.D * np.log(2 * _PI * sigma ** 2)
+        return self._loglik_estep(model_params, my_data), 1.0, c
+
     @tracing.traced
     def M_step(self, anneal, model_params, my_suff_stat, my_data):
         """New W, pi, sigma (, mu) from the posterior over the truncated states

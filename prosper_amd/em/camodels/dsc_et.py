@@ -303,6 +303,13 @@ class DSC_ET(DeviceCAModel):
         tracing.tracepoint("E_step:iterating")
         return {'logpj': self._dsc_estep(anneal, "dsc_stats", par, res, cand, tab, S, prior, P, Kt, model_params['pi'])}
 
+    def _loglik_terms(self, model_params, my_data):
+        """log_likelihood.  At T = 1 a column of ``logpj`` is - |y - W s|^2 / (2 sigma^2) plus pre_F, the
+        log-prior of the state over ALL H latents (``state_abs`` counts the non-candidate zeros too, dsc_et.py:539-558):
+        c = - D/2 log(2 pi sigma^2), exactly the reference's ``L`` (dsc_et.py:845-869) and a = 1."""
+        sigma = float(model_params['sigma'])
+        return self._loglik_estep(model_params, my_data), 1.0, -0.5 * self.D * np.log(2 * np.pi * sigma ** 2)
+
     @tracing.traced
     def M_step(self, anneal, model_params, my_suff_stat, my_data):
         """New W, pi, sigma (dsc_et.py:587-774).  Logs ``prior_mass``, ``L`` and ``N_use``."""

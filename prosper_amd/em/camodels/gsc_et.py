@@ -292,7 +292,9 @@ class GSC(DeviceCAModel):
         pi = np.asarray(model_params['pi'], dtype=np.float64)
         sig = np.asarray(model_params['sigma_sq'], dtype=np.float64)
         par = self._par
-        same = (par.get("ykey") == res["key"] and par.get("W") is not None and par["W"].shape == W.shape
+        lpi_scale = getattr(self, "_lpi_scale", 1.0)     # (log_likelihood: 2, the doubled logits of _loglik_terms)
+        same = (par.get("lpi_scale", 1.0) == lpi_scale and par.get("ykey") == res["key"] and par.get("W") is not None
+                and par["W"].shape == W.shape
                 and np.array_equal(par["W"], W) and np.array_equal(par["mu"], mu) and np.array_equal(par["psi"], psi)
                 and np.array_equal(par["pi"], pi) and par["sig"].shape == sig.shape and np.array_equal(par["sig"], sig))
         if same:
@@ -344,11 +346,13 @@ class GSC(DeviceCAModel):
         with np.errstate(divide='ignore', invalid='ignore'):
             c0 = -(np.log(psid) + np.log(lam)) - mu * mu * Gd / s2
             lpi = np.log(pi) - np.log(1 - pi)
+            if lpi_scale != 1.0:
+                lpi = lpi_scale * lpi
         tables = np.stack([c0, 2. * mu / s2, Gd * mu, 1. / (lam * s2 * s2), 1. / (lam * s2), 1. / lam, mu, lpi])
         self._par = {"ykey": res["key"], "W": W.copy(), "mu": mu.copy(), "psi": psi.copy(), "pi": pi.copy(),
                      "sig": sig.copy(), "s2": s2, "Wt": Wt, "Wst": Wst, "G": G, "yn": yn,
                      "psi_d": self._upload("gsc_psi", psi), "tables": self._upload("gsc_tab", tables),
-                     "scores": scores}
+                     "scores": scores, "lpi_scale": lpi_scale}
         return self._par
 
     def _speculate(self, res, Wt):
@@ -506,6 +510,32 @@ class GSC(DeviceCAModel):
         logpj = torch.empty((N, K), dtype=torch.float64, device=self.device)
         cand, _, _, _ = self._run(1.0, model_params, res, None, logpj=logpj)
         return DeviceArray(logpj), DeviceArray(cand, np.int64)
+
+    def _loglik_terms(self, model_params, my_data):
+        """log_likelihood.  Given s, y is Gaussian: N(y; W_s mu_s, C_s), C_s = Sigma + W_s Psi_s W_s^T, Sigma the
+        noise covariance (scalar, diagonal or full).  By the determinant lemma and Woodbury, log det C_s = log det Sigma +
+        log det Psi_s + log det Lambda_s and r^T C_s^-1 r = r^T Sigma^-1 r - b^T Lambda_s^-1 b -- the terms of the E-step's
+        lp (gsc_et.py:321-356, 481-511), which carries them WITHOUT the factor 1/2, plus sum_{h in s} logit(pi_h).  So the
+        log-joints come from ``compute_lpj``'s pass with every logit of the tables doubled (``_lpi_scale``) and are scaled by
+        a = 1/2:  a lp' = log N(y; W_s mu_s, C_s) + D/2 log(2 pi) + 1/2 log det Sigma + sum_{h in s} logit(pi_h),
+        hence c = sum_h log(1 - pi_h) - D/2 log(2 pi) - 1/2 log det Sigma."""
+        pi = np.broadcast_to(np.asarray(model_params['pi'], dtype=np.float64), (self.H,))
+        sig = np.asarray(model_params['sigma_sq'], dtype=np.float64)
+        if (np.linalg.eigvalsh(0.5 * (sig + sig.T)).min() <= 0) if sig.ndim == 2 else not np.all(sig > 0):
+            # a noise covariance that is not positive definite: every row NaN (nothing raises, no datapoint is dropped)
+            N = self._resident(my_data['y'])["Y"].shape[0]
+            return torch.full((N, 1), float("nan"), dtype=torch.float64, device=self.device), 1.0, float("nan")
+        self._lpi_scale = 2.0          # (an attribute of the evaluation only: _eval_end restores the model's)
+        logpj, _ = self.compute_lpj(None, model_params, my_data)
+        if sig.ndim == 0:
+            logdet = self.D * np.log(float(sig))
+        elif sig.ndim == 1:
+            logdet = float(np.log(sig).sum())
+        else:
+            sign, logdet = np.linalg.slogdet(sig)
+            logdet = float(logdet) if sign > 0 else float("nan")
+        c = float(np.log(1. - pi).sum()) - 0.5 * self.D * np.log(2 * np.pi) - 0.5 * logdet
+        return logpj.tensor, 0.5, c
 
     @tracing.traced
     def compute_posterior_hprime(self, anneal, model_params, my_data):

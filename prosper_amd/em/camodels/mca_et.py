@@ -219,7 +219,8 @@ class MCA_ET(DeviceCAModel):
             ncut = anneal['Ncut_factor'] > 0.0
             defer = (ncut and self.defer_stats and getattr(self, "_in_step", False) and H <= 512
                      and 8 * N * Hp * D <= self.defer_max_bytes)
-            if self.fuse_em and (not ncut or defer) and D <= 512 and Hp <= 12 and dpl * hp_tile <= 48:
+            if self.fuse_em and not getattr(self, "_loglik_eval", False) and (not ncut or defer) and D <= 512 and Hp <= 12 \
+                    and dpl * hp_tile <= 48:
                 # the M-step's per-datapoint statistics come out of the same pass (every multi-cause power is evaluated once
                 # instead of twice): accumulated in the pass when no data truncation is ahead; with one ahead (49 of the 50
                 # steps of the reference's schedules) left as per-datapoint records that M_step adds once the cut is known
@@ -243,6 +244,20 @@ class MCA_ET(DeviceCAModel):
         out.lse1 = lse1         # log sum exp(logpj): the likelihood term Q
         out.T = T
         return {'logpj': out}
+
+    def _loglik_terms(self, model_params, my_data):
+        """log_likelihood.  The model is the one the E-step evaluates at T = 1: y ~ N(Wbar_s, sigma^2 I) with
+        Wbar_sd = (sum_{h in s} W_hd^rho)^(1/rho) at rho = 1 / (1 - 1/T_rho), T_rho = the bound on T -- 21 for MCA
+        (mca_et.py:143-173), 6 for MMCA's signed form (mmca_et.py:159-193) -- not the exact max.  Its columns are
+        pil_bar |s| - |y - Wbar_s|^2 / (2 sigma^2), so c = H log(1 - pi) - D/2 log(2 pi sigma^2) (the lAi of the reference's
+        ``Q``, mca_et.py:370-377) and a = 1."""
+        # (at the W the next E-step would see: M_step returns W unclamped, CAModel.step clamps it first -- check_params,
+        # on a private copy, since MMCA's clamps in place)
+        model_params['W'] = np.array(model_params['W'], dtype=np.float64, copy=True)
+        model_params = self.check_params(model_params)
+        pies, sigma = float(model_params['pi']), float(model_params['sigma'])
+        c = self.H * np.log(1. - pies) - 0.5 * self.D * np.log(2 * _PI * sigma ** 2)
+        return self._loglik_estep(model_params, my_data), 1.0, c
 
     @tracing.traced
     def M_step(self, anneal, model_params, my_suff_stat, my_data):

@@ -258,6 +258,15 @@ class TSC_ET(DeviceCAModel):
         tracing.tracepoint("E_step:iterating")
         return {'logpj': self._dsc_estep(anneal, "tsc_stats", par, res, cand, tab, S, prior, P, S, [model_params['pi']])}
 
+    def _loglik_terms(self, model_params, my_data):
+        """log_likelihood.  At T = 1 a column of ``logpj`` is - |y - W s|^2 / (2 sigma^2) plus the log-prior of
+        the state's Hprime candidate positions only (pi / 2 for -1 and +1, 1 - pi for 0; tsc_et.py:320-351): the H - Hprime
+        other latents are 0 with probability 1 - pi each, so c = (H - Hprime) log(1 - pi) - D/2 log(2 pi sigma^2) -- the
+        reference's ``L`` (tsc_et.py:447-451) without its - log A_pi_gamma, plus the missing prior -- and a = 1."""
+        pies, sigma = float(model_params['pi']), float(model_params['sigma'])
+        c = (self.H - self.Hprime) * np.log(1. - pies) - 0.5 * self.D * np.log(2 * np.pi * sigma ** 2)
+        return self._loglik_estep(model_params, my_data), 1.0, c
+
     @tracing.traced
     def M_step(self, anneal, model_params, my_suff_stat, my_data):
         """New W, pi, sigma (tsc_et.py:359-542).  Logs ``L`` and ``N_use``."""

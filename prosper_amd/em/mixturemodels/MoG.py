@@ -115,6 +115,23 @@ class MoG(DeviceMixture, MixtureModel):
             c[(sig <= 0).any(1)] = np.nan
         return self._estep_dev(my_y, -beta, c, lp, Bl=Bl, Bq=Bq)
 
+    def _loglik_rows(self, model_params, res, rows):
+        """log_likelihood: rows[n] = log sum_h pies_h N(y_n; w_h, Sigma_h).  Diagonal: the scores kernel's log-likelihood
+        mode with coef = -1/2, c_h = sum_d w^2/sigma^2 + sum_d log sigma^2 and lp_h = log pies_h - D/2 log(2 pi).  Full:
+        ``_loglik_full``."""
+        W = np.asarray(model_params['W'], dtype=np.float64)
+        sig = np.asarray(model_params['sigmas_sq'], dtype=np.float64)
+        pies = np.asarray(model_params['pies'], dtype=np.float64)
+        if self.sigmas_sq_type == 'full':
+            return self._loglik_full(res, rows, W, sig, pies)
+        with np.errstate(all='ignore'):
+            lp = np.log(pies) - 0.5 * self.D * np.log(2 * np.pi)
+            Bq = 1. / sig
+            Bl = -2. * W.T * Bq
+            c = np.sum(W.T ** 2 * Bq, 1) + np.sum(np.log(sig), 1)
+            c[(sig <= 0).any(1)] = np.nan
+        self._loglik_scores(res, rows, -0.5, c, lp, Bl, Bq=Bq)
+
     def log_p_y(self, model_params, my_y, beta=1.0):
         """log_p_y of the reference (MoG.py:231-281): the scores part of ``posterior`` (with pies = 1), an ndarray."""
         mp = dict(model_params, pies=np.ones(self.H))

@@ -100,6 +100,25 @@ class MoP(DeviceMixture, MixtureModel):
                 logW = np.where(np.isneginf(logW), 0.0, logW)
         return self._estep_dev(my_y, beta, c, lp, Bl=logW, scaled=raw)
 
+    def _loglik_rows(self, model_params, res, rows):
+        """log_likelihood: rows[n] = log sum_h pies_h prod_d Poisson(x_nd; w_dh) with x = y (A nan) or x = s y + 1 (A set,
+        the data the E-step sees): the scores kernel's log-likelihood mode with coef = 1, Bl = log W^T on the scaled rows,
+        c_h = sum_d log w_dh (the "+1" of x, A set) - sum_d w_dh, lp = log pies, and the row term - sum_d lgamma(x_nd + 1)."""
+        W = np.asarray(model_params['W'], dtype=np.float64)
+        normed = not np.isnan(self.A)
+        with np.errstate(all='ignore'):
+            lp = np.log(np.asarray(model_params['pies'], dtype=np.float64))
+            logW = np.log(W.T)
+            c = -np.sum(W, 0)
+            if normed:
+                c = c + np.sum(logW, 1)
+                logW = np.where(np.isneginf(logW), 0.0, logW)
+            else:
+                # a zero rate: pmf 1 at a zero count, 0 otherwise -- y log w with log w = -1e300 gives exactly that weight
+                # (0 * -inf would be NaN)
+                logW = np.where(np.isneginf(logW), -1e300, logW)
+        self._loglik_scores(res, rows, 1.0, c, lp, logW, pmf=1, yoff=1.0 if normed else 0.0)
+
     def log_p_y(self, model_params, my_y, beta=1.0):
         """log_p_y of the reference (MoP.py:193-232): the scores part of ``posterior`` (with pies = 1), an ndarray;
         ``my_y`` as for ``posterior`` (normalised when A is set)."""

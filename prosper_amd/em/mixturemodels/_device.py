@@ -77,8 +77,91 @@ class DeviceMixture(object):
         return self._data
 
     def invalidate_data(self):
-        """Forget the resident shard (call after modifying ``my_data['y']`` in place)."""
+        """Forget the resident shards, the training one and the one of ``log_likelihood`` (call after modifying
+        ``my_data['y']`` in place, or to release the held-out data's device memory)."""
         self._data = {}
+        self.__dict__.pop("_eval_slot", None)
+
+    # ---- held-out log-likelihood (DESIGN 4.12) --------------------------------------------------------------------------
+    def log_likelihood(self, model_params, my_data, per_datapoint=False):
+        """Exact held-out log-likelihood sum_n log sum_h pies_h p(y_n | h) of ``my_data['y']`` (host array, torch tensor or
+        DeviceArray) with the proper densities: MoG with the 1/2 and (2 pi)^(-D/2) factors (diagonal: sum_d log sigma^2;
+        full: log det from the device Cholesky), MoP the Poisson pmf including - sum_d lgamma(y_nd + 1) on the data the
+        E-step sees (normalised when A is set).  The reference's E-step quirk (no 1/2, MoG.py:213-281) stays in E_step /
+        posterior / log_p_y; this method does not reuse it.
+
+        Returns the sum over ALL ranks' datapoints as a float (collective; per-rank sums added in rank order, the same bits
+        on every rank), or with ``per_datapoint=True`` this rank's (my_N,) float64 values.  A component with pies_h > 0 whose
+        full covariance the Cholesky rejects makes every row NaN, a NaN in a data row that row.  ``model_params`` and the
+        training shard are left as they were (the evaluation keeps its data and workspaces in a slot of its own)."""
+        saved = dict(self.__dict__)
+        slot = saved.get("_eval_slot") or {"_data": {}, "_ws": {}}
+        self._data, self._ws = slot["_data"], slot["_ws"]
+        try:
+            res = self._resident(my_data['y'])
+            N = res["Y"].shape[0]
+            lib = _lib.load()
+            rows = torch.empty(N, dtype=torch.float64, device=self.device)
+            if N:
+                self._loglik_rows(dict(model_params), res, rows)
+            work = torch.empty(int(lib.pm_rows_lse_work_len(N)), dtype=torch.float64, device=self.device)
+            total = torch.empty(1, dtype=torch.float64, device=self.device)
+            # (the ordered total of the rows: the log-sum-exp of a row of one entry is that entry)
+            _lib.call("pm_rows_lse_f64", _ptr(rows), 1, N, 1, 1.0, None, None, _ptr(work), _ptr(total), self._stream())
+            out = rows.cpu().numpy() if per_datapoint else float(total.cpu()[0])
+        finally:
+            slot = {"_data": self._data, "_ws": self._ws}
+            self.__dict__.clear()
+            self.__dict__.update(saved)
+            self._eval_slot = slot
+        if per_datapoint:
+            return out
+        acc = 0.0
+        for v in self.comm.allgather(out):
+            acc += v
+        return acc
+
+    def _loglik_scores(self, res, rows, coef, c, lp, Bl, Bq=None, pmf=0, yoff=0.0):
+        """pm_mix_loglik_f64: rows[n] = log sum_h exp((S[n,h] + c_h) coef + lp_h) - (pmf: sum_d lgamma(s_n y_nd + yoff + 1))."""
+        Y, H, D = res["Y"], self.H, self.D
+        # (the device copies are held here until the launch: a temporary freed inside the argument list hands its block to
+        # the next upload)
+        Bq_d = self._dev(Bq) if Bq is not None else None
+        Bl_d, c_d, lp_d = self._dev(Bl), self._dev(c), self._dev(lp)
+        _lib.call("pm_mix_loglik_f64", _ptr(Y), D, _ptr(res["rs"]) if pmf else None, _ptr(Bq_d), _ptr(Bl_d), D, _ptr(c_d),
+                  float(coef), _ptr(lp_d), Y.shape[0], D, H, int(pmf), float(yoff), _ptr(rows), self._stream())
+
+    def _loglik_full(self, res, rows, W, sig, pies):
+        """MoG full: pm_mix_chol_f64 -> L^-1, log det per component; pm_mix_maha_f64 -> |L^-1 (y - w)|^2 (N, H);
+        pm_rows_lse_f64 with a = -1/2 and the column offsets log pies_h - 1/2 log det_h - D/2 log(2 pi).  A component the
+        Cholesky rejects gets a zero B in mode 1 (S = 0) and offset NaN (pies_h > 0) or -inf (pies_h = 0)."""
+        H, D = self.H, self.D
+        Y = res["Y"]
+        N = Y.shape[0]
+        S_d = self._dev(sig)
+        Lw = self._buf("ll_chol_L", (H, D, D))
+        B = self._buf("ll_chol_B", (H, D, D))
+        logdet_d = torch.empty(H, dtype=torch.float64, device=self.device)
+        status_d = torch.empty(H, dtype=torch.int32, device=self.device)
+        st = self._stream()
+        _lib.call("pm_mix_chol_f64", _ptr(S_d), D, H, _ptr(Lw), _ptr(B), _ptr(logdet_d), _ptr(status_d), st)
+        status = status_d.cpu().numpy()
+        logdet = logdet_d.cpu().numpy().copy()
+        bad = np.nonzero(status)[0]
+        mode = np.zeros(H, dtype=np.int32)
+        for h in bad:
+            B[h].zero_()
+            mode[h] = 1
+        with np.errstate(divide='ignore', invalid='ignore'):
+            off = np.log(pies) - 0.5 * logdet - 0.5 * D * np.log(2 * np.pi)
+        off[bad] = np.where(pies[bad] > 0, np.nan, -np.inf)
+        mode_d = torch.from_numpy(mode).to(self.device)
+        M = self._buf("ll_maha", (N, H))
+        W_d, off_d = self._dev(W.T), self._dev(off)
+        _lib.call("pm_mix_maha_f64", _ptr(Y), D, _ptr(W_d), _ptr(B), _ptr(mode_d), N, D, H, _ptr(M), H, st)
+        work = torch.empty(int(_lib.load().pm_rows_lse_work_len(N)), dtype=torch.float64, device=self.device)
+        total = torch.empty(1, dtype=torch.float64, device=self.device)
+        _lib.call("pm_rows_lse_f64", _ptr(M), H, N, H, -0.5, _ptr(off_d), _ptr(rows), _ptr(work), _ptr(total), st)
 
     # ---- E-step -------------------------------------------------------------------------------------------------------
     def _full_factors(self, sig):
