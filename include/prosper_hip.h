@@ -844,6 +844,41 @@ int pm_mix_loglik_f64(const double *Y, int64_t ldy, const double *rowscale, cons
 int pm_rows_lse_f64(const double *logpj, int64_t ld, int64_t N, int64_t S, double a, const double *col_offset,
                     double *rows_out, double *work, double *total, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Exact held-out log-likelihood (loglik_exact.hip)
+ * ---------------------------------------------------------------------------------------
+ * v_n = log sum_{all s} p(s, y_n | Theta) over the model's WHOLE state space, by enumeration on the device: states are
+ * decoded from their index inside the kernels, nothing is stored per state.  rows_out (N; NULL = not written) receives v,
+ * total[0] = sum_n v_n in a fixed order; the grid splits the state space into ranges whose number depends on N alone, the
+ * (max, sum exp) partials of every (range, datapoint) are combined in range order, no atomics: the same bits on every run
+ * and in both builds.  N == 0 writes total[0] = 0.  A state of zero prior contributes nothing, a NaN in y_n gives v_n = NaN
+ * (that row only).  `work`: pm_loglik_exact_work_len(N, H) doubles (a function of N and H only, linear in H).  Every entry
+ * checks its arguments before it touches a device: PM_EINVAL for a null pointer, N < 0, D < 1, H < 1, ldy < D or a bad K,
+ * PM_ERANGE past the bounds: K^H <= 2^32 and H <= 32 (linear models), H <= 32 (MCA / MMCA), H <= 16 (GSC). */
+int64_t pm_loglik_exact_work_len(int64_t N, int64_t H);
+/* BSC, TSC, DSC: log p(s, y) = sum_h logp[h*K + k_h] - 1/2 s^T G s + x^T P s + cst + qcoef |x|^2, x = y - ymu (ymu: D values
+ * or NULL for 0, BSC's mu), s_h = values[k_h] (K in 2..8 values, any reals), i.e. P = W / sigma^2 (D x H row-major),
+ * G = W^T W / sigma^2 (H x H), logp the per-latent log-prior table (-inf for a value of zero prior), cst = -D/2 log(2 pi
+ * sigma^2), qcoef = -1 / (2 sigma^2).  All pointers but the outputs and Y are small device arrays. */
+int pm_loglik_exact_lin_f64(const double *Y, int64_t ldy, const double *ymu, const double *P, const double *G,
+                            const double *logp, const double *values, int64_t K, double cst, double qcoef, int64_t N, int64_t D,
+                            int64_t H, double *rows_out, double *work, double *total, void *stream);
+/* MCA (signed_w = 0) and MMCA (signed_w = 1): log p(s, y) = |s| lp1 + (H - |s|) lp0 - inv_s2 / 2 |y - Wbar(s)|^2 + cst, with
+ * Wbar_d(s) = (sum_{h in s} Wrho[h*D + d])^inv_rho (signed: sign(t) |t|^inv_rho), Wbar(0) = 0, Wrho = W^rho (signed:
+ * sign(W) |W|^rho) as H x D rows; lp1 = log pi, lp0 = log(1 - pi), cst = -D/2 log(2 pi sigma^2). */
+int pm_loglik_exact_mca_f64(const double *Y, int64_t ldy, const double *Wrho, double inv_rho, int signed_w, double lp1,
+                            double lp0, double inv_s2, double cst, int64_t N, int64_t D, int64_t H, double *rows_out,
+                            double *work, double *total, void *stream);
+/* GSC: log p(s, y) = sum_h logp[2h + s_h] + log N(y; W_s mu_s, Sigma + W_s Psi_s W_s^T), from the whitened products
+ * P = Sigma^-1 W (D x H), M = W^T Sigma^-1 W (H x H), y^T Sigma^-1 y = sum_d wdiag_d y_d^2 (scalar / diagonal Sigma) or
+ * |Lw y|^2 (full: Lw = chol(Sigma)^-1, D x D lower; at most one of wdiag and Lw), Psi (H x H), mu (H), logp[2h] =
+ * log(1 - pi_h), logp[2h + 1] = log pi_h and cst = -D/2 log(2 pi) - 1/2 log det Sigma.  Per support, a wavefront factors
+ * Psi_s = Lp Lp^T and I + Lp^T M_ss Lp in LDS (determinant lemma and Woodbury); a factor that is not positive definite
+ * gives NaN. */
+int pm_loglik_exact_gsc_f64(const double *Y, int64_t ldy, const double *P, const double *wdiag, const double *Lw,
+                            const double *M, const double *Psi, const double *mu, const double *logp, double cst, int64_t N,
+                            int64_t D, int64_t H, double *rows_out, double *work, double *total, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

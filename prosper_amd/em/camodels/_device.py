@@ -1132,12 +1132,29 @@ class DeviceCAModel(CAModel):
         log-joints leave out, so that log sum_s p(s, y_n | Theta) = log sum_s exp(a logpj[n, s]) + c."""
         raise NotImplementedError("%s has no log_likelihood" % type(self).__name__)
 
+    def _loglik_exact(self, model_params):
+        """Per model: what ``log_likelihood(..., exact=True)`` hands the enumeration kernels (include/prosper_hip.h,
+        pm_loglik_exact_*): ``(kind, arrays, scalars)`` with kind 'lin' (BSC, TSC, DSC), 'mca' (MCA, MMCA) or 'gsc'.  Host
+        products of the parameters only; the data never leaves the device."""
+        raise NotImplementedError("%s has no exact log_likelihood" % type(self).__name__)
+
+    def _exact_linear(self, W, sigma, values, logp, mu=None):
+        """The 'lin' hook of ``_loglik_exact`` for y ~ N(mu + W s, sigma^2 I): P = W / sigma^2, G = W^T W / sigma^2, the
+        per-latent log-prior table ``logp`` (H, K) over ``values`` (K,)."""
+        W = np.asarray(W, dtype=np.float64)
+        s2 = float(sigma) ** 2
+        arrays = {"P": W / s2, "G": (W.T @ W) / s2, "logp": np.asarray(logp, dtype=np.float64),
+                  "values": np.asarray(values, dtype=np.float64)}
+        if mu is not None:
+            arrays["mu"] = np.asarray(mu, dtype=np.float64).reshape(-1)
+        return "lin", arrays, {"cst": -0.5 * self.D * np.log(2 * np.pi * s2), "qcoef": -0.5 / s2}
+
     def _loglik_estep(self, model_params, my_data):
         """select_Hprimes + E_step at ``LoglikPoint`` through the training kernels: the (N, K) device log-joints."""
         data = self.select_Hprimes(model_params, my_data)
         return self.E_step(LoglikPoint(), model_params, data)['logpj'].tensor
 
-    def log_likelihood(self, model_params, my_data, per_datapoint=False):
+    def log_likelihood(self, model_params, my_data, per_datapoint=False, exact=False):
         """Held-out log-likelihood F(Theta; Y) = sum_n log sum_{s in K_n} p(s, y_n | Theta) of ``my_data['y']`` (host
         array, torch tensor or DeviceArray) under ``model_params``.
 
@@ -1152,7 +1169,14 @@ class DeviceCAModel(CAModel):
         order, so every rank returns the same bits), or with ``per_datapoint=True`` this rank's (my_N,) float64 values in
         datapoint order (no collective).  ``model_params``, the training shard's residency, the records the last M-step
         left for the next step and Hprime / gamma are left as they were: a call between two EM steps does not change the
-        training trajectory.  Runs the E-step kernels and pm_rows_lse_f64 on the device."""
+        training trajectory.  Runs the E-step kernels and pm_rows_lse_f64 on the device.
+
+        ``exact=True``: log p(y_n | Theta) = log sum_{all s} p(s, y_n | Theta) summed over the model's WHOLE state space by
+        enumeration on the device (pm_loglik_exact_*), the same generative model at the same annealing point:
+        no candidates, no state table, no E-step, and a result independent of Hprime, gamma and the annealing state.  The
+        state count is bounded (include/prosper_hip.h): past the bound this raises ``HipError``."""
+        if exact:
+            return self._log_likelihood_exact(model_params, my_data, per_datapoint)
         saved = self._eval_begin()
         try:
             logpj, a, c = self._loglik_terms(dict(model_params), {'y': my_data['y']})
@@ -1167,6 +1191,47 @@ class DeviceCAModel(CAModel):
             if per_datapoint:
                 return rows.cpu().numpy() + c
             local = float(total.cpu()[0]) + N * c
+        finally:
+            self._eval_end(saved)
+        parts = self.comm.allgather(local)
+        out = 0.0
+        for v in parts:
+            out += v
+        return out
+
+    def _log_likelihood_exact(self, model_params, my_data, per_datapoint):
+        saved = self._eval_begin()
+        try:
+            res = self._resident(my_data['y'])
+            Y = res["Y"]
+            N, D, H = Y.shape[0], self.D, self.H
+            kind, arrays, sc = self._loglik_exact(dict(model_params))
+            dev = {k: (torch.from_numpy(np.array(v, dtype=np.float64, order="C")).to(self.device) if v is not None else None)
+                   for k, v in arrays.items()}
+            lib = _lib.load(self.deterministic)
+            wl = int(lib.pm_loglik_exact_work_len(N, H))
+            work = torch.empty(max(wl, 1), dtype=torch.float64, device=self.device)
+            total = torch.empty(1, dtype=torch.float64, device=self.device)
+            rows = torch.empty(N, dtype=torch.float64, device=self.device) if per_datapoint else None
+            Yp = _ptr(Y) if N else None
+            ld = max(int(Y.stride(0)), D) if N else D
+            out = (_ptr(rows), _ptr(work), _ptr(total), self._stream())
+            dbl = ctypes.c_double
+            if kind == "lin":
+                self._call("loglik_exact", "pm_loglik_exact_lin_f64", Yp, ld, _ptr(dev.get("mu")), _ptr(dev["P"]),
+                           _ptr(dev["G"]), _ptr(dev["logp"]), _ptr(dev["values"]), int(arrays["values"].shape[0]),
+                           dbl(sc["cst"]), dbl(sc["qcoef"]), N, D, H, *out)
+            elif kind == "mca":
+                self._call("loglik_exact", "pm_loglik_exact_mca_f64", Yp, ld, _ptr(dev["Wrho"]), dbl(sc["inv_rho"]),
+                           int(sc["signed"]), dbl(sc["lp1"]), dbl(sc["lp0"]), dbl(sc["inv_s2"]), dbl(sc["cst"]), N, D, H,
+                           *out)
+            else:
+                self._call("loglik_exact", "pm_loglik_exact_gsc_f64", Yp, ld, _ptr(dev["P"]), _ptr(dev.get("wdiag")),
+                           _ptr(dev.get("Lw")), _ptr(dev["M"]), _ptr(dev["Psi"]), _ptr(dev["mu"]), _ptr(dev["logp"]),
+                           dbl(sc["cst"]), N, D, H, *out)
+            if per_datapoint:
+                return rows.cpu().numpy()
+            local = float(total.cpu()[0])
         finally:
             self._eval_end(saved)
         parts = self.comm.allgather(local)

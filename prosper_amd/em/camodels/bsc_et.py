@@ -615,6 +615,15 @@ class BSC_ET(DeviceCAModel):
         c = self.H * np.log(1. - pies) - 0.5 * self.D * np.log(2 * _PI * sigma ** 2)
         return self._loglik_estep(model_params, my_data), 1.0, c
 
+    def _loglik_exact(self, model_params):
+        """exact log_likelihood: states {0,1}^H, log prior |s| log pi + (H - |s|) log(1 - pi), y ~ N(mu + W s,
+        sigma^2 I) (mu when given)."""
+        pi = float(model_params['pi'])
+        with np.errstate(divide='ignore'):
+            lp = np.log([1. - pi, pi])
+        return self._exact_linear(model_params['W'], model_params['sigma'], [0., 1.], np.tile(lp, (self.H, 1)),
+                                  mu=model_params.get('mu'))
+
     @tracing.traced
     def M_step(self, anneal, model_params, my_suff_stat, my_data):
         """New W, pi, sigma (, mu) from the posterior over the truncated states

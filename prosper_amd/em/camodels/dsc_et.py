@@ -310,6 +310,14 @@ class DSC_ET(DeviceCAModel):
         sigma = float(model_params['sigma'])
         return self._loglik_estep(model_params, my_data), 1.0, -0.5 * self.D * np.log(2 * np.pi * sigma ** 2)
 
+    def _loglik_exact(self, model_params):
+        """exact log_likelihood: states values^H (``states``), log prior sum_h log pi[k_h] (a value of zero
+        prior contributes nothing)."""
+        with np.errstate(divide='ignore'):
+            lp = np.log(np.asarray(model_params['pi'], dtype=np.float64).reshape(-1))
+        assert lp.shape == (self.K,)
+        return self._exact_linear(model_params['W'], model_params['sigma'], self.states, np.tile(lp, (self.H, 1)))
+
     @tracing.traced
     def M_step(self, anneal, model_params, my_suff_stat, my_data):
         """New W, pi, sigma (dsc_et.py:587-774).  Logs ``prior_mass``, ``L`` and ``N_use``."""

@@ -537,6 +537,38 @@ class GSC(DeviceCAModel):
         c = float(np.log(1. - pi).sum()) - 0.5 * self.D * np.log(2 * np.pi) - 0.5 * logdet
         return logpj.tensor, 0.5, c
 
+    def _loglik_exact(self, model_params):
+        """exact log_likelihood: supports {0,1}^H, log prior sum_h s_h log pi_h + (1 - s_h) log(1 - pi_h),
+        y ~ N(W_s mu_s, Sigma + W_s Psi_s W_s^T).  The kernel takes the Sigma^-1-whitened products P = Sigma^-1 W and
+        M = W^T Sigma^-1 W, y^T Sigma^-1 y through wdiag (scalar, diagonal) or Lw = chol(Sigma)^-1 (full), and
+        cst = -D/2 log(2 pi) - 1/2 log det Sigma.  A noise covariance that is not positive definite gives NaN rows."""
+        D, H = self.D, self.H
+        W = np.asarray(model_params['W'], dtype=np.float64)
+        pi = np.broadcast_to(np.asarray(model_params['pi'], dtype=np.float64), (H,))
+        mu = np.broadcast_to(np.asarray(model_params['mu'], dtype=np.float64), (H,))
+        Psi = np.asarray(model_params['psi_sq'], dtype=np.float64)
+        Psi = 0.5 * (Psi + Psi.T) if Psi.ndim == 2 else np.diag(np.broadcast_to(Psi, (H,)))
+        sig = np.asarray(model_params['sigma_sq'], dtype=np.float64)
+        arrays = {"Psi": Psi, "mu": mu}
+        if (np.linalg.eigvalsh(0.5 * (sig + sig.T)).min() <= 0) if sig.ndim == 2 else not np.all(sig > 0):
+            # (as _loglik_terms: every row NaN -- the kernel runs on neutral products, the constant carries the NaN)
+            arrays.update(P=np.zeros((D, H)), M=np.zeros((H, H)), wdiag=np.ones(D))
+            logdet = float("nan")
+        elif sig.ndim < 2:
+            wd = np.broadcast_to(1. / sig, (D,)).astype(np.float64)
+            P = W * wd[:, None]
+            arrays.update(P=P, M=W.T @ P, wdiag=wd)
+            logdet = float(np.log(np.broadcast_to(sig, (D,))).sum())
+        else:
+            L = np.linalg.cholesky(0.5 * (sig + sig.T))
+            Lw = np.linalg.inv(L)
+            P = Lw.T @ (Lw @ W)
+            arrays.update(P=P, M=W.T @ P, Lw=np.tril(Lw))
+            logdet = 2. * float(np.log(np.diag(L)).sum())
+        with np.errstate(divide='ignore'):
+            arrays["logp"] = np.stack([np.log(1. - pi), np.log(pi)], axis=1)
+        return "gsc", arrays, {"cst": -0.5 * D * np.log(2 * np.pi) - 0.5 * logdet}
+
     @tracing.traced
     def compute_posterior_hprime(self, anneal, model_params, my_data):
         """gsc_et.py:260-398: for ONE data cluster -- ``my_data['y']`` (n, D), all rows sharing the candidate set

@@ -259,6 +259,21 @@ class MCA_ET(DeviceCAModel):
         c = self.H * np.log(1. - pies) - 0.5 * self.D * np.log(2 * _PI * sigma ** 2)
         return self._loglik_estep(model_params, my_data), 1.0, c
 
+    def _loglik_exact(self, model_params):
+        """exact log_likelihood: states {0,1}^H, y ~ N(Wbar(s), sigma^2 I) with the rho-combination of
+        ``_loglik_terms`` at T = 1 (MMCA: signed), W clamped by ``check_params`` on a private copy, Wbar(0) = 0."""
+        model_params['W'] = np.array(model_params['W'], dtype=np.float64, copy=True)
+        model_params = self.check_params(model_params)
+        Wt = np.ascontiguousarray(np.asarray(model_params['W'], dtype=np.float64).T)       # (H, D)
+        rho = self._rho(1.0)
+        signed = bool(self.signed_w)
+        Wrho = np.sign(Wt) * np.abs(Wt) ** rho if signed else Wt ** rho
+        pi, sigma = float(model_params['pi']), float(model_params['sigma'])
+        with np.errstate(divide='ignore'):
+            lp1, lp0 = np.log(pi), np.log(1. - pi)
+        return "mca", {"Wrho": Wrho}, {"inv_rho": 1. / rho, "signed": signed, "lp1": lp1, "lp0": lp0,
+                                       "inv_s2": 1. / sigma ** 2, "cst": -0.5 * self.D * np.log(2 * _PI * sigma ** 2)}
+
     @tracing.traced
     def M_step(self, anneal, model_params, my_suff_stat, my_data):
         """New W, pi, sigma and the ET log-likelihood Q (mca_et.py:182-377)."""

@@ -267,6 +267,13 @@ class TSC_ET(DeviceCAModel):
         c = (self.H - self.Hprime) * np.log(1. - pies) - 0.5 * self.D * np.log(2 * np.pi * sigma ** 2)
         return self._loglik_estep(model_params, my_data), 1.0, c
 
+    def _loglik_exact(self, model_params):
+        """exact log_likelihood: states {-1,0,1}^H, log prior nz(s) log(pi / 2) + (H - nz(s)) log(1 - pi)."""
+        pi = float(model_params['pi'])
+        with np.errstate(divide='ignore'):
+            lp = np.log([0.5 * pi, 1. - pi, 0.5 * pi])
+        return self._exact_linear(model_params['W'], model_params['sigma'], [-1., 0., 1.], np.tile(lp, (self.H, 1)))
+
     @tracing.traced
     def M_step(self, anneal, model_params, my_suff_stat, my_data):
         """New W, pi, sigma (tsc_et.py:359-542).  Logs ``L`` and ``N_use``."""

@@ -83,7 +83,7 @@ class DeviceMixture(object):
         self.__dict__.pop("_eval_slot", None)
 
     # ---- held-out log-likelihood --------------------------------------------------------------------------
-    def log_likelihood(self, model_params, my_data, per_datapoint=False):
+    def log_likelihood(self, model_params, my_data, per_datapoint=False, exact=False):
         """Exact held-out log-likelihood sum_n log sum_h pies_h p(y_n | h) of ``my_data['y']`` (host array, torch tensor or
         DeviceArray) with the proper densities: MoG with the 1/2 and (2 pi)^(-D/2) factors (diagonal: sum_d log sigma^2;
         full: log det from the device Cholesky), MoP the Poisson pmf including - sum_d lgamma(y_nd + 1) on the data the
@@ -93,7 +93,9 @@ class DeviceMixture(object):
         Returns the sum over ALL ranks' datapoints as a float (collective; per-rank sums added in rank order, the same bits
         on every rank), or with ``per_datapoint=True`` this rank's (my_N,) float64 values.  A component with pies_h > 0 whose
         full covariance the Cholesky rejects makes every row NaN, a NaN in a data row that row.  ``model_params`` and the
-        training shard are left as they were (the evaluation keeps its data and workspaces in a slot of its own)."""
+        training shard are left as they were (the evaluation keeps its data and workspaces in a slot of its own).
+        ``exact`` is accepted for the component-analysis models' signature: a mixture's value is exact either
+        way, and ``exact=True`` returns the same bits."""
         saved = dict(self.__dict__)
         slot = saved.get("_eval_slot") or {"_data": {}, "_ws": {}}
         self._data, self._ws = slot["_data"], slot["_ws"]
