@@ -23,6 +23,62 @@ from prosper_amd.utils.barstest import generate_bars_dict, find_permutation   # 
 from prosper_amd.utils.datalog import dlog, StoreInMemory      # noqa: E402
 
 
+def build(name, size, Hprime, gamma, comm):
+    """(model, ground-truth parameters) of the bars test of ``name`` at the truncation Hprime / gamma."""
+    H, D = 2 * size, size ** 2
+    bars = 10 * generate_bars_dict(H)
+    if name == "bsc":
+        from prosper_amd.em.camodels.bsc_et import BSC_ET as Model
+        model = Model(D, H, Hprime, gamma, comm=comm)
+        gt = {'W': bars, 'pi': 2. / H, 'sigma': 1.0}
+    elif name == "mca":
+        from prosper_amd.em.camodels.mca_et import MCA_ET as Model
+        model = Model(D, H, Hprime, gamma, comm=comm)
+        gt = {'W': bars, 'pi': 2. / H, 'sigma': 1.0}
+    elif name == "mmca":
+        from prosper_amd.em.camodels.mmca_et import MMCA_ET as Model
+        model = Model(D, H, Hprime, gamma, comm=comm)
+        gt = {'W': 10 * generate_bars_dict(H, neg_bars=True), 'pi': 2. / H, 'sigma': 1.0}
+    elif name == "dsc":
+        from prosper_amd.em.camodels.dsc_et import DSC_ET as Model
+        model = Model(D, H, Hprime, gamma, states=np.array([-1., 0., 1.]), comm=comm)
+        gt = {'W': bars, 'pi': np.array([1. / H, 1 - 2. / H, 1. / H]), 'sigma': 1.0}
+    elif name == "tsc":
+        from prosper_amd.em.camodels.tsc_et import TSC_ET as Model
+        model = Model(D, H, Hprime, gamma, comm=comm)
+        gt = {'W': bars, 'pi': 2. / H, 'sigma': 1.0}
+    elif name == "mog":     # examples/barstests/param-bars-mog.py of the reference: diagonal covariances
+        from prosper_amd.em.mixturemodels.MoG import MoG
+        model = MoG(D, H, sigmas_sq_type='diagonal', comm=comm)
+        gt = {'W': bars, 'pies': np.ones(H) / H, 'sigmas_sq': np.ones((H, D))}
+    elif name == "mop":     # param-bars-mop.py: A = nan (no normalisation)
+        from prosper_amd.em.mixturemodels.MoP import MoP
+        model = MoP(D, H, comm=comm)
+        gt = {'W': bars, 'pies': np.ones(H) / H}
+    else:
+        from prosper_amd.em.camodels.gsc_et import GSC as Model
+        model = Model(D, H, Hprime, gamma, 'scalar', comm=comm)
+        gt = {'W': bars / 10., 'pi': np.full(H, 2. / H), 'mu': np.full(H, 5.0), 'psi_sq': np.eye(H),
+              'sigma_sq': 1.0}
+
+    return model, gt
+
+
+def noiseless_mean(name, gt, drawn):
+    """The mean of the data given the latents the generator drew (``generate_data`` returns them as ``s``; GSC: ``z``)."""
+    W = np.asarray(gt['W'], dtype=np.float64)
+    s = np.asarray(drawn['s'])
+    if name in ("mog", "mop"):
+        return W.T[s.astype(int)]
+    if name == "gsc":
+        return np.asarray(drawn['z'], dtype=np.float64) @ W.T
+    if name in ("mca", "mmca"):      # per dimension the active cause of largest magnitude (MCA: the maximum), 0 without one
+        act = np.where(s[:, None, :] != 0, W[None, :, :], 0.0)                  # (N, D, H)
+        idx = np.abs(act).argmax(axis=2)
+        return np.take_along_axis(act, idx[:, :, None], axis=2)[:, :, 0]
+    return s.astype(np.float64) @ W.T
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("model", nargs="?", default="bsc", choices=["bsc", "mca", "mmca", "dsc", "tsc", "gsc", "mog",
@@ -38,6 +94,10 @@ def main():
     ap.add_argument("--exact", action="store_true",
                     help="with --heldout: also the exact held-out log-likelihood of the learned parameters, summed over "
                     "every latent state (DESIGN 4.13), next to the truncated bound and their difference per datapoint")
+    ap.add_argument("--reconstruct", action="store_true",
+                    help="with --heldout: denoise the held-out datapoints (reconstruct, DESIGN 4.14) and print the mean squared "
+                    "error of the noisy data and of the reconstruction against the noiseless data, for the learned and for "
+                    "the generating parameters")
     a = ap.parse_args()
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         import torch
@@ -47,43 +107,8 @@ def main():
     comm = parallel.Comm()
     np.random.seed(1 + comm.rank)
 
-    size = a.size
-    H, D = 2 * size, size ** 2
-    Hprime, gamma = 5, 3
-    bars = 10 * generate_bars_dict(H)
-    if a.model == "bsc":
-        from prosper_amd.em.camodels.bsc_et import BSC_ET as Model
-        model = Model(D, H, Hprime, gamma, comm=comm)
-        gt = {'W': bars, 'pi': 2. / H, 'sigma': 1.0}
-    elif a.model == "mca":
-        from prosper_amd.em.camodels.mca_et import MCA_ET as Model
-        model = Model(D, H, Hprime, gamma, comm=comm)
-        gt = {'W': bars, 'pi': 2. / H, 'sigma': 1.0}
-    elif a.model == "mmca":
-        from prosper_amd.em.camodels.mmca_et import MMCA_ET as Model
-        model = Model(D, H, Hprime, gamma, comm=comm)
-        gt = {'W': 10 * generate_bars_dict(H, neg_bars=True), 'pi': 2. / H, 'sigma': 1.0}
-    elif a.model == "dsc":
-        from prosper_amd.em.camodels.dsc_et import DSC_ET as Model
-        model = Model(D, H, Hprime, gamma, states=np.array([-1., 0., 1.]), comm=comm)
-        gt = {'W': bars, 'pi': np.array([1. / H, 1 - 2. / H, 1. / H]), 'sigma': 1.0}
-    elif a.model == "tsc":
-        from prosper_amd.em.camodels.tsc_et import TSC_ET as Model
-        model = Model(D, H, Hprime, gamma, comm=comm)
-        gt = {'W': bars, 'pi': 2. / H, 'sigma': 1.0}
-    elif a.model == "mog":     # examples/barstests/param-bars-mog.py of the reference: diagonal covariances
-        from prosper_amd.em.mixturemodels.MoG import MoG
-        model = MoG(D, H, sigmas_sq_type='diagonal', comm=comm)
-        gt = {'W': bars, 'pies': np.ones(H) / H, 'sigmas_sq': np.ones((H, D))}
-    elif a.model == "mop":     # param-bars-mop.py: A = nan (no normalisation)
-        from prosper_amd.em.mixturemodels.MoP import MoP
-        model = MoP(D, H, comm=comm)
-        gt = {'W': bars, 'pies': np.ones(H) / H}
-    else:
-        from prosper_amd.em.camodels.gsc_et import GSC as Model
-        model = Model(D, H, Hprime, gamma, 'scalar', comm=comm)
-        gt = {'W': bars / 10., 'pi': np.full(H, 2. / H), 'mu': np.full(H, 5.0), 'psi_sq': np.eye(H),
-              'sigma_sq': 1.0}
+    model, gt = build(a.model, a.size, 5, 3, comm)
+    H = 2 * a.size
 
     first, last = parallel.stride_data(a.N, comm=comm)
     my_data = model.generate_data(gt, last - first)
@@ -91,7 +116,9 @@ def main():
     heldout = None
     if a.heldout > 0:
         hf, hl = parallel.stride_data(a.heldout, comm=comm)
-        heldout = {'y': model.generate_data(gt, hl - hf)['y']}
+        drawn = model.generate_data(gt, hl - hf)
+        heldout = {'y': drawn['y']}
+        clean = noiseless_mean(a.model, gt, drawn)
 
     anneal = LinearAnnealing(a.steps)
     anneal['T'] = [(0, 2.), (.7, 1.)]
@@ -132,6 +159,19 @@ def main():
             if comm.rank == 0:
                 print("held-out log-likelihood per datapoint of the learned parameters: truncated bound %.6f, exact %.6f, "
                       "difference %.3e" % (learned, exact, exact - learned))
+        if a.reconstruct:
+            y = np.asarray(heldout['y'], dtype=np.float64)
+            sq = lambda x: float(((np.asarray(x) - clean) ** 2).sum())
+            # the posterior mean over a wider truncated state set than training uses (H' = 7, gamma = 5, the reference's
+            # settings for inference on the bars): a datapoint with more than gamma bars has no state near it otherwise,
+            # and one missed bar of height 10 costs more than the noise of the whole datapoint
+            rmodel = model if a.model in ("mog", "mop") else build(a.model, a.size, min(H, 7), min(H, 5), comm)[0]
+            sums = comm.allreduce(np.array([sq(y), sq(rmodel.reconstruct(dict(em.lparams), heldout)),
+                                            sq(rmodel.reconstruct(dict(gt), heldout)), float(y.size)]))
+            if comm.rank == 0:
+                print("held-out mean squared error against the noiseless data (%d datapoints): noisy data %.4f, reconstruction "
+                      "with the learned parameters %.4f, with the generating parameters %.4f"
+                      % (a.heldout, sums[0] / sums[3], sums[1] / sums[3], sums[2] / sums[3]))
 
 
 if __name__ == "__main__":

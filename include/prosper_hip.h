@@ -879,6 +879,41 @@ int pm_loglik_exact_gsc_f64(const double *Y, int64_t ldy, const double *P, const
                             const double *M, const double *Psi, const double *mu, const double *logp, double cst, int64_t N,
                             int64_t D, int64_t H, double *rows_out, double *work, double *total, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Posterior-mean reconstruction (reconstruct_kernels.hip)
+ * ---------------------------------------------------------------------------------------
+ * yhat_n = sum_{s in K_n} q_n(s) ybar(s), q_n(s) = exp(a logpj[n,s] + o_s - lse_n), over exactly the states whose log-joints
+ * an E-step pass left in logpj (N, ld >= K).  No atomics: every output element is written by one lane and the sums over a
+ * row's states run in a fixed order, so both builds return the same bits and a row's value does not depend on the others.
+ * Every entry checks its arguments before it touches a device (PM_EINVAL: null pointer, N < 0, short leading dimension,
+ * inconsistent layout; PM_ERANGE: past a kernel's limit); N == 0 launches nothing.
+ *
+ * pm_gemm_nt_rows_f64: C = A . B^T as pm_gemm_nt_f64, but as ONE launch of one kernel with the whole K range per tile (no
+ * K-slices, no second tile shape for a ragged last round): a row of C depends on its row of A and on B alone. */
+int pm_gemm_nt_rows_f64(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t M,
+                        int64_t N, int64_t K, void *stream);
+/* Posterior expectation of the latents from a log-joint row.  Columns of logpj: [single_off, single_off + nblocks H) the
+ * one-cause blocks -- in block c latent h takes the value block_values_host[c] (HOST memory, nblocks <= 8 values; BSC: {1},
+ * DSC: the non-zero values in order) --, [multi_off, multi_off + S) the table states -- in state s the latent at candidate
+ * position j, cand[n, j], takes state_vals[s * Hprime + j] (S x Hprime doubles, device); a latent held by two positions (TSC)
+ * receives both --; any other column below K (the null state) carries weight only.  lse: the rows' log-sum-exp where the
+ * E-step left it (then a == 1 and col_offset == NULL), or NULL: a maximum pass and a sum pass over a logpj + col_offset (K
+ * values or NULL), NaN for a row with a NaN entry.  out (N, ldo >= out_cols >= H): out[n, h] = E[s_h | y_n] for h < H, 1 in
+ * column ones_col (-1: none; else H <= ones_col < out_cols: the column that carries mu through the product) and 0 in the
+ * other columns up to out_cols.  With single_off = 0, nblocks = 1, the value 1 and S = 0 this is the row softmax of
+ * a X + o: a mixture's responsibilities.  Hprime <= PM_MAX_HPRIME. */
+int pm_recon_expect_f64(const double *logpj, int64_t ld, const double *lse, double a, const double *col_offset,
+                        const int32_t *cand, const double *state_vals, const double *block_values_host, int64_t N, int64_t H,
+                        int64_t Hprime, int64_t K, int64_t single_off, int64_t nblocks, int64_t multi_off, int64_t S,
+                        double *out, int64_t ldo, int64_t out_cols, int64_t ones_col, void *stream);
+/* MCA (signed_w = 0) / MMCA (1): Yhat[n, d] += sum_s q_n(s) Wbar_d(s) over the S multi-cause states (columns 1 + H + s of
+ * logpj, ld >= 1 + H + S; masks over the candidate positions as pm_mca_estep_f64), Wbar_d(s) = (sum_{j in s} Wrho[cand[n,j],
+ * d])^inv_rho (signed: sign(t) |t|^inv_rho) with the E-step's power functions; lse as above (a = 1).  The null and one-cause
+ * part of Yhat is pm_recon_expect_f64 + pm_gemm_nt_rows_f64 against W.  D <= 1024, Hprime <= PM_MAX_HPRIME. */
+int pm_recon_mca_f64(const double *logpj, int64_t ld, const double *lse, const int32_t *cand, const uint16_t *state_masks,
+                     const double *Wrho, double inv_rho, int signed_w, int64_t N, int64_t H, int64_t D, int64_t Hprime,
+                     int64_t S, double *Yhat, int64_t ldy, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

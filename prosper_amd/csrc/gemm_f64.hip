@@ -885,6 +885,22 @@ extern "C" int pm_gemm_nt_f64(const double *A, int64_t lda, const double *B, int
     return (int)hipGetLastError();
 }
 
+// The same product as ONE launch of ONE kernel with the whole K range per tile: no K-slices, no second tile shape for the
+// ragged last round.  Every element of C is written once, in a summation order that depends on K alone -- a row of C is a
+// function of its row of A and of B only, in both builds (reconstruct(), DESIGN 4.14: Yhat = E[s] W^T).
+extern "C" int pm_gemm_nt_rows_f64(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc,
+                                   int64_t M, int64_t N, int64_t K, void *stream) {
+    if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || lda < K || ldb < K || ldc < N) return PM_EINVAL;
+    if (M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return PM_ERANGE;
+    const bool al = aligned16(A) && aligned16(B) && (lda % 2 == 0) && (ldb % 2 == 0) && (K % 2 == 0);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (al && K % DK == 0)
+        launch_nt_dma(A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, 1, s);
+    else
+        launch_nt_mt<4>(al, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, s);
+    return (int)hipGetLastError();
+}
+
 extern "C" int pm_gemm_tn_acc_f64(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc,
                                   int64_t M, int64_t N, int64_t K, void *stream) {
     return pm_gemm_tn_acc_gated_f64(A, lda, B, ldb, C, ldc, M, N, K, nullptr, stream);

@@ -602,6 +602,10 @@ class DeviceCAModel(CAModel):
         # small outputs (Gram matrices, the H x H x D solve products): the deterministic one-workgroup-per-tile kernel --
         # every rank holding the same operands gets the same bits, and no zero fill + K-slice atomics
         fn = "pm_gemm_nt_small_f64" if (M <= 512 and N <= 512) else "pm_gemm_nt_f64"
+        if getattr(self, "_rows_gemm", False):
+            # reconstruct: one kernel whatever the shape, so that a row of the product is the same bits in a
+            # whole array and in a shard of it (the two above pick kernels and K-slices by the number of rows)
+            fn = "pm_gemm_nt_rows_f64"
         # (a matrix of ONE row reports whatever stride its history left -- (D, 1).t().contiguous() keeps (1, 1): H = 1 -- and
         # any leading dimension >= its row length describes it)
         ld = lambda t, cols: t.stride(0) if t.shape[0] > 1 else max(int(t.stride(0)), int(cols))
@@ -1198,6 +1202,108 @@ class DeviceCAModel(CAModel):
         for v in parts:
             out += v
         return out
+
+    # ---- posterior-mean reconstruction --------------------------------------------------------------------
+    def _recon_layout(self, model_params):
+        """Per model: what ``reconstruct`` needs beside the E-step's log-joints -- ``params`` (the parameters the E-step is
+        run with), ``blocks`` (the latent value of every block of H one-cause columns, starting at column ``soff``),
+        ``table`` ((S, Hprime) latent values per candidate position of the table states, starting at column ``moff``; None:
+        no table term in E[s]), ``W`` (D, H) and ``mu`` (D,) or None of the mean ybar(s) = mu + W s; ``mca``: True when the
+        multi-cause states' mean is the rho-combination instead (pm_recon_mca_f64)."""
+        raise NotImplementedError("%s has no reconstruct" % type(self).__name__)
+
+    def _recon_expect(self, X, K, N, a=1.0, lse=None, off=None, cand=None, table=None, blocks=(1.0,), soff=0, moff=0,
+                      ones=False):
+        """pm_recon_expect_f64 into an (N, Kp) workspace, Kp = H (+ 1 for the column of ones) padded to a multiple of 8 with
+        zero columns: the K range of the product that follows."""
+        H = self.H
+        Kp = (H + (1 if ones else 0) + 7) // 8 * 8
+        es = self._buf("recon_es", (N, Kp))
+        S = 0 if table is None else int(table.shape[0])
+        tab_d = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float64)).to(self.device) if S else None
+        if lse is not None and not (torch.is_tensor(lse) and lse.dtype == torch.float64 and tuple(lse.shape) == (N,)
+                                    and lse.is_contiguous() and a == 1.0 and off is None):
+            lse = None
+        bv = (ctypes.c_double * 8)(*([float(v) for v in blocks] + [0.0] * (8 - len(blocks))))
+        ld = X.stride(0) if N > 1 else max(int(X.stride(0)), K)
+        self._call("recon_expect", "pm_recon_expect_f64", _ptr(X), ld, _ptr(lse), ctypes.c_double(a), _ptr(off),
+                   _ptr(cand) if S else None, _ptr(tab_d), bv, N, H, self.Hprime if S else 0, K, soff, len(blocks), moff, S,
+                   _ptr(es), Kp, Kp, H if ones else -1, self._stream())
+        return es
+
+    def _recon_product(self, es, ld, cols, W, mu=None):
+        """Yhat (N, D) = es[:, :cols] . [W | mu | 0]^T through pm_gemm_nt_rows_f64 (``es`` carries a column of ones at H when
+        ``mu`` is given)."""
+        N, D, H = es.shape[0], self.D, self.H
+        Wp = np.zeros((D, cols))
+        Wp[:, :H] = np.asarray(W, dtype=np.float64)
+        if mu is not None:
+            Wp[:, H] = np.asarray(mu, dtype=np.float64).reshape(-1)
+        Wd = torch.from_numpy(Wp).to(self.device)
+        out = torch.empty((N, D), dtype=torch.float64, device=self.device)
+        self._call("recon_gemm", "pm_gemm_nt_rows_f64", _ptr(es), ld, _ptr(Wd), cols, _ptr(out), D, N, D, cols,
+                   self._stream())
+        return out
+
+    def _reconstruct(self, model_params, my_data, N):
+        """The (N, D) device tensor of ``reconstruct`` for the models whose E-step leaves (N, K) log-joints."""
+        lay = self._recon_layout(model_params)
+        mp = lay["params"]
+        data = self.select_Hprimes(mp, my_data)
+        out = self.E_step(LoglikPoint(), mp, data)['logpj']
+        cand = self._device_candidates(data['candidates'], N)
+        lp = out.tensor
+        K = lp.shape[1]
+        mca = bool(lay.get("mca"))
+        # (the rows' log-sum-exp is formed again by the kernels, not taken from the E-step: the fused E-step kernels reduce a
+        # row in an order that depends on the tile shape its position in the shard gets, so their ``lse`` differs in the last
+        # bit between a row of a whole array and the same row of a shard -- and a row of Yhat must not)
+        lse = None
+        mu = lay.get("mu")
+        if mu is not None and not np.any(np.asarray(mu)):
+            mu = None
+        es = self._recon_expect(lp, K, N, lse=lse, cand=cand, table=lay.get("table"), blocks=lay["blocks"],
+                                soff=lay["soff"], moff=lay["moff"], ones=mu is not None)
+        Yhat = self._recon_product(es, es.shape[1], es.shape[1], lay["W"], mu)
+        if mca and self.no_states:
+            par = self._tables_for(mp['W'], 1.0, self._resident(my_data['y']))
+            ld = lp.stride(0) if N > 1 else max(int(lp.stride(0)), K)
+            self._call("recon_mca", "pm_recon_mca_f64", _ptr(lp), ld, None, _ptr(cand), _ptr(self._masks()),
+                       _ptr(par["Wrho"]), ctypes.c_double(1. / par["rho"]), int(bool(self.signed_w)), N, self.H, self.D,
+                       self.Hprime, self.no_states, _ptr(Yhat), self.D, self._stream())
+        return Yhat
+
+    def reconstruct(self, model_params, my_data, device=False):
+        """Posterior-mean denoising: yhat_n = sum_{s in K_n} q_n(s) ybar(s; Theta), q_n(s) = p(s, y_n | Theta) / sum_{s' in K_n}
+        p(s', y_n | Theta), for ``my_data['y']`` (host array, torch tensor or DeviceArray): the model's estimate of the
+        noiseless data.  K_n and p are exactly those of ``log_likelihood``: the state set the E-step scores
+        for y_n, the full generative joint, at T = 1 with no prior annealing, data truncation, partial data or parameter
+        noise; ybar(s) is the mean of the data given the state (mu + W s for the linear models, the
+        rho-combination the E-step evaluates for MCA / MMCA, W_s E[z_s | s, y_n] for GSC).  No weight is dropped or
+        thresholded.  At H' = gamma = H this is the exact posterior mean, the minimum-mean-square estimate.  TSC's candidates
+        may repeat a latent (tsc_et.py:142-213): such a row holds pseudo-states, whose mean counts the latent at both
+        positions, as the E-step's energy does; the exactness does not hold for that row.
+
+        Returns this rank's (my_N, D) float64 rows in datapoint order as a NumPy array, or with ``device=True`` as a
+        ``DeviceArray`` left on the device; there is no collective.  A NaN in a data row makes that row NaN and no other.
+        ``model_params``, the training shard's residency, the records the last M-step left and Hprime / gamma stay as they
+        were: a call between two EM steps does not change the training trajectory.  The results do not depend on
+        ``deterministic``.  Runs the E-step kernels, pm_recon_* and pm_gemm_nt_rows_f64 on the device."""
+        y = my_data['y']
+        N = int(y.shape[0])
+        if N == 0:
+            return DeviceArray(torch.empty((0, self.D), dtype=torch.float64, device=self.device)) if device \
+                else np.empty((0, self.D))
+        saved = self._eval_begin()
+        try:
+            # every product of the pass through the one-kernel GEMM, on parameter products of its own: a row of the result
+            # is a function of that row of the data and of the parameters alone (attributes of the evaluation only)
+            self._par, self._rows_gemm = {}, True
+            Yhat = self._reconstruct(dict(model_params), {'y': y}, N)
+            return DeviceArray(Yhat) if device else Yhat.cpu().numpy()
+        finally:
+            self._par = {}
+            self._eval_end(saved)
 
     def _log_likelihood_exact(self, model_params, my_data, per_datapoint):
         saved = self._eval_begin()

@@ -615,6 +615,17 @@ class BSC_ET(DeviceCAModel):
         c = self.H * np.log(1. - pies) - 0.5 * self.D * np.log(2 * _PI * sigma ** 2)
         return self._loglik_estep(model_params, my_data), 1.0, c
 
+    def _recon_layout(self, model_params):
+        """reconstruct: columns [null ; H one-cause states ; S multi-cause states over the candidates], binary
+        latents, ybar(s) = mu + W s (mu when the parameters carry it).  The log-joints come from the general E-step kernels
+        (pm_bsc_select_f64 / pm_bsc_estep_f64, one pass per row whatever its place in the shard) and not from the fused
+        tile kernels, whose main and tail launches round a row's energies differently: a row of the result must not depend
+        on how many rows travel with it (an attribute of the evaluation only: _eval_end restores the model's)."""
+        self.use_rows16 = False
+        return {"params": model_params, "blocks": (1.0,), "soff": 1, "moff": 1 + self.H,
+                "table": self.state_matrix if self.no_states else None, "W": model_params['W'],
+                "mu": model_params.get('mu')}
+
     def _loglik_exact(self, model_params):
         """exact log_likelihood: states {0,1}^H, log prior |s| log pi + (H - |s|) log(1 - pi), y ~ N(mu + W s,
         sigma^2 I) (mu when given)."""

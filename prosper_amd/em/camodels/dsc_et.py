@@ -234,8 +234,10 @@ class DSC_ET(DeviceCAModel):
         H, K, K0 = self.H, self.K, self._K_0
         pre_F = np.empty(1 + (K - 1) * H + self.no_states)
         l_pis = np.zeros(self.no_states)
-        for i in range(K):
-            l_pis += self.state_abs[i] * np.log(pi[i])
+        with np.errstate(divide='ignore', invalid='ignore'):
+            for i in range(K):
+                # (a value of zero prior: -inf for the states that use it, nothing -- not 0 * -inf = NaN -- for the others)
+                l_pis += np.where(self.state_abs[i] > 0, self.state_abs[i] * np.log(pi[i]), 0.0)
         pre_F[0] = H * np.log(pi[K0])
         c = 0
         for state in range(K):
@@ -309,6 +311,13 @@ class DSC_ET(DeviceCAModel):
         c = - D/2 log(2 pi sigma^2), exactly the reference's ``L`` (dsc_et.py:845-869) and a = 1."""
         sigma = float(model_params['sigma'])
         return self._loglik_estep(model_params, my_data), 1.0, -0.5 * self.D * np.log(2 * np.pi * sigma ** 2)
+
+    def _recon_layout(self, model_params):
+        """reconstruct: columns [null ; one block of H one-cause states per non-zero value, in the order of
+        ``states`` ; S multi-cause states], ``state_matrix`` holds the latent values themselves; ybar(s) = W s."""
+        blocks = tuple(float(v) for k, v in enumerate(self.states) if k != self._K_0)
+        return {"params": model_params, "blocks": blocks, "soff": 1, "moff": 1 + (self.K - 1) * self.H,
+                "table": self.state_matrix if self.no_states else None, "W": model_params['W'], "mu": None}
 
     def _loglik_exact(self, model_params):
         """exact log_likelihood: states values^H (``states``), log prior sum_h log pi[k_h] (a value of zero

@@ -537,6 +537,27 @@ class GSC(DeviceCAModel):
         c = float(np.log(1. - pi).sum()) - 0.5 * self.D * np.log(2 * np.pi) - 0.5 * logdet
         return logpj.tensor, 0.5, c
 
+    def _reconstruct(self, model_params, my_data, N):
+        """reconstruct: yhat_n = W E[s z | y_n] = sum_s q_n(s) W_s kappa_s(y_n), kappa_s = mu_s + Lambda_s^-1
+        W_s^T Sigma^-1 (y_n - W_s mu_s) = E[z_s | s, y_n].  The E-step pass returns xpt_sz = sum_s w_n(s) kappa_s with the
+        reference's weights exp(beta (lp + prior)), lp carrying the Gaussian terms WITHOUT the 1/2 (gsc_et.py:341-354): at
+        beta = 1/2 with every logit doubled (``_lpi_scale``, as ``_loglik_terms``) the weight is exp(lp / 2 + prior), the
+        generative model's, and kappa_s does not depend on beta.  Then Yhat = xpt_sz W^T.  The pass floors every state's
+        weight at DBL_MIN as the reference does (:355-356): visible only in a row whose weights all underflow.  A noise
+        covariance that is not positive definite: every row NaN."""
+        sig = np.asarray(model_params['sigma_sq'], dtype=np.float64)
+        if (np.linalg.eigvalsh(0.5 * (sig + sig.T)).min() <= 0) if sig.ndim == 2 else not np.all(sig > 0):
+            return torch.full((N, self.D), float("nan"), dtype=torch.float64, device=self.device)
+        self._lpi_scale = 2.0          # (an attribute of the evaluation only: _eval_end restores the model's)
+        self._require_scalar()
+        res = self._resident(my_data['y'])
+        _, _, xsz, _ = self._run(2.0, model_params, res, None)
+        W = torch.from_numpy(np.ascontiguousarray(model_params['W'], dtype=np.float64)).to(self.device)
+        out = torch.empty((N, self.D), dtype=torch.float64, device=self.device)
+        self._call("recon_gemm", "pm_gemm_nt_rows_f64", _ptr(xsz), max(int(xsz.stride(0)), self.H), _ptr(W), self.H,
+                   _ptr(out), self.D, N, self.D, self.H, self._stream())
+        return out
+
     def _loglik_exact(self, model_params):
         """exact log_likelihood: supports {0,1}^H, log prior sum_h s_h log pi_h + (1 - s_h) log(1 - pi_h),
         y ~ N(W_s mu_s, Sigma + W_s Psi_s W_s^T).  The kernel takes the Sigma^-1-whitened products P = Sigma^-1 W and

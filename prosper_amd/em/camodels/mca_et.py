@@ -259,6 +259,15 @@ class MCA_ET(DeviceCAModel):
         c = self.H * np.log(1. - pies) - 0.5 * self.D * np.log(2 * _PI * sigma ** 2)
         return self._loglik_estep(model_params, my_data), 1.0, c
 
+    def _recon_layout(self, model_params):
+        """reconstruct: the mean of ``_loglik_terms``' model -- W_h for a one-cause state (the E-step's energy
+        uses W itself there), the rho-combination Wbar(s) at T = 1 for a multi-cause state (pm_recon_mca_f64), 0 for the null
+        state; W clamped by ``check_params`` on a private copy."""
+        model_params['W'] = np.array(model_params['W'], dtype=np.float64, copy=True)
+        model_params = self.check_params(model_params)
+        return {"params": model_params, "blocks": (1.0,), "soff": 1, "moff": 1 + self.H, "table": None,
+                "W": model_params['W'], "mu": None, "mca": True}
+
     def _loglik_exact(self, model_params):
         """exact log_likelihood: states {0,1}^H, y ~ N(Wbar(s), sigma^2 I) with the rho-combination of
         ``_loglik_terms`` at T = 1 (MMCA: signed), W clamped by ``check_params`` on a private copy, Wbar(0) = 0."""

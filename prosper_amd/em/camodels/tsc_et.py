@@ -267,6 +267,13 @@ class TSC_ET(DeviceCAModel):
         c = (self.H - self.Hprime) * np.log(1. - pies) - 0.5 * self.D * np.log(2 * np.pi * sigma ** 2)
         return self._loglik_estep(model_params, my_data), 1.0, c
 
+    def _recon_layout(self, model_params):
+        """reconstruct: one column per row of the ternary state table (values -1 / 0 / +1 per candidate
+        POSITION), no null / one-cause prefix; ybar(s) = sum_j s_j W_{cand_j}: a latent that two positions hold is counted at
+        both, as in the E-step's energy."""
+        return {"params": model_params, "blocks": (), "soff": 0, "moff": 0, "table": self.state_matrix,
+                "W": model_params['W'], "mu": None}
+
     def _loglik_exact(self, model_params):
         """exact log_likelihood: states {-1,0,1}^H, log prior nz(s) log(pi / 2) + (H - nz(s)) log(1 - pi)."""
         pi = float(model_params['pi'])

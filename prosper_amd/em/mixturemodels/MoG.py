@@ -115,22 +115,41 @@ class MoG(DeviceMixture, MixtureModel):
             c[(sig <= 0).any(1)] = np.nan
         return self._estep_dev(my_y, -beta, c, lp, Bl=Bl, Bq=Bq)
 
-    def _loglik_rows(self, model_params, res, rows):
-        """log_likelihood: rows[n] = log sum_h pies_h N(y_n; w_h, Sigma_h).  Diagonal: the scores kernel's log-likelihood
-        mode with coef = -1/2, c_h = sum_d w^2/sigma^2 + sum_d log sigma^2 and lp_h = log pies_h - D/2 log(2 pi).  Full:
-        ``_loglik_full``."""
+    def _proper_terms(self, model_params):
+        """The arguments of the scores kernel for the proper diagonal density: (S[n,h] + c_h) coef + lp_h = log pies_h +
+        log N(y_n; w_h, diag sigma_h^2), coef = -1/2, c_h = sum_d w^2/sigma^2 + sum_d log sigma^2, lp_h = log pies_h -
+        D/2 log(2 pi)."""
         W = np.asarray(model_params['W'], dtype=np.float64)
         sig = np.asarray(model_params['sigmas_sq'], dtype=np.float64)
         pies = np.asarray(model_params['pies'], dtype=np.float64)
-        if self.sigmas_sq_type == 'full':
-            return self._loglik_full(res, rows, W, sig, pies)
         with np.errstate(all='ignore'):
             lp = np.log(pies) - 0.5 * self.D * np.log(2 * np.pi)
             Bq = 1. / sig
             Bl = -2. * W.T * Bq
             c = np.sum(W.T ** 2 * Bq, 1) + np.sum(np.log(sig), 1)
             c[(sig <= 0).any(1)] = np.nan
-        self._loglik_scores(res, rows, -0.5, c, lp, Bl, Bq=Bq)
+        return {"coef": -0.5, "c": c, "lp": lp, "Bl": Bl, "Bq": Bq}
+
+    def _loglik_rows(self, model_params, res, rows):
+        """log_likelihood: rows[n] = log sum_h pies_h N(y_n; w_h, Sigma_h).  Diagonal: the scores kernel's log-likelihood
+        mode with coef = -1/2, c_h = sum_d w^2/sigma^2 + sum_d log sigma^2 and lp_h = log pies_h - D/2 log(2 pi).  Full:
+        ``_loglik_full``."""
+        if self.sigmas_sq_type == 'full':
+            return self._loglik_full(res, rows, np.asarray(model_params['W'], dtype=np.float64),
+                                     np.asarray(model_params['sigmas_sq'], dtype=np.float64),
+                                     np.asarray(model_params['pies'], dtype=np.float64))
+        t = self._proper_terms(model_params)
+        self._loglik_scores(res, rows, t["coef"], t["c"], t["lp"], t["Bl"], Bq=t["Bq"])
+
+    def _recon_scores(self, model_params, res):
+        """reconstruct: ``(X, a, offsets)`` with r_nh = softmax_h(a X[n,h] + o_h) the responsibilities of the
+        proper densities -- diagonal: the scores kernel's log-joints; full: the Mahalanobis terms of ``_loglik_full``."""
+        if self.sigmas_sq_type == 'full':
+            M, off_d = self._full_scores(res, np.asarray(model_params['W'], dtype=np.float64),
+                                         np.asarray(model_params['sigmas_sq'], dtype=np.float64),
+                                         np.asarray(model_params['pies'], dtype=np.float64))
+            return M, -0.5, off_d
+        return self._proper_logpj(res, self._proper_terms(model_params)), 1.0, None
 
     def log_p_y(self, model_params, my_y, beta=1.0):
         """log_p_y of the reference (MoG.py:231-281): the scores part of ``posterior`` (with pies = 1), an ndarray."""

@@ -100,10 +100,9 @@ class MoP(DeviceMixture, MixtureModel):
                 logW = np.where(np.isneginf(logW), 0.0, logW)
         return self._estep_dev(my_y, beta, c, lp, Bl=logW, scaled=raw)
 
-    def _loglik_rows(self, model_params, res, rows):
-        """log_likelihood: rows[n] = log sum_h pies_h prod_d Poisson(x_nd; w_dh) with x = y (A nan) or x = s y + 1 (A set,
-        the data the E-step sees): the scores kernel's log-likelihood mode with coef = 1, Bl = log W^T on the scaled rows,
-        c_h = sum_d log w_dh (the "+1" of x, A set) - sum_d w_dh, lp = log pies, and the row term - sum_d lgamma(x_nd + 1)."""
+    def _proper_terms(self, model_params):
+        """The arguments of the scores kernel for the Poisson pmf on the data the E-step sees: coef = 1, Bl = log W^T on the
+        scaled rows, c_h = sum_d log w_dh (the "+1" of x, A set) - sum_d w_dh, lp = log pies."""
         W = np.asarray(model_params['W'], dtype=np.float64)
         normed = not np.isnan(self.A)
         with np.errstate(all='ignore'):
@@ -117,7 +116,19 @@ class MoP(DeviceMixture, MixtureModel):
                 # a zero rate: pmf 1 at a zero count, 0 otherwise -- y log w with log w = -1e300 gives exactly that weight
                 # (0 * -inf would be NaN)
                 logW = np.where(np.isneginf(logW), -1e300, logW)
-        self._loglik_scores(res, rows, 1.0, c, lp, logW, pmf=1, yoff=1.0 if normed else 0.0)
+        return {"coef": 1.0, "c": c, "lp": lp, "Bl": logW, "Bq": None, "pmf": 1, "yoff": 1.0 if normed else 0.0}
+
+    def _loglik_rows(self, model_params, res, rows):
+        """log_likelihood: rows[n] = log sum_h pies_h prod_d Poisson(x_nd; w_dh) with x = y (A nan) or x = s y + 1 (A set,
+        the data the E-step sees): the scores kernel's log-likelihood mode with coef = 1, Bl = log W^T on the scaled rows,
+        c_h = sum_d log w_dh (the "+1" of x, A set) - sum_d w_dh, lp = log pies, and the row term - sum_d lgamma(x_nd + 1)."""
+        t = self._proper_terms(model_params)
+        self._loglik_scores(res, rows, t["coef"], t["c"], t["lp"], t["Bl"], pmf=t["pmf"], yoff=t["yoff"])
+
+    def _recon_scores(self, model_params, res):
+        """reconstruct: the log-joints log pies_h + log Poisson(x_n; w_h) up to the row term
+        - sum_d lgamma(x_nd + 1), which the responsibilities do not see."""
+        return self._proper_logpj(res, self._proper_terms(model_params), scaled=True), 1.0, None
 
     def log_p_y(self, model_params, my_y, beta=1.0):
         """log_p_y of the reference (MoP.py:193-232): the scores part of ``posterior`` (with pies = 1), an ndarray;

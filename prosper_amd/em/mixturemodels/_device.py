@@ -133,10 +133,11 @@ class DeviceMixture(object):
         _lib.call("pm_mix_loglik_f64", _ptr(Y), D, _ptr(res["rs"]) if pmf else None, _ptr(Bq_d), _ptr(Bl_d), D, _ptr(c_d),
                   float(coef), _ptr(lp_d), Y.shape[0], D, H, int(pmf), float(yoff), _ptr(rows), self._stream())
 
-    def _loglik_full(self, res, rows, W, sig, pies):
-        """MoG full: pm_mix_chol_f64 -> L^-1, log det per component; pm_mix_maha_f64 -> |L^-1 (y - w)|^2 (N, H);
-        pm_rows_lse_f64 with a = -1/2 and the column offsets log pies_h - 1/2 log det_h - D/2 log(2 pi).  A component the
-        Cholesky rejects gets a zero B in mode 1 (S = 0) and offset NaN (pies_h > 0) or -inf (pies_h = 0)."""
+    def _full_scores(self, res, W, sig, pies):
+        """MoG full: pm_mix_chol_f64 -> L^-1, log det per component; pm_mix_maha_f64 -> M[n,h] = |L^-1 (y - w)|^2 (N, H) and
+        the column offsets log pies_h - 1/2 log det_h - D/2 log(2 pi), so that log pies_h N(y_n; w_h, Sigma_h) = - M / 2 +
+        offset.  A component the Cholesky rejects gets a zero B in mode 1 (M = 0) and offset NaN (pies_h > 0) or -inf
+        (pies_h = 0).  Returns the device pair (M, offsets)."""
         H, D = self.H, self.D
         Y = res["Y"]
         N = Y.shape[0]
@@ -161,9 +162,70 @@ class DeviceMixture(object):
         M = self._buf("ll_maha", (N, H))
         W_d, off_d = self._dev(W.T), self._dev(off)
         _lib.call("pm_mix_maha_f64", _ptr(Y), D, _ptr(W_d), _ptr(B), _ptr(mode_d), N, D, H, _ptr(M), H, st)
+        return M, off_d
+
+    def _loglik_full(self, res, rows, W, sig, pies):
+        """MoG full: ``_full_scores``, then pm_rows_lse_f64 with a = -1/2 and the column offsets."""
+        N = res["Y"].shape[0]
+        M, off_d = self._full_scores(res, W, sig, pies)
         work = torch.empty(int(_lib.load().pm_rows_lse_work_len(N)), dtype=torch.float64, device=self.device)
         total = torch.empty(1, dtype=torch.float64, device=self.device)
-        _lib.call("pm_rows_lse_f64", _ptr(M), H, N, H, -0.5, _ptr(off_d), _ptr(rows), _ptr(work), _ptr(total), st)
+        _lib.call("pm_rows_lse_f64", _ptr(M), self.H, N, self.H, -0.5, _ptr(off_d), _ptr(rows), _ptr(work), _ptr(total),
+                  self._stream())
+
+    # ---- posterior-mean reconstruction (DESIGN 4.14) ------------------------------------------------------------------
+    def _proper_logpj(self, res, t, scaled=False):
+        """pm_mix_scores_f64 with the proper densities' terms ``t`` (``_proper_terms``): the (N, H) device log-joints
+        (S + c_h) coef + lp_h.  (The posteriors the kernel writes beside them are the reference's un-stabilised ones and
+        are not used.)"""
+        Y, H, D = res["Y"], self.H, self.D
+        N = Y.shape[0]
+        logpj = self._buf("recon_logpj", (N, H))
+        post = self._buf("recon_post", (N, H))
+        Bq_d = self._dev(t["Bq"]) if t.get("Bq") is not None else None
+        Bl_d, c_d, lp_d = self._dev(t["Bl"]), self._dev(t["c"]), self._dev(t["lp"])
+        _lib.call("pm_mix_scores_f64", _ptr(Y), D, _ptr(res["rs"]) if scaled else None, _ptr(Bq_d), _ptr(Bl_d), D, _ptr(c_d),
+                  float(t["coef"]), _ptr(lp_d), N, D, H, _ptr(logpj), _ptr(post), self._stream())
+        return logpj
+
+    def reconstruct(self, model_params, my_data, device=False):
+        """Posterior-mean denoising: yhat_n = sum_h r_nh W_h with the responsibilities r_nh = pies_h p(y_n | h) / sum_h'
+        pies_h' p(y_n | h') of the proper densities of ``log_likelihood`` (MoG with the 1/2; not the reference's E-step
+        quirk), for ``my_data['y']`` (host array, torch tensor or DeviceArray).  MoP: in the units of the data its E-step
+        sees -- x = y, or the normalised x = s y + 1 when ``A`` is set (W holds rates of x).
+
+        Returns this rank's (my_N, D) float64 rows as a NumPy array, or with ``device=True`` a ``DeviceArray`` left on the
+        device; no collective.  A NaN in a data row makes that row NaN and no other; a component with pies_h > 0 whose
+        covariance is not positive definite makes every row NaN.  ``model_params`` and the training shard are left as they
+        were.  The responsibilities are written as an (N, H) array by pm_recon_expect_f64 (a row softmax in a maximum and a
+        sum pass) and multiplied with W by pm_gemm_nt_rows_f64; H within pm_mix_scores_f64's bound for MoG diagonal / MoP."""
+        y = my_data['y']
+        N, H, D = int(y.shape[0]), self.H, self.D
+        if N == 0:
+            return DeviceArray(torch.empty((0, D), dtype=torch.float64, device=self.device)) if device else np.empty((0, D))
+        saved = dict(self.__dict__)
+        slot = saved.get("_eval_slot") or {"_data": {}, "_ws": {}}
+        self._data, self._ws = slot["_data"], slot["_ws"]
+        try:
+            res = self._resident(y)
+            X, a, off_d = self._recon_scores(dict(model_params), res)
+            Kp = (H + 7) // 8 * 8
+            r = self._buf("recon_r", (N, Kp))
+            one = (ctypes.c_double * 8)(1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+            st = self._stream()
+            _lib.call("pm_recon_expect_f64", _ptr(X), H, None, ctypes.c_double(a), _ptr(off_d), None, None, one, N, H, 0, H,
+                      0, 1, 0, 0, _ptr(r), Kp, Kp, -1, st)
+            Wp = np.zeros((D, Kp))
+            Wp[:, :H] = np.asarray(model_params['W'], dtype=np.float64)
+            W_d = self._dev(Wp)
+            out = torch.empty((N, D), dtype=torch.float64, device=self.device)
+            _lib.call("pm_gemm_nt_rows_f64", _ptr(r), Kp, _ptr(W_d), Kp, _ptr(out), D, N, D, Kp, st)
+            return DeviceArray(out) if device else out.cpu().numpy()
+        finally:
+            slot = {"_data": self._data, "_ws": self._ws}
+            self.__dict__.clear()
+            self.__dict__.update(saved)
+            self._eval_slot = slot
 
     # ---- E-step -------------------------------------------------------------------------------------------------------
     def _full_factors(self, sig):
