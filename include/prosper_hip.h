@@ -914,6 +914,51 @@ int pm_recon_mca_f64(const double *logpj, int64_t ld, const double *lse, const i
                      const double *Wrho, double inv_rho, int signed_w, int64_t N, int64_t H, int64_t D, int64_t Hprime,
                      int64_t S, double *Yhat, int64_t ldy, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Whole-image denoising by overlapping patches (patch_kernels.hip)
+ * ---------------------------------------------------------------------------------------
+ * The patch grid.  Along an axis of length L, patches of length p at stride s >= 1 start at 0, s, 2s, ... while start + p <=
+ * L, plus at L - p if the last of these is not L - p: every position is covered for every stride s <= p (and for s > p when
+ * L <= 2p; any other stride leaves positions between the regular starts uncovered and is refused below).
+ * pm_patches_count(L, p, s) is the number of starts (-1 for p > L, a non-positive argument or L > 2^30).  An image stack (B, Hi, Wi) -- row i of image
+ * b at image + (b Hi + i) ld -- with patches of ph x pw values has N = B nr nc patches, nr = count(Hi, ph, s), nc =
+ * count(Wi, pw, s), numbered row-major over (image, start row, start column); a patch is a row of D = ph pw values, element
+ * (a, b) at a pw + b.  The entries below work on the rows [n0, n0 + n) of the (N, D) patch matrix, handed over as the
+ * pointer to row n0, so that a caller walks an image in chunks and never holds the whole matrix.
+ *
+ * No entry holds an atomic or a branch on the build: both libraries return the same bits.  Every entry checks its arguments
+ * before it touches a device: PM_EINVAL for a null pointer, B, Hi, Wi, ph, pw or stride < 1, ph > Hi, pw > Wi, a stride that
+ * leaves pixels uncovered (stride > ph with Hi > 2 ph, or stride > pw with Wi > 2 pw), a leading
+ * dimension shorter than its row, n0 < 0, n < 0 or n0 + n > N; PM_ERANGE for Hi or Wi > 2^30 or D > 4096.  n == 0 launches
+ * nothing.
+ *
+ * pm_patches_extract_f64 / _f32 (the image's element type; f32 is converted exactly): out (n, ldo >= D) receives the patches.
+ * center != 0: means (n) receives each patch's mean and out the patch minus its mean.  The mean's summation order is fixed
+ * by D alone: with g the smallest power of two >= min(D, 64), partial sum l (l < g) adds the elements l, l + g, l + 2g, ...
+ * in ascending order starting from the first (a partial sum without elements is +0), the g partial sums are combined by
+ * butterflies v_l <- v_l + v_(l xor o) for o = g/2, g/4, ..., 1, and the result is divided by D once.  A patch's bits depend
+ * on the patch alone, not on n0, n or its position among the rows. */
+int64_t pm_patches_count(int64_t length, int64_t patch, int64_t stride);
+int pm_patches_extract_f64(const double *image, int64_t ldi, int64_t B, int64_t Hi, int64_t Wi, int64_t ph, int64_t pw,
+                           int64_t stride, int64_t n0, int64_t n, int center, double *out, int64_t ldo, double *means,
+                           void *stream);
+int pm_patches_extract_f32(const float *image, int64_t ldi, int64_t B, int64_t Hi, int64_t Wi, int64_t ph, int64_t pw,
+                           int64_t stride, int64_t n0, int64_t n, int center, double *out, int64_t ldo, double *means,
+                           void *stream);
+/* acc (B, Hi, Wi; row stride lda >= Wi), a running sum the caller zeroes once: every pixel receives, ONE ADDITION AT A TIME IN
+ * ASCENDING PATCH NUMBER, acc <- acc + est[k - n0, e] (means == NULL) or acc <- acc + (est[k - n0, e] + means[k - n0]) of the
+ * patches k in [n0, n0 + n) that cover it (e: the pixel's element of patch k).  A pixel is owned by one lane (gather form); a
+ * workgroup stages the estimate rows that reach its tile of pixels in LDS and reads them as rows.  Called with ascending,
+ * disjoint ranges that together cover [0, N), the sequence of additions of a pixel -- and so the sum's bits -- is the same
+ * for every split into ranges. */
+int pm_patches_accumulate_f64(const double *est, int64_t lde, const double *means, int64_t n0, int64_t n, double *acc,
+                              int64_t lda, int64_t B, int64_t Hi, int64_t Wi, int64_t ph, int64_t pw, int64_t stride,
+                              void *stream);
+/* out[b, i, j] = acc[b, i, j] / cover(i, j), one IEEE division; cover: the number of patches of the grid that contain the
+ * pixel, computed from the grid rule.  out may be acc. */
+int pm_patches_finish_f64(const double *acc, int64_t lda, double *out, int64_t ldo, int64_t B, int64_t Hi, int64_t Wi,
+                          int64_t ph, int64_t pw, int64_t stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,11 @@ SIGNATURES = {
                                       i64, c_dp, i64, i64, i64, c_dp]),
     "pm_recon_mca_f64": (C.c_int, [c_dp, i64, c_dp, c_dp, c_dp, c_dp, C.c_double, C.c_int, i64, i64, i64, i64, i64, c_dp, i64,
                                    c_dp]),
+    "pm_patches_count": (i64, [i64, i64, i64]),
+    "pm_patches_extract_f64": (C.c_int, [c_dp, i64, i64, i64, i64, i64, i64, i64, i64, i64, C.c_int, c_dp, i64, c_dp, c_dp]),
+    "pm_patches_extract_f32": (C.c_int, [c_dp, i64, i64, i64, i64, i64, i64, i64, i64, i64, C.c_int, c_dp, i64, c_dp, c_dp]),
+    "pm_patches_accumulate_f64": (C.c_int, [c_dp, i64, c_dp, i64, i64, c_dp, i64, i64, i64, i64, i64, i64, i64, c_dp]),
+    "pm_patches_finish_f64": (C.c_int, [c_dp, i64, c_dp, i64, i64, i64, i64, i64, i64, i64, c_dp]),
 }
 
 
@@ -198,7 +203,7 @@ class HipError(RuntimeError):
     pass
 
 
-MIN_VERSION = 1018
+MIN_VERSION = 1019
 _lib = None
 _lib_det = None
 LIB_PATH_DET = os.path.join(os.path.dirname(LIB_PATH), "libprosper_hip_det.so")

@@ -53,6 +53,13 @@ class MixtureModel(Model):
     def check_params(self, model_params):
         raise NotImplementedError
 
+    def reconstruct_image(self, model_params, image, **kw):
+        """Whole-image denoising by overlapping patches: ``utils.patches.denoise_image(self, model_params,
+        image, **kw)`` -- every patch through ``reconstruct()``, the estimates averaged where they overlap.  Keywords:
+        ``patch``, ``stride``, ``center``, ``chunk``, ``device``."""
+        from ...utils.patches import denoise_image
+        return denoise_image(self, model_params, image, **kw)
+
     @tracing.traced
     def generate_data(self, model_params, my_N):
         """Component labels from ``scipy.stats.rv_discrete(values=(arange(H), pies)).rvs(size=my_N)`` (the reference's

@@ -1,0 +1,247 @@
+"""Whole-image denoising by overlapping patches: cut an image into p_h x p_w patches on the device, estimate
+every patch with a model's ``reconstruct()``, put the estimates back and average where they overlap.  The patch matrix is
+built, consumed and folded back on the device in chunks of whole patch rows (pm_patches_* of include/prosper_hip.h); there
+is no CPU fallback.
+
+The patch grid (one rule, used everywhere): along an axis of length L, patches of length p at stride s >= 1 start at 0, s,
+2s, ... while start + p <= L, plus at L - p if the last of these is not L - p: every pixel is covered for every stride
+s <= p (a larger stride would leave gaps between the regular starts and is refused where an image is cut).  Patches are
+numbered row-major over (image, start row, start column); inside a patch the D = p_h p_w values are row-major, (a, b) ->
+a p_w + b."""
+import ctypes
+
+import numpy as np
+
+from .. import _lib
+
+try:
+    import torch
+except Exception:  # pragma: no cover
+    torch = None
+
+CHUNK_BYTES = 1 << 30      # default budget of one chunk of denoise_image: its input rows plus its output rows
+
+
+def patch_starts(length, patch, stride=1):
+    """The patch starts along an axis of ``length`` positions, as a list (the grid rule of the module docstring)."""
+    length, patch, stride = int(length), int(patch), int(stride)
+    if patch < 1 or stride < 1:
+        raise ValueError("patch and stride must be at least 1 (got patch=%d, stride=%d)" % (patch, stride))
+    if length < patch:
+        raise ValueError("an axis of length %d holds no patch of length %d" % (length, patch))
+    starts = list(range(0, length - patch + 1, stride))
+    if starts[-1] != length - patch:
+        starts.append(length - patch)
+    return starts
+
+
+def _patch_pair(patch):
+    if isinstance(patch, (tuple, list, np.ndarray)):
+        if len(patch) != 2:
+            raise ValueError("patch is an int or a pair (p_h, p_w), got %r" % (patch,))
+        ph, pw = int(patch[0]), int(patch[1])
+    else:
+        ph = pw = int(patch)
+    if ph < 1 or pw < 1:
+        raise ValueError("patch sides must be at least 1, got %r" % (patch,))
+    return ph, pw
+
+
+def _geometry(shape, patch, stride):
+    """((B, Hi, Wi), (ph, pw), stride, nr, nc) of an image shape, or ValueError."""
+    shape = tuple(int(v) for v in shape)
+    if len(shape) == 2:
+        shape = (1,) + shape
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError("an image is (H, W) or a stack (B, H, W) with no empty axis, got shape %r (colour channels are "
+                         "out of scope)" % (shape,))
+    ph, pw = _patch_pair(patch)
+    if int(stride) != stride or int(stride) < 1:
+        raise ValueError("stride must be an integer >= 1, got %r" % (stride,))
+    nr, nc = len(patch_starts(shape[1], ph, stride)), len(patch_starts(shape[2], pw, stride))
+    for L, p in ((shape[1], ph), (shape[2], pw)):
+        if stride > p and L > 2 * p:
+            raise ValueError("stride %d leaves pixels between patches of length %d uncovered on an axis of length %d: an "
+                             "average needs stride <= patch" % (stride, p, L))
+    return shape, (ph, pw), int(stride), nr, nc
+
+
+def _shape_of(a):
+    t = getattr(a, "tensor", a)
+    return tuple(t.shape)
+
+
+def _device(model=None):
+    if getattr(model, "device", None) is not None:
+        return torch.device(model.device)
+    if torch is None or not torch.cuda.is_available():
+        raise _lib.HipError("the patch kernels need a HIP device: there is no CPU fallback")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _image_tensor(image, dev):
+    """The (B, Hi, Wi) float32 / float64 device tensor of ``image`` with unit column stride and images Hi rows apart, and its
+    row stride.  A device tensor that already has this layout is used in place."""
+    t = getattr(image, "tensor", image)
+    if torch.is_tensor(t):
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.cpu().to(torch.float64)
+    else:
+        t = np.asarray(t)
+        if t.dtype not in (np.float32, np.float64):
+            t = t.astype(np.float64)
+        t = torch.from_numpy(np.ascontiguousarray(t))
+    t = t.to(dev)
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    B, Hi, Wi = t.shape
+    if t.stride(2) != 1 or t.stride(1) < Wi or (B > 1 and t.stride(0) != Hi * t.stride(1)):
+        t = t.contiguous()
+    return t, int(t.stride(1)) if Hi > 1 else max(int(t.stride(1)), Wi)
+
+
+def _rows_tensor(Y, D, dev, what):
+    """An (n, D) float64 device tensor with unit column stride of ``Y`` (host array, tensor or DeviceArray), and its leading
+    dimension."""
+    t = getattr(Y, "tensor", Y)
+    if not torch.is_tensor(t):
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(t), dtype=np.float64))
+    if t.dim() != 2 or t.shape[1] != D:
+        raise ValueError("%s must be (N, %d), got %r" % (what, D, tuple(t.shape)))
+    t = t.to(device=dev, dtype=torch.float64)
+    if t.stride(1) != 1 or t.stride(0) < D:
+        t = t.contiguous()
+    return t, int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), D)
+
+
+def _extract(img, ldi, geo, n0, n, center, det):
+    (B, Hi, Wi), (ph, pw), stride, nr, nc = geo
+    dev = img.device
+    Y = torch.empty((n, ph * pw), dtype=torch.float64, device=dev)
+    means = torch.empty(n, dtype=torch.float64, device=dev) if center else None
+    entry = "pm_patches_extract_f32" if img.dtype == torch.float32 else "pm_patches_extract_f64"
+    _lib.call(entry, _ptr(img), ldi, B, Hi, Wi, ph, pw, stride, n0, n, int(bool(center)), _ptr(Y), ph * pw, _ptr(means),
+              _stream(dev), det=det)
+    return Y, means
+
+
+def _accumulate(acc, est, lde, means, geo, n0, n, det):
+    (B, Hi, Wi), (ph, pw), stride, nr, nc = geo
+    _lib.call("pm_patches_accumulate_f64", _ptr(est), lde, _ptr(means), n0, n, _ptr(acc), Wi, B, Hi, Wi, ph, pw, stride,
+              _stream(acc.device), det=det)
+
+
+def _finish(acc, geo, det):
+    (B, Hi, Wi), (ph, pw), stride, nr, nc = geo
+    out = torch.empty_like(acc)
+    _lib.call("pm_patches_finish_f64", _ptr(acc), Wi, _ptr(out), Wi, B, Hi, Wi, ph, pw, stride, _stream(acc.device), det=det)
+    return out
+
+
+def _hand_back(t, squeeze, device):
+    from ..em.camodels._device import DeviceArray
+    if t is None:
+        return None
+    if squeeze:
+        t = t[0]
+    return DeviceArray(t) if device else t.cpu().numpy()
+
+
+def extract_patches(image, patch, stride=1, center=False, device=False):
+    """The (N, D) float64 patch matrix of ``image`` -- (H_i, W_i) or a stack (B, H_i, W_i); NumPy array, torch tensor (a
+    device tensor is read in place) or ``DeviceArray``; float32 and float64 go to the kernel as they are, other types are
+    converted to float64 on the host -- on the grid of the module docstring, built on the device by pm_patches_extract_*.
+
+    Returns ``(Y, means)``: ``means`` is None, or with ``center=True`` the (N,) patch means, ``Y`` then holding each patch
+    minus its mean.  NumPy arrays, or with ``device=True`` ``DeviceArray``s left on the device: ``Y`` is accepted as
+    ``my_data['y']`` by ``EM``, ``model.step``, ``reconstruct`` and ``log_likelihood`` as it is."""
+    geo = _geometry(_shape_of(image), patch, stride)
+    dev = _device()
+    img, ldi = _image_tensor(image, dev)
+    Y, means = _extract(img, ldi, geo, 0, geo[0][0] * geo[3] * geo[4], center, False)
+    return _hand_back(Y, False, device), _hand_back(means, False, device)
+
+
+def average_patches(Y, image_shape, patch, stride=1, means=None, device=False):
+    """Put the (N, D) patches ``Y`` (+ their ``means`` (N,), if given) back onto an image of ``image_shape`` ((H_i, W_i) or
+    (B, H_i, W_i)) and average where they overlap: every pixel is the sum of its patches' values, added one at a time in
+    ascending patch number, divided by their number (pm_patches_accumulate_f64, pm_patches_finish_f64; no atomics, the same
+    bits on every run).  Returns the float64 image as a NumPy array, or with ``device=True`` as a ``DeviceArray``."""
+    geo = _geometry(image_shape, patch, stride)
+    (B, Hi, Wi), (ph, pw), _, nr, nc = geo
+    N = B * nr * nc
+    if _shape_of(Y) != (N, ph * pw):
+        raise ValueError("Y must be (%d, %d) for this image, patch and stride, got %r" % (N, ph * pw, _shape_of(Y)))
+    if means is not None and _shape_of(means) != (N,):
+        raise ValueError("means must be (%d,), got %r" % (N, _shape_of(means)))
+    dev = _device()
+    est, lde = _rows_tensor(Y, ph * pw, dev, "Y")
+    if means is not None:
+        means = getattr(means, "tensor", means)
+        if not torch.is_tensor(means):
+            means = torch.from_numpy(np.ascontiguousarray(np.asarray(means), dtype=np.float64))
+        means = means.to(device=dev, dtype=torch.float64).contiguous()
+    acc = torch.zeros((B, Hi, Wi), dtype=torch.float64, device=dev)
+    _accumulate(acc, est, lde, means, geo, 0, N, False)
+    return _hand_back(_finish(acc, geo, False), len(tuple(image_shape)) == 2, device)
+
+
+def denoise_image(model, model_params, image, patch=None, stride=1, center=False, chunk=None, device=False):
+    """Denoise ``image`` ((H_i, W_i) or a stack (B, H_i, W_i); NumPy array, torch tensor -- a device tensor is used in place,
+    without a host round trip -- or ``DeviceArray``) with ``model`` at ``model_params``: every overlapping patch on the grid of
+    the module docstring is replaced by its posterior mean ``model.reconstruct()`` and every pixel by the average of the
+    estimates of the patches that contain it, added in ascending patch number.
+
+    ``patch``: an int or a pair (p_h, p_w) with p_h p_w = model.D; None: the square patch with p^2 = model.D.  ``center``:
+    each patch's mean is removed before the model sees it and added back to its estimate.  The patches are walked in chunks
+    of whole patch rows: extract -> ``model.reconstruct(model_params, {'y': chunk}, device=True)`` -> accumulate, then one
+    division per pixel.  ``chunk``: patches per chunk, rounded down to whole patch rows (at least one); None: as many patch
+    rows as keep a chunk's input rows plus output rows within 1 GiB (``CHUNK_BYTES``).  Device memory is bounded by the chunk,
+    not by the image, and the result's bits do not depend on ``chunk`` (a row of ``reconstruct()`` depends on that row and the
+    parameters alone; the additions of a pixel run in the same order for every chunking).
+
+    It inherits from ``reconstruct()``: this rank's images only, no collective; the training state, ``model_params`` and
+    Hprime / gamma are left as they were; MoP with ``A`` set works in the normalised units ``reconstruct()`` documents; every
+    ``HipError`` limit of ``reconstruct()`` applies.  A NaN pixel makes NaN exactly the pixels of the patches that contain it.
+    Returns the float64 image (the shape of ``image``) as a NumPy array, or with ``device=True`` as a ``DeviceArray``."""
+    from ..em.camodels._device import DeviceArray
+    D = int(model.D)
+    if patch is None:
+        p = int(round(D ** 0.5))
+        if p * p != D:
+            raise ValueError("model.D = %d is not a square: give patch=(p_h, p_w)" % D)
+        patch = (p, p)
+    ph, pw = _patch_pair(patch)
+    if ph * pw != D:
+        raise ValueError("a %d x %d patch has %d values, model.D is %d" % (ph, pw, ph * pw, D))
+    shape = _shape_of(image)
+    geo = _geometry(shape, (ph, pw), stride)
+    (B, Hi, Wi), _, _, nr, nc = geo
+    if chunk is None:
+        chunk = CHUNK_BYTES // (16 * D)
+    elif int(chunk) != chunk or int(chunk) < 1:
+        raise ValueError("chunk must be a positive number of patches, got %r" % (chunk,))
+    rows = max(1, int(chunk) // nc)
+    dev = _device(model)
+    det = bool(getattr(model, "deterministic", False))
+    img, ldi = _image_tensor(image, dev)
+    acc = torch.zeros((B, Hi, Wi), dtype=torch.float64, device=dev)
+    for R0 in range(0, B * nr, rows):
+        n0, n = R0 * nc, min(rows, B * nr - R0) * nc
+        Y, means = _extract(img, ldi, geo, n0, n, center, det)
+        est = model.reconstruct(model_params, {'y': DeviceArray(Y)}, device=True)
+        del Y
+        if _shape_of(est) != (n, D):
+            raise ValueError("reconstruct() returned %r for a chunk of (%d, %d)" % (_shape_of(est), n, D))
+        est, lde = _rows_tensor(est, D, dev, "reconstruct()'s result")
+        _accumulate(acc, est, lde, means, geo, n0, n, det)
+        del est, means
+    return _hand_back(_finish(acc, geo, det), len(shape) == 2, device)
