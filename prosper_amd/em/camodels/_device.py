@@ -149,6 +149,8 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+_LOG_UNDERFLOW = -745.1332191019412      # log(2^-1075): exp() of anything below rounds to 0.0
+
 _DET_QUANTA_SET = {}      # unit -> the quanta last installed in libprosper_hip_det.so's symbols (process-global, like them)
 
 
@@ -345,117 +347,6 @@ class DeviceCAModel(CAModel):
             return CAModel.step(self, anneal, model_params, my_data)
         finally:
             self._in_step = was
-
-    def _dsc_estep(self, anneal, stats_name, par, res, cand, tab, S, prior, P, Kt, pi_key):
-        """DSC / TSC E-step launch.  Inside ``step`` with no data truncation ahead the sixteen-lane kernel also produces the
-        M-step's row statistics (pm_dsc_estep_mstats_f64: E[s] rows and their non-zero lists, Wq, qdiag, value counts,
-        scalars) from the exponentials its log-sum-exp evaluates anyway -- ``M_step`` then skips its pass over the
-        log-joints.  Returns the DeviceArray of log-joints with ``.lse`` and, fused, ``.mstats``."""
-        N = res["Y"].shape[0]
-        H, D, Hp = self.H, self.D, self.Hprime
-        lib = _lib.load()
-        logpj = torch.empty((N, Kt), dtype=torch.float64, device=self.device)
-        lse = torch.empty((N,), dtype=torch.float64, device=self.device)
-        out = DeviceArray(logpj)
-        out.lse = lse
-        out.mstats = None
-        if not N:
-            return out
-        st = self._stream()
-        if self.deterministic:
-            self._det_dsc_quanta(res, par, P, prior, Kt)
-        fuse = (getattr(self, "_in_step", False) and getattr(self, "fuse_mstats", True) and anneal['Ncut_factor'] <= 0.0
-                and bool(lib.pm_dsc_estep_mstats_supported(H, Hp, S, int(P.K), int(P.flags))))
-        if fuse:
-            stats = self._buf(stats_name, (lib.pm_dsc_stats_len(H, D),))
-            stats.zero_()
-            expect = self._buf("expect", (N, H))
-            nz = None
-            if getattr(self, "sparse_wp", True):
-                nz = (self._buf("nz_idx", (N, 16), torch.int16), self._buf("nz_val", (N, 16)))
-            self._call("estep_mstats", "pm_dsc_estep_mstats_f64", _ptr(par["A"]), H, _ptr(par["G"]), _ptr(res["ynorm2"]),
-                       _ptr(cand), _ptr(tab), S, _ptr(prior), ctypes.byref(P), N, H, D, Hp, _ptr(logpj), Kt, _ptr(lse),
-                       _ptr(expect), H, _ptr(stats), _ptr(nz[0]) if nz else None, _ptr(nz[1]) if nz else None, st)
-            out.mstats = {"stats": stats, "expect": expect, "nz": nz, "res": res, "cand": cand,
-                          "P": (float(P.ecoef), float(P.pscale), int(P.flags)), "pi": np.array(pi_key, dtype=np.float64, copy=True)}
-        else:
-            self._call("estep", "pm_dsc_estep_f64", _ptr(par["A"]), H, _ptr(par["G"]), _ptr(res["ynorm2"]), _ptr(cand),
-                       _ptr(tab), S, _ptr(prior), ctypes.byref(P), N, H, Hp, _ptr(logpj), Kt, _ptr(lse), st)
-        return out
-
-    def _det_dsc_quanta(self, res, par, P, prior, Kt):
-        """Deterministic mode, DSC / TSC: bounds of the statistics' partial sums (latent values v_k, |v| <= vmax) -> quanta of
-        the row kernels, the sparse product and the dense GEMM behind its gate (pm_common.h, PM_Q).  Set ahead of the E-step,
-        whose parameters the M-step of the same EM step shares."""
-        ymax, ynmax = self._det_data_bounds(res)
-        W = np.asarray(par["W"], dtype=np.float64)
-        wn = float(np.sqrt((W * W).sum(axis=0)).max()) if W.size else 0.0
-        vmax = float(max(abs(P.values[k]) for k in range(int(P.K))))
-        emax = (ynmax + self.gamma * vmax * wn) ** 2
-        lpmax = abs(P.pscale) * float(prior.abs().max()) + abs(P.ecoef) * emax + np.log(max(Kt, 2))
-        n = float(res["Y"].shape[0])
-        self._det_set("dsc", [n * max(1.0, vmax * vmax), n * emax, n * lpmax])
-        self._det_set("wp_sparse", [n * vmax * ymax])
-        self._det_set("gemm", [n * max(1.0, vmax) * ymax, n * ymax])
-
-    def _dsc_fused_stats(self, logpj, res, cand, P, pi_key, lse_cut):
-        """The statistics workspace the E-step pass has already filled for exactly this M-step, or None."""
-        ms = getattr(logpj, "mstats", None) if isinstance(logpj, DeviceArray) else None
-        if ms is None:
-            return None
-        logpj.mstats = None
-        if (ms["res"] is res and ms["cand"] is cand and lse_cut == float("-inf")
-                and ms["P"] == (float(P.ecoef), float(P.pscale), int(P.flags))
-                and np.array_equal(ms["pi"], np.asarray(pi_key, dtype=np.float64))):
-            return ms
-        return None
-
-    def _rows_and_wp(self, rows_args, lp_ld, expect, Y, stats, my_N, K, flags, Hp, S, fused=None, cut_dev=None):
-        """DSC / TSC M-step: the per-datapoint pass (pm_dsc_mstep_rows[_nz]_f64) and Wp = E[s]^T Y.  Where the
-        sixteen-lane kernel applies the pass also leaves the non-zero lists of E[s] and Wp is accumulated from them
-        (pm_wp_sparse_f64); the dense product follows behind the device-side gate (last scalar of `stats`: rows whose
-        list overflowed) and only does work then.  ``fused``: the record of an E-step pass that has already produced the
-        row statistics (``_dsc_estep``): only the product is left."""
-        H, D = self.H, self.D
-        lib = _lib.load()
-        st = self._stream()
-        gate = ctypes.c_void_p(stats.data_ptr() + 8 * (lib.pm_dsc_stats_len(H, D) - 1))
-        if fused is not None:
-            nz = fused["nz"]
-            if nz is not None:
-                self._call("stats_sparse", "pm_wp_sparse_f64", _ptr(nz[0]), _ptr(nz[1]), _ptr(Y), Y.stride(0), _ptr(stats),
-                           D, gate, my_N, H, D, st)
-                self._call("stats_gemm", "pm_gemm_tn_acc_gated_f64", _ptr(expect), H, _ptr(Y), D, _ptr(stats), D, H, D,
-                           my_N, gate, st)
-            else:
-                self._call("stats_gemm", "pm_gemm_tn_acc_f64", _ptr(expect), H, _ptr(Y), D, _ptr(stats), D, H, D, my_N, st)
-            return
-        sparse = (getattr(self, "sparse_wp", True) and Y.is_cuda and H <= 256
-                  and bool(lib.pm_dsc_rows16_supported(H, Hp, S, K, flags)))
-        if cut_dev is not None:
-            # ``cut_dev``: the data-truncation cut as the radix select left it on the device (round 6: no host round trip
-            # between the select and this pass -- on a slow host the device idled a quarter of the step there)
-            rows_args = rows_args[:4] + (_ptr(cut_dev),) + rows_args[4:]
-            nzb = (self._buf("nz_idx", (my_N, 16), torch.int16), self._buf("nz_val", (my_N, 16))) if sparse else (None, None)
-            self._call("mstep_rows", "pm_dsc_mstep_rows_cutp_f64", *(rows_args + (_ptr(nzb[0]), _ptr(nzb[1]), st)))
-            if sparse:
-                self._call("stats_sparse", "pm_wp_sparse_f64", _ptr(nzb[0]), _ptr(nzb[1]), _ptr(Y), Y.stride(0), _ptr(stats),
-                           D, gate, my_N, H, D, st)
-                self._call("stats_gemm", "pm_gemm_tn_acc_gated_f64", _ptr(expect), H, _ptr(Y), D, _ptr(stats), D, H, D,
-                           my_N, gate, st)
-            else:
-                self._call("stats_gemm", "pm_gemm_tn_acc_f64", _ptr(expect), H, _ptr(Y), D, _ptr(stats), D, H, D, my_N, st)
-            return
-        if sparse:
-            nz_idx, nz_val = self._buf("nz_idx", (my_N, 16), torch.int16), self._buf("nz_val", (my_N, 16))
-            self._call("mstep_rows", "pm_dsc_mstep_rows_nz_f64", *(rows_args + (_ptr(nz_idx), _ptr(nz_val), st)))
-            self._call("stats_sparse", "pm_wp_sparse_f64", _ptr(nz_idx), _ptr(nz_val), _ptr(Y), Y.stride(0), _ptr(stats),
-                       D, gate, my_N, H, D, st)
-            self._call("stats_gemm", "pm_gemm_tn_acc_gated_f64", _ptr(expect), H, _ptr(Y), D, _ptr(stats), D, H, D,
-                       my_N, gate, st)
-        else:
-            self._call("mstep_rows", "pm_dsc_mstep_rows_f64", *(rows_args + (st,)))
-            self._call("stats_gemm", "pm_gemm_tn_acc_f64", _ptr(expect), H, _ptr(Y), D, _ptr(stats), D, H, D, my_N, st)
 
     def _buf(self, name, shape, dtype=None):
         """Reusable device workspace (no allocation inside the EM loop once warm)."""
@@ -678,66 +569,6 @@ class DeviceCAModel(CAModel):
         ev.synchronize()
         return dst.numpy()
 
-    # ---- EM-loop pipelining shared by the linear models whose M-step solves W^T on the device (DSC, TSC) ----
-    def _seed_next(self, res, Wt):
-        """Next step's Gram matrix and scores from ``Wt`` = W_new^T (H,D), which the M-step has just solved on the
-        device -- enqueued behind the M-step's download so they run while the host unpacks it.  ``_take_seed``
-        hands them to the next ``select_Hprimes`` if the caller feeds the returned W back unchanged."""
-        Y = res["Y"]
-        N, H = Y.shape[0], self.H
-        A = self._buf("scores_spec", (N, H))
-        if self._par.get("A") is A:
-            self._par = {}                 # the cached parameters' scores live in the buffer overwritten now
-        G = self._gemm_nt(Wt, Wt, torch.empty((H, H), dtype=torch.float64, device=self.device), "gram_gemm")
-        if N:
-            self._gemm_nt(Y, Wt, A, "scores_gemm")
-        self._seed_rec = {"ykey": res["key"], "Wt": Wt, "G": G, "A": A, "W": None}
-
-    def _scores_params(self, W, res):
-        """DSC / TSC: device copy of W^T (H,D), the Gram matrix and the scores for the current W and data.  In an EM loop
-        the last M-step has left all three on the device (``_seed_next``): W is compared with ITS snapshot first, and once
-        per ``step`` -- select_Hprimes, E_step and M_step see the same array object there, and a 256 x 128 comparison costs
-        27 us of host time that sits on the loop's critical path (three of them per step until round 4: the device idled
-        ~0.1 ms per 0.7 ms iteration waiting for the E-step launch)."""
-        W_in = W
-        W = np.asarray(W, dtype=np.float64)
-        par = self._par
-        # The once-per-step shortcut keys on the IDENTITY of the caller's array, so only for an object that is already the
-        # float64 ndarray the comparison would read (a converted temporary's id() can be recycled), and the record keeps a
-        # reference to it (an id() is only unique among live objects).  Contract: W is not edited in place between
-        # select_Hprimes, E_step and M_step of one ``step`` (CAModel.step never does).
-        tag = (getattr(self, "_step_id", 0), id(W)) if (getattr(self, "_in_step", False) and W is W_in) else None
-        if tag is not None and par.get("checked") == tag and par.get("checked_obj") is W and par.get("ykey") == res["key"]:
-            return par
-        if getattr(self, "_seed_rec", None) is not None:
-            seeded = self._take_seed(W, res)
-            if seeded is not None:           # W^T, Gram matrix and scores left on the device by the last M-step
-                seeded["checked"], seeded["checked_obj"] = tag, (W if tag is not None else None)
-                self._par = seeded
-                return seeded
-        if par.get("ykey") == res["key"] and par.get("W") is not None and par["W"].shape == W.shape \
-                and np.array_equal(par["W"], W):
-            par["checked"], par["checked_obj"] = tag, (W if tag is not None else None)
-            return par
-        Wt = self._upload("W", W).t().contiguous()
-        G = self._gemm_nt(Wt, Wt, self._buf("gram", (self.H, self.H)), "gram_gemm")
-        Y = res["Y"]
-        A = self._buf("scores", (Y.shape[0], self.H))
-        if Y.shape[0]:
-            self._gemm_nt(Y, Wt, A, "scores_gemm")
-        self._par = {"ykey": res["key"], "W": W.copy(), "Wt": Wt, "G": G, "A": A, "checked": tag,
-                     "checked_obj": W if tag is not None else None}
-        return self._par
-
-    def _take_seed(self, W, res):
-        """The seeded parameter record if ``W`` (D,H) is what the last M-step returned (compared with a private
-        snapshot, so in-place edits by the caller are seen); the seed is consumed either way."""
-        seed, self._seed_rec = getattr(self, "_seed_rec", None), None
-        if seed is None or seed["W"] is None or seed["ykey"] != res["key"] or seed["W"].shape != W.shape \
-                or not np.array_equal(seed["W"], W):
-            return None
-        return {"ykey": res["key"], "W": seed["W"], "Wt": seed["Wt"], "G": seed["G"], "A": seed["A"]}
-
     def _invert_normal_matrix(self, Wq_u, qdiag, status=None):
         """Wq = triu(Wq_u) + triu(Wq_u, 1)^T + diag(qdiag) and its inverse, enqueued on the CURRENT stream:
         ``(Wq, Winv, status)`` -- one-workgroup SPD inverse (csrc/spd_inverse.hip) instead of ~40 rocSOLVER launches.
@@ -808,9 +639,9 @@ class DeviceCAModel(CAModel):
     def _solve_normal_eq(self, Wq_u, qdiag, rhs, pre=None, out=None, status=None):
         """X = Wq^-1 . rhs, enqueued on the device, for the symmetric second-moment matrix
         Wq = triu(Wq_u) + triu(Wq_u, 1)^T + diag(qdiag) -- the models' ``np.linalg.lstsq(Wq, Wp)``
-        (bsc_et.py:380, dsc_et.py:741).  Returns (X (H,D), status (3,) = [smallest, largest pivot of the elimination --
-        smallest <= 0 marks a failed factorisation --, accurate], Wq (H,H)); the caller fetches the status with its one
-        download, checks the pivots (``_solve_ok``: "singular" -> LAPACK's lstsq on the host) and hands status[2] to
+        (bsc_et.py:380; the table models': camodels/_table.py).  Returns (X (H,D), status (3,) = [smallest, largest pivot of
+        the elimination -- smallest <= 0 marks a failed factorisation --, accurate], Wq (H,H)); the caller fetches the status
+        with its one download, checks the pivots (``_solve_ok``: "singular" -> LAPACK's lstsq on the host) and hands status[2] to
         ``_solve_accurate``.  ``pre``: the result of ``_invert_normal_matrix`` when the caller has already run it;
         ``out`` / ``status``: device tensors to write X / the status into (slices of the caller's download buffer)."""
         H, D = rhs.shape
@@ -993,6 +824,82 @@ class DeviceCAModel(CAModel):
         return out
 
     # ------------------------------------------------------------------ inference ("next" row)
+    def _adaptive_inference(self, anneal, model_params, test_data, topK, adaptive, Hprime_max, gamma_max,
+                            run_pass, regenerate, restore):
+        """The loop every model's ``inference`` runs (camodels/__init__.py:256-375): log-joints of the datapoints still in
+        play from ``compute_lpj``, one pass of the model's top-K kernel over them, and with ``adaptive`` the datapoints whose
+        MAP state has exactly gamma active units again with Hprime+1 / gamma+1 until none remain or the caps are reached.
+
+        ``run_pass(lp, cd, k_eff, ind_n, buf)``: launch the model's pm_infer_topk* kernel on the (n, K) log-joints ``lp`` and
+        the (n, Hprime) int64 candidates ``cd``, hand the ranked state indices to ``_refuse_nan`` and write rows ``ind_n`` of
+        ``buf['s']`` (first ``k_eff`` entries), ``buf['m']`` and ``buf['p']``.  ``regenerate()``: the model's state tables
+        for the grown ``self.Hprime`` / ``self.gamma``; ``restore()``: what the model does once both are back at their
+        starting values, whatever happened.  Returns ``buf``: device tensors ``s`` (N,topK,H) int8, ``m`` (N,H), ``p``
+        (N,topK), ``gamma`` and ``Hprime`` (N,)."""
+        comm = self.comm
+        my_y = test_data['y']
+        if isinstance(my_y, DeviceArray):
+            my_y = my_y.tensor
+        my_N, H = my_y.shape[0], self.H
+        Hprime_start, gamma_start = self.Hprime, self.gamma
+        if topK == -1:
+            topK = self.state_matrix.shape[0]
+        dev = self.device
+        buf = {'s': torch.zeros((my_N, topK, H), dtype=torch.int8, device=dev),
+               'm': torch.zeros((my_N, H), dtype=torch.float64, device=dev),
+               'p': torch.zeros((my_N, topK), dtype=torch.float64, device=dev),
+               'gamma': torch.zeros((my_N,), dtype=torch.float64, device=dev),
+               'Hprime': torch.zeros((my_N,), dtype=torch.float64, device=dev)}
+
+        cur_y = my_y
+        which = torch.ones(my_N, dtype=torch.bool, device=dev)
+        try:
+            while bool(which.any()):
+                ind_n = torch.nonzero(which).flatten()
+                logpj, cand = self.compute_lpj(anneal, model_params, {'y': cur_y})
+                lp = logpj.tensor if isinstance(logpj, DeviceArray) else torch.as_tensor(np.asarray(logpj)).to(dev)
+                cd = (cand.tensor if isinstance(cand, DeviceArray) else torch.as_tensor(np.asarray(cand)).to(dev)).long()
+                lp = lp.contiguous() if lp.stride(1) != 1 else lp
+                run_pass(lp, cd, min(topK, lp.shape[1]), ind_n, buf)
+                buf['Hprime'][ind_n] = float(self.Hprime)
+                buf['gamma'][ind_n] = float(self.gamma)
+                if not adaptive:
+                    break
+                which = ((buf['s'][:, 0, :] != 0).sum(-1) == self.gamma)
+                if not bool(which.any()):
+                    break
+                if (Hprime_max is not None and self.Hprime == Hprime_max) and \
+                        (gamma_max is not None and self.gamma == gamma_max):
+                    break
+                cur_y = my_y[which.cpu().numpy()] if not torch.is_tensor(my_y) else my_y[which]
+                print("Rank %i: For %i data points MAP state has activity equal to gamma." % (comm.rank, int(which.sum())))
+                if not ((self.Hprime == self.H) or (Hprime_max is not None and self.Hprime == Hprime_max)):
+                    self.Hprime += 1
+                if (self.gamma == self.H) or (gamma_max is not None and self.gamma == gamma_max):
+                    continue
+                self.gamma += 1
+                print("Rank %i: Updating state matrix and running again." % comm.rank)
+                regenerate()
+        finally:
+            self.Hprime, self.gamma = Hprime_start, gamma_start
+            restore()
+        return buf
+
+    @staticmethod
+    def _refuse_nan(top_idx):
+        """Fewer than topK comparable log-joints in some row (NaN: a non-finite datapoint or parameter).  The reference's
+        argsort would rank the NaNs somewhere and carry on; indexing with -1 here would silently report a wrapped state --
+        refuse instead."""
+        if bool((top_idx < 0).any()):
+            raise _lib.HipError("inference: non-finite log-joints (NaN) in %d datapoint(s)"
+                                % int((top_idx < 0).any(dim=1).sum()))
+
+    @staticmethod
+    def _inference_result(buf, logprob):
+        m_out = buf['m'] if logprob else torch.exp(buf['m'])
+        return {'s': buf['s'].cpu().numpy(), 'm': m_out.cpu().numpy(), 'p': buf['p'].cpu().numpy(),
+                'gamma': buf['gamma'].cpu().numpy(), 'Hprime': buf['Hprime'].cpu().numpy()}
+
     def inference(self, anneal, model_params, test_data, topK=10, logprob=False, adaptive=True,
                   Hprime_max=None, gamma_max=None):
         """Top-K posterior states and marginals per datapoint (camodels/__init__.py:256-375).
@@ -1005,103 +912,55 @@ class DeviceCAModel(CAModel):
         from . import generate_state_matrix
         assert 'y' in test_data, "Key 'y' in test_data dict not defined."
         model_params = self.check_params(model_params)
-        comm = self.comm
-        my_y = test_data['y']
-        if isinstance(my_y, DeviceArray):
-            my_y = my_y.tensor
-        my_N, D = my_y.shape
-        H = self.H
-        Hprime_start, gamma_start = self.Hprime, self.gamma
-        if topK == -1:
-            topK = self.state_matrix.shape[0]
-        dev = self.device
-        res_s = torch.zeros((my_N, topK, H), dtype=torch.int8, device=dev)
-        res_m = torch.zeros((my_N, H), dtype=torch.float64, device=dev)
-        res_p = torch.zeros((my_N, topK), dtype=torch.float64, device=dev)
-        res_gamma = torch.zeros((my_N,), dtype=torch.float64, device=dev)
-        res_Hprime = torch.zeros((my_N,), dtype=torch.float64, device=dev)
+        H, dev = self.H, self.device
 
-        cur_y = my_y
-        which = torch.ones(my_N, dtype=torch.bool, device=dev)
-        try:
-            while bool(which.any()):
-                ind_n = torch.nonzero(which).flatten()
-                logpj, cand = self.compute_lpj(anneal, model_params, {'y': cur_y})
-                lp = logpj.tensor if isinstance(logpj, DeviceArray) else torch.as_tensor(np.asarray(logpj)).to(dev)
-                cd = cand.tensor if isinstance(cand, DeviceArray) else torch.as_tensor(np.asarray(cand)).to(dev)
-                cd = cd.long()
-                n_cur, K = lp.shape
-                Hp = self.Hprime
-                k_eff = min(topK, K)
-                # top-K columns of the normalised posterior and the log-marginals: one HIP pass over the rows
-                # (csrc/infer_kernels.hip).  Upstream quirk (:309-312): logprob=False reports exp(logpj - max), NOT the
-                # normalised value -- the kernel returns both
-                SMh = self.state_matrix.astype(np.int64)
-                mk = (SMh << np.arange(SMh.shape[1])[None, :]).sum(axis=1).astype(np.uint16) if SMh.size else np.zeros(1, np.uint16)
-                masks_d = torch.from_numpy(mk.view(np.int16).copy()).to(dev)
-                lp = lp.contiguous() if lp.stride(1) != 1 else lp
-                cd32 = cd.to(torch.int32).contiguous()
-                top_idx32 = torch.empty((n_cur, k_eff), dtype=torch.int32, device=dev)
-                top_val = torch.empty((n_cur, k_eff), dtype=torch.float64, device=dev)
-                top_rel = torch.empty((n_cur, k_eff), dtype=torch.float64, device=dev)
-                m_blk = torch.empty((n_cur, H), dtype=torch.float64, device=dev)
-                self._call("infer_topk", "pm_infer_topk_f64", _ptr(lp), lp.stride(0), _ptr(cd32), _ptr(masks_d), n_cur, H, Hp,
-                           self.no_states, k_eff, _ptr(top_idx32), _ptr(top_val), _ptr(top_rel), _ptr(m_blk), H, self._stream())
-                if bool((top_idx32 < 0).any()):
-                    # fewer than topK comparable log-joints in some row (NaN: a non-finite datapoint or parameter).  The
-                    # reference's argsort would rank the NaNs somewhere and carry on; indexing with -1 here would silently
-                    # report a wrapped state -- refuse instead
-                    raise _lib.HipError("inference: non-finite log-joints (NaN) in %d datapoint(s)"
-                                        % int((top_idx32 < 0).any(dim=1).sum()))
-                top_idx = top_idx32.long()
-                res_Hprime[ind_n] = float(self.Hprime)
-                res_gamma[ind_n] = float(self.gamma)
-                # top-K states as H-dimensional binary vectors
-                SM = torch.from_numpy(self.state_matrix.astype(np.int8)).to(dev) if self.no_states else \
-                    torch.zeros((1, Hp), dtype=torch.int8, device=dev)
-                # upstream quirk (:313-319): a re-run datapoint's earlier entries are never cleared -- one-cause
-                # states only SET their bit, the null state writes nothing, multi-cause states overwrite the
-                # candidate positions; start from what is there
-                s_blk = res_s[ind_n, :k_eff].clone()
-                single = (top_idx >= 1) & (top_idx <= H)
-                if bool(single.any()):
-                    nn_, mm_ = torch.nonzero(single, as_tuple=True)
-                    s_blk[nn_, mm_, top_idx[nn_, mm_] - 1] = 1
-                multi = top_idx > H
-                if bool(multi.any()):
-                    nn_, mm_ = torch.nonzero(multi, as_tuple=True)
-                    rows = SM[top_idx[nn_, mm_] - H - 1]                           # (M, Hp)
-                    s_blk[nn_[:, None].expand(-1, Hp), mm_[:, None].expand(-1, Hp), cd[nn_]] = rows
-                res_s[ind_n, :k_eff] = s_blk
-                res_p[ind_n, :k_eff] = top_val if logprob else torch.exp(top_rel)
-                res_m[ind_n] = m_blk        # log p(s_h = 1 | y): log-sum-exp over the states containing h (the kernel)
-                if not adaptive:
-                    break
-                which = ((res_s[:, 0, :] != 0).sum(-1) == self.gamma)
-                if not bool(which.any()):
-                    break
-                if (Hprime_max is not None and self.Hprime == Hprime_max) and \
-                        (gamma_max is not None and self.gamma == gamma_max):
-                    break
-                cur_y = my_y[which.cpu().numpy()] if not torch.is_tensor(my_y) else my_y[which]
-                n_left = int(which.sum())
-                print("Rank %i: For %i data points MAP state has activity equal to gamma." % (comm.rank, n_left))
-                if not ((self.Hprime == self.H) or (Hprime_max is not None and self.Hprime == Hprime_max)):
-                    self.Hprime += 1
-                if (self.gamma == self.H) or (gamma_max is not None and self.gamma == gamma_max):
-                    continue
-                self.gamma += 1
-                print("Rank %i: Updating state matrix and running again." % comm.rank)
-                (self.state_list, self.no_states, self.state_matrix,
-                 self.state_abs) = generate_state_matrix(self.Hprime, self.gamma)
-        finally:
-            comm.Barrier()
-            self.Hprime, self.gamma = Hprime_start, gamma_start
+        def run_pass(lp, cd, k_eff, ind_n, buf):
+            n_cur, Hp = lp.shape[0], self.Hprime
+            # top-K columns of the normalised posterior and the log-marginals: one HIP pass over the rows
+            # (csrc/infer_kernels.hip).  Upstream quirk (:309-312): logprob=False reports exp(logpj - max), NOT the
+            # normalised value -- the kernel returns both
+            SMh = self.state_matrix.astype(np.int64)
+            mk = (SMh << np.arange(SMh.shape[1])[None, :]).sum(axis=1).astype(np.uint16) if SMh.size else np.zeros(1, np.uint16)
+            masks_d = torch.from_numpy(mk.view(np.int16).copy()).to(dev)
+            cd32 = cd.to(torch.int32).contiguous()
+            top_idx32 = torch.empty((n_cur, k_eff), dtype=torch.int32, device=dev)
+            top_val = torch.empty((n_cur, k_eff), dtype=torch.float64, device=dev)
+            top_rel = torch.empty((n_cur, k_eff), dtype=torch.float64, device=dev)
+            m_blk = torch.empty((n_cur, H), dtype=torch.float64, device=dev)
+            self._call("infer_topk", "pm_infer_topk_f64", _ptr(lp), lp.stride(0), _ptr(cd32), _ptr(masks_d), n_cur, H, Hp,
+                       self.no_states, k_eff, _ptr(top_idx32), _ptr(top_val), _ptr(top_rel), _ptr(m_blk), H, self._stream())
+            self._refuse_nan(top_idx32)
+            top_idx = top_idx32.long()
+            # top-K states as H-dimensional binary vectors
+            SM = torch.from_numpy(self.state_matrix.astype(np.int8)).to(dev) if self.no_states else \
+                torch.zeros((1, Hp), dtype=torch.int8, device=dev)
+            # upstream quirk (:313-319): a re-run datapoint's earlier entries are never cleared -- one-cause
+            # states only SET their bit, the null state writes nothing, multi-cause states overwrite the
+            # candidate positions; start from what is there
+            s_blk = buf['s'][ind_n, :k_eff].clone()
+            single = (top_idx >= 1) & (top_idx <= H)
+            if bool(single.any()):
+                nn_, mm_ = torch.nonzero(single, as_tuple=True)
+                s_blk[nn_, mm_, top_idx[nn_, mm_] - 1] = 1
+            multi = top_idx > H
+            if bool(multi.any()):
+                nn_, mm_ = torch.nonzero(multi, as_tuple=True)
+                rows = SM[top_idx[nn_, mm_] - H - 1]                           # (M, Hp)
+                s_blk[nn_[:, None].expand(-1, Hp), mm_[:, None].expand(-1, Hp), cd[nn_]] = rows
+            buf['s'][ind_n, :k_eff] = s_blk
+            buf['p'][ind_n, :k_eff] = top_val if logprob else torch.exp(top_rel)
+            buf['m'][ind_n] = m_blk        # log p(s_h = 1 | y): log-sum-exp over the states containing h (the kernel)
+
+        def regenerate():
             (self.state_list, self.no_states, self.state_matrix,
              self.state_abs) = generate_state_matrix(self.Hprime, self.gamma)
-        m_out = res_m if logprob else torch.exp(res_m)
-        return {'s': res_s.cpu().numpy(), 'm': m_out.cpu().numpy(), 'p': res_p.cpu().numpy(),
-                'gamma': res_gamma.cpu().numpy(), 'Hprime': res_Hprime.cpu().numpy()}
+
+        def restore():
+            self.comm.Barrier()
+            regenerate()
+
+        return self._inference_result(self._adaptive_inference(anneal, model_params, test_data, topK, adaptive, Hprime_max,
+                                                               gamma_max, run_pass, regenerate, restore), logprob)
 
     # ---- held-out log-likelihood --------------------------------------------------------------------------
     # What a log_likelihood call swaps out: the resident shard, the parameter products computed on it, the workspaces and
@@ -1197,9 +1056,12 @@ class DeviceCAModel(CAModel):
             local = float(total.cpu()[0]) + N * c
         finally:
             self._eval_end(saved)
-        parts = self.comm.allgather(local)
+        return self._sum_over_ranks(local)
+
+    def _sum_over_ranks(self, local):
+        """The ranks' values added in rank order: every rank returns the same bits."""
         out = 0.0
-        for v in parts:
+        for v in self.comm.allgather(local):
             out += v
         return out
 
@@ -1340,8 +1202,4 @@ class DeviceCAModel(CAModel):
             local = float(total.cpu()[0])
         finally:
             self._eval_end(saved)
-        parts = self.comm.allgather(local)
-        out = 0.0
-        for v in parts:
-            out += v
-        return out
+        return self._sum_over_ranks(local)

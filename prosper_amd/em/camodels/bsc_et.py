@@ -23,7 +23,8 @@ from math import pi as _PI
 import numpy as np
 from scipy.special import comb
 
-from ._device import (DeviceCAModel, DeviceArray, LazyCandidates, KernelTimer, _ptr, small_blas)  # noqa: F401
+from ._device import (DeviceCAModel, DeviceArray, LazyCandidates, KernelTimer, _LOG_UNDERFLOW, _ptr,  # noqa: F401
+                      small_blas)
 from ... import _lib
 from ...utils import parallel
 from ...utils import tracing
@@ -713,7 +714,7 @@ class BSC_ET(DeviceCAModel):
         if ncut and rec is None:
             tracing.tracepoint("M_step:truncating")
             lse_cut = self._kth_largest_global(lse, N_use)
-            if lse_cut < -745.1332191019412:     # log(2^-1075): the reference's un-stabilised evidence sums are exactly
+            if lse_cut < _LOG_UNDERFLOW:          # the reference's un-stabilised evidence sums are exactly
                 lse_cut = float("-inf")          # 0 there, and `all_denoms >= 0` keeps every datapoint (bsc_et.py:253)
         if mine and rec is not None:
             # The E-step pass has left every datapoint's statistics as a record beside its non-zero list (a data-truncation

@@ -17,7 +17,8 @@ import itertools as itls
 import numpy as np
 from scipy.special import gammaln
 
-from ._device import DeviceCAModel, DeviceArray, _ptr, small_blas
+from ._device import DeviceArray, _LOG_UNDERFLOW, _ptr
+from ._table import TableCAModel
 from ... import _lib
 from ...utils import parallel
 from ...utils import tracing
@@ -27,9 +28,6 @@ try:
     import torch
 except Exception:  # pragma: no cover
     torch = None
-
-
-_LOG_UNDERFLOW = -745.1332191019412      # log(2^-1075): exp() of anything below rounds to 0.0
 
 
 def multinom2(n, k):
@@ -51,12 +49,12 @@ def generate_state_matrix(Hprime, gamma, states=np.array([0, 1])):
     return state_matrix.shape[0], state_matrix, (state_matrix != 0).sum(axis=1)
 
 
-class DSC_ET(DeviceCAModel):
+class DSC_ET(TableCAModel):
     """Discrete Sparse Coding (K-ary latents, linear superposition) with Expectation Truncation."""
 
     def __init__(self, D, H, Hprime, gamma, states=np.array([-1., 0., 1.]), to_learn=['W', 'pi', 'sigma'],
                  comm=parallel.COMM_WORLD, device=None):
-        DeviceCAModel.__init__(self, D, H, Hprime, gamma, to_learn, comm, device)
+        TableCAModel.__init__(self, D, H, Hprime, gamma, to_learn, comm, device)
         if not type(states) == np.ndarray:
             raise TypeError("DSC: states must be of type numpy.ndarray")
         if Hprime > H:
@@ -295,15 +293,15 @@ class DSC_ET(DeviceCAModel):
         """Log-pseudo-joints ``{'logpj': (N, 1 + (K-1)H + S)}`` (dsc_et.py:492-585)."""
         res = self._resident(my_data['y'])
         N = res["Y"].shape[0]
-        H, Hp, S = self.H, self.Hprime, self.no_states
+        S = self.no_states
         tab = self._tables()
         par = self._params_dev(model_params['W'], res)
         cand = self._device_candidates(my_data['candidates'], N)
         P = self._params(anneal, model_params['pi'], model_params['sigma'])
-        prior = self._upload("dsc_prior", self._prior(np.asarray(model_params['pi'], dtype=np.float64)))
-        Kt = 1 + (self.K - 1) * H + S
+        prior = self._upload(self._prior_ws, self._prior(np.asarray(model_params['pi'], dtype=np.float64)))
         tracing.tracepoint("E_step:iterating")
-        return {'logpj': self._dsc_estep(anneal, "dsc_stats", par, res, cand, tab, S, prior, P, Kt, model_params['pi'])}
+        return {'logpj': self._dsc_estep(anneal, self._stats_ws, par, res, cand, tab, S, prior, P, self._n_logpj(),
+                                         model_params['pi'])}
 
     def _loglik_terms(self, model_params, my_data):
         """log_likelihood.  At T = 1 a column of ``logpj`` is - |y - W s|^2 / (2 sigma^2) plus pre_F, the
@@ -327,90 +325,30 @@ class DSC_ET(DeviceCAModel):
         assert lp.shape == (self.K,)
         return self._exact_linear(model_params['W'], model_params['sigma'], self.states, np.tile(lp, (self.H, 1)))
 
-    @tracing.traced
-    def M_step(self, anneal, model_params, my_suff_stat, my_data):
-        """New W, pi, sigma (dsc_et.py:587-774).  Logs ``prior_mass``, ``L`` and ``N_use``."""
-        comm = self.comm
-        H, Hp, D, S, K = self.H, self.Hprime, self.D, self.no_states, self.K
+    # ------------------------------------------------------------------ what TableCAModel.M_step asks of the model
+    _stats_ws, _prior_ws = "dsc_stats", "dsc_prior"
+    # data truncation (dsc_et.py:825-843): keep the datapoints STRICTLY above the N_use-th largest evidence.  The reference
+    # cuts on un-stabilised sums of exp(logpj), which are exactly 0 below the underflow boundary: with the cut among those
+    # only strictly positive sums survive
+    _cut_rule = (lambda c: torch.clamp_min(c, _LOG_UNDERFLOW), lambda c: max(c, _LOG_UNDERFLOW))
+
+    def _n_logpj(self):
+        return 1 + (self.K - 1) * self.H + self.no_states
+
+    def _prior_factors(self, model_params):
+        """Logs ``prior_mass``."""
         pi = np.asarray(model_params['pi'], dtype=np.float64)
-        sigma = model_params['sigma']
-        res = self._resident(my_data['y'])
-        Y = res["Y"]
-        my_N = Y.shape[0]
-        tab = self._tables()
-        cand = self._device_candidates(my_data['candidates'], my_N)
-        Kt = 1 + (K - 1) * H + S
-
-        logpj = my_suff_stat['logpj']
-        if isinstance(logpj, DeviceArray) and getattr(logpj, "lse", None) is not None:
-            lp, lse = logpj.tensor, logpj.lse
-        else:
-            lp = torch.from_numpy(np.ascontiguousarray(np.asarray(logpj), dtype=np.float64)).to(self.device)
-            lse = torch.logsumexp(lp, dim=1)
-        lp, lse = lp.contiguous(), lse.contiguous()
-        assert tuple(lp.shape) == (my_N, Kt)
-        N = self._global_count(res, my_N)
-
         A_pi_gamma = self.get_scaling_factors(pi)
         dlog.append("prior_mass", A_pi_gamma)
-
-        # data truncation (dsc_et.py:825-843): keep the datapoints STRICTLY above the N_use-th largest evidence
-        lse_cut, cut_dev = float("-inf"), None
-        if anneal['Ncut_factor'] > 0.0:
-            tracing.tracepoint("M_step:truncating")
-            N_use = int(N * (1 - (1 - A_pi_gamma) * anneal['Ncut_factor'])) or N    # (0: upstream's allsort(...)[-0] keeps everything)
-            # the reference cuts on un-stabilised sums of exp(logpj), which are exactly 0 below the
-            # underflow boundary: with the cut among those only strictly positive sums survive
-            if lse.is_cuda and my_N:      # (the cut stays on the device: the row pass reads it there)
-                cut_dev = torch.clamp_min(self._kth_select_dev(lse, N_use), _LOG_UNDERFLOW)
-                lse_cut = float("nan")    # (not -inf: statistics a fused E-step pass may have left do not apply)
-            else:
-                lse_cut = max(self._kth_largest_global(lse, N_use), _LOG_UNDERFLOW)
-
-        tracing.tracepoint("M_step:iterating")
-        lib = _lib.load()
-        n_stats = lib.pm_dsc_stats_len(H, D)
-        P = self._params(anneal, pi, sigma)
-        fused = self._dsc_fused_stats(logpj, res, cand, P, pi, lse_cut) if my_N else None
-        stats = fused["stats"] if fused else self._buf("dsc_stats", (n_stats,))
-        if not fused:
-            stats.zero_()
-        expect = self._buf("expect", (my_N, H))
-        # (the fused pass has used the prior already; only the M-step's own row pass needs it again)
-        prior = None if fused else self._upload("dsc_prior", self._prior(pi))
-        if my_N:
-            self._rows_and_wp((_ptr(lp), Kt, _ptr(lse), ctypes.c_double(lse_cut), _ptr(cand), _ptr(tab), S,
-                               _ptr(prior) if prior is not None else None,
-                               ctypes.byref(P), my_N, H, D, Hp, _ptr(expect), H, _ptr(stats)),
-                              Kt, expect, Y, stats, my_N, self.K, int(P.flags), Hp, S, fused=fused, cut_dev=cut_dev)
-        comm.allreduce_device(stats)      # replaces dsc_et.py:648,738,739,747,769 and the allreduce in get_likelihood
-        self._mstep_res = res
-        return self._finalize(stats, model_params)
+        return pi, pi, A_pi_gamma, ()
 
     def _finalize(self, stats, model_params):
-        """Parameter updates from the all-reduced statistics (dsc_et.py:736-774), one device->host copy."""
+        """Parameter updates from the all-reduced statistics (dsc_et.py:736-774), one device->host copy.  Logs ``L`` and
+        ``N_use``.  A numerically singular Wq goes to the reference's own LAPACK lstsq on the host."""
         H, D, K, K0 = self.H, self.D, self.K, self._K_0
         pi = np.asarray(model_params['pi'], dtype=np.float64)
         sigma = model_params['sigma']
-        o_wq, o_qd = H * D, H * D + H * H
-        o_cnt = o_qd + H
-        Wp = stats[:o_wq].view(H, D)
-        Wq_u = stats[o_wq:o_qd].view(H, H)
-        qdiag = stats[o_qd:o_cnt]
-        parts = [stats[o_cnt:o_cnt + 8 + 4]]
-        learn_W = 'W' in self.to_learn
-        Wq = None
-        if learn_W:
-            tracing.tracepoint("M_step:update W")
-            X, status, Wq = self._solve_normal_eq(Wq_u, qdiag, Wp.contiguous())
-            parts += [status, X.reshape(-1)]
-        flat = torch.cat(parts)
-        self._seed_rec = None
-        res = getattr(self, "_mstep_res", None)
-        if flat.is_cuda and learn_W and res is not None and self.speculate:
-            host = self._download(flat, then=lambda: self._seed_next(res, X))
-        else:
-            host = self._download(flat) if flat.is_cuda else flat.numpy()
+        host, W_out = self._update_W(stats, model_params, lambda Wq, Wp: np.linalg.lstsq(Wq, Wp, rcond=None)[0])
         cnt = host[:8]
         my_sigma, Fs, N_use = float(host[8]) / D, float(host[9]), int(round(host[10]))
 
@@ -420,27 +358,6 @@ class DSC_ET(DeviceCAModel):
         with np.errstate(divide='ignore', invalid='ignore'):
             L = -0.5 * D * np.log(2 * np.pi * sigma ** 2) + np.float64(Fs) / Nf          # dsc_et.py:845-870
         dlog.append('L', L)
-
-        W = np.asarray(model_params['W'])
-        if learn_W:
-            ok = self._solve_ok(float(host[12]), float(host[13]))
-            redo = self._solve_accurate(float(host[14])) if ok else None
-            if redo is not None:    # the device rejected the inverse's warm start: W from the refined solve, seed void
-                self._seed_rec = None
-                W_new = redo
-            elif ok:
-                W_new = host[15:15 + H * D].reshape(H, D).copy()
-                if self._seed_rec is not None:
-                    self._seed_rec["W"] = W_new.copy().transpose()   # private snapshot of the W handed back (same memory order: a
-                                                                     # contiguous copy and a contiguous comparison)
-            else:   # numerically singular Wq: the reference's own LAPACK lstsq on the host
-                self._seed_rec = None
-                self._winv_prev = None        # never warm-start the next inverse from a rejected one
-                with small_blas():
-                    W_new = np.linalg.lstsq(Wq.cpu().numpy(), Wp.cpu().numpy(), rcond=None)[0]
-            W_out = W_new.transpose()
-        else:
-            W_out = W
 
         if 'pi' in self.to_learn:
             tracing.tracepoint("M_step:update pi")
@@ -488,96 +405,51 @@ class DSC_ET(DeviceCAModel):
         upstream the proper (K, S) ``state_abs`` is restored afterwards (upstream leaves the 1-D one behind)."""
         assert 'y' in test_data, "Key 'y' in test_data dict not defined."
         model_params = self.check_params(model_params)
-        comm = self.comm
-        my_y = test_data['y']
-        if isinstance(my_y, DeviceArray):
-            my_y = my_y.tensor
-        my_N, D = my_y.shape
-        H, K = self.H, self.K
-        nss = (K - 1) * H
-        Hprime_start, gamma_start = self.Hprime, self.gamma
-        if topK == -1:
-            topK = self.state_matrix.shape[0]
-        dev = self.device
-        res_s = torch.zeros((my_N, topK, H), dtype=torch.int8, device=dev)
-        res_m = torch.zeros((my_N, H), dtype=torch.float64, device=dev)
-        res_p = torch.zeros((my_N, topK), dtype=torch.float64, device=dev)
-        res_gamma = torch.zeros((my_N,), dtype=torch.float64, device=dev)
-        res_Hprime = torch.zeros((my_N,), dtype=torch.float64, device=dev)
-        nz_vals = torch.tensor([self.states[k] for k in range(K) if k != self._K_0], dtype=torch.int8, device=dev)
+        H, dev = self.H, self.device
+        nss = (self.K - 1) * H
+        nz_vals = torch.tensor([self.states[k] for k in range(self.K) if k != self._K_0], dtype=torch.int8, device=dev)
 
-        cur_y = my_y
-        which = torch.ones(my_N, dtype=torch.bool, device=dev)
-        try:
-            while bool(which.any()):
-                ind_n = torch.nonzero(which).flatten()
-                logpj, cand = self.compute_lpj(anneal, model_params, {'y': cur_y})
-                lp = logpj.tensor if isinstance(logpj, DeviceArray) else torch.as_tensor(np.asarray(logpj)).to(dev)
-                cd = (cand.tensor if isinstance(cand, DeviceArray) else torch.as_tensor(np.asarray(cand)).to(dev)).long()
-                n_cur, Kt = lp.shape
-                Hp = self.Hprime
-                k_eff = min(topK, Kt)
-                # normalisation, top-K columns and the marginals (:983-1016): one HIP pass over the rows
-                # (pm_infer_topk_cols_f64; the marginal of a candidate combines its FIRST non-zero value's one-cause state
-                # with the multi-cause states in which it takes the value 1: the masks mark exactly those)
-                SMh = self.state_matrix if self.no_states else np.zeros((1, Hp))
-                mk = ((SMh == 1).astype(np.int64) << np.arange(SMh.shape[1])[None, :]).sum(axis=1).astype(np.uint16)
-                masks_d = torch.from_numpy(mk.view(np.int16).copy()).to(dev)
-                lp = lp.contiguous() if lp.stride(1) != 1 else lp
-                cd32 = cd.to(torch.int32).contiguous()
-                top_idx32 = torch.empty((n_cur, k_eff), dtype=torch.int32, device=dev)
-                top_val = torch.empty((n_cur, k_eff), dtype=torch.float64, device=dev)
-                top_rel = torch.empty((n_cur, k_eff), dtype=torch.float64, device=dev)
-                m_blk = torch.empty((n_cur, H), dtype=torch.float64, device=dev)
-                self._call("infer_topk", "pm_infer_topk_cols_f64", _ptr(lp), lp.stride(0), _ptr(cd32), _ptr(masks_d), n_cur, H,
-                           Hp, self.no_states, nss, k_eff, _ptr(top_idx32), _ptr(top_val), _ptr(top_rel), _ptr(m_blk), H,
-                           self._stream())
-                if bool((top_idx32 < 0).any()):
-                    raise _lib.HipError("inference: non-finite log-joints (NaN) in %d datapoint(s)"
-                                        % int((top_idx32 < 0).any(dim=1).sum()))
-                top_idx = top_idx32.long()
-                res_Hprime[ind_n] = float(self.Hprime)
-                res_gamma[ind_n] = float(self.gamma)
-                SM = torch.from_numpy(self.state_matrix.astype(np.int8)).to(dev) if self.no_states else \
-                    torch.zeros((1, Hp), dtype=torch.int8, device=dev)
-                s_blk = res_s[ind_n, :k_eff].clone()
-                single = (top_idx >= 1) & (top_idx <= nss)
-                if bool(single.any()):
-                    nn_, mm_ = torch.nonzero(single, as_tuple=True)
-                    si = top_idx[nn_, mm_] - 1
-                    s_blk[nn_, mm_, si % H] = nz_vals[si // H]
-                multi = top_idx > nss
-                if bool(multi.any()):
-                    nn_, mm_ = torch.nonzero(multi, as_tuple=True)
-                    rows = SM[top_idx[nn_, mm_] - nss - 1]                           # (M, Hp) latent values
-                    s_blk[nn_[:, None].expand(-1, Hp), mm_[:, None].expand(-1, Hp), cd[nn_]] = rows
-                res_s[ind_n, :k_eff] = s_blk
-                res_p[ind_n, :k_eff] = top_val if logprob else torch.exp(top_rel)
-                res_m[ind_n] = m_blk
-                if not adaptive:
-                    break
-                which = ((res_s[:, 0, :] != 0).sum(-1) == self.gamma)
-                if not bool(which.any()):
-                    break
-                if (Hprime_max is not None and self.Hprime == Hprime_max) and \
-                        (gamma_max is not None and self.gamma == gamma_max):
-                    break
-                cur_y = my_y[which.cpu().numpy()] if not torch.is_tensor(my_y) else my_y[which]
-                print("Rank %i: For %i data points MAP state has activity equal to gamma." % (comm.rank, int(which.sum())))
-                if not ((self.Hprime == self.H) or (Hprime_max is not None and self.Hprime == Hprime_max)):
-                    self.Hprime += 1
-                if (self.gamma == self.H) or (gamma_max is not None and self.gamma == gamma_max):
-                    continue
-                self.gamma += 1
-                print("Rank %i: Updating state matrix and running again." % comm.rank)
-                self.no_states, self.state_matrix, self.state_abs = generate_state_matrix(self.Hprime, self.gamma,
-                                                                                           self.states)
-        finally:
-            self.Hprime, self.gamma = Hprime_start, gamma_start
-            self._build_state_tables()
-        m_out = res_m if logprob else torch.exp(res_m)
-        return {'s': res_s.cpu().numpy(), 'm': m_out.cpu().numpy(), 'p': res_p.cpu().numpy(),
-                'gamma': res_gamma.cpu().numpy(), 'Hprime': res_Hprime.cpu().numpy()}
+        def run_pass(lp, cd, k_eff, ind_n, buf):
+            n_cur, Hp = lp.shape[0], self.Hprime
+            # normalisation, top-K columns and the marginals (:983-1016): one HIP pass over the rows
+            # (pm_infer_topk_cols_f64; the marginal of a candidate combines its FIRST non-zero value's one-cause state
+            # with the multi-cause states in which it takes the value 1: the masks mark exactly those)
+            SMh = self.state_matrix if self.no_states else np.zeros((1, Hp))
+            mk = ((SMh == 1).astype(np.int64) << np.arange(SMh.shape[1])[None, :]).sum(axis=1).astype(np.uint16)
+            masks_d = torch.from_numpy(mk.view(np.int16).copy()).to(dev)
+            cd32 = cd.to(torch.int32).contiguous()
+            top_idx32 = torch.empty((n_cur, k_eff), dtype=torch.int32, device=dev)
+            top_val = torch.empty((n_cur, k_eff), dtype=torch.float64, device=dev)
+            top_rel = torch.empty((n_cur, k_eff), dtype=torch.float64, device=dev)
+            m_blk = torch.empty((n_cur, H), dtype=torch.float64, device=dev)
+            self._call("infer_topk", "pm_infer_topk_cols_f64", _ptr(lp), lp.stride(0), _ptr(cd32), _ptr(masks_d), n_cur, H,
+                       Hp, self.no_states, nss, k_eff, _ptr(top_idx32), _ptr(top_val), _ptr(top_rel), _ptr(m_blk), H,
+                       self._stream())
+            self._refuse_nan(top_idx32)
+            top_idx = top_idx32.long()
+            SM = torch.from_numpy(self.state_matrix.astype(np.int8)).to(dev) if self.no_states else \
+                torch.zeros((1, Hp), dtype=torch.int8, device=dev)
+            s_blk = buf['s'][ind_n, :k_eff].clone()
+            single = (top_idx >= 1) & (top_idx <= nss)
+            if bool(single.any()):
+                nn_, mm_ = torch.nonzero(single, as_tuple=True)
+                si = top_idx[nn_, mm_] - 1
+                s_blk[nn_, mm_, si % H] = nz_vals[si // H]
+            multi = top_idx > nss
+            if bool(multi.any()):
+                nn_, mm_ = torch.nonzero(multi, as_tuple=True)
+                rows = SM[top_idx[nn_, mm_] - nss - 1]                           # (M, Hp) latent values
+                s_blk[nn_[:, None].expand(-1, Hp), mm_[:, None].expand(-1, Hp), cd[nn_]] = rows
+            buf['s'][ind_n, :k_eff] = s_blk
+            buf['p'][ind_n, :k_eff] = top_val if logprob else torch.exp(top_rel)
+            buf['m'][ind_n] = m_blk
+
+        def regenerate():
+            self.no_states, self.state_matrix, self.state_abs = generate_state_matrix(self.Hprime, self.gamma, self.states)
+
+        return self._inference_result(self._adaptive_inference(anneal, model_params, test_data, topK, adaptive, Hprime_max,
+                                                               gamma_max, run_pass, regenerate, self._build_state_tables),
+                                      logprob)
 
     def calculate_respons(self, anneal, model_params, data):
         """Posterior over the truncated states (dsc_et.py:776-784)."""
