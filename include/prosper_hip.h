@@ -118,6 +118,33 @@ int pm_gemm_tn_acc_rows_f64(const double *A, int64_t lda, const double *B, int64
                             int64_t N, const int32_t *rows, const int32_t *count, int64_t max_rows, int64_t zero_row,
                             void *stream);
 
+/* Which kernels pm_gemm_nt_f64 would launch for an (M, N, K) product on the current device -- the function its launcher
+ * takes every decision from; nothing is launched.  `aligned`: A and B 16-byte aligned with even lda and ldb (what the
+ * launcher derives from its pointers).  Returns a mask of PM_NT_PLAN_* (> 0), or PM_EINVAL (null `out`, M, N or K < 1) /
+ * PM_ERANGE (a dimension above INT32_MAX) as the launcher does; out[0] = resident workgroup slots (2 per CU; 512 without a
+ * device), out[1] = 128-row panels that run as whole rounds of un-split tiles, out[2] = K-slices of the ragged remainder's
+ * tiles (1: not split).  The deterministic build never splits K and reports its own choice. */
+#define PM_NT_PLAN_DMA_MAIN 0x001       /* LDS-DMA kernel, whole rounds of un-split 128-row tiles                        */
+#define PM_NT_PLAN_DMA_REST 0x002       /* ... the ragged remainder (or a product below one round) un-split, own launch  */
+#define PM_NT_PLAN_DMA_REST_SPLIT 0x004 /* ... split over K (zero fill + f64 atomics), own launch                        */
+#define PM_NT_PLAN_DMA_FUSED 0x008      /* whole rounds and the remainder's K-slices in ONE launch                       */
+#define PM_NT_PLAN_DMA_REST64 0x010     /* the remainder in un-split 64-row tiles                                        */
+#define PM_NT_PLAN_REG_MT1 0x020        /* register-staged kernel, 32-row tiles                                          */
+#define PM_NT_PLAN_REG_MT2 0x040        /* ... 64-row tiles                                                              */
+#define PM_NT_PLAN_REG_MT4 0x080        /* ... 128-row tiles                                                             */
+#define PM_NT_PLAN_ALIGNED 0x100        /* the 16-byte-load flavour (every LDS-DMA path; register kernels: even K too)   */
+#define PM_NT_PLAN_DMA_WHOLE 0x200      /* deterministic build: rounds and un-split remainder as ONE launch of 128-row tiles */
+int pm_gemm_nt_plan(int64_t M, int64_t N, int64_t K, int aligned, int32_t *out);
+/* The same for pm_gemm_tn_acc_f64 / pm_gemm_tn_acc_gated_f64 (`aligned` as above; PM_EINVAL for null `out`, M or N < 1,
+ * K < 0; PM_ERANGE for M or N above INT32_MAX).  K == 0 launches nothing: mask 0.  out[0] = slots, out[1] = K-splits
+ * (grid.y of the first launch), out[2] = rows of K per split (saturated at INT32_MAX). */
+#define PM_TN_PLAN_DMA 0x01             /* LDS-DMA kernel (whole 128 x 128 tiles, K >= 64)                               */
+#define PM_TN_PLAN_REG 0x02             /* register-staged kernel                                                        */
+#define PM_TN_PLAN_ALIGNED 0x04         /* the 16-byte-load flavour                                                      */
+#define PM_TN_PLAN_REMAP 0x08           /* K-splits a multiple of 8: all tiles of a split on one XCD                     */
+#define PM_TN_PLAN_TAIL 0x10            /* a register-staged launch for the last K % 8 rows follows the LDS-DMA one      */
+int pm_gemm_tn_plan(int64_t M, int64_t N, int64_t K, int aligned, int32_t *out);
+
 /* out[n] = sum_d Y[n,d]^2 -- np.inner(y, y) of bsc_et.py:111 and (y**2).sum() of :172;
  * computed once per resident data shard. */
 int pm_row_sqnorm_f64(const double *Y, int64_t ldy, int64_t N, int64_t D, double *out, void *stream);

@@ -40,6 +40,8 @@ SIGNATURES = {
     "pm_gemm_nn_small_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, i64, i64, i64, i64, c_dp]),
     "pm_gemm_nt_small_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, i64, i64, i64, i64, c_dp]),
     "pm_gemm_tn_acc_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, i64, i64, i64, i64, c_dp]),
+    "pm_gemm_nt_plan": (C.c_int, [i64, i64, i64, C.c_int, C.POINTER(C.c_int32)]),
+    "pm_gemm_tn_plan": (C.c_int, [i64, i64, i64, C.c_int, C.POINTER(C.c_int32)]),
     "pm_row_sqnorm_f64": (C.c_int, [c_dp, i64, i64, i64, c_dp, c_dp]),
     "pm_col_moments_f64": (C.c_int, [c_dp, i64, i64, i64, c_dp, c_dp, c_dp]),
     "pm_row_wsqnorm_f64": (C.c_int, [c_dp, i64, i64, i64, c_dp, c_dp, c_dp]),
@@ -203,7 +205,7 @@ class HipError(RuntimeError):
     pass
 
 
-MIN_VERSION = 1019
+MIN_VERSION = 1020
 _lib = None
 _lib_det = None
 LIB_PATH_DET = os.path.join(os.path.dirname(LIB_PATH), "libprosper_hip_det.so")

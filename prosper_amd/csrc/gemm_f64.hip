@@ -772,13 +772,10 @@ void launch_nt_mt(bool al, const double *A, int64_t lda, const double *B, int64_
                            tiles_n);
 }
 
-// LDS-DMA kernel over M rows; nsplit > 1 zeroes C and splits K over grid.y
+// LDS-DMA kernel over M rows; nsplit > 1 zeroes C and splits K over grid.y in slices of kps K-steps (nt_slices)
 void launch_nt_dma(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int M, int N,
-                   int K, int nsplit, hipStream_t s) {
+                   int K, int kps, int nsplit, hipStream_t s) {
     const int tiles_m = (M + 127) / 128, tiles_n = (N + BN - 1) / BN;
-    const int nk = K / DK;
-    int kps = (nk + nsplit - 1) / nsplit;
-    nsplit = (nk + kps - 1) / kps;
     if (nsplit > 1) (void)hipMemset2DAsync(C, (size_t)ldc * sizeof(double), 0, (size_t)N * sizeof(double), (size_t)M, s);
     dim3 grid((unsigned)((int64_t)tiles_m * tiles_n), (unsigned)nsplit), block(256);
     if (nsplit > 1)
@@ -800,11 +797,9 @@ void launch_nt_dma64(const double *A, int64_t lda, const double *B, int64_t ldb,
 
 // whole rounds of un-split tiles + K-slices of the ragged last round's tiles in ONE launch (see the kernel)
 void launch_nt_dma_fused(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int M, int N,
-                         int K, int main_panels, int nsplit, hipStream_t s) {
+                         int K, int main_panels, int rest_kps, int nsplit, hipStream_t s) {
     const int tiles_m = (M + 127) / 128, tiles_n = (N + BN - 1) / BN;
     const int nk = K / DK;
-    int rest_kps = (nk + nsplit - 1) / nsplit;
-    nsplit = (nk + rest_kps - 1) / rest_kps;
     const int main_tiles = main_panels * tiles_n, rest_tiles = (tiles_m - main_panels) * tiles_n;
     (void)hipMemset2DAsync(C + (int64_t)main_panels * 128 * ldc, (size_t)ldc * sizeof(double), 0, (size_t)N * sizeof(double),
                            (size_t)(M - main_panels * 128), s);
@@ -813,29 +808,42 @@ void launch_nt_dma_fused(const double *A, int64_t lda, const double *B, int64_t 
                        main_tiles, rest_kps);
 }
 
-}  // namespace
+// ---------------------------------------------------------------------------------------------
+// The dispatch decisions, apart from the launches: pm_gemm_nt_f64 / pm_gemm_tn_acc_gated_f64 switch on what these return
+// and pm_gemm_nt_plan / pm_gemm_tn_plan report it (a test can then say which kernel its shape runs).
+// ---------------------------------------------------------------------------------------------
+struct NtPlan {
+    int mask;             // PM_NT_PLAN_*
+    int slots;
+    int64_t main_panels;  // 128-row panels in whole rounds of un-split tiles
+    int nsplit, kps;      // K-slices of the remainder's tiles and K-steps (of DK columns) per slice
+};
 
-extern "C" int pm_gemm_nt_f64(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc,
-                              int64_t M, int64_t N, int64_t K, void *stream) {
-    if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || lda < K || ldb < K || ldc < N) return PM_EINVAL;
-    if (M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return PM_ERANGE;
-    const bool al = aligned16(A) && aligned16(B) && (lda % 2 == 0) && (ldb % 2 == 0) && (K % 2 == 0);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+// `want` K-slices of nk K-steps: the slice length, and the number of slices that are not empty
+inline void nt_slices(int nk, int want, int &kps, int &nsplit) {
+    kps = (nk + want - 1) / want;
+    nsplit = (nk + kps - 1) / kps;
+}
 
+// `aligned`: A and B 16-byte aligned, lda and ldb even.  M, N, K in [1, INT32_MAX].
+NtPlan nt_plan(int64_t M, int64_t N, int64_t K, bool aligned) {
+    NtPlan p = {0, resident_slots(), 0, 1, 0};
+    const bool al = aligned && (K % 2 == 0);
     // Workgroups resident at once ("slots", 2 per CU) process the grid in rounds.  Whole rounds of
     // 128x128 tiles run un-split; the ragged remainder (and any problem smaller than one round, e.g.
     // the H x H Gram matrix) is split over K so that it still covers the chip for a fraction of a
     // round instead of leaving most CUs idle for a whole one.
-    const int slots = resident_slots();
+    const int slots = p.slots;
     const int64_t tiles_n = (N + BN - 1) / BN;
     if (al && K % DK == 0) {
+        const int nk = (int)(K / DK);
         const int64_t panels = (M + 127) / 128;
         const int64_t per_round = slots / tiles_n > 0 ? slots / tiles_n : 1;
         const int64_t main_panels = (M / 128) / per_round * per_round;
         const int64_t rest_rows = M - main_panels * 128;
+        const int64_t rest_tiles = (panels - main_panels) * tiles_n;
         int64_t nsplit = 1;
         if (rest_rows > 0) {
-            const int64_t rest_tiles = (panels - main_panels) * tiles_n;
             nsplit = slots / rest_tiles;                   // fill the slots once
             const int64_t max_split = (K / DK) / 8;        // at least 8 K-steps per workgroup
             if (nsplit > max_split) nsplit = max_split;
@@ -844,6 +852,9 @@ extern "C" int pm_gemm_nt_f64(const double *A, int64_t lda, const double *B, int
             // (3392 x 256 x 1024: 9 slices 67 us, 4 slices 56 us, 2 slices 77 us)
             if (nsplit > 4 && rest_tiles >= 32) nsplit = nsplit / 2 > 4 ? nsplit / 2 : 4;
         }
+        p.mask = PM_NT_PLAN_ALIGNED;
+        p.main_panels = main_panels;
+        p.kps = nk;
 #ifdef PM_DETERMINISTIC
         // The K-slices of a split remainder meet in f64 atomics, whose order is not fixed -- and this product (scores, selection
         // distances, ragged remainders) has no bound of its own from which a quantum could be derived: the deterministic build
@@ -855,33 +866,107 @@ extern "C" int pm_gemm_nt_f64(const double *A, int64_t lda, const double *B, int
         // ... and as ONE launch: the remainder's tiles take the slots the last whole round frees (as a launch of its own it ran
         // alone behind the rounds: 37 us for 27 tiles at GSC's config 4, on the EM loop's critical path)
         if (main_panels > 0 && rest_rows > 0) {
-            launch_nt_dma(A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, 1, s);
-            return (int)hipGetLastError();
+            p.mask |= PM_NT_PLAN_DMA_WHOLE;
+            return p;
         }
 #endif
         if (main_panels > 0 && rest_rows > 0 && nsplit > 1 && fuse_remainder()) {
-            launch_nt_dma_fused(A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, (int)main_panels, (int)nsplit, s);
-            return (int)hipGetLastError();
+            nt_slices(nk, (int)nsplit, p.kps, p.nsplit);
+            p.mask |= PM_NT_PLAN_DMA_FUSED;
+            return p;
         }
-        if (main_panels > 0) launch_nt_dma(A, lda, B, ldb, C, ldc, (int)(main_panels * 128), (int)N, (int)K, 1, s);
+        if (main_panels > 0) p.mask |= PM_NT_PLAN_DMA_MAIN;
         if (rest_rows > 0) {
-            const int64_t rest_tiles = (panels - main_panels) * tiles_n;
-            if (nsplit == 1 && main_panels > 0 && rest_tiles * 4 >= slots && rest_tiles * 10 < (int64_t)slots * 7)
-                launch_nt_dma64(A + main_panels * 128 * lda, lda, B, ldb, C + main_panels * 128 * ldc, ldc, (int)rest_rows,
-                                (int)N, (int)K, s);
-            else
-                launch_nt_dma(A + main_panels * 128 * lda, lda, B, ldb, C + main_panels * 128 * ldc, ldc, (int)rest_rows,
-                              (int)N, (int)K, (int)nsplit, s);
+            if (nsplit == 1 && main_panels > 0 && rest_tiles * 4 >= slots && rest_tiles * 10 < (int64_t)slots * 7) {
+                p.mask |= PM_NT_PLAN_DMA_REST64;
+            } else {
+                nt_slices(nk, (int)nsplit, p.kps, p.nsplit);
+                p.mask |= p.nsplit > 1 ? PM_NT_PLAN_DMA_REST_SPLIT : PM_NT_PLAN_DMA_REST;
+            }
         }
-        return (int)hipGetLastError();
+        return p;
     }
     // register-staged kernels: any alignment, any K; small tiles for small problems
     const int64_t t128 = (M + 127) / 128 * tiles_n;
     if (t128 * 2 <= slots && M > 32)
-        (M + 31) / 32 * tiles_n <= slots ? launch_nt_mt<1>(al, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, s)
-                                         : launch_nt_mt<2>(al, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, s);
+        p.mask = (M + 31) / 32 * tiles_n <= slots ? PM_NT_PLAN_REG_MT1 : PM_NT_PLAN_REG_MT2;
     else
-        launch_nt_mt<4>(al, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, s);
+        p.mask = PM_NT_PLAN_REG_MT4;
+    if (al) p.mask |= PM_NT_PLAN_ALIGNED;
+    return p;
+}
+
+struct TnPlan {
+    int mask;         // PM_TN_PLAN_*
+    int slots;
+    int64_t nsplit;   // grid.y of the first launch
+    int64_t kps;      // rows of K per split (a multiple of BK)
+};
+
+// `aligned`: A and B 16-byte aligned, lda and ldb even.  M, N in [1, INT32_MAX], K >= 1.
+TnPlan tn_plan(int64_t M, int64_t N, int64_t K, bool aligned) {
+    TnPlan p = {0, resident_slots(), 1, 0};
+    const int64_t tiles = ((M + TN_BM - 1) / TN_BM) * ((N + BN - 1) / BN);
+    // K-splits: whole rounds of resident workgroups (2 per CU), at least 8 K-steps each
+    const int slots = p.slots;
+    int64_t nsplit = (2 * slots + tiles - 1) / tiles;
+    if (nsplit * tiles > 2 * slots && nsplit > 1) nsplit = 2 * slots / tiles > 0 ? 2 * slots / tiles : 1;
+    const int64_t max_split = (K + 8 * BK - 1) / (8 * BK);
+    if (nsplit > max_split) nsplit = max_split;
+    if (nsplit < 1) nsplit = 1;
+    if (nsplit > 65535) nsplit = 65535;
+    int64_t kps = (K + nsplit - 1) / nsplit;
+    kps = (kps + BK - 1) / BK * BK;
+    nsplit = (K + kps - 1) / kps;
+    const bool al = aligned && (M % 2 == 0) && (N % 2 == 0);
+    p.kps = kps;
+    p.nsplit = nsplit;
+    if (al && M % TN_BM == 0 && N % BN == 0 && K >= 8 * DK) {
+        // LDS-DMA kernel over the first K - K % 8 rows (every split a whole number of 8-row steps, kps is a
+        // multiple of 16); the last K % 8 rows go through the register-staged kernel
+        const int64_t K8 = K - K % DK;
+        p.nsplit = (K8 + kps - 1) / kps;
+        p.mask = PM_TN_PLAN_DMA | PM_TN_PLAN_ALIGNED | (K8 < K ? PM_TN_PLAN_TAIL : 0);
+    } else {
+        p.mask = PM_TN_PLAN_REG | (al ? PM_TN_PLAN_ALIGNED : 0);
+    }
+    if (p.nsplit % 8 == 0) p.mask |= PM_TN_PLAN_REMAP;      // (gridDim.y % 8 == 0 in the kernels)
+    return p;
+}
+
+}  // namespace
+
+extern "C" int pm_gemm_nt_plan(int64_t M, int64_t N, int64_t K, int aligned, int32_t *out) {
+    if (!out || M <= 0 || N <= 0 || K <= 0) return PM_EINVAL;
+    if (M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return PM_ERANGE;
+    const NtPlan p = nt_plan(M, N, K, aligned != 0);
+    out[0] = p.slots;
+    out[1] = (int32_t)p.main_panels;
+    out[2] = p.nsplit;
+    return p.mask;
+}
+
+extern "C" int pm_gemm_nt_f64(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc,
+                              int64_t M, int64_t N, int64_t K, void *stream) {
+    if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || lda < K || ldb < K || ldc < N) return PM_EINVAL;
+    if (M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return PM_ERANGE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const NtPlan p = nt_plan(M, N, K, aligned16(A) && aligned16(B) && (lda % 2 == 0) && (ldb % 2 == 0));
+    const bool al = (p.mask & PM_NT_PLAN_ALIGNED) != 0;
+    const int main_rows = (int)(p.main_panels * 128), nk = (int)(K / DK);
+    if (p.mask & PM_NT_PLAN_DMA_WHOLE) launch_nt_dma(A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, nk, 1, s);
+    if (p.mask & PM_NT_PLAN_DMA_FUSED)
+        launch_nt_dma_fused(A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, (int)p.main_panels, p.kps, p.nsplit, s);
+    if (p.mask & PM_NT_PLAN_DMA_MAIN) launch_nt_dma(A, lda, B, ldb, C, ldc, main_rows, (int)N, (int)K, nk, 1, s);
+    if (p.mask & PM_NT_PLAN_DMA_REST64)
+        launch_nt_dma64(A + (int64_t)main_rows * lda, lda, B, ldb, C + (int64_t)main_rows * ldc, ldc, (int)M - main_rows,
+                        (int)N, (int)K, s);
+    if (p.mask & (PM_NT_PLAN_DMA_REST | PM_NT_PLAN_DMA_REST_SPLIT))
+        launch_nt_dma(A + (int64_t)main_rows * lda, lda, B, ldb, C + (int64_t)main_rows * ldc, ldc, (int)M - main_rows,
+                      (int)N, (int)K, p.kps, p.nsplit, s);
+    if (p.mask & PM_NT_PLAN_REG_MT1) launch_nt_mt<1>(al, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, s);
+    if (p.mask & PM_NT_PLAN_REG_MT2) launch_nt_mt<2>(al, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, s);
+    if (p.mask & PM_NT_PLAN_REG_MT4) launch_nt_mt<4>(al, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, s);
     return (int)hipGetLastError();
 }
 
@@ -895,7 +980,7 @@ extern "C" int pm_gemm_nt_rows_f64(const double *A, int64_t lda, const double *B
     const bool al = aligned16(A) && aligned16(B) && (lda % 2 == 0) && (ldb % 2 == 0) && (K % 2 == 0);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (al && K % DK == 0)
-        launch_nt_dma(A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, 1, s);
+        launch_nt_dma(A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, (int)(K / DK), 1, s);
     else
         launch_nt_mt<4>(al, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, s);
     return (int)hipGetLastError();
@@ -906,6 +991,18 @@ extern "C" int pm_gemm_tn_acc_f64(const double *A, int64_t lda, const double *B,
     return pm_gemm_tn_acc_gated_f64(A, lda, B, ldb, C, ldc, M, N, K, nullptr, stream);
 }
 
+extern "C" int pm_gemm_tn_plan(int64_t M, int64_t N, int64_t K, int aligned, int32_t *out) {
+    if (!out || M <= 0 || N <= 0 || K < 0) return PM_EINVAL;
+    if (M > INT32_MAX || N > INT32_MAX) return PM_ERANGE;
+    out[0] = resident_slots();
+    out[1] = out[2] = 0;
+    if (K == 0) return 0;
+    const TnPlan p = tn_plan(M, N, K, aligned != 0);
+    out[1] = (int32_t)p.nsplit;
+    out[2] = p.kps > INT32_MAX ? INT32_MAX : (int32_t)p.kps;
+    return p.mask;
+}
+
 extern "C" int pm_gemm_tn_acc_gated_f64(const double *A, int64_t lda, const double *B, int64_t ldb, double *C,
                                         int64_t ldc, int64_t M, int64_t N, int64_t K, const double *gate,
                                         void *stream) {
@@ -914,31 +1011,18 @@ extern "C" int pm_gemm_tn_acc_gated_f64(const double *A, int64_t lda, const doub
     if (K == 0) return PM_OK;
     const int tiles_m = (int)((M + TN_BM - 1) / TN_BM), tiles_n = (int)((N + BN - 1) / BN);
     const int64_t tiles = (int64_t)tiles_m * tiles_n;
-    // K-splits: whole rounds of resident workgroups (2 per CU), at least 8 K-steps each
-    const int slots = resident_slots();
-    int64_t nsplit = (2 * slots + tiles - 1) / tiles;
-    if (nsplit * tiles > 2 * slots && nsplit > 1) nsplit = 2 * slots / tiles > 0 ? 2 * slots / tiles : 1;
-    const int64_t max_split = (K + 8 * BK - 1) / (8 * BK);
-    if (nsplit > max_split) nsplit = max_split;
-    if (nsplit < 1) nsplit = 1;
-    if (nsplit > 65535) nsplit = 65535;
-    int64_t kps = (K + nsplit - 1) / nsplit;
-    kps = (kps + BK - 1) / BK * BK;
-    nsplit = (K + kps - 1) / kps;
-    const bool al = aligned16(A) && aligned16(B) && (lda % 2 == 0) && (ldb % 2 == 0) && (M % 2 == 0) && (N % 2 == 0);
-    dim3 grid((unsigned)tiles, (unsigned)nsplit), block(256);
+    const TnPlan p = tn_plan(M, N, K, aligned16(A) && aligned16(B) && (lda % 2 == 0) && (ldb % 2 == 0));
+    const int64_t kps = p.kps;
+    dim3 grid((unsigned)tiles, (unsigned)p.nsplit), block(256);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (al && M % TN_BM == 0 && N % BN == 0 && K >= 8 * DK) {
-        // LDS-DMA kernel over the first K - K % 8 rows (every split a whole number of 8-row steps, kps is a
-        // multiple of 16); the last K % 8 rows go through the register-staged kernel
+    if (p.mask & PM_TN_PLAN_DMA) {
         const int64_t K8 = K - K % DK;
-        dim3 g8((unsigned)tiles, (unsigned)((K8 + kps - 1) / kps));
-        hipLaunchKernelGGL(gemm_tn_f64_dma_kernel<false>, g8, block, 0, s, A, lda, B, ldb, C, ldc, tiles_n, K8, kps, gate,
+        hipLaunchKernelGGL(gemm_tn_f64_dma_kernel<false>, grid, block, 0, s, A, lda, B, ldb, C, ldc, tiles_n, K8, kps, gate,
                            nullptr, nullptr, 0);
-        if (K8 < K)
+        if (p.mask & PM_TN_PLAN_TAIL)
             hipLaunchKernelGGL(gemm_tn_f64_kernel<true>, dim3((unsigned)tiles, 1), block, 0, s, A + K8 * lda, lda,
                                B + K8 * ldb, ldb, C, ldc, (int)M, (int)N, K - K8, tiles_n, (int64_t)BK, gate);
-    } else if (al)
+    } else if (p.mask & PM_TN_PLAN_ALIGNED)
         hipLaunchKernelGGL(gemm_tn_f64_kernel<true>, grid, block, 0, s, A, lda, B, ldb, C, ldc, (int)M, (int)N, K,
                            tiles_n, kps, gate);
     else

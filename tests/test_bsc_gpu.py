@@ -77,20 +77,44 @@ def test_gemm_nt_small_matches_numpy_and_is_deterministic(dev, M, N, K):
         np.testing.assert_allclose(G, A @ A.T, rtol=1e-12, atol=1e-12 * np.abs(A @ A.T).max())
 
 
-@pytest.mark.parametrize("M,N,K", [(100000, 128, 256), (70000, 256, 64), (65536 + 64 * 150 + 7, 128, 256)])
-def test_gemm_nt_ragged_last_round_in_64_row_tiles(dev, M, N, K):
-    """pm_gemm_nt_f64 on tall products whose last round of 128-row tiles would fill a quarter to 70 % of the resident
-    slots and whose K is too short to split: that round runs in 64-row tiles (gemm_nt_f64_dma_kernel<false, 64>).  Rows
-    across the seam between the two launches and the ragged end against torch."""
+def _gemm_nt_tall_against_torch(dev, M, N, K, want_bits, forbidden_bits):
     from prosper_amd import _lib
     g = torch.Generator(device=dev).manual_seed(M + N)
     a = torch.randn(M, K, generator=g, device=dev, dtype=torch.float64)
     b = torch.randn(N, K, generator=g, device=dev, dtype=torch.float64)
     c = torch.full((M, N), float("nan"), dtype=torch.float64, device=dev)
+    out = (ctypes.c_int32 * 3)()
+    mask = _lib.load().pm_gemm_nt_plan(M, N, K, 1, out)
+    assert out[0] == 2 * torch.cuda.get_device_properties(dev).multi_processor_count
+    assert mask & want_bits == want_bits and mask & forbidden_bits == 0, hex(mask)      # (shapes chosen for 256 CUs)
     _lib.call("pm_gemm_nt_f64", _p(a), K, _p(b), K, _p(c), N, M, N, K, _stream())
     ref = a @ b.t()
     err = float((c - ref).abs().max())
     assert err <= 1e-11 * float(ref.abs().max()), err
+
+
+# PM_NT_PLAN_* of include/prosper_hip.h
+_NT_MAIN, _NT_REST, _NT_REST_SPLIT, _NT_FUSED, _NT_REST64 = 0x001, 0x002, 0x004, 0x008, 0x010
+
+
+@pytest.mark.parametrize("M,N,K", [(100000, 128, 256),                  # 270 tiles behind one round of 512: too many to split
+                                   (65536 + 128 * 300 + 7, 128, 256),   # 301 tiles
+                                   (65536 + 128 * 100 + 7, 256, 64),    # 202 tiles, 8 K-steps: too short to split
+                                   (32768 + 128 * 40 + 65, 400, 40)])   # 164 tiles with a ragged column tile, 5 K-steps
+def test_gemm_nt_ragged_last_round_in_64_row_tiles(dev, M, N, K):
+    """pm_gemm_nt_f64 on tall products whose last round of 128-row tiles would fill a quarter to 70 % of the resident
+    slots and whose K is too short to split (or whose tiles are too many to): that round runs in 64-row tiles
+    (gemm_nt_f64_dma_kernel<false, 64>) -- pm_gemm_nt_plan says so.  Rows across the seam between the two launches and the
+    ragged end against torch."""
+    _gemm_nt_tall_against_torch(dev, M, N, K, _NT_MAIN | _NT_REST64, _NT_REST | _NT_REST_SPLIT | _NT_FUSED)
+
+
+@pytest.mark.parametrize("M,N,K,bits", [(70000, 256, 64, _NT_MAIN | _NT_REST),          # 70 tiles: under a quarter of a round, un-split
+                                        (65536 + 64 * 150 + 7, 128, 256, _NT_FUSED)])  # 76 tiles in 4 K-slices, one launch
+def test_gemm_nt_ragged_last_round_in_128_row_tiles(dev, M, N, K, bits):
+    """... and the tall products whose last round stays in 128-row tiles: a remainder below a quarter of the slots that
+    cannot be split (main rounds, then an un-split launch), and one that splits over K inside the main launch."""
+    _gemm_nt_tall_against_torch(dev, M, N, K, bits, _NT_REST64 | (0x00F & ~bits))
 
 
 def test_gemm_nt_layout_asymmetric(dev):
