@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
 """Whole-image denoising by overlapping patches on an image the models are correctly specified for.
 
-    python examples/denoise_image.py [bsc|mca] [--size 128] [--p 5] [--stride 1] [--steps 50]
+    python examples/denoise_image.py [bsc|mca] [--size 128] [--p 5] [--stride 1] [--steps 50] [--missing FRACTION]
 
 No file is read.  The script draws a *bars image*: row indicators r_i and column indicators c_j ~ Bernoulli(pi),
 clean[i, j] = a (r_i + c_j) (MCA: a max(r_i, c_j)), plus Gaussian noise of standard deviation sigma.  Every p x p patch of
 that image is a datapoint of the bars model with H = 2p (p horizontal and p vertical bars of height a), so the model is
 correctly specified for every overlapping patch.  The model is trained on the noisy image's own patches -- extracted on the
 device and handed to EM as they are, with the annealing schedule of examples/bars_learning.py -- and the image is denoised
-with ``reconstruct_image`` at the learned and at the generating parameters; noisy and denoised MSE / PSNR are printed."""
+with ``reconstruct_image`` at the learned and at the generating parameters; noisy and denoised MSE / PSNR are printed.
+
+``--missing FRACTION`` (missing values): after the noise that share of the pixels is dropped at random.  The
+model still trains on the complete noisy image -- training on incomplete patches is not built --, the reconstruction runs
+with the mask (``reconstruct_image(..., mask=)``; the dropped pixels hold NaN), and the MSE is printed separately over the
+observed pixels (denoising) and over the missing ones (inpainting, next to filling them with the observed pixels' mean)."""
 import argparse
 import os
 import sys
@@ -61,6 +66,8 @@ def main():
     ap.add_argument("--sigma", type=float, default=1.0)
     ap.add_argument("--pi", type=float, default=0.2)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--missing", type=float, default=0.0, metavar="FRACTION",
+                    help="share of pixels dropped after the noise; the reconstruction runs with the mask")
     a = ap.parse_args()
     np.random.seed(a.seed)
     rng = np.random.RandomState(a.seed)
@@ -86,6 +93,19 @@ def main():
     peak = float(clean.max()) or 1.0
     print("%s, %d x %d bars image (a = %g, sigma = %g, pi = %g), %d x %d patches at stride %d, %d patches trained on, %d EM steps"
           % (a.model.upper(), a.size, a.size, a.a, a.sigma, a.pi, a.p, a.p, a.stride, len(Y), a.steps))
+    if a.missing > 0.0:
+        if not a.missing < 1.0:
+            ap.error("--missing is a fraction in [0, 1)")
+        mask = rng.uniform(size=clean.shape) >= a.missing
+        holes = np.where(mask, noisy, np.nan)
+        print("  %.1f %% of the pixels dropped after the noise; trained on the complete noisy image" % (100 * (1 - mask.mean())))
+        mse = lambda img, sel: float(((np.asarray(img) - clean)[sel] ** 2).mean())
+        print("  %-44s MSE observed %.4f   missing %.4f (filled with the observed mean)"
+              % ("noisy image", mse(noisy, mask), mse(np.full_like(clean, noisy[mask].mean()), ~mask)))
+        for tag, params in (("learned", learned), ("generating", gt)):
+            out = rmodel.reconstruct_image(params, holes, mask=mask, stride=a.stride)
+            print("  %-44s MSE observed %.4f   missing %.4f" % ("reconstructed, %s parameters" % tag, mse(out, mask), mse(out, ~mask)))
+        return
     report("noisy image", noisy, clean, peak)
     report("denoised, learned parameters", rmodel.reconstruct_image(learned, noisy, stride=a.stride), clean, peak)
     report("denoised, generating parameters", rmodel.reconstruct_image(gt, noisy, stride=a.stride), clean, peak)

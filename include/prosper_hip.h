@@ -986,6 +986,45 @@ int pm_patches_accumulate_f64(const double *est, int64_t lde, const double *mean
 int pm_patches_finish_f64(const double *acc, int64_t lda, double *out, int64_t ldo, int64_t B, int64_t Hi, int64_t Wi,
                           int64_t ph, int64_t pw, int64_t stride, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Missing values: masked E-steps for inference (masked_kernels.hip)
+ * ---------------------------------------------------------------------------------------
+ * mask (N, ldm >= D) bytes, non-zero = observed.  An unobserved value is selected away where it is read (m ? v : 0), never
+ * multiplied: NaN or inf there changes no bit of any output.  No atomics, every output element is written once by one lane
+ * and a row's sums over d run in an order fixed by D alone: both builds return the same bits and a row's bits depend on that
+ * row (of the data and of the mask) and on the parameters alone.  Every entry checks its arguments before it touches a
+ * device: PM_EINVAL for a null pointer, a negative size or a short leading dimension, PM_ERANGE past a limit; N == 0
+ * launches nothing.
+ *
+ * pm_masked_prepare_f64: X0[n,d] = m ? Y[n,d] - mu[d] : 0 (mu NULL: 0), Mf[n,d] = m ? 1 : 0 (Mf may be NULL), xnorm2[n] =
+ * sum_d X0^2, dn[n] = number of observed dimensions.  With these the terms that are dense over H are two products of
+ * pm_gemm_nt_rows_f64: b = X0 . W (N, H) and diag G_n = Mf . (W o W) (N, H). */
+int pm_masked_prepare_f64(const double *Y, int64_t ldy, const uint8_t *mask, int64_t ldm, const double *mu, int64_t N,
+                          int64_t D, double *X0, int64_t ldx, double *Mf, int64_t ldf, double *xnorm2, int32_t *dn,
+                          void *stream);
+/* BSC: per row, the Hprime candidates with the largest b_h / sqrt(g_h) (a term with g_h = 0 counts as 0; ascending, ties
+ * towards the larger index: the order of pm_bsc_select_f64; a row with nothing observed gets the Hprime largest indices)
+ * into cand (N, Hprime), the Hprime (Hprime - 1) / 2 masked products sum_d m_d Wt[c_i, d] Wt[c_j, d] of the candidates' rows
+ * of Wt (H, ldw >= D), and logpj (N, ldl >= 1 + H + S) in the layout of pm_bsc_estep_f64 with
+ *   e_0 = xnorm2, e_h = g_h - 2 b_h + xnorm2, e_s = xnorm2 - 2 sum b_c + sum g_c + 2 sum_{i<j} pair_ij
+ * (params.mu_sqnorm is not read: mu is part of X0).  H <= PM_MAX_H, Hprime <= PM_MAX_HPRIME, S <= 65535. */
+int pm_bsc_masked_estep_f64(const double *b, int64_t ldb, const double *g, int64_t ldg, const double *xnorm2,
+                            const uint8_t *mask, int64_t ldm, const double *Wt, int64_t ldw, const uint16_t *state_masks,
+                            int64_t S, const pm_bsc_estep_params *params_host, int64_t N, int64_t H, int64_t D,
+                            int64_t Hprime, int32_t *cand, double *logpj, int64_t ldl, void *stream);
+/* MCA / MMCA selection scores R[n,h] = sum_d m_d max(W[h,d] - Y[n,d], 0): pm_mca_select_scores_f64 over the observed
+ * dimensions. */
+int pm_mca_masked_select_scores_f64(const double *Y, int64_t ldy, const uint8_t *mask, int64_t ldm, const double *W,
+                                    int64_t ldw, double *R, int64_t ldr, int64_t N, int64_t H, int64_t D, void *stream);
+/* MCA / MMCA E-step: pm_mca_estep_f64 with e_s = sum_d m_d (X0[n,d] - Wbar_d(s))^2 for the multi-cause states and, for the
+ * one-cause states, the per-row wnorm2_obs (N, ldwn >= H) = Mf . (W o W), scores = X0 . W and xnorm2, all from
+ * pm_masked_prepare_f64 with mu = NULL.  Same power functions, limits (D <= 1024) and outputs. */
+int pm_mca_masked_estep_f64(const double *scores, int64_t lds, const double *wnorm2_obs, int64_t ldwn, const double *xnorm2,
+                            const double *X0, int64_t ldx, const uint8_t *mask, int64_t ldm, const double *Wrho,
+                            const int32_t *cand, const uint16_t *state_masks, int64_t S, const pm_mca_params *params_host,
+                            int64_t N, int64_t H, int64_t D, int64_t Hprime, double *logpj, int64_t ldl, double *lse1,
+                            double *lseb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

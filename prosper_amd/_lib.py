@@ -193,6 +193,12 @@ SIGNATURES = {
                                       i64, c_dp, i64, i64, i64, c_dp]),
     "pm_recon_mca_f64": (C.c_int, [c_dp, i64, c_dp, c_dp, c_dp, c_dp, C.c_double, C.c_int, i64, i64, i64, i64, i64, c_dp, i64,
                                    c_dp]),
+    "pm_masked_prepare_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, i64, i64, c_dp, i64, c_dp, i64, c_dp, c_dp, c_dp]),
+    "pm_bsc_masked_estep_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, c_dp, i64, c_dp, i64, c_dp, i64,
+                                          C.POINTER(EStepParams), i64, i64, i64, i64, c_dp, c_dp, i64, c_dp]),
+    "pm_mca_masked_select_scores_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, i64, c_dp, i64, i64, i64, i64, c_dp]),
+    "pm_mca_masked_estep_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, c_dp, i64, c_dp, i64, c_dp, c_dp, c_dp, i64,
+                                          C.POINTER(McaParams), i64, i64, i64, i64, c_dp, i64, c_dp, c_dp, c_dp]),
     "pm_patches_count": (i64, [i64, i64, i64]),
     "pm_patches_extract_f64": (C.c_int, [c_dp, i64, i64, i64, i64, i64, i64, i64, i64, i64, C.c_int, c_dp, i64, c_dp, c_dp]),
     "pm_patches_extract_f32": (C.c_int, [c_dp, i64, i64, i64, i64, i64, i64, i64, i64, i64, C.c_int, c_dp, i64, c_dp, c_dp]),
@@ -205,7 +211,7 @@ class HipError(RuntimeError):
     pass
 
 
-MIN_VERSION = 1020
+MIN_VERSION = 1021
 _lib = None
 _lib_det = None
 LIB_PATH_DET = os.path.join(os.path.dirname(LIB_PATH), "libprosper_hip_det.so")

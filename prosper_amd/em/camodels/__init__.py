@@ -116,12 +116,13 @@ class CAModel(Model):
         W_init = W_mean[:, None] + np.random.normal(scale=sigma_init / 4., size=[D, self.H])
         return {'W': W_init, 'pi': 1. / self.H, 'sigma': sigma_init}
 
-    def reconstruct_image(self, model_params, image, **kw):
+    def reconstruct_image(self, model_params, image, mask=None, **kw):
         """Whole-image denoising by overlapping patches: ``utils.patches.denoise_image(self, model_params,
         image, **kw)`` -- every patch through ``reconstruct()``, the estimates averaged where they overlap.  Keywords:
-        ``patch``, ``stride``, ``center``, ``chunk``, ``device``."""
+        ``patch``, ``stride``, ``center``, ``chunk``, ``device``.  ``mask`` (the image's shape, non-zero = observed pixel;
+        DESIGN 4.16): the patches go through the masked ``reconstruct()`` -- inpainting."""
         from ...utils.patches import denoise_image
-        return denoise_image(self, model_params, image, **kw)
+        return denoise_image(self, model_params, image, mask=mask, **kw)
 
     def compute_lpj(self, anneal, model_params, my_data):
         """Candidates + log-pseudo-joints for ``my_data['y']`` (upstream :238-253)."""

@@ -1037,7 +1037,13 @@ class DeviceCAModel(CAModel):
         ``exact=True``: log p(y_n | Theta) = log sum_{all s} p(s, y_n | Theta) summed over the model's WHOLE state space by
         enumeration on the device (pm_loglik_exact_*), the same generative model at the same annealing point:
         no candidates, no state table, no E-step, and a result independent of Hprime, gamma and the annealing state.  The
-        state count is bounded (include/prosper_hip.h): past the bound this raises ``HipError``."""
+        state count is bounded (include/prosper_hip.h): past the bound this raises ``HipError``.
+
+        ``my_data['mask']`` (N, D; non-zero = observed; BSC, MCA and MMCA): log sum_{s in K_n} p(s, y_obs,n), the
+        unobserved dimensions left out of the likelihood and never read into the arithmetic.  Other models and
+        ``exact=True`` raise ``NotImplementedError``, a mask of another shape ``ValueError``."""
+        if my_data.get('mask') is not None:
+            return self._log_likelihood_masked(model_params, my_data, per_datapoint, exact)
         if exact:
             return self._log_likelihood_exact(model_params, my_data, per_datapoint)
         saved = self._eval_begin()
@@ -1150,9 +1156,17 @@ class DeviceCAModel(CAModel):
         ``DeviceArray`` left on the device; there is no collective.  A NaN in a data row makes that row NaN and no other.
         ``model_params``, the training shard's residency, the records the last M-step left and Hprime / gamma stay as they
         were: a call between two EM steps does not change the training trajectory.  The results do not depend on
-        ``deterministic``.  Runs the E-step kernels, pm_recon_* and pm_gemm_nt_rows_f64 on the device."""
+        ``deterministic``.  Runs the E-step kernels, pm_recon_* and pm_gemm_nt_rows_f64 on the device.
+
+        ``my_data['mask']`` (N, D; non-zero = observed; NumPy, torch or DeviceArray of any numeric type; BSC,
+        MCA and MMCA): q_n comes from the joint of the observed dimensions alone, yhat_n still covers all D -- the missing
+        ones are inpainted.  Whatever an unobserved entry holds changes no bit; a row's bits depend on that row of ``y``,
+        that row of the mask and the parameters alone.  Other models raise ``NotImplementedError`` before any launch."""
         y = my_data['y']
         N = int(y.shape[0])
+        mask = my_data.get('mask')
+        if mask is not None:
+            self._masked_admit(y, mask)
         if N == 0:
             return DeviceArray(torch.empty((0, self.D), dtype=torch.float64, device=self.device)) if device \
                 else np.empty((0, self.D))
@@ -1161,11 +1175,122 @@ class DeviceCAModel(CAModel):
             # every product of the pass through the one-kernel GEMM, on parameter products of its own: a row of the result
             # is a function of that row of the data and of the parameters alone (attributes of the evaluation only)
             self._par, self._rows_gemm = {}, True
-            Yhat = self._reconstruct(dict(model_params), {'y': y}, N)
+            if mask is not None:
+                Yhat = self._reconstruct_masked(dict(model_params), y, mask, N)
+            else:
+                Yhat = self._reconstruct(dict(model_params), {'y': y}, N)
             return DeviceArray(Yhat) if device else Yhat.cpu().numpy()
         finally:
             self._par = {}
             self._eval_end(saved)
+
+    # ---- missing values -----------------------------------------------------------------------------------
+    def _masked_estep(self, model_params, y, mask):
+        """Per model: selection and T = 1 E-step of ``y`` over the dimensions its ``mask`` marks as observed (non-zero), run
+        inside an evaluation with ``_rows_gemm`` set.  Returns a dict: ``logpj`` (N, K) device log-joints in the layout of the
+        unmasked E-step, ``cand`` (N, Hprime) int32, ``dn`` (N,) int32 observed dimensions per row, ``c0`` / ``c1`` with
+        log p(s, y_obs) = logpj + c0 + D_n c1, ``lay`` (``_recon_layout``) and, for MCA, ``par`` (the power tables)."""
+        raise NotImplementedError("%s: missing values (my_data['mask']) are not built for this model; BSC_ET, MCA_ET and "
+                                  "MMCA_ET have the masked E-step" % type(self).__name__)
+
+    def _masked_admit(self, y, mask, exact=False):
+        """Everything that refuses a masked call, before any launch: the model, ``exact=True``, the mask's shape, H'."""
+        if type(self)._masked_estep is DeviceCAModel._masked_estep:
+            self._masked_estep(None, None, None)
+        if exact:
+            raise NotImplementedError("%s.log_likelihood: exact=True with a mask is not built (the enumeration kernels "
+                                      "read every dimension)" % type(self).__name__)
+        shape = tuple(getattr(mask, "tensor", mask).shape) if hasattr(getattr(mask, "tensor", mask), "shape") \
+            else np.asarray(mask).shape
+        if len(shape) != 2:
+            raise ValueError("my_data['mask'] must be two-dimensional (N, D), got shape %r" % (shape,))
+        if shape != tuple(y.shape):
+            raise ValueError("my_data['mask'] has shape %r, my_data['y'] %r" % (shape, tuple(y.shape)))
+        if self.Hprime > 16:
+            raise _lib.HipError("%s: the masked E-step holds H' <= 16 candidates, got %d" % (type(self).__name__, self.Hprime))
+
+    def _mask_resident(self, mask):
+        """``mask`` (NumPy, torch or DeviceArray; bool, uint8 or numeric, non-zero = observed) as a uint8 device tensor with
+        unit column stride, and its leading dimension.  A uint8 / bool device tensor of that layout is used in place."""
+        t = getattr(mask, "tensor", mask)
+        if not torch.is_tensor(t):
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(t) != 0).view(np.uint8))
+        t = t.to(self.device)
+        if t.dtype == torch.bool:
+            t = t.view(torch.uint8)
+        elif t.dtype != torch.uint8:
+            t = (t != 0).view(torch.uint8)
+        N, D = t.shape
+        if t.stride(1) != 1 or t.stride(0) < D:
+            t = t.contiguous()
+        return t, int(t.stride(0)) if N > 1 else max(int(t.stride(0)), D)
+
+    def _masked_prepare(self, Y, M, ldm, mu=None):
+        """pm_masked_prepare_f64: (X0 = m ? y - mu : 0, Mf = m ? 1 : 0, |X0|^2 per row, D_n per row)."""
+        N, D = Y.shape
+        X0, Mf = self._buf("mask_x0", (N, D)), self._buf("mask_mf", (N, D))
+        xn2 = self._buf("mask_xn2", (N,))
+        dn = torch.empty(N, dtype=torch.int32, device=self.device)
+        mu_d = torch.from_numpy(np.ascontiguousarray(mu, dtype=np.float64).reshape(-1)).to(self.device) if mu is not None else None
+        self._call("masked_prepare", "pm_masked_prepare_f64", _ptr(Y), max(int(Y.stride(0)), D), _ptr(M), ldm, _ptr(mu_d), N, D,
+                   _ptr(X0), D, _ptr(Mf), D, _ptr(xn2), _ptr(dn), self._stream())
+        return X0, Mf, xn2, dn
+
+    def _masked_dense(self, X0, Mf, Wt):
+        """The terms that are dense over H, as two products of the one-kernel GEMM: b = X0 . W and diag G_n = Mf . (W o W)."""
+        N, H = X0.shape[0], self.H
+        b = self._gemm_nt(X0, Wt, self._buf("mask_b", (N, H)), "masked_gemm")
+        g = self._gemm_nt(Mf, (Wt * Wt).contiguous(), self._buf("mask_g", (N, H)), "masked_gemm")
+        return b, g
+
+    def _reconstruct_masked(self, model_params, y, mask, N):
+        """``_reconstruct`` from the masked E-step's log-joints: the expectation and product kernels are the unmasked ones,
+        so the estimate covers all D dimensions."""
+        out = self._masked_estep(model_params, y, mask)
+        lay, lp, cand = out["lay"], out["logpj"], out["cand"]
+        K = lp.shape[1]
+        mu = lay.get("mu")
+        if mu is not None and not np.any(np.asarray(mu)):
+            mu = None
+        es = self._recon_expect(lp, K, N, cand=cand, table=lay.get("table"), blocks=lay["blocks"], soff=lay["soff"],
+                                moff=lay["moff"], ones=mu is not None)
+        Yhat = self._recon_product(es, es.shape[1], es.shape[1], lay["W"], mu)
+        if lay.get("mca") and self.no_states:
+            par = out["par"]
+            ld = lp.stride(0) if N > 1 else max(int(lp.stride(0)), K)
+            self._call("recon_mca", "pm_recon_mca_f64", _ptr(lp), ld, None, _ptr(cand), _ptr(self._masks()),
+                       _ptr(par["Wrho"]), ctypes.c_double(1. / par["rho"]), int(bool(self.signed_w)), N, self.H, self.D,
+                       self.Hprime, self.no_states, _ptr(Yhat), self.D, self._stream())
+        return Yhat
+
+    def _log_likelihood_masked(self, model_params, my_data, per_datapoint, exact):
+        """``log_likelihood`` with ``my_data['mask']``: log sum_{s in K_n} p(s, y_obs,n), the per-row constant c0 + D_n c1."""
+        y, mask = my_data['y'], my_data['mask']
+        self._masked_admit(y, mask, exact)
+        N = int(y.shape[0])
+        if N == 0:
+            return np.empty(0) if per_datapoint else self._sum_over_ranks(0.0)
+        saved = self._eval_begin()
+        try:
+            self._par, self._rows_gemm = {}, True
+            out = self._masked_estep(dict(model_params), y, mask)
+            logpj, dn, c0, c1 = out["logpj"], out["dn"], out["c0"], out["c1"]
+            K = logpj.shape[1]
+            lib = _lib.load(self.deterministic)
+            work = torch.empty(int(lib.pm_rows_lse_work_len(N)), dtype=torch.float64, device=self.device)
+            total = torch.empty(1, dtype=torch.float64, device=self.device)
+            rows = torch.empty(N, dtype=torch.float64, device=self.device) if per_datapoint else None
+            ld = logpj.stride(0) if N > 1 else max(int(logpj.stride(0)), K)
+            self._call("loglik_rows", "pm_rows_lse_f64", _ptr(logpj), ld, N, K, ctypes.c_double(1.0), None, _ptr(rows),
+                       _ptr(work), _ptr(total), self._stream())
+            if per_datapoint:
+                return rows.cpu().numpy() + (c0 + dn.cpu().numpy().astype(np.float64) * c1)
+            # (the rows' sum in pm_rows_lse_f64's fixed order; sum_n D_n exactly, in integers)
+            local = float(total.cpu()[0]) + N * c0 + int(dn.sum(dtype=torch.int64)) * c1
+        finally:
+            self._par = {}
+            self._eval_end(saved)
+        return self._sum_over_ranks(local)
 
     def _log_likelihood_exact(self, model_params, my_data, per_datapoint):
         saved = self._eval_begin()

@@ -24,7 +24,7 @@ import numpy as np
 from scipy.special import comb
 
 from ._device import (DeviceCAModel, DeviceArray, LazyCandidates, KernelTimer, _LOG_UNDERFLOW, _ptr,  # noqa: F401
-                      small_blas)
+                      small_blas, LoglikPoint)
 from ... import _lib
 from ...utils import parallel
 from ...utils import tracing
@@ -626,6 +626,32 @@ class BSC_ET(DeviceCAModel):
         return {"params": model_params, "blocks": (1.0,), "soff": 1, "moff": 1 + self.H,
                 "table": self.state_matrix if self.no_states else None, "W": model_params['W'],
                 "mu": model_params.get('mu')}
+
+    def _masked_estep(self, model_params, y, mask):
+        """Missing values: x = y - mu over the observed dimensions, b = W^T diag(m) x and diag G_n = diag(W^T
+        diag(m) W) as two one-kernel GEMMs, then pm_bsc_masked_estep_f64 -- candidates by b_h / sqrt(G_n[h,h]), the
+        candidates' masked pair products, log-joints in the unmasked layout.  c0 = H log(1 - pi), c1 = -1/2 log(2 pi sigma^2)."""
+        lay = self._recon_layout(model_params)
+        res = self._resident(y)
+        Y = res["Y"]
+        N, D = Y.shape
+        H, Hp, S = self.H, self.Hprime, self.no_states
+        M, ldm = self._mask_resident(mask)
+        mu = model_params.get('mu')
+        if mu is not None and not np.any(np.asarray(mu)):
+            mu = None
+        X0, Mf, xn2, dn = self._masked_prepare(Y, M, ldm, mu)
+        Wt = torch.from_numpy(np.ascontiguousarray(np.asarray(model_params['W'], dtype=np.float64).T)).to(self.device)
+        b, g = self._masked_dense(X0, Mf, Wt)
+        pies, sigma = float(model_params['pi']), float(model_params['sigma'])
+        P = self._estep_params(LoglikPoint(), pies, sigma, np.zeros(1))
+        cand = torch.empty((N, Hp), dtype=torch.int32, device=self.device)
+        logpj, _ = self._estep_outputs(N)
+        self._call("masked_estep", "pm_bsc_masked_estep_f64", _ptr(b), H, _ptr(g), H, _ptr(xn2), _ptr(M), ldm, _ptr(Wt), D,
+                   _ptr(self._state_tables()["masks"]), S, ctypes.byref(P), N, H, D, Hp, _ptr(cand), _ptr(logpj),
+                   logpj.stride(0), self._stream())
+        return {"logpj": logpj, "cand": cand, "dn": dn, "c0": H * np.log(1. - pies),
+                "c1": -0.5 * np.log(2 * _PI * sigma ** 2), "lay": lay}
 
     def _loglik_exact(self, model_params):
         """exact log_likelihood: states {0,1}^H, log prior |s| log pi + (H - |s|) log(1 - pi), y ~ N(mu + W s,

@@ -17,7 +17,7 @@ from math import pi as _PI
 import numpy as np
 from scipy.special import comb
 
-from ._device import DeviceCAModel, DeviceArray, _ptr
+from ._device import DeviceCAModel, DeviceArray, LoglikPoint, _ptr
 from ... import _lib
 from ...utils import parallel
 from ...utils import tracing
@@ -267,6 +267,53 @@ class MCA_ET(DeviceCAModel):
         model_params = self.check_params(model_params)
         return {"params": model_params, "blocks": (1.0,), "soff": 1, "moff": 1 + self.H, "table": None,
                 "W": model_params['W'], "mu": None, "mca": True}
+
+    def _masked_select(self, res, M, ldm, par, A, wn, xn2):
+        """Masked selection: the H' smallest R[n,h] = sum_d m_d max(W_hd - y_d, 0), ranked as ``_select_on_device`` does."""
+        Y = res["Y"]
+        N, D = Y.shape
+        H = self.H
+        R = self._buf("mca_sim", (N, H))
+        self._call("select_scores", "pm_mca_masked_select_scores_f64", _ptr(Y), D, _ptr(M), ldm, _ptr(par["Wt"]), D, _ptr(R),
+                   H, N, H, D, self._stream())
+        return self._rank_smallest(R, res)
+
+    def _rank_smallest(self, R, res):
+        """The H' smallest entries of each row of R (N, H), ascending: the selection kernel in raw mode."""
+        N, H, Hp = R.shape[0], self.H, self.Hprime
+        cand = torch.empty((N, Hp), dtype=torch.int32, device=self.device)
+        gdummy = self._buf("mca_gdummy", (H, H))
+        self._call("select", "pm_bsc_select_estep_f64", _ptr(R), H, _ptr(gdummy), _ptr(res["ynorm2"]), None, None,
+                   None, None, None, 0, self.gamma, None, N, H, Hp, 1 | 4 | 8, _ptr(cand), None, 0, None, self._stream())
+        return cand
+
+    def _masked_estep(self, model_params, y, mask):
+        """Missing values: the model of ``_loglik_terms`` over the observed dimensions.  One-cause energies
+        from |W_h|^2_obs - 2 <W_h, y>_obs + |y|^2_obs (two one-kernel GEMMs on pm_masked_prepare_f64's outputs), multi-cause
+        energies sum_d m_d (y_d - Wbar_d(s))^2 in pm_mca_masked_estep_f64.  c0 = H log(1 - pi), c1 = -1/2 log(2 pi sigma^2)."""
+        lay = self._recon_layout(model_params)
+        mp = lay["params"]
+        res = self._resident(y)
+        Y = res["Y"]
+        N, D = Y.shape
+        H, Hp, S = self.H, self.Hprime, self.no_states
+        M, ldm = self._mask_resident(mask)
+        masks = self._masks()
+        X0, Mf, xn2, dn = self._masked_prepare(Y, M, ldm)
+        par = self._tables_for(mp['W'], 1.0, res)
+        A, wn = self._masked_dense(X0, Mf, par["Wt"])
+        cand = self._masked_select(res, M, ldm, par, A, wn, xn2)
+        pies, sigma = float(mp['pi']), float(mp['sigma'])
+        P = self._params(LoglikPoint(), pies, sigma, par["rho"])
+        K = 1 + H + S
+        logpj = torch.empty((N, K), dtype=torch.float64, device=self.device)
+        lse1 = torch.empty((N,), dtype=torch.float64, device=self.device)
+        lseb = torch.empty((N,), dtype=torch.float64, device=self.device)
+        self._call("masked_estep", "pm_mca_masked_estep_f64", _ptr(A), H, _ptr(wn), H, _ptr(xn2), _ptr(X0), D, _ptr(M), ldm,
+                   _ptr(par["Wrho"]), _ptr(cand), _ptr(masks), S, ctypes.byref(P), N, H, D, Hp, _ptr(logpj), K, _ptr(lse1),
+                   _ptr(lseb), self._stream())
+        return {"logpj": logpj, "cand": cand, "dn": dn, "c0": H * np.log(1. - pies),
+                "c1": -0.5 * np.log(2 * _PI * sigma ** 2), "lay": lay, "par": par}
 
     def _loglik_exact(self, model_params):
         """exact log_likelihood: states {0,1}^H, y ~ N(Wbar(s), sigma^2 I) with the rho-combination of

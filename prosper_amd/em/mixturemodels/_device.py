@@ -82,6 +82,13 @@ class DeviceMixture(object):
         self._data = {}
         self.__dict__.pop("_eval_slot", None)
 
+    def _refuse_mask(self, my_data):
+        """Missing values are built for BSC and MCA / MMCA only: a mask is refused before any launch, never
+        ignored."""
+        if my_data.get('mask') is not None:
+            raise NotImplementedError("%s: missing values (my_data['mask']) are not built for the mixture models; BSC_ET, "
+                                      "MCA_ET and MMCA_ET have the masked E-step" % type(self).__name__)
+
     # ---- held-out log-likelihood (DESIGN 4.12) --------------------------------------------------------------------------
     def log_likelihood(self, model_params, my_data, per_datapoint=False, exact=False):
         """Exact held-out log-likelihood sum_n log sum_h pies_h p(y_n | h) of ``my_data['y']`` (host array, torch tensor or
@@ -95,7 +102,8 @@ class DeviceMixture(object):
         full covariance the Cholesky rejects makes every row NaN, a NaN in a data row that row.  ``model_params`` and the
         training shard are left as they were (the evaluation keeps its data and workspaces in a slot of its own).
         ``exact`` is accepted for the component-analysis models' signature: a mixture's value is exact either
-        way, and ``exact=True`` returns the same bits."""
+        way, and ``exact=True`` returns the same bits.  ``my_data['mask']`` (missing values) is refused."""
+        self._refuse_mask(my_data)
         saved = dict(self.__dict__)
         slot = saved.get("_eval_slot") or {"_data": {}, "_ws": {}}
         self._data, self._ws = slot["_data"], slot["_ws"]
@@ -199,6 +207,7 @@ class DeviceMixture(object):
         covariance is not positive definite makes every row NaN.  ``model_params`` and the training shard are left as they
         were.  The responsibilities are written as an (N, H) array by pm_recon_expect_f64 (a row softmax in a maximum and a
         sum pass) and multiplied with W by pm_gemm_nt_rows_f64; H within pm_mix_scores_f64's bound for MoG diagonal / MoP."""
+        self._refuse_mask(my_data)
         y = my_data['y']
         N, H, D = int(y.shape[0]), self.H, self.D
         if N == 0:

@@ -194,7 +194,18 @@ def average_patches(Y, image_shape, patch, stride=1, means=None, device=False):
     return _hand_back(_finish(acc, geo, False), len(tuple(image_shape)) == 2, device)
 
 
-def denoise_image(model, model_params, image, patch=None, stride=1, center=False, chunk=None, device=False):
+def _mask_image(mask, shape, dev):
+    """The 0 / 1 float64 device image of ``mask`` (non-zero = observed; any type ``_image_tensor`` reads), cut into patches
+    by the extraction kernel like the image itself."""
+    if _shape_of(mask) != tuple(shape):
+        raise ValueError("mask has shape %r, the image %r" % (_shape_of(mask), tuple(shape)))
+    t = getattr(mask, "tensor", mask)
+    if not torch.is_tensor(t):
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(t) != 0))
+    return _image_tensor((t.to(dev) != 0).to(torch.float64), dev)
+
+
+def denoise_image(model, model_params, image, patch=None, stride=1, center=False, chunk=None, device=False, mask=None):
     """Denoise ``image`` ((H_i, W_i) or a stack (B, H_i, W_i); NumPy array, torch tensor -- a device tensor is used in place,
     without a host round trip -- or ``DeviceArray``) with ``model`` at ``model_params``: every overlapping patch on the grid of
     the module docstring is replaced by its posterior mean ``model.reconstruct()`` and every pixel by the average of the
@@ -211,8 +222,17 @@ def denoise_image(model, model_params, image, patch=None, stride=1, center=False
     It inherits from ``reconstruct()``: this rank's images only, no collective; the training state, ``model_params`` and
     Hprime / gamma are left as they were; MoP with ``A`` set works in the normalised units ``reconstruct()`` documents; every
     ``HipError`` limit of ``reconstruct()`` applies.  A NaN pixel makes NaN exactly the pixels of the patches that contain it.
+
+    ``mask`` (missing values): an array of the image's shape, non-zero = observed pixel.  Its patches are cut on
+    the same grid and every chunk goes through ``model.reconstruct(model_params, {'y': chunk, 'mask': chunk's mask})``: the
+    unobserved pixels of a patch leave its likelihood and are read from its estimate (inpainting), whatever the image holds
+    there -- NaN included.  The overlap average is unchanged and covers every pixel.  ``center=True`` with a mask raises
+    ``ValueError`` (a mean over the observed pixels only is not built); a model without the masked E-step raises
+    ``NotImplementedError``.
     Returns the float64 image (the shape of ``image``) as a NumPy array, or with ``device=True`` as a ``DeviceArray``."""
     from ..em.camodels._device import DeviceArray
+    if mask is not None and center:
+        raise ValueError("center=True with a mask is not built: the patch mean would have to run over the observed pixels only")
     D = int(model.D)
     if patch is None:
         p = int(round(D ** 0.5))
@@ -230,15 +250,24 @@ def denoise_image(model, model_params, image, patch=None, stride=1, center=False
     elif int(chunk) != chunk or int(chunk) < 1:
         raise ValueError("chunk must be a positive number of patches, got %r" % (chunk,))
     rows = max(1, int(chunk) // nc)
+    if mask is not None:
+        if _shape_of(mask) != tuple(shape):
+            raise ValueError("mask has shape %r, the image %r" % (_shape_of(mask), tuple(shape)))
+        # (an empty masked call: a model without the masked E-step refuses here, before anything reaches the device)
+        model.reconstruct(model_params, {'y': np.empty((0, D)), 'mask': np.empty((0, D), dtype=bool)})
     dev = _device(model)
     det = bool(getattr(model, "deterministic", False))
     img, ldi = _image_tensor(image, dev)
+    mimg, ldmi = _mask_image(mask, shape, dev) if mask is not None else (None, 0)
     acc = torch.zeros((B, Hi, Wi), dtype=torch.float64, device=dev)
     for R0 in range(0, B * nr, rows):
         n0, n = R0 * nc, min(rows, B * nr - R0) * nc
         Y, means = _extract(img, ldi, geo, n0, n, center, det)
-        est = model.reconstruct(model_params, {'y': DeviceArray(Y)}, device=True)
-        del Y
+        data = {'y': DeviceArray(Y)}
+        if mimg is not None:
+            data['mask'] = DeviceArray((_extract(mimg, ldmi, geo, n0, n, False, det)[0] != 0).view(torch.uint8))
+        est = model.reconstruct(model_params, data, device=True)
+        del Y, data
         if _shape_of(est) != (n, D):
             raise ValueError("reconstruct() returned %r for a chunk of (%d, %d)" % (_shape_of(est), n, D))
         est, lde = _rows_tensor(est, D, dev, "reconstruct()'s result")
