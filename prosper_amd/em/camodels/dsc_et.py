@@ -36,11 +36,29 @@ def multinom2(n, k):
 
 
 def get_states(states, Hprime, gamma):
-    """All Hprime-vectors over ``states`` with 2..gamma non-zeros, itertools.product order (dsc_et.py:56-63)."""
+    """All Hprime-vectors over ``states`` with 2..gamma non-zeros, itertools.product order (dsc_et.py:56-63).  Built from
+    the positions and values of the non-zeros and then put into that order -- the reference filters all K^Hprime vectors,
+    16.7 million at K = 4, Hprime = 12 (99 s for 594 states); the result is the same array."""
     assert len(states.shape) == 1
-    sl = [np.array(c) for c in itls.product(states, repeat=Hprime)
-          if (np.sum(np.array(c) != 0) <= gamma and np.sum(np.array(c) != 0) > 1)]
-    return np.array(sl) if sl else np.zeros((0, Hprime))
+    zero = [k for k in range(len(states)) if states[k] == 0]
+    if len(zero) != 1:          # (no zero value, or several: the reference's own enumeration defines the table)
+        sl = [np.array(c) for c in itls.product(states, repeat=Hprime)
+              if (np.sum(np.array(c) != 0) <= gamma and np.sum(np.array(c) != 0) > 1)]
+        return np.array(sl) if sl else np.zeros((0, Hprime))
+    nonzero = [k for k in range(len(states)) if k != zero[0]]
+    rows = []
+    for n in range(2, min(gamma, Hprime) + 1):
+        for pos in itls.combinations(range(Hprime), n):
+            for vals in itls.product(nonzero, repeat=n):
+                r = [zero[0]] * Hprime
+                for j, v in zip(pos, vals):
+                    r[j] = v
+                rows.append(r)
+    if not rows:
+        return np.zeros((0, Hprime))
+    idx = np.array(rows)
+    idx = idx[np.lexsort(idx.T[::-1])]          # product order: lexicographic in the value indices, first position slowest
+    return states[idx]
 
 
 def generate_state_matrix(Hprime, gamma, states=np.array([0, 1])):

@@ -1,7 +1,8 @@
 """NumPy restatement of the masked joints of DESIGN 4.16 (missing values), shared by tests/test_masked_cpu.py and
 tests/test_masked_gpu.py: the posterior mean and log sum_s p(s, y_obs) by plain enumeration of every state, the same sums
-over a truncated state set rebuilt from a given candidate array, and the candidate selections.  An unobserved value is
-selected away (np.where), never multiplied.  Not a test module."""
+over a truncated state set rebuilt from a given candidate array, the candidate selections with their scores and the gap at
+the selection boundary, and pm_bsc_masked_estep_f64 restated for exact inputs (tests/test_eval_kernels_gpu.py).  An
+unobserved value is selected away (np.where), never multiplied.  Not a test module."""
 import itertools
 
 import numpy as np
@@ -63,31 +64,102 @@ def evaluate(Y, M, states_per_row, mean, H, pi, sigma):
 
 
 # ------------------------------------------------------------------------------------------------------------ selections
-def select_bsc(Y, M, W, Hp, mu=None):
-    """The H' largest b_h / sqrt(G_n[h,h]) (0 where G_n[h,h] = 0), ascending, ties towards the larger index."""
+def score_bsc(Y, M, W, mu=None):
+    """b_h / sqrt(G_n[h,h]) (0 where G_n[h,h] = 0): the H' LARGEST are selected."""
     M = np.asarray(M) != 0
     X = np.where(M, np.asarray(Y, dtype=np.float64) - (0.0 if mu is None else np.asarray(mu)[None, :]), 0.0)
     b = X @ W
     g = M.astype(np.float64) @ (W * W)
     with np.errstate(divide="ignore", invalid="ignore"):
-        score = np.where(g > 0, b / np.sqrt(g), 0.0)
-    return np.argsort(score, axis=1, kind="stable")[:, -Hp:]
+        return np.where(g > 0, b / np.sqrt(g), 0.0)
+
+
+def score_mca(Y, M, W):
+    """sum_d m_d max(W_dh - y_d, 0): the H' SMALLEST are selected."""
+    M = np.asarray(M) != 0
+    Yc = np.where(M, Y, 0.0)
+    return np.where(M[:, :, None], np.maximum(W[None, :, :] - Yc[:, :, None], 0.0), 0.0).sum(axis=1)
+
+
+def score_mmca(Y, M, W):
+    """MMCA ranks by distance, sum_d m_d (W_dh - y_d)^2: the H' SMALLEST are selected."""
+    M = np.asarray(M) != 0
+    Yc = np.where(M, Y, 0.0)
+    return np.where(M[:, :, None], (W[None, :, :] - Yc[:, :, None]) ** 2, 0.0).sum(axis=1)
+
+
+def select_bsc(Y, M, W, Hp, mu=None):
+    """The H' largest b_h / sqrt(G_n[h,h]) (0 where G_n[h,h] = 0), ascending, ties towards the larger index."""
+    return np.argsort(score_bsc(Y, M, W, mu), axis=1, kind="stable")[:, -Hp:]
 
 
 def select_mca(Y, M, W, Hp):
     """The H' smallest sum_d m_d max(W_dh - y_d, 0), ascending."""
-    M = np.asarray(M) != 0
-    Yc = np.where(M, Y, 0.0)
-    R = np.where(M[:, :, None], np.maximum(W[None, :, :] - Yc[:, :, None], 0.0), 0.0).sum(axis=1)
-    return np.argsort(R, axis=1, kind="stable")[:, :Hp]
+    return np.argsort(score_mca(Y, M, W), axis=1, kind="stable")[:, :Hp]
 
 
 def select_mmca(Y, M, W, Hp):
     """MMCA ranks by distance: the H' smallest sum_d m_d (W_dh - y_d)^2, ascending."""
-    M = np.asarray(M) != 0
-    Yc = np.where(M, Y, 0.0)
-    R = np.where(M[:, :, None], (W[None, :, :] - Yc[:, :, None]) ** 2, 0.0).sum(axis=1)
-    return np.argsort(R, axis=1, kind="stable")[:, :Hp]
+    return np.argsort(score_mmca(Y, M, W), axis=1, kind="stable")[:, :Hp]
+
+
+def boundary_gap(score, Hp, largest):
+    """Per row: the relative distance |a - b| / max(|a|, |b|) between the last score selected and the first one left out (the
+    H'-th and (H'+1)-th in the ranking's direction); 0 for an exact tie, inf when every latent is selected.  An exact
+    comparison of candidate lists against another implementation of the scores means something only where this is well
+    above the two implementations' rounding."""
+    score = np.asarray(score, dtype=np.float64)
+    N, H = score.shape
+    if Hp >= H:
+        return np.full(N, np.inf)
+    srt = np.sort(score, axis=1)
+    a, b = (srt[:, H - Hp], srt[:, H - Hp - 1]) if largest else (srt[:, Hp - 1], srt[:, Hp])
+    scale = np.maximum(np.abs(a), np.abs(b))
+    return np.where(a == b, 0.0, np.abs(a - b) / np.where(scale > 0, scale, 1.0))
+
+
+def model_scores(kind, params, Y, M):
+    """(scores (N, H), True when the largest are selected) of 'bsc', 'mca' or 'mmca'."""
+    W = np.asarray(params["W"], dtype=np.float64)
+    if kind == "bsc":
+        return score_bsc(Y, M, W, params.get("mu")), True
+    return (score_mca if kind == "mca" else score_mmca)(Y, M, W), False
+
+
+# ------------------------------------------------------------- pm_bsc_masked_estep_f64 restated for exact (integer) inputs
+def bsc_select_rule(b, g, Hp):
+    """The kernel's selection from given b and g: score b / sqrt(g) where g > 0, else 0; a NaN score ranks lowest (as -inf);
+    the H' largest, ascending, ties towards the larger index (a stable ascending sort keeps equal scores in index order, so
+    the larger index of a tie sits nearer the top)."""
+    b, g = np.asarray(b, dtype=np.float64), np.asarray(g, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        score = np.where(g > 0, b / np.sqrt(np.where(g > 0, g, 1.0)), 0.0)
+    score = np.where(np.isnan(score), -np.inf, score)
+    return np.argsort(score, axis=1, kind="stable")[:, -Hp:]
+
+
+def bsc_masked_terms(b, g, xnorm2, M, Wt, cand, state_matrix):
+    """The two terms of every column of the masked BSC log-joints, [null ; H singletons ; S table states over ``cand``]:
+    (|s| (N, K), e (N, K)) with logpj = ppil |s| + ecoef e and
+    e_s = |x|^2_obs - 2 sum_{h in s} b_h + sum_{h,h' in s} G_n[h,h'],  G_n[h,h'] = sum_d m_d Wt[h,d] Wt[h',d]
+    (the diagonal taken from ``g``).  On integer inputs every sum is exact in f64 in any order."""
+    b, g, Wt = (np.asarray(v, dtype=np.float64) for v in (b, g, Wt))
+    xnorm2 = np.asarray(xnorm2, dtype=np.float64)
+    Mf = (np.asarray(M) != 0).astype(np.float64)
+    SM = np.asarray(state_matrix, dtype=np.float64)                    # (S, Hp)
+    cand = np.asarray(cand)
+    N, H = b.shape
+    S = SM.shape[0]
+    size = np.concatenate([[0.0], np.ones(H), SM.sum(axis=1)])[None, :].repeat(N, axis=0)
+    e = np.empty((N, 1 + H + S))
+    e[:, 0] = xnorm2
+    e[:, 1:1 + H] = g - 2.0 * b + xnorm2[:, None]
+    for n in range(N):
+        Wc = Wt[cand[n]]                                               # (Hp, D)
+        G = (Wc * Mf[n][None, :]) @ Wc.T
+        G[np.diag_indices_from(G)] = g[n, cand[n]]
+        e[n, 1 + H:] = xnorm2[n] - 2.0 * (SM @ b[n, cand[n]]) + np.einsum("si,ij,sj->s", SM, G, SM)
+    return size, e
 
 
 # ------------------------------------------------------------------------------------------------------- the four models

@@ -1,6 +1,7 @@
 """NumPy restatements of reconstruct(), shared by tests/test_reconstruct_cpu.py and
 tests/test_reconstruct_gpu.py: the posterior mean by plain enumeration of every state with the proper densities, and the
-same sum over a truncated state set rebuilt from an E-step's (logpj, candidates).  Not a test module."""
+same sum over a truncated state set rebuilt from an E-step's (logpj, candidates); its two parts on their own
+(expect_from_lpj, mca_multi_from_lpj) are what tests/test_eval_kernels_gpu.py holds the two kernels to.  Not a test module."""
 import itertools
 
 import numpy as np
@@ -106,13 +107,12 @@ def gsc_from_sets(p, Y, sets_per_row):
 
 
 # ---------------------------------------------------------------------- from an E-step's log-joints (truncated state set)
-def linear_from_lpj(logpj, a, cand, W, blocks, soff, moff, table, mu=None):
-    """E[s] from the columns of ``logpj`` -- blocks of H one-cause columns from ``soff`` (block c: value blocks[c]), table
-    states from ``moff`` (state s: value table[s, j] at latent cand[n, j]; a repeated latent receives both positions) --
-    then mu + E[s] W^T."""
+def expect_from_lpj(logpj, a, cand, H, blocks, soff, moff, table, off=None):
+    """E[s] (N, H) under q = softmax(a logpj + off) -- blocks of H one-cause columns from ``soff`` (block c: value blocks[c]),
+    table states from ``moff`` (state s: value table[s, j] at latent cand[n, j]; a repeated latent receives both positions);
+    every other column carries weight and no value."""
     N = logpj.shape[0]
-    H = W.shape[1]
-    q = softmax_rows(a * np.asarray(logpj, dtype=np.float64))
+    q = softmax_rows(a * np.asarray(logpj, dtype=np.float64) + (0.0 if off is None else np.asarray(off)[None, :]))
     es = np.zeros((N, H))
     for c, v in enumerate(blocks):
         es += v * q[:, soff + c * H: soff + (c + 1) * H]
@@ -121,7 +121,29 @@ def linear_from_lpj(logpj, a, cand, W, blocks, soff, moff, table, mu=None):
         t = q[:, moff: moff + table.shape[0]] @ table             # (N, Hp)
         for j in range(table.shape[1]):
             np.add.at(es, (np.arange(N), np.asarray(cand)[:, j]), t[:, j])
+    return es
+
+
+def linear_from_lpj(logpj, a, cand, W, blocks, soff, moff, table, mu=None):
+    """``expect_from_lpj``, then mu + E[s] W^T."""
+    es = expect_from_lpj(logpj, a, cand, W.shape[1], blocks, soff, moff, table)
     return es @ W.T + (0.0 if mu is None else np.asarray(mu)[None, :])
+
+
+def mca_multi_from_lpj(logpj, lse, cand, state_matrix, Wrho, rho, signed):
+    """sum over the S multi-cause columns [1 + H, 1 + H + S) of exp(logpj - lse) Wbar(s), Wbar_d(s) = (sum_{j in s}
+    Wrho[c_j, d])^(1/rho) (signed: sign(T) |T|^(1/rho)) from the table of powers ``Wrho`` (H, D) itself: what
+    pm_recon_mca_f64 adds to Yhat."""
+    logpj, Wrho = np.asarray(logpj, dtype=np.float64), np.asarray(Wrho, dtype=np.float64)
+    H = Wrho.shape[0]
+    SM = np.asarray(state_matrix) != 0
+    out = np.zeros((logpj.shape[0], Wrho.shape[1]))
+    for n in range(logpj.shape[0]):
+        for s, row in enumerate(SM):
+            T = Wrho[np.asarray(cand)[n, row]].sum(axis=0)
+            wbar = np.sign(T) * np.abs(T) ** (1. / rho) if signed else T ** (1. / rho)
+            out[n] += np.exp(logpj[n, 1 + H + s] - lse[n]) * wbar
+    return out
 
 
 def mca_from_lpj(logpj, cand, state_matrix, W, rho, signed):

@@ -104,6 +104,73 @@ def test_truncated_sums_at_the_full_candidate_set_are_the_enumeration():
     assert np.array_equal(MR.select_bsc(Y, M, p["W"], 3, p["mu"])[0], [2, 3, 4])
 
 
+def test_boundary_gap_of_the_selection_scores():
+    """The distance between the last score selected and the first left out, in the ranking's direction; 0 for a tie."""
+    sc = np.array([[5., 1., 4., 2., 3.], [1., 2., 2., 0., 7.], [0., 0., 0., 0., 0.], [-4., -2., 8., -1., 6.]])
+    np.testing.assert_allclose(MR.boundary_gap(sc, 2, True), [0.25, 0.0, 0.0, 7. / 6.])        # 4|3, 2|2, 0|0, 6|-1
+    np.testing.assert_allclose(MR.boundary_gap(sc, 2, False), [1. / 3., 0.5, 0.0, 0.5])        # 2|3, 1|2, 0|0, -2|-1
+    assert np.isinf(MR.boundary_gap(sc, 5, True)).all() and np.isinf(MR.boundary_gap(sc, 5, False)).all()
+    # ... and the scores are the ones the selections rank
+    for kind in ("bsc", "mca", "mmca"):
+        p, Y, rng = _case(kind, 15, H=7)
+        M = rng.uniform(size=Y.shape) < 0.6
+        sc, largest = MR.model_scores(kind, p, Y, M)
+        _, sel = MR.model_terms(kind, p)
+        cand = sel(Y, M, 3)
+        rest = np.array([np.setdiff1d(np.arange(7), c) for c in cand])
+        picked, left = np.take_along_axis(sc, cand, 1), np.take_along_axis(sc, rest, 1)
+        assert ((picked.min(1) >= left.max(1)) if largest else (picked.max(1) <= left.min(1))).all()
+        edge = np.abs(picked.min(1) - left.max(1)) if largest else np.abs(left.min(1) - picked.max(1))
+        scale = np.maximum(np.abs(picked.min(1) if largest else picked.max(1)), np.abs(left.max(1) if largest else left.min(1)))
+        np.testing.assert_allclose(MR.boundary_gap(sc, 3, largest), edge / scale, rtol=1e-14)
+
+
+def test_bsc_selection_rule_on_ties_nan_and_infinities():
+    inf, nan = np.inf, np.nan
+    b = np.array([[6., 9., 1., 0., 7., 0.],            # 6/2 == 9/3: the larger index of the tie is nearer the top
+                  [nan, 5., nan, 1., 2., 3.],          # NaN ranks lowest
+                  [-inf, -inf, 1., -inf, -inf, -inf],  # -inf fills from the largest index
+                  [nan, nan, nan, nan, nan, nan]])
+    g = np.array([[4., 9., 1., 0., 0., 4.], [1.] * 6, [1.] * 6, [1.] * 6])
+    assert np.array_equal(MR.bsc_select_rule(b, g, 2), [[0, 1], [5, 1], [5, 2], [4, 5]])
+    assert np.array_equal(MR.bsc_select_rule(b, g, 5)[0], [4, 5, 2, 0, 1])     # of the three zeros (g = 0 twice, b = 0) the larger indices
+    assert np.array_equal(MR.bsc_select_rule(b, g, 3)[1], [4, 5, 1])
+    assert np.array_equal(MR.bsc_select_rule(b, g, 6)[1], [0, 2, 3, 4, 5, 1])
+    # on continuous data it is select_bsc
+    p, Y, rng = _case("bsc", 16, H=7)
+    M = rng.uniform(size=Y.shape) < 0.6
+    X = np.where(M, Y - p["mu"], 0.0)
+    assert np.array_equal(MR.bsc_select_rule(X @ p["W"], M.astype(float) @ p["W"] ** 2, 3), MR.select_bsc(Y, M, p["W"], 3, p["mu"]))
+
+
+def test_bsc_masked_terms_are_the_masked_energies():
+    """Integer data: e_s of bsc_masked_terms equals sum_d m_d (x_d - sum_{h in s} W_dh)^2 written out state by state,
+    exactly, and |s| is the state's size; with continuous data the columns are the log-joints ``evaluate`` sums."""
+    from prosper_amd.em.camodels import generate_state_matrix
+    rng = np.random.RandomState(17)
+    N, D, H, Hp = 6, 11, 9, 4
+    SM = generate_state_matrix(Hp, 3)[2]
+    Wt = rng.randint(-3, 4, size=(H, D)).astype(np.float64)
+    X = rng.randint(-8, 9, size=(N, D)).astype(np.float64)
+    M = rng.uniform(size=(N, D)) < 0.6
+    M[1] = False
+    X0, Mf = np.where(M, X, 0.0), M.astype(np.float64)
+    b, g, xn2 = X0 @ Wt.T, Mf @ (Wt * Wt).T, (X0 * X0).sum(1)
+    cand = MR.bsc_select_rule(b, g, Hp)
+    size, e = MR.bsc_masked_terms(b, g, xn2, M, Wt, cand, SM)
+    for n in range(N):
+        states = MR.truncated_states(H, cand[n], SM)
+        assert len(states) == e.shape[1]
+        for k, s in enumerate(states):
+            assert size[n, k] == len(s)
+            assert e[n, k] == (Mf[n] * (X[n] - Wt[list(s)].sum(axis=0)) ** 2).sum(), (n, k)
+    pi, sigma = 0.2, 1.1
+    _, ll = MR.evaluate(X, M, [MR.truncated_states(H, c, SM) for c in cand], MR.bsc_mean(Wt.T), H, pi, sigma)
+    lj = np.log(pi / (1 - pi)) * size - 0.5 / sigma ** 2 * e
+    want = logsumexp(lj, axis=1) + H * np.log(1 - pi) - 0.5 * M.sum(1) * np.log(2 * np.pi * sigma ** 2)
+    np.testing.assert_allclose(ll, want, rtol=1e-13)
+
+
 def test_new_entries_in_header_binding_and_both_libraries():
     from prosper_amd import _lib
     header = open(os.path.join(ROOT, "include", "prosper_hip.h")).read()

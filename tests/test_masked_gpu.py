@@ -123,8 +123,39 @@ def test_against_enumeration(dev, kind):
 
 
 # --------------------------------------------------------------------------------------------------------- 2: truncated
-TRUNC = [(k, 70, 24, 6, 3, 130) for k in KINDS] + [("mca", 1024, 24, 6, 3, 24), ("mca", 1, 8, 4, 2, 24),
-                                                    ("mmca", 1024, 12, 5, 2, 16)]
+# One case per instantiation and branch of the launchers (dispatch is a function of H, D and H' alone, so the shape names
+# the branch; test -> branch in DESIGN 4.16):
+#   bsc_masked_estep_kernel<VPL>      H = 24 / 65 (first latent of the second slot) / 130 / 257 / 520 / 1024 (PM_MAX_H):
+#                                     VPL 1, 2, 4, 8, 16, 16; H' = 12 and 16 give 66 and 120 candidate pairs: the second
+#                                     pair a lane owns (own1 / a1 / pi_[1])
+#   mca_masked_estep_kernel<DPL>      D = 64 / 70, 128 / 129, 200, 256 / 257, 512 / 513, 1024: DPL 1 / 2, 2 / 4, 4, 4 / 8,
+#                                     8 / 16, 16 -- each full last slab (D = 64 DPL) once; H' = 12 and 16; the largest
+#                                     dynamic LDS request (D = 1024, H' = 16: one wavefront per workgroup)
+#   mca_masked_select_scores_kernel   H = 65, 70 (two H tiles), 130 (three), none a multiple of 64
+#   recon_mca_kernel<DPL>             the same D buckets, from masked log-joints
+TRUNC = ([(k, 70, 24, 6, 3, 130) for k in KINDS] +
+         [("mca", 1024, 24, 6, 3, 24), ("mca", 1, 8, 4, 2, 24), ("mmca", 1024, 12, 5, 2, 16)] +
+         [(k, D, H, Hp, g, 64) for k in ("bsc", "bsc_mu")
+          for D, H, Hp, g in ((33, 65, 6, 3), (70, 130, 12, 3), (33, 257, 6, 3), (24, 520, 5, 2), (40, 1024, 16, 2))] +
+         [(k, D, H, Hp, g, 64) for k in ("mca", "mmca")
+          for D, H, Hp, g in ((129, 24, 6, 3), (200, 70, 12, 2), (257, 65, 5, 2), (513, 130, 6, 3), (1024, 20, 16, 2))] +
+         [("mca", 64, 24, 6, 3, 64), ("mmca", 128, 24, 6, 3, 64), ("mca", 256, 24, 5, 2, 64), ("mmca", 512, 20, 5, 2, 64)])
+GAP = 1e-9
+
+
+def _entries(m):
+    """The model's launch hook, wrapped to keep the names of the entry points that ran."""
+    calls = []
+    orig = m._call
+    m._call = lambda label, entry, *args: (calls.append(entry), orig(label, entry, *args))[1]
+    return calls
+
+
+def _masked_entries(kind):
+    if kind.startswith("bsc"):
+        return {"pm_masked_prepare_f64", "pm_bsc_masked_estep_f64", "pm_recon_expect_f64"}
+    sel = {"pm_mca_masked_select_scores_f64"} if kind == "mca" else set()
+    return sel | {"pm_masked_prepare_f64", "pm_mca_masked_estep_f64", "pm_recon_expect_f64", "pm_recon_mca_f64"}
 
 
 @pytest.mark.parametrize("kind,D,H,Hp,g,N", TRUNC)
@@ -133,8 +164,20 @@ def test_truncated_candidates_and_sums(dev, kind, D, H, Hp, g, N):
     m, p, Y = _problem(kind, rng, D, H, N, Hp, g)
     M = _mask(rng, N, D)
     Yg = np.where(M, Y, 1e300)
+    # candidate lists are compared exactly: that says something only where the reference's own scores at the selection
+    # boundary (the H'-th and (H'+1)-th) are further apart than two f64 evaluations of them can differ -- asserted on the
+    # reference, for every row with an observed value (the unobserved row has its index rule below)
+    sc, largest = MR.model_scores(_ref_kind(kind), p, Yg, M)
+    gap = MR.boundary_gap(sc, Hp, largest)[M.any(axis=1)]              # (D = 1: half of the rows are unobserved)
+    print("masked selection %-28s smallest boundary gap %.3e (needs > %.1e)" % ("%s D=%d H=%d H'=%d" % (kind, D, H, Hp),
+                                                                               gap.min(), GAP))
+    # (D = 1: a score is ONE term, max(w - y, 0) or b / sqrt(g), with nothing to sum -- both sides hold the same bits, zeros
+    # tie exactly and the index rule decides them on both sides)
+    assert gap.size == (N - 1 if D > 1 else M.any(axis=1).sum()) and ((gap > GAP).all() or D == 1), gap.min()
     kept = _capture(m)
+    calls = _entries(m)
     got_y = m.reconstruct(p, {"y": Yg, "mask": M})
+    assert _masked_entries(kind) <= set(calls), calls
     cand = kept["out"]["cand"].cpu().numpy()
     _, select = MR.model_terms(_ref_kind(kind), p)
     want_c = select(Yg, M, Hp)
@@ -145,9 +188,59 @@ def test_truncated_candidates_and_sums(dev, kind, D, H, Hp, g, N):
     want_y, want_l = MR.from_candidates(_ref_kind(kind), p, Yg, M, cand, m.state_matrix)
     tag = "%s D=%d H=%d H'=%d" % (kind, D, H, Hp)
     _check_rows(tag, got_y, want_y)
+    del calls[:]
     got_l = m.log_likelihood(p, {"y": Yg, "mask": M}, per_datapoint=True)
+    assert (_masked_entries(kind) - {"pm_recon_expect_f64", "pm_recon_mca_f64"}) <= set(calls), calls
     np.testing.assert_array_equal(kept["out"]["cand"].cpu().numpy(), cand)
     _check_ll(tag, got_l, want_l, np.ones_like(M), p, H)      # (a truncated set's prior mass is below 1: no computed zero)
+
+
+# ------------------------------------------------------------------------------- 2b: second trip of the grid-stride loops
+# masked kernels: at most 2048 workgroups of four rows (grid_for_rows), so row 8192 is the first of a second trip; the recon
+# kernels that consume the masked log-joints: 8192 workgroups, row 32768
+@pytest.mark.parametrize("kind,N", [("bsc", 8192 + 77), ("mca", 8192 + 77), ("mca", 32768 + 77)])
+def test_second_trip_of_the_row_loops(dev, kind, N):
+    """Every per-wavefront LDS area (s_c / s_ac / s_gc, s_wr / s_e) is used again after the trailing wave_lds_sync().  The
+    rows from 150 before each boundary onwards against the NumPy sums over the device's candidates; the whole result bit
+    for bit against the same calls on shards of 4096 rows (a row's bits depend on that row alone)."""
+    D, H, Hp, g = 8, 6, 4, 2
+    rng = np.random.RandomState(N % 1000 + KINDS.index(kind))
+    m, p, Y = _problem(kind, rng, D, H, N, Hp, g)
+    M = _mask(rng, N, D)
+    Yg = np.where(M, Y, np.nan)
+    kept = _capture(m)
+    got_y = m.reconstruct(p, {"y": Yg, "mask": M})
+    cand = kept["out"]["cand"].cpu().numpy()
+    got_l = m.log_likelihood(p, {"y": Yg, "mask": M}, per_datapoint=True)
+    assert got_y.shape == (N, D) and np.isfinite(got_y).all() and np.isfinite(got_l).all()
+    rows = np.concatenate([np.arange(b - 150, min(b + 227, N)) for b in (8192, 32768) if b < N])
+    _, select = MR.model_terms(_ref_kind(kind), p)
+    np.testing.assert_array_equal(cand[rows], select(Yg[rows], M[rows], Hp))
+    want_y, want_l = MR.from_candidates(_ref_kind(kind), p, Yg[rows], M[rows], cand[rows], m.state_matrix)
+    _check_rows("%s N=%d second trip" % (kind, N), got_y[rows], want_y)
+    _check_ll("%s N=%d second trip" % (kind, N), got_l[rows], want_l, np.ones_like(M[rows]), p, H)
+    parts = [(m.reconstruct(p, {"y": Yg[i:i + 4096], "mask": M[i:i + 4096]}),
+              m.log_likelihood(p, {"y": Yg[i:i + 4096], "mask": M[i:i + 4096]}, per_datapoint=True)) for i in range(0, N, 4096)]
+    _same_bits(np.concatenate([a for a, _ in parts]), got_y, "reconstruct in shards")
+    _same_bits(np.concatenate([b for _, b in parts]), got_l, "log_likelihood in shards")
+
+
+# ------------------------------------------------------------------------------------------------------------ 2c: limits
+# (AT the limits -- H = PM_MAX_H = 1024 with H' = PM_MAX_HPRIME = 16, D = 1024 with H' = 16 -- are cases of TRUNC above)
+@pytest.mark.parametrize("kind,D,H,Hp", [("bsc", 16, 1025, 4), ("bsc", 16, 40, 17), ("mca", 1025, 12, 4), ("mca", 16, 40, 17),
+                                          ("mmca", 1025, 12, 4)])
+def test_one_past_a_limit_raises(dev, kind, D, H, Hp):
+    """HipError -- the library's PM_ERANGE or the host's own range check (some in the constructor) -- and no result."""
+    from prosper_amd import _lib
+    rng = np.random.RandomState(D + H + Hp)
+    N = 12
+    with pytest.raises(_lib.HipError):
+        m, p, Y = _problem(kind, rng, D, H, N, Hp, 2)
+        M = _mask(rng, N, D)
+        m.reconstruct(p, {"y": Y, "mask": M})
+    with pytest.raises(_lib.HipError):
+        m, p, Y = _problem(kind, rng, D, H, N, Hp, 2)
+        m.log_likelihood(p, {"y": Y, "mask": _mask(rng, N, D)}, per_datapoint=True)
 
 
 # --------------------------------------------------------------------------------------------------------- 3: sub-model

@@ -153,3 +153,73 @@ def test_gsc_and_mca_restatements_agree_with_enumeration():
     Y = rng.normal(size=(N, D))
     logpj = 2.0 * np.stack([R.gsc_state_terms(p, Y, a)[0] for a in sets], axis=1)
     assert R.row_rel_err(R.gsc_from_lpj(p, Y, logpj, cand, SM), R.enum_gsc(p, Y)) < 1e-12
+
+
+def test_expect_from_lpj_with_scale_and_offset_and_repeated_candidates():
+    """E[s] under softmax(a X + off), written out column by column: one-cause blocks, table states scattered to their
+    candidates (a repeated latent receives both positions), weight-only columns."""
+    rng = np.random.RandomState(31)
+    N, H, Hp = 5, 6, 3
+    blocks = (-1.0, 2.0)
+    table = rng.choice([-1.0, 0.0, 1.0], size=(4, Hp))
+    soff, moff = 2, 2 + 2 * H
+    K = moff + 4 + 1                                   # two leading and one trailing column carry weight only
+    X, off, a = rng.normal(size=(N, K)), rng.normal(size=K), 0.7
+    cand = np.array([rng.permutation(H)[:Hp] for _ in range(N)])
+    cand[1] = [4, 4, 2]
+    got = R.expect_from_lpj(X, a, cand, H, blocks, soff, moff, table, off=off)
+    Z = a * X + off[None, :]
+    q = np.exp(Z - Z.max(1, keepdims=True))
+    q /= q.sum(1, keepdims=True)
+    want = np.zeros((N, H))
+    for n in range(N):
+        for h in range(H):
+            want[n, h] = sum(v * q[n, soff + c * H + h] for c, v in enumerate(blocks))
+            for j in range(Hp):
+                if cand[n, j] == h:
+                    want[n, h] += sum(q[n, moff + s] * table[s, j] for s in range(4))
+    np.testing.assert_allclose(got, want, rtol=1e-13, atol=1e-15)
+    W = rng.normal(size=(7, H))
+    np.testing.assert_allclose(R.linear_from_lpj(X, 1.0, cand, W, blocks, soff, moff, table),
+                               R.expect_from_lpj(X, 1.0, cand, H, blocks, soff, moff, table) @ W.T, rtol=1e-14)
+
+
+@pytest.mark.parametrize("signed,rho", [(False, 21.0), (True, 6.0), (False, 3.5)])
+def test_mca_multi_from_lpj_is_the_multi_cause_part_of_mca_from_lpj(signed, rho):
+    from prosper_amd.em.camodels import generate_state_matrix
+    from scipy.special import logsumexp
+    rng = np.random.RandomState(32)
+    N, D, H, Hp = 6, 9, 7, 4
+    SM = generate_state_matrix(Hp, 3)[2]
+    W = rng.uniform(0.2, 3.0, size=(D, H)) * (rng.choice([-1.0, 1.0], size=(D, H)) if signed else 1.0)
+    lp = rng.normal(size=(N, 1 + H + len(SM)))
+    cand = np.array([rng.permutation(H)[:Hp] for _ in range(N)])
+    Wrho = (np.sign(W) * np.abs(W) ** rho).T
+    multi = R.mca_multi_from_lpj(lp, logsumexp(lp, axis=1), cand, SM, Wrho, rho, signed)
+    whole = R.mca_from_lpj(lp, cand, SM, W, rho, signed)
+    np.testing.assert_allclose(R.softmax_rows(lp)[:, 1:1 + H] @ W.T + multi, whole, rtol=1e-12, atol=1e-13)
+
+
+def test_dsc_state_table_equals_the_references_enumeration():
+    """DSC_ET's table of multi-cause states is built from the non-zeros' positions and values; it must be the array the
+    reference's filter over all K^Hprime vectors gives (dsc_et.py:56-63), order and dtype included -- and H' = 12 with four
+    latent values (test_against_the_esteps_log_joints[dsc4-24-130-12-2]) must not take minutes."""
+    import itertools
+    import time
+    from prosper_amd.em.camodels.dsc_et import get_states
+
+    def reference(states, Hprime, gamma):
+        sl = [np.array(c) for c in itertools.product(states, repeat=Hprime)
+              if (np.sum(np.array(c) != 0) <= gamma and np.sum(np.array(c) != 0) > 1)]
+        return np.array(sl) if sl else np.zeros((0, Hprime))
+    for states in (np.array([0, 1]), np.array([-1., 0., 1.]), np.array([0., 1., 2., 3.]),
+                   np.array([-3., -2., -1., 0., 1., 2., 3., 4.]), np.array([1., 2.]), np.array([0., 0., 1.])):
+        for Hp, g in ((1, 1), (2, 1), (2, 2), (3, 2), (4, 3), (5, 2), (5, 5), (6, 4)):
+            if len(states) ** Hp > 40000:
+                continue
+            want, got = reference(states, Hp, g), get_states(states, Hp, g)
+            assert got.shape == want.shape and got.dtype == want.dtype and np.array_equal(got, want), (states, Hp, g)
+    t = time.time()
+    table = get_states(np.array([0., 1., 2., 3.]), 12, 2)
+    assert table.shape == (66 * 9, 12) and time.time() - t < 5.0
+

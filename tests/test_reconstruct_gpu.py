@@ -81,7 +81,7 @@ def _problem(name, rng, D, H, N, Hp, g):
         m = (MMCA_ET if signed else MCA_ET)(D, H, Hp, g)
         return m, {"W": W, "pi": pi, "sigma": sigma}, Y, clean, lambda Y: R.enum_mca(Y, W, rho, signed, pi, sigma)
     if name.startswith("dsc"):
-        states = np.array([-1., 0., 1.] if name == "dsc3" else [0., 1., 2., 3.])
+        states = np.array({"dsc3": [-1., 0., 1.], "dsc8": [-3., -2., -1., 0., 1., 2., 3., 4.]}.get(name, [0., 1., 2., 3.]))
         K = len(states)
         pi = rng.uniform(0.5, 1.5, size=K)
         pi[list(states).index(0.)] += 4
@@ -187,17 +187,54 @@ TRUNC = [("bsc", 25, 10, 8, 5), ("bsc_mu", 25, 10, 8, 5), ("mca", 25, 10, 8, 5),
          ("tsc", 25, 10, 7, 5), ("gsc_scalar", 25, 10, 7, 4),
          ("bsc", 256, 128, 6, 3), ("bsc_mu", 64, 40, 8, 4), ("mca", 64, 32, 10, 3), ("mmca", 96, 24, 8, 3),
          ("dsc4", 64, 32, 6, 3), ("tsc", 64, 32, 5, 3), ("gsc_diagonal", 48, 24, 6, 3), ("gsc_full", 40, 16, 5, 3)]
+# one case per branch of the two kernels that the shapes above leave out (test -> branch in DESIGN 4.14):
+#   recon_mca_kernel<DPL>   D = 200, 400 and 500, 1000: DPL 4, 8, 16 (the shapes above: 1 and 2); 200, 500 and 1000 reach the
+#                           lane's last slab of 64 dimensions (D > 64 (DPL - 1)), 400 leaves the last of its eight empty
+#   recon_expect_kernel     H' = 16 (PM_MAX_HPRIME; above: <= 10); DSC with H = 130 > 64 (the lane-strided H loop over
+#                           soff + c H + h, three blocks) at H' = 12; TSC with H = 70 (repeated candidates, H > 64); a DSC
+#                           model of 8 latent values: nblk = 7 blocks
+TRUNC_MORE = [(k, D, 24, 6, 3) for k in ("mca", "mmca") for D in (200, 400, 1000)] + [("mca", 500, 24, 6, 3)] + \
+             [("bsc", 40, 48, 16, 2), ("dsc4", 24, 130, 12, 2), ("tsc", 24, 70, 5, 3), ("dsc8", 16, 12, 3, 2)]
 
 
-@pytest.mark.parametrize("name,D,H,Hp,g", TRUNC)
+def _entries(m):
+    """The model's launch hook, wrapped to keep the names of the entry points that ran."""
+    calls = []
+    orig = m._call
+    m._call = lambda label, entry, *args: (calls.append(entry), orig(label, entry, *args))[1]
+    return calls
+
+
+@pytest.mark.parametrize("name,D,H,Hp,g", TRUNC + TRUNC_MORE)
 def test_against_the_esteps_log_joints(dev, name, D, H, Hp, g):
-    N = 160
+    N = 160 if (name, D, H, Hp, g) in TRUNC else 96
     m, p, Y, _, _ = _problem(name, np.random.RandomState(D + H + Hp), D, H, N, Hp, g)
     if name in ("mca", "mmca"):
         p = m.check_params({k: np.array(v, copy=True) for k, v in p.items()})
     want = _truncated_reference(m, name, p, Y)
+    calls = _entries(m)
     got = m.reconstruct(p, {"y": Y})
+    if not name.startswith("gsc"):
+        assert "pm_recon_expect_f64" in calls and ("pm_recon_mca_f64" in calls) == (name in ("mca", "mmca")), calls
     _check("%s D=%d H=%d H'=%d g=%d" % (name, D, H, Hp, g), got, want)
+
+
+# the second trip of the kernels' grid-stride loops: both launch at most REC_MAX_BLOCKS = 8192 workgroups of four rows
+@pytest.mark.parametrize("name", ["bsc", "mca", "dsc3"])
+def test_second_trip_of_the_row_loops(dev, name):
+    """N = 32768 + 77: every wavefront of the first 77 / 4 workgroups takes a second row.  The rows from 150 before the
+    boundary to the end against the NumPy sums over an E-step of those rows alone; the whole result bit for bit against
+    the same call on shards of 4096 rows (rows are independent and a row's sums run in a fixed order)."""
+    D, H, Hp, g, N = 8, 6, 4, 2, 32768 + 77
+    m, p, Y, _, _ = _problem(name, np.random.RandomState(900 + len(name)), D, H, N, Hp, g)
+    if name == "mca":
+        p = m.check_params({k: np.array(v, copy=True) for k, v in p.items()})
+    got = m.reconstruct(p, {"y": Y})
+    assert got.shape == (N, D) and np.isfinite(got).all()
+    tail = slice(32768 - 150, N)
+    _check("%s second trip" % name, got[tail], _truncated_reference(m, name, p, Y[tail]))
+    shards = np.concatenate([m.reconstruct(p, {"y": Y[i:i + 4096]}) for i in range(0, N, 4096)])
+    assert np.array_equal(shards.view(np.uint64), got.view(np.uint64))
 
 
 def test_bsc_fallback_path_past_512_latents(dev):
@@ -417,6 +454,24 @@ def test_limits_raise_hip_error(dev):
     p = {"W": rng.uniform(0.5, 2.0, size=(D, H)), "pi": 0.2, "sigma": 1.0}
     with pytest.raises(_lib.HipError):
         MCA_ET(D, H, 4, 2).reconstruct(p, {"y": rng.uniform(0, 2, size=(5, D))})
+
+
+def test_at_and_one_past_the_candidate_and_latent_limits(dev):
+    """PM_MAX_HPRIME = 16 runs (TRUNC_MORE), 17 raises; BSC with PM_MAX_H = 1024 latents runs, 1025 raises -- HipError from
+    the library or from the constructor's own range check, before any row is produced."""
+    from prosper_amd import _lib
+    from prosper_amd.em.camodels.bsc_et import BSC_ET
+    rng = np.random.RandomState(6)
+    D, N = 16, 48
+    for H, Hp, ok in ((1024, 4, True), (1025, 4, False), (40, 17, False)):
+        p = {"W": rng.normal(size=(D, H)), "pi": 2.0 / H, "sigma": 1.0}
+        Y = rng.normal(size=(N, D))
+        if ok:
+            m = BSC_ET(D, H, Hp, 2)
+            _check("bsc H=%d" % H, m.reconstruct(p, {"y": Y}), _truncated_reference(m, "bsc", p, Y))
+        else:
+            with pytest.raises(_lib.HipError):
+                BSC_ET(D, H, Hp, 2).reconstruct(p, {"y": Y})
 
 
 # ------------------------------------------------------------------------------------------------------- 8: two ranks
