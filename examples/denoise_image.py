@@ -2,6 +2,7 @@
 """Whole-image denoising by overlapping patches on an image the models are correctly specified for.
 
     python examples/denoise_image.py [bsc|mca] [--size 128] [--p 5] [--stride 1] [--steps 50] [--missing FRACTION]
+                                     [--train-missing]
 
 No file is read.  The script draws a *bars image*: row indicators r_i and column indicators c_j ~ Bernoulli(pi),
 clean[i, j] = a (r_i + c_j) (MCA: a max(r_i, c_j)), plus Gaussian noise of standard deviation sigma.  Every p x p patch of
@@ -11,9 +12,15 @@ device and handed to EM as they are, with the annealing schedule of examples/bar
 with ``reconstruct_image`` at the learned and at the generating parameters; noisy and denoised MSE / PSNR are printed.
 
 ``--missing FRACTION`` (missing values): after the noise that share of the pixels is dropped at random.  The
-model still trains on the complete noisy image -- training on incomplete patches is not built --, the reconstruction runs
-with the mask (``reconstruct_image(..., mask=)``; the dropped pixels hold NaN), and the MSE is printed separately over the
-observed pixels (denoising) and over the missing ones (inpainting, next to filling them with the observed pixels' mean)."""
+model trains on the complete noisy image, the reconstruction runs with the mask (``reconstruct_image(..., mask=)``; the
+dropped pixels hold NaN), and the MSE is printed separately over the observed pixels (denoising) and over the missing ones
+(inpainting, next to filling them with the observed pixels' mean).
+
+``--train-missing`` (``bsc`` with ``--missing``): nobody has the complete image -- the model trains on the
+incomplete image's own patches.  The mask image goes through ``extract_patches`` on the same grid and travels as
+``my_data['mask']`` through EM; ``Ncut_factor`` stays 0 (data truncation is not defined across rows with different numbers
+of observed pixels); the start parameters come from the image with its holes filled by the observed mean.  The same
+observed / missing MSE lines are printed."""
 import argparse
 import os
 import sys
@@ -68,7 +75,11 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--missing", type=float, default=0.0, metavar="FRACTION",
                     help="share of pixels dropped after the noise; the reconstruction runs with the mask")
+    ap.add_argument("--train-missing", action="store_true",
+                    help="bsc with --missing: train on the incomplete image's own patches (my_data['mask'])")
     a = ap.parse_args()
+    if a.train_missing and (a.model != "bsc" or not 0.0 < a.missing < 1.0):
+        ap.error("--train-missing needs the bsc model and --missing FRACTION in (0, 1)")
     np.random.seed(a.seed)
     rng = np.random.RandomState(a.seed)
     mca = a.model == "mca"
@@ -77,14 +88,26 @@ def main():
     gt = {'W': bars_dict(a.p, a.a), 'pi': a.pi, 'sigma': a.sigma}
 
     # train on the noisy image's own patches: the (N, D) matrix never exists on the host
-    Y, _ = extract_patches(noisy, a.p, stride=1, device=True)
     model = build(a.model, a.p, min(H, 5), min(H, 3))
-    init = model.standard_init({'y': Y})
     anneal = LinearAnnealing(a.steps)
     anneal['T'] = [(0, 2.), (.7, 1.)]
-    anneal['Ncut_factor'] = [(0, 0.), (2. / 3, 1.)]
     anneal['anneal_prior'] = False
-    em = EM(model=model, anneal=anneal, data={'y': Y}, lparams=init)
+    mask = None
+    if a.train_missing:
+        # ... of the INCOMPLETE image: the mask image's patches on the same grid are the patches' masks
+        mask = rng.uniform(size=clean.shape) >= a.missing
+        holes = np.where(mask, noisy, np.nan)
+        Y, _ = extract_patches(holes, a.p, stride=1, device=True)
+        Mp, _ = extract_patches(mask.astype(np.float64), a.p, stride=1, device=True)
+        filled, _ = extract_patches(np.where(mask, noisy, noisy[mask].mean()), a.p, stride=1, device=True)
+        init = model.standard_init({'y': filled})
+        data = {'y': Y, 'mask': Mp}
+    else:
+        Y, _ = extract_patches(noisy, a.p, stride=1, device=True)
+        init = model.standard_init({'y': Y})
+        anneal['Ncut_factor'] = [(0, 0.), (2. / 3, 1.)]
+        data = {'y': Y}
+    em = EM(model=model, anneal=anneal, data=data, lparams=init)
     em.run()
     learned = dict(em.lparams)
 
@@ -96,9 +119,12 @@ def main():
     if a.missing > 0.0:
         if not a.missing < 1.0:
             ap.error("--missing is a fraction in [0, 1)")
-        mask = rng.uniform(size=clean.shape) >= a.missing
+        if mask is None:
+            mask = rng.uniform(size=clean.shape) >= a.missing
         holes = np.where(mask, noisy, np.nan)
-        print("  %.1f %% of the pixels dropped after the noise; trained on the complete noisy image" % (100 * (1 - mask.mean())))
+        print("  %.1f %% of the pixels dropped after the noise; trained on the %s" % (
+            100 * (1 - mask.mean()), "incomplete image's own patches (%d dimensions of W kept their row in the last step)"
+            % model.W_kept if a.train_missing else "complete noisy image"))
         mse = lambda img, sel: float(((np.asarray(img) - clean)[sel] ** 2).mean())
         print("  %-44s MSE observed %.4f   missing %.4f (filled with the observed mean)"
               % ("noisy image", mse(noisy, mask), mse(np.full_like(clean, noisy[mask].mean()), ~mask)))

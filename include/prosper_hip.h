@@ -1025,6 +1025,46 @@ int pm_mca_masked_estep_f64(const double *scores, int64_t lds, const double *wno
                             int64_t N, int64_t H, int64_t D, int64_t Hprime, double *logpj, int64_t ldl, double *lse1,
                             double *lseb, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Missing values: the M-step of BSC on incomplete rows (masked_train.hip)
+ * ---------------------------------------------------------------------------------------
+ * With a mask every data dimension d has its own normal equations A_d w_d = r_d, A_d = sum_n m_nd E_q[s s^T]_n (H x H).  No
+ * atomics: every output element is written once and every sum over rows runs in ascending row order, so both builds return
+ * the same bits on every run.  Every entry checks its arguments before it touches a device (PM_EINVAL: null pointer,
+ * negative size, short leading dimension; PM_ERANGE: past a limit); N == 0 launches nothing.
+ *
+ * pm_bsc_mtrain_rows_f64: from a row's log-joints (layout of pm_bsc_masked_estep_f64), its log-sum-exp lse[n] (pm_rows_lse_f64),
+ * its candidates and the state masks, with q(s) = exp(logpj_s - lse): es[n,h] = E[s_h] (lde >= H), q2[n,p] = sum of q over the
+ * table states holding both candidates of pair p, pairs in the order (0,1), (0,2), ..., (Hprime-2, Hprime-1) (ldq >=
+ * Hprime (Hprime - 1) / 2; q2 may be NULL at Hprime = 1), energy[n] = sum_s q(s) e_s with e_s = (logpj_s - prior_scale pil_bar
+ * |s|) / ecoef, the energy the E-step scaled (params.ecoef < 0, else PM_EINVAL).  H <= PM_MAX_H, Hprime <= PM_MAX_HPRIME,
+ * S <= 65535.  A row's outputs depend on that row alone. */
+int pm_bsc_mtrain_rows_f64(const double *logpj, int64_t ldl, const double *lse, const int32_t *cand,
+                           const uint16_t *state_masks, int64_t S, const pm_bsc_estep_params *params_host, int64_t N,
+                           int64_t H, int64_t Hprime, double *es, int64_t lde, double *q2, int64_t ldq, double *energy,
+                           void *stream);
+/* out[c] = sum_n X[n,c] (X: N x C, ld >= C) in a fixed order: workgroups add fixed row ranges (a function of N alone) in
+ * ascending order into work (pm_col_sum_ordered_work_len(N, C) doubles), the partials are added in index order.  N == 0
+ * launches nothing and leaves out as it is. */
+int64_t pm_col_sum_ordered_work_len(int64_t N, int64_t C);
+int pm_col_sum_ordered_f64(const double *X, int64_t ld, int64_t N, int64_t C, double *work, double *out, void *stream);
+/* A (D, H, H) dense: A[d, c_i, c_j] = A[d, c_j, c_i] = sum_n m_nd q2[n, (i,j)] over the rows' candidates cand (N, Hprime), each
+ * cell added in ascending n; A[d, h, h] = diag[h, d] (H, ldd >= D: the dense product E[s]^T Mf); every other cell 0.  A
+ * candidate outside [0, H) or a pair of equal candidates is skipped.  A workgroup owns 64 dimensions x
+ * pm_bsc_mtrain_pairs_tile_rows(H) latent rows x H columns in LDS.  H <= 256, Hprime <= PM_MAX_HPRIME, D H^2 <= 2^28,
+ * N <= INT32_MAX. */
+int pm_bsc_mtrain_pairs_f64(const int32_t *cand, const double *q2, int64_t ldq, const uint8_t *mask, int64_t ldm,
+                            const double *diag, int64_t ldd, int64_t N, int64_t D, int64_t H, int64_t Hprime, double *A,
+                            void *stream);
+int64_t pm_bsc_mtrain_pairs_tile_rows(int64_t H);
+/* Behind pm_spd_inverse_batch_f64 (batch = D): Wt_new[h,d] = (Ainv_d r_d + Ainv_d (r_d - A_d Ainv_d r_d))[h] with r_d = r[:, d]
+ * (H, ldr >= D), A and Ainv dense symmetric (D, H, H), where pivots (D, 2) = [smallest, largest] pass smallest > 0 and
+ * smallest / largest > 1e-11; elsewhere Wt_new[:, d] = Wt_old[:, d] bit for bit.  status[d] = 1 solved, 0 kept.  H <= 256,
+ * D H^2 <= 2^28. */
+int pm_bsc_mtrain_solve_f64(const double *A, const double *Ainv, const double *pivots, const double *r, int64_t ldr,
+                            const double *Wt_old, int64_t ldw, int64_t D, int64_t H, double *Wt_new, int64_t ldo,
+                            int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,6 +199,13 @@ SIGNATURES = {
     "pm_mca_masked_select_scores_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, i64, c_dp, i64, i64, i64, i64, c_dp]),
     "pm_mca_masked_estep_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, c_dp, i64, c_dp, i64, c_dp, c_dp, c_dp, i64,
                                           C.POINTER(McaParams), i64, i64, i64, i64, c_dp, i64, c_dp, c_dp, c_dp]),
+    "pm_bsc_mtrain_rows_f64": (C.c_int, [c_dp, i64, c_dp, c_dp, c_dp, i64, C.POINTER(EStepParams), i64, i64, i64, c_dp, i64,
+                                         c_dp, i64, c_dp, c_dp]),
+    "pm_col_sum_ordered_work_len": (i64, [i64, i64]),
+    "pm_col_sum_ordered_f64": (C.c_int, [c_dp, i64, i64, i64, c_dp, c_dp, c_dp]),
+    "pm_bsc_mtrain_pairs_f64": (C.c_int, [c_dp, c_dp, i64, c_dp, i64, c_dp, i64, i64, i64, i64, i64, c_dp, c_dp]),
+    "pm_bsc_mtrain_pairs_tile_rows": (i64, [i64]),
+    "pm_bsc_mtrain_solve_f64": (C.c_int, [c_dp, c_dp, c_dp, c_dp, i64, c_dp, i64, i64, i64, c_dp, i64, c_dp, c_dp]),
     "pm_patches_count": (i64, [i64, i64, i64]),
     "pm_patches_extract_f64": (C.c_int, [c_dp, i64, i64, i64, i64, i64, i64, i64, i64, i64, C.c_int, c_dp, i64, c_dp, c_dp]),
     "pm_patches_extract_f32": (C.c_int, [c_dp, i64, i64, i64, i64, i64, i64, i64, i64, i64, C.c_int, c_dp, i64, c_dp, c_dp]),

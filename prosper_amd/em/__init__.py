@@ -27,6 +27,13 @@ class Model(object):
     def standard_init(self, data):
         raise NotImplementedError
 
+    def _refuse_training_mask(self, my_data):
+        """Training on incomplete data is built for BSC_ET alone: a ``'mask'`` entry is never ignored
+        silently -- every other model's ``step`` / ``E_step`` / ``M_step`` refuses it here, before any launch."""
+        if isinstance(my_data, dict) and my_data.get('mask') is not None:
+            raise NotImplementedError("%s: training on incomplete data (my_data['mask'] in step / E_step / M_step) is not "
+                                      "built for this model; BSC_ET has the masked EM step" % type(self).__name__)
+
     @tracing.traced
     def noisify_params(self, model_params, anneal):
         """Add annealed Gaussian noise to parameters named in ``self.noise_policy``

@@ -341,12 +341,17 @@ class DeviceCAModel(CAModel):
 
     def step(self, anneal, model_params, my_data):
         """CAModel.step (camodels/__init__.py:163-193); the E-step knows that the M-step follows with the same arguments."""
+        self._refuse_training_mask(my_data)
         was, self._in_step = getattr(self, "_in_step", False), True
         self._step_id = getattr(self, "_step_id", 0) + 1
         try:
             return CAModel.step(self, anneal, model_params, my_data)
         finally:
             self._in_step = was
+
+    def _plain_step(self, anneal, model_params, my_data):
+        """CAModel.step with none of the bookkeeping the unmasked EM loop keeps between its steps."""
+        return CAModel.step(self, anneal, model_params, my_data)
 
     def _buf(self, name, shape, dtype=None):
         """Reusable device workspace (no allocation inside the EM loop once warm)."""

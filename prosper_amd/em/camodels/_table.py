@@ -195,6 +195,7 @@ class TableCAModel(DeviceCAModel):
     def M_step(self, anneal, model_params, my_suff_stat, my_data):
         """New W, pi, sigma (dsc_et.py:587-774, tsc_et.py:359-542): the statistics of the kept datapoints, one all-reduce,
         the model's ``_finalize``."""
+        self._refuse_training_mask(my_data)
         H, Hp, D = self.H, self.Hprime, self.D
         S, Kt = self.state_matrix.shape[0], self._n_logpj()
         sigma = model_params['sigma']

@@ -408,6 +408,10 @@ class BSC_ET(DeviceCAModel):
 
     def _materialize_candidates(self, ticket):
         """Selection on its own (someone looked at the lazy candidates before E_step ran)."""
+        if "masked" in ticket:      # (the masked selection does not depend on the annealing point: any point serves)
+            self._mt_launch_estep(ticket["masked"], _lib.EStepParams(pil_bar=0.0, ecoef=-0.5, prior_scale=1.0, mu_sqnorm=0.0),
+                                  ticket)
+            return
         res, par = ticket["res"], ticket["par"]
         N = res["Y"].shape[0]
         cand = torch.empty((N, self.Hprime), dtype=torch.int32, device=self.device)
@@ -429,7 +433,12 @@ class BSC_ET(DeviceCAModel):
 
     # ------------------------------------------------------------------ hot path
     def step(self, anneal, model_params, my_data):
-        """CAModel.step (camodels/__init__.py:163-193); E_step knows that M_step follows with the same arguments."""
+        """CAModel.step (camodels/__init__.py:163-193); E_step knows that M_step follows with the same arguments.
+        ``my_data['mask']`` (N, D; non-zero = observed): the EM step on incomplete data."""
+        if my_data.get('mask') is not None:
+            # (on records of its own: nothing the unmasked loop keeps between its steps is read or touched)
+            self._mt_admit(my_data, anneal)
+            return self._plain_step(anneal, model_params, my_data)
         self._in_step = True
         self._par.pop("checked", None)        # the first look at W in every step is a full comparison (_same_W)
         self._next_anneal = self._predict_anneal(anneal)
@@ -441,7 +450,10 @@ class BSC_ET(DeviceCAModel):
     @tracing.traced
     def select_Hprimes(self, model_params, data):
         """Annotate ``data`` with ``data['candidates']`` (N, Hprime): per datapoint the
-        Hprime latents with the largest <W_h,y>/|W_h|/|y|, ascending (bsc_et.py:98-115)."""
+        Hprime latents with the largest <W_h,y>/|W_h|/|y|, ascending (bsc_et.py:98-115).  With ``data['mask']``: the largest
+        b_h / sqrt(G_n[h,h]) over the observed dimensions."""
+        if data.get('mask') is not None:
+            return self._mt_select(model_params, data)
         res = self._resident(data['y'])
         N = res["Y"].shape[0]
         if self._state_tables()["fast"]:
@@ -561,6 +573,8 @@ class BSC_ET(DeviceCAModel):
     def E_step(self, anneal, model_params, my_data):
         """Log-pseudo-joints of the truncated state set -> ``{'logpj': (N, 1+H+S)}``
         (bsc_et.py:119-192).  Inserts ``model_params['mu']`` when absent, as upstream."""
+        if my_data.get('mask') is not None:
+            return self._mt_estep(anneal, model_params, my_data)
         res = self._resident(my_data['y'])
         N, D = res["Y"].shape
         H, Hp, S = self.H, self.Hprime, self.no_states
@@ -665,7 +679,10 @@ class BSC_ET(DeviceCAModel):
     @tracing.traced
     def M_step(self, anneal, model_params, my_suff_stat, my_data):
         """New W, pi, sigma (, mu) from the posterior over the truncated states
-        (bsc_et.py:195-438).  Logs ``N``, ``L`` (free energy) and ``N_use`` to dlog."""
+        (bsc_et.py:195-438).  Logs ``N``, ``L`` (free energy) and ``N_use`` to dlog.  With ``my_data['mask']``: one solve per
+        data dimension; ``W_kept`` = the dimensions that kept their row of W."""
+        if my_data.get('mask') is not None:
+            return self._mt_mstep(anneal, model_params, my_suff_stat, my_data)
         comm = self.comm
         H, Hp, D, gamma, S = self.H, self.Hprime, self.D, self.gamma, self.no_states
         W_DH = np.asarray(model_params['W'])
@@ -834,6 +851,230 @@ class BSC_ET(DeviceCAModel):
         # the exchange of the step (replaces bsc_et.py:225,258,266,373,374,387,417,426,427)
         comm.allreduce_device(packed)
         return self._finalize(packed, model_params, A_pi_gamma, E_pi_gamma, res, None, anneal)
+
+    # ------------------------------------------------------------------ training on incomplete data
+    MT_MAX_H = 256
+    MT_MAX_CELLS = 1 << 28       # D H^2: A and the inverses are two tensors of at most 2 GiB
+
+    def _mt_admit(self, my_data, anneal=None):
+        """Everything that refuses a masked training call, before any launch."""
+        y, mask = my_data['y'], my_data['mask']
+        m = getattr(mask, "tensor", mask)
+        shape = tuple(m.shape) if hasattr(m, "shape") else np.asarray(m).shape
+        if shape != tuple(y.shape) or len(shape) != 2:
+            raise ValueError("my_data['mask'] has shape %r, my_data['y'] %r" % (shape, tuple(y.shape)))
+        if 'mu' in self.to_learn:
+            raise NotImplementedError("BSC_ET: learning 'mu' on incomplete data (my_data['mask']) is not built")
+        if anneal is not None and anneal['Ncut_factor'] > 0:
+            raise NotImplementedError("BSC_ET: anneal['Ncut_factor'] > 0 with my_data['mask'] is not defined (evidences of rows "
+                                      "with different numbers of observed dimensions are densities in different spaces)")
+        if anneal is not None and anneal['data_noise'] > 0:
+            raise NotImplementedError("anneal['data_noise'] > 0 is not supported by the HIP M-step")
+        if self.Hprime > 16 or self.H > self.MT_MAX_H or self.D * self.H * self.H > self.MT_MAX_CELLS:
+            raise _lib.HipError("BSC_ET: the masked EM step holds H' <= 16, H <= %d and D H^2 <= 2^28, got H' = %d, H = %d, "
+                                "D H^2 = %d" % (self.MT_MAX_H, self.Hprime, self.H, self.D * self.H * self.H))
+
+    @staticmethod
+    def _mt_version(a):
+        """Fingerprint of a data or mask array: tensors by their version counter, host arrays by a checksum of ~16 evenly
+        spaced rows (bytes, so NaN holes compare equal to themselves)."""
+        t = getattr(a, "tensor", a)
+        if torch.is_tensor(t):
+            return (t._version, tuple(t.shape))
+        a = np.asarray(t)
+        n = a.shape[0]
+        import zlib
+        return (zlib.crc32(np.ascontiguousarray(a[::max(1, n // 16)]).tobytes()) if n else 0, a.shape)
+
+    def _mt_prepare(self, model_params, my_data):
+        """The record of the masked shard: Y, the mask, X0 / Mf / |X0|^2 / D_n (pm_masked_prepare_f64) and, for the current W,
+        W^T, b and diag G_n (pm_gemm_nt_rows_f64) -- kept between select_Hprimes, E_step and M_step, apart from the
+        unmasked loop's residency."""
+        y, mask = my_data['y'], my_data['mask']
+        mu = model_params.get('mu')
+        mu = None if mu is None or not np.any(np.asarray(mu)) else np.array(mu, dtype=np.float64)
+        rec = getattr(self, "_mt", None)
+        ver = (self._mt_version(y), self._mt_version(mask))
+        if not (rec is not None and rec["y"] is y and rec["mask"] is mask and rec["ver"] == ver
+                and (mu is None) == (rec["mu"] is None) and (mu is None or np.array_equal(mu, rec["mu"]))):
+            t = getattr(y, "tensor", y)
+            if torch.is_tensor(t):
+                Y = t.to(device=self.device, dtype=torch.float64).contiguous()
+            else:
+                Y = torch.from_numpy(np.ascontiguousarray(np.asarray(t), dtype=np.float64)).to(self.device)
+            assert Y.shape[1] == self.D
+            M, ldm = self._mask_resident(mask)
+            N = Y.shape[0]
+            if N:
+                X0, Mf, xn2, dn = self._masked_prepare(Y, M, ldm, mu)
+            else:
+                X0 = Mf = torch.zeros((0, self.D), dtype=torch.float64, device=self.device)
+                xn2, dn = X0[:, 0], torch.zeros(0, dtype=torch.int32, device=self.device)
+            rec = self._mt = {"y": y, "mask": mask, "ver": ver, "mu": mu, "Y": Y, "M": M, "ldm": ldm, "X0": X0, "Mf": Mf,
+                              "xn2": xn2, "dn": dn, "N": N, "W": None}
+        W = np.asarray(model_params['W'], dtype=np.float64)
+        if rec["W"] is None or not np.array_equal(rec["W"], W):
+            Wt = torch.from_numpy(np.ascontiguousarray(W.T)).to(self.device)
+            b = g = None
+            if rec["N"]:
+                # one kernel whatever the number of rows: a row's b and g do not depend on the rows that travel with it
+                was, self._rows_gemm = getattr(self, "_rows_gemm", False), True
+                try:
+                    b, g = self._masked_dense(rec["X0"], rec["Mf"], Wt)
+                finally:
+                    self._rows_gemm = was
+            rec.update(W=W.copy(), Wt=Wt, b=b, g=g)
+        return rec
+
+    def _mt_launch_estep(self, rec, P, ticket=None):
+        """pm_bsc_masked_estep_f64 on the record: candidates (they do not depend on ``P``) and log-joints at ``P``."""
+        N, H, D, Hp, S = rec["N"], self.H, self.D, self.Hprime, self.no_states
+        cand = torch.empty((N, Hp), dtype=torch.int32, device=self.device)
+        logpj, _ = self._estep_outputs(N)
+        if N:
+            self._call("masked_estep", "pm_bsc_masked_estep_f64", _ptr(rec["b"]), H, _ptr(rec["g"]), H, _ptr(rec["xn2"]),
+                       _ptr(rec["M"]), rec["ldm"], _ptr(rec["Wt"]), D, _ptr(self._state_tables()["masks"]), S,
+                       ctypes.byref(P), N, H, D, Hp, _ptr(cand), _ptr(logpj), logpj.stride(0), self._stream())
+        if ticket is not None:
+            ticket["cand"] = cand
+        return cand, logpj
+
+    def _mt_select(self, model_params, data):
+        """Masked ``select_Hprimes``: the dense terms are enqueued, the selection itself rides on the E-step's kernel (or
+        runs on its own when somebody looks at the candidates first)."""
+        self._mt_admit(data)
+        rec = self._mt_prepare(model_params, data)
+        data['candidates'] = LazyCandidates(self, {"cand": None, "masked": rec}, (rec["N"], self.Hprime))
+        return data
+
+    def _mt_estep(self, anneal, model_params, my_data):
+        self._mt_admit(my_data, anneal)
+        if 'mu' not in model_params:
+            model_params['mu'] = np.zeros(self.D)
+        rec = self._mt_prepare(model_params, my_data)
+        P = self._estep_params(anneal, model_params['pi'], model_params['sigma'], np.zeros(1))
+        cobj = my_data.get('candidates')
+        ticket = None
+        if isinstance(cobj, LazyCandidates) and cobj.pending and cobj._ticket.get("masked") is rec:
+            ticket = cobj._ticket
+        cand, logpj = self._mt_launch_estep(rec, P, ticket)
+        out = DeviceArray(logpj)
+        out.mt_cand = cand
+        return {'logpj': out}
+
+    def _mt_mstep(self, anneal, model_params, my_suff_stat, my_data):
+        """The M-step on incomplete rows: per-row statistics, their ordered totals, r = E[s]^T X0 and the diagonals E[s]^T Mf,
+        the per-dimension pair tensor, ONE all-reduce of [A | r | sum E[s] | sum energy, sum lse, N, sum D_n], D inverses and
+        solves, one download."""
+        self._mt_admit(my_data, anneal)
+        H, Hp, D, S = self.H, self.Hprime, self.D, self.no_states
+        pies, sigma = model_params['pi'], model_params['sigma']
+        mu = np.asarray(model_params.get('mu', np.zeros(D)), dtype=np.float64)
+        rec = self._mt_prepare(model_params, my_data)
+        my_N, dev, st = rec["N"], self.device, self._stream()
+        K = 1 + H + S
+        npair = Hp * (Hp - 1) // 2
+        learn_W = 'W' in self.to_learn
+
+        cand = self._device_candidates(my_data['candidates'], my_N)
+        logpj = my_suff_stat['logpj']
+        lp = logpj.tensor if isinstance(logpj, DeviceArray) else \
+            torch.from_numpy(np.ascontiguousarray(np.asarray(logpj), dtype=np.float64)).to(dev)
+        if lp.dim() != 2 or lp.stride(1) != 1:
+            lp = lp.contiguous()
+        assert tuple(lp.shape) == (my_N, K)
+        ldl = max(int(lp.stride(0)), K) if my_N else K
+
+        A_pi_gamma = 0
+        B_pi_gamma = 0
+        for gamma_p in range(self.gamma + 1):
+            t = comb(H, gamma_p) * (pies ** gamma_p) * ((1 - pies) ** (H - gamma_p))
+            A_pi_gamma += t
+            B_pi_gamma += gamma_p * t
+        E_pi_gamma = pies * H * A_pi_gamma / B_pi_gamma
+
+        tracing.tracepoint("M_step:iterating")
+        lib = _lib.load(self.deterministic)
+        nA, nr = (D * H * H, H * D) if learn_W else (0, 0)
+        packed = self._buf("mt_packed", (nA + nr + H + 4,))
+        A = packed[:nA].view(D, H, H) if learn_W else None
+        r = packed[nA:nA + nr].view(H, D) if learn_W else None
+        sumE = packed[nA + nr:nA + nr + H]
+        scal = packed[nA + nr + H:]
+        P = self._estep_params(anneal, pies, sigma, np.zeros(1))
+        if my_N:
+            lse = self._buf("mt_lse", (my_N,))
+            work = self._buf("mt_lse_work", (int(lib.pm_rows_lse_work_len(my_N)),))
+            self._call("mt_lse", "pm_rows_lse_f64", _ptr(lp), ldl, my_N, K, ctypes.c_double(1.0), None, _ptr(lse),
+                       _ptr(work), _ptr(scal[1:2]), st)
+            es = self._buf("mt_es", (my_N, H))
+            q2 = self._buf("mt_q2", (my_N, max(npair, 1)))
+            energy = self._buf("mt_energy", (my_N,))
+            self._call("mt_rows", "pm_bsc_mtrain_rows_f64", _ptr(lp), ldl, _ptr(lse), _ptr(cand),
+                       _ptr(self._state_tables()["masks"]), S, ctypes.byref(P), my_N, H, Hp, _ptr(es), H, _ptr(q2),
+                       max(npair, 1), _ptr(energy), st)
+            cwork = self._buf("mt_cs_work", (int(lib.pm_col_sum_ordered_work_len(my_N, H)),))
+            self._call("mt_colsum", "pm_col_sum_ordered_f64", _ptr(es), H, my_N, H, _ptr(cwork), _ptr(sumE), st)
+            self._call("mt_colsum", "pm_col_sum_ordered_f64", _ptr(energy), 1, my_N, 1, _ptr(cwork), _ptr(scal[0:1]), st)
+            scal[2] = float(my_N)
+            scal[3] = rec["dn"].sum(dtype=torch.int64).to(torch.float64)       # (sum D_n in integers)
+            if learn_W:
+                # r = E[s]^T X0 and the diagonals E[s]^T Mf through the one-kernel GEMM on the transposed operands: the whole
+                # row range per output tile, no K-slices meeting in atomics -- the same bits on every run and in both builds
+                esT = es.t().contiguous()
+                diag = self._buf("mt_diag", (H, D))
+                self._call("mt_gemm", "pm_gemm_nt_rows_f64", _ptr(esT), my_N, _ptr(rec["X0"].t().contiguous()), my_N,
+                           _ptr(r), D, H, D, my_N, st)
+                self._call("mt_gemm", "pm_gemm_nt_rows_f64", _ptr(esT), my_N, _ptr(rec["Mf"].t().contiguous()), my_N,
+                           _ptr(diag), D, H, D, my_N, st)
+                self._call("mt_pairs", "pm_bsc_mtrain_pairs_f64", _ptr(cand), _ptr(q2), max(npair, 1), _ptr(rec["M"]),
+                           rec["ldm"], _ptr(diag), D, my_N, D, H, Hp, _ptr(A), st)
+        else:
+            packed.zero_()
+
+        # the exchange of the step
+        self.comm.allreduce_device(packed)
+
+        n_head = H + 4
+        o_kept, o_x = n_head, n_head + 2
+        flat = torch.empty(o_x + (H * D if learn_W else 0), dtype=torch.float64, device=dev)
+        flat[:n_head] = packed[nA + nr:]
+        flat[o_kept:o_x] = 0.0
+        if learn_W:
+            tracing.tracepoint("M_step:update W")
+            Ainv = self._buf("mt_ainv", (D, H, H))
+            piv = self._buf("mt_piv", (D, 2))
+            for d0 in range(0, D, 65535):           # (pm_spd_inverse_batch_f64 takes 65535 matrices per launch)
+                nb = min(65535, D - d0)
+                self._call("mt_inverse", "pm_spd_inverse_batch_f64", _ptr(A[d0:]), H, H * H, None, H, None, _ptr(Ainv[d0:]),
+                           H, H * H, _ptr(piv[d0:]), nb, st)
+            status = self._buf("mt_status", (D,), torch.int32)
+            self._call("mt_solve", "pm_bsc_mtrain_solve_f64", _ptr(A), _ptr(Ainv), _ptr(piv), _ptr(r), D, _ptr(rec["Wt"]), D,
+                       D, H, _ptr(flat[o_x:]), D, _ptr(status), st)
+            flat[o_kept] = (status == 0).sum().to(torch.float64)
+        host = self._download(flat, slot="mt_mstep")
+
+        sum_energy, sum_lse = float(host[H]), float(host[H + 1])
+        N, sum_dn = int(round(host[H + 2])), int(round(host[H + 3]))
+        pi_new = E_pi_gamma * float(host[:H].sum()) / H / N if 'pi' in self.to_learn else pies
+        sigma_new = np.sqrt(sum_energy / sum_dn) if 'sigma' in self.to_learn else sigma
+        dlog.append('N', N)
+        c0, c1 = H * np.log(1 - pies), -0.5 * np.log(2 * _PI * sigma ** 2)
+        L = (N * c0 + sum_dn * c1 + sum_lse) / N - np.log(A_pi_gamma)
+        dlog.append('L', L)
+        if learn_W:
+            W_new = host[o_x:o_x + H * D].reshape(H, D).copy().T
+            self.W_kept = int(round(host[o_kept]))
+        else:
+            W_new = np.asarray(model_params['W'])
+            self.W_kept = 0
+        if 'pi' in self.to_learn:
+            tracing.tracepoint("M_step:update pi")
+        if 'sigma' in self.to_learn:
+            tracing.tracepoint("M_step:update sigma")
+        dlog.append('W_kept', self.W_kept)
+        dlog.append('N_use', N)
+        return {'W': W_new, 'pi': pi_new, 'sigma': sigma_new, 'mu': mu}
 
     def _det_quanta(self, res, W_DH, mu, P, N):
         """Deterministic mode: bounds no partial sum of the M-step's statistics can exceed on this shard with these

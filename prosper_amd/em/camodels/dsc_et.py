@@ -309,6 +309,7 @@ class DSC_ET(TableCAModel):
     @tracing.traced
     def E_step(self, anneal, model_params, my_data):
         """Log-pseudo-joints ``{'logpj': (N, 1 + (K-1)H + S)}`` (dsc_et.py:492-585)."""
+        self._refuse_training_mask(my_data)
         res = self._resident(my_data['y'])
         N = res["Y"].shape[0]
         S = self.no_states

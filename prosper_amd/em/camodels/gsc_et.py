@@ -453,6 +453,7 @@ class GSC(DeviceCAModel):
 
     def step(self, anneal, model_params, my_data):
         """CAModel.step; M_step knows that an E_step of the next EM step is likely to follow."""
+        self._refuse_training_mask(my_data)
         self._in_step = True
         self._next_anneal = self._predict_anneal(anneal)     # (round 6: across a temperature ramp too, not only a flat schedule)
         try:
@@ -653,6 +654,7 @@ class GSC(DeviceCAModel):
     def E_step(self, anneal, model_params, my_data):
         """Posterior moments over the truncated state set (gsc_et.py:401-580): ``xpt_s``, ``xpt_sz``
         (N,H) device handles, ``xpt_ss`` / ``xpt_szsz`` as sums over datapoints."""
+        self._refuse_training_mask(my_data)
         res = self._resident(my_data['y'])
         N = res["Y"].shape[0]
         cand_in = None
@@ -695,6 +697,7 @@ class GSC(DeviceCAModel):
     def M_step(self, anneal, model_params, suff_stats, my_data):
         """gsc_et.py:584-718 for scalar sigma_sq: the three contractions over datapoints are f64 MFMA
         GEMMs into one packed buffer (ONE all-reduce), the H x H algebra follows upstream on the host."""
+        self._refuse_training_mask(my_data)
         comm = self.comm
         H, D = self.H, self.D
         res = self._resident(my_data['y'])

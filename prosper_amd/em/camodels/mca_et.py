@@ -139,6 +139,7 @@ class MCA_ET(DeviceCAModel):
     # ------------------------------------------------------------------ hot path
     def step(self, anneal, model_params, my_data):
         """CAModel.step; the M-step builds the next step's power tables for the NEXT annealing point's rho."""
+        self._refuse_training_mask(my_data)
         self._next_anneal = self._predict_anneal(anneal)
         return DeviceCAModel.step(self, anneal, model_params, my_data)
 
@@ -190,6 +191,7 @@ class MCA_ET(DeviceCAModel):
     @tracing.traced
     def E_step(self, anneal, model_params, my_data):
         """Log-pseudo-joints ``{'logpj': (N, 1+H+S)}`` (mca_et.py:114-179; no beta here)."""
+        self._refuse_training_mask(my_data)
         res = self._resident(my_data['y'])
         Y = res["Y"]
         N, D = Y.shape
@@ -333,6 +335,7 @@ class MCA_ET(DeviceCAModel):
     @tracing.traced
     def M_step(self, anneal, model_params, my_suff_stat, my_data):
         """New W, pi, sigma and the ET log-likelihood Q (mca_et.py:182-377)."""
+        self._refuse_training_mask(my_data)
         comm = self.comm
         H, Hp, D, gamma, S = self.H, self.Hprime, self.D, self.gamma, self.no_states
         pies, sigma = model_params['pi'], model_params['sigma']

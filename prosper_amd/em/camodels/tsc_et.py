@@ -215,6 +215,7 @@ class TSC_ET(TableCAModel):
     @tracing.traced
     def E_step(self, anneal, model_params, my_data):
         """Log-pseudo-joints ``{'logpj': (N, S)}``, one column per table row (tsc_et.py:277-356)."""
+        self._refuse_training_mask(my_data)
         res = self._resident(my_data['y'])
         N = res["Y"].shape[0]
         S = self.state_matrix.shape[0]

@@ -86,6 +86,7 @@ class MoG(DeviceMixture, MixtureModel):
     @tracing.traced
     def E_step(self, anneal, model_params, my_data):
         """``posterior(model_params, y, 1/T)`` (MoG.py:133-140)."""
+        self._refuse_training_mask(my_data)
         return self.posterior(model_params, my_data['y'], 1. / anneal['T'])
 
     @tracing.traced
@@ -162,6 +163,7 @@ class MoG(DeviceMixture, MixtureModel):
         W = (Y^T P) / (sum P + tiny); diagonal sigma^2 = (Y^2)^T P / sum - W^2; full sigma_h = sum_n p_nh y_n y_n^T / sum_h
         - w_h w_h^T (un-centred, with the new W when W is learned); pies = sum / sum(sum).  As in the reference the
         given parameter dict is updated and returned."""
+        self._refuse_training_mask(my_data)
         H, D = self.H, self.D
         tiny = np.finfo(np.float64).tiny
         full = self.sigmas_sq_type == 'full'

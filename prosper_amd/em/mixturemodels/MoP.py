@@ -73,6 +73,7 @@ class MoP(DeviceMixture, MixtureModel):
         """``posterior`` of the normalised data at beta = 1/T (MoP.py:93-103).  The normalisation ``s y + 1`` is not
         materialised: the kernel scales the rows of the resident raw data by s (``_rowscale_host``) and adds the "+1"
         through the column constant."""
+        self._refuse_training_mask(my_data)
         return self._posterior(model_params, my_data['y'], 1. / anneal['T'], raw=True)
 
     @tracing.traced
@@ -142,6 +143,7 @@ class MoP(DeviceMixture, MixtureModel):
         Y' = s Y + 1, i.e. s-scaled Y^T P + colsum(P); W = W_num / sum P + eps, or with A set
         W_num / (colsum(W_num) / A + eps) + eps; pies = (sum P + tiny) normalised.  The given dict is updated and
         returned, as in the reference."""
+        self._refuse_training_mask(my_data)
         H, D, A = self.H, self.D, self.A
         tiny = np.finfo(np.float64).tiny
         eps = np.finfo(np.float64).eps
