@@ -68,7 +68,28 @@ def _gsc(shape):
     return (lambda: GSC(D, H, Hp, g, "scalar")), p, y, ("W", "pi", "mu", "psi_sq", "sigma_sq")
 
 
+def _mmca(shape):
+    from oracle import mmca_oracle as O
+    from prosper_amd.em.camodels.mmca_et import MMCA_ET
+    D, H, Hp, g, N = shape
+    rng = np.random.RandomState(16)
+    W = rng.normal(size=(D, H)) * 3.0
+    y = O.generate_from_hidden(W, rng.random_sample((N, H)) < 2.0 / H) + rng.normal(size=(N, D))
+    return (lambda: MMCA_ET(D, H, Hp, g)), {"W": W * rng.uniform(0.9, 1.1, size=W.shape), "pi": 2.4 / H, "sigma": 1.1}, y, ("W", "pi", "sigma")
+
+
+def _tsc(shape):
+    from prosper_amd.em.camodels.tsc_et import TSC_ET
+    D, H, Hp, g, N = shape
+    rng = np.random.RandomState(17)
+    W = rng.normal(size=(D, H)) * 2.0
+    s = rng.choice([-1., 0., 1.], size=(N, H), p=[1.0 / H, 1 - 2.0 / H, 1.0 / H])
+    y = s @ W.T + rng.normal(size=(N, D))
+    return (lambda: TSC_ET(D, H, Hp, g)), {"W": W + 0.2 * rng.normal(size=(D, H)), "pi": 2.4 / H, "sigma": 1.1}, y, ("W", "pi", "sigma")
+
+
 _CASES = {
+    "mmca": (_mmca, (64, 40, 6, 3, 600)), "tsc": (_tsc, (32, 24, 5, 3, 900)),       # the models that inherit the mode
     "bsc_small": (_bsc, (20, 12, 5, 3, 700)), "bsc_fast": (_bsc, (64, 160, 8, 3, 1500)),      # fast: the 16-wavefront kernel's shapes
     "mca": (_mca, (64, 128, 8, 3, 900)), "dsc": (_dsc, (32, 24, 5, 3, 900)), "gsc": (_gsc, (128, 128, 6, 3, 1200)),
     # shapes whose scores GEMM (pm_gemm_nt_f64) would split K in the default build -- a ragged remainder behind whole rounds
