@@ -676,6 +676,29 @@ int pm_dsc_estep_mstats_f64(const double *scores, int64_t lds, const double *gra
                             int64_t N, int64_t H, int64_t D, int64_t Hprime, double *logpj, int64_t ldl, double *lse,
                             double *expect, int64_t lde, double *stats, uint16_t *nz_idx, double *nz_val, void *stream);
 
+/* Host-only query (no device call): the launch that pm_dsc_estep_f64 (`which` = PM_DSC_PLAN_ESTEP), pm_dsc_estep_mstats_f64
+ * (PM_DSC_PLAN_ESTEP_MSTATS) or pm_dsc_mstep_rows_f64 / _nz_f64 / _cutp_f64 (PM_DSC_PLAN_MSTEP_ROWS) would make for N >= 1
+ * datapoints of this shape; the launchers switch on the same function.  out[0..7]:
+ *   0 kernel family   PM_DSC_PLAN_LANES16 (sixteen lanes per datapoint) or PM_DSC_PLAN_WAVE (one wavefront per datapoint)
+ *   1 MAXHP           8 or PM_MAX_HPRIME: the instantiation's bound on Hprime
+ *   2 VPL             8 or 16 latents per lane (sixteen-lane family; 0 for the wavefront family)
+ *   3 KM              value counters per lane: 4 or PM_DSC_MAX_K (mstats), PM_DSC_MAX_K (mstep_rows), 0 (estep: none)
+ *   4 stage           1: the log-prior table is held in LDS, 0: read from global memory
+ *   5 NT              entries of the energy-term tables, 0: the generic walk over all positions (always 0 for mstep_rows).
+ *                     A state table with more than three non-zero positions in some state turns the tables off inside
+ *                     the kernel; that is not part of the plan.
+ *   6 LDS bytes       dynamic shared memory of the launch
+ *   7 grid            workgroups (sixteen-lane family: 16 datapoints each per sweep; wavefront family: 4)
+ * Returns PM_OK, PM_EINVAL (null `out`, a size < 1, S < 0, K outside 2..PM_DSC_MAX_K, unknown `which`) or PM_ERANGE where
+ * the launcher returns PM_ERANGE for the shape (Hprime > H, Hprime > PM_MAX_HPRIME, H > 65536, LDS; mstats where
+ * pm_dsc_estep_mstats_supported is 0).  pm_dsc_mstep_rows_nz_f64 with lists needs family PM_DSC_PLAN_LANES16. */
+#define PM_DSC_PLAN_ESTEP 0
+#define PM_DSC_PLAN_ESTEP_MSTATS 1
+#define PM_DSC_PLAN_MSTEP_ROWS 2
+#define PM_DSC_PLAN_LANES16 1
+#define PM_DSC_PLAN_WAVE 2
+int pm_dsc_plan(int which, int64_t H, int64_t Hprime, int64_t S, int64_t K, int flags, int64_t N, int32_t *out);
+
 /* ---------------------------------------------------------------------------------------
  * Gaussian (spike-and-slab) Sparse Coding, scalar noise (prosper/em/camodels/gsc_et.py, GSC)
  * ------------------------------------------------------------------------------------- */

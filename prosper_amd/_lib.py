@@ -138,6 +138,7 @@ SIGNATURES = {
                                              i64, i64, i64, i64, c_dp, i64, c_dp, c_dp, c_dp, c_dp]),
     "pm_dsc_rows16_supported": (C.c_int, [i64, i64, i64, i64, C.c_int]),
     "pm_dsc_estep_mstats_supported": (C.c_int, [i64, i64, i64, i64, C.c_int]),
+    "pm_dsc_plan": (C.c_int, [C.c_int, i64, i64, i64, i64, C.c_int, i64, C.POINTER(C.c_int32)]),
     "pm_dsc_estep_mstats_f64": (C.c_int, [c_dp, i64, c_dp, c_dp, c_dp, c_dp, i64, c_dp, C.POINTER(DscParams), i64, i64, i64,
                                           i64, c_dp, i64, c_dp, c_dp, i64, c_dp, c_dp, c_dp, c_dp]),
     "pm_wp_sparse_f64": (C.c_int, [c_dp, c_dp, c_dp, i64, c_dp, i64, c_dp, i64, i64, i64, c_dp]),
@@ -218,7 +219,7 @@ class HipError(RuntimeError):
     pass
 
 
-MIN_VERSION = 1021
+MIN_VERSION = 1022
 _lib = None
 _lib_det = None
 LIB_PATH_DET = os.path.join(os.path.dirname(LIB_PATH), "libprosper_hip_det.so")

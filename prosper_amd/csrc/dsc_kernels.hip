@@ -1187,75 +1187,6 @@ extern "C" int pm_dsc_select_scores_f64(const double *scores, int64_t lds, const
     return (int)hipGetLastError();
 }
 
-extern "C" int pm_dsc_estep_f64(const double *scores, int64_t lds, const double *gram, const double *ynorm2,
-                                const int32_t *cand, const uint8_t *state_idx, int64_t S, const double *prior,
-                                const pm_dsc_params *params_host, int64_t N, int64_t H, int64_t Hprime, double *logpj,
-                                int64_t ldl, double *lse, void *stream) {
-    if (N == 0) return PM_OK;
-    if (!scores || !gram || !ynorm2 || !cand || !prior || !logpj || !lse || N < 0 || H <= 0 || Hprime <= 0 || S < 0 ||
-        lds < H || bad_params(params_host) || (S > 0 && !state_idx))
-        return PM_EINVAL;
-    if (ldl < ((params_host->flags & PM_DSC_TABLE_ONLY) ? S : 1 + (params_host->K - 1) * H + S)) return PM_EINVAL;
-    if (Hprime > PM_MAX_HPRIME || Hprime > H || H > 65536) return PM_ERANGE;
-    const int64_t Kt = (params_host->flags & PM_DSC_TABLE_ONLY) ? S : 1 + (params_host->K - 1) * H + S;
-#ifndef PM_DSC_WAVE64
-    {
-        // sixteen lanes per datapoint where its LDS layout fits four workgroups per CU
-        const int64_t Kn16 = params_host->K - 1;
-        int64_t NT16 = 1 + Hprime * Kn16 + Hprime * (Hprime - 1) / 2 * Kn16 * Kn16;
-        if (NT16 > 256 || S == 0) NT16 = 0;
-        if (S * Hprime < (1 << 20) && Kt < (1 << 20)) {
-            int stage16 = 1;
-            Lay16 L = dsc_lay16((int)H, (int)Hprime, (int)S, (int)Kt, (int)NT16, stage16);
-            if (L.bytes > 40 * 1024) {
-                stage16 = 0;
-                L = dsc_lay16((int)H, (int)Hprime, (int)S, (int)Kt, (int)NT16, stage16);
-            }
-            if (L.bytes <= 40 * 1024 && H <= 256) {
-                const int64_t blocks16 = (N + 15) / 16;
-                const unsigned grid16 = (unsigned)(blocks16 < 256 * 4 ? blocks16 : 256 * 4);
-#define PM_LAUNCH16(M, V)                                                                                              \
-    do {                                                                                                               \
-        if (int e = allow_lds_dsc(reinterpret_cast<const void *>(dsc_estep16_kernel<M, V>), (size_t)L.bytes)) return e; \
-        hipLaunchKernelGGL((dsc_estep16_kernel<M, V>), dim3(grid16), dim3(256), (size_t)L.bytes,                       \
-                           static_cast<hipStream_t>(stream), scores, lds, gram, ynorm2, cand, state_idx, (int)S, prior, \
-                           *params_host, N, (int)H, (int)Hprime, logpj, ldl, lse, stage16, (int)NT16);                 \
-    } while (0)
-                if (Hprime <= 8 && H <= 128) PM_LAUNCH16(8, 8);
-                else if (Hprime <= 8) PM_LAUNCH16(8, 16);
-                else if (H <= 128) PM_LAUNCH16(PM_MAX_HPRIME, 8);
-                else PM_LAUNCH16(PM_MAX_HPRIME, 16);
-#undef PM_LAUNCH16
-                return (int)hipGetLastError();
-            }
-        }
-    }
-#endif
-    size_t shmem = sizeof(double) * (H + WAVES * (Hprime + Hprime * Hprime)) + align8((size_t)S * Hprime);
-    if (shmem > 150 * 1024) return PM_ERANGE;
-    const size_t staged = shmem + sizeof(double) * (size_t)(WAVES + 1) * (size_t)Kt;
-    const int stage = staged <= 30 * 1024 ? 1 : 0;       // keep five workgroups per CU
-    if (stage) shmem = staged;
-    // the energy-term tables (see the kernel): where they fit beside the rest
-    const int64_t Kn = params_host->K - 1;
-    int64_t NT = 1 + Hprime * Kn + Hprime * (Hprime - 1) / 2 * Kn * Kn;
-    const size_t fast_off = align8(shmem);
-    const size_t fast_bytes = (size_t)S * 8 + 2 * (size_t)((NT + 7) & ~7) + sizeof(double) * (size_t)NT * (2 + WAVES);
-    if (NT > 256 || S == 0 || fast_off + fast_bytes > 40 * 1024) NT = 0;
-    else shmem = fast_off + fast_bytes;
-#define PM_LAUNCH(M)                                                                                                 \
-    do {                                                                                                             \
-        if (int e = allow_lds_dsc(reinterpret_cast<const void *>(dsc_estep_kernel<M>), shmem)) return e;             \
-        hipLaunchKernelGGL(dsc_estep_kernel<M>, dim3(row_grid(N, M <= 8 ? 5 : 4)), dim3(64 * WAVES), shmem,            \
-                           static_cast<hipStream_t>(stream), scores, lds, gram, ynorm2, cand, state_idx, (int)S, prior, \
-                           *params_host, N, (int)H, (int)Hprime, logpj, ldl, lse, stage, (int)fast_off, (int)NT);   \
-    } while (0)
-    if (Hprime <= 8) PM_LAUNCH(8);
-    else PM_LAUNCH(PM_MAX_HPRIME);
-#undef PM_LAUNCH
-    return (int)hipGetLastError();
-}
-
 // E-step + M-step row statistics in one pass (dsc_estep16_ms_kernel): its LDS layout, or 0 where it does not apply
 static size_t dsc_estep_ms_lds(int64_t H, int64_t Hprime, int64_t S, int64_t Kt, int64_t Kn, int *stage16, int *nt16) {
 #ifdef PM_DSC_WAVE64
@@ -1278,6 +1209,175 @@ static size_t dsc_estep_ms_lds(int64_t H, int64_t Hprime, int64_t S, int64_t Kt,
 #endif
 }
 
+// the launch geometry of dsc_mstep_rows16_kernel, or 0 bytes where it does not apply
+static size_t dsc_rows16_lds(int64_t H, int64_t Hprime, int64_t S, int64_t Kt, int *stage16) {
+#ifdef PM_DSC_WAVE64
+    return 0;
+#else
+    if (!(H <= 256 && S * Hprime < (1 << 20) && Kt < (1 << 20))) return 0;
+    const size_t fixed = sizeof(double) * (H + PM_DSC_MAX_K + 4) + align8((size_t)S * Hprime);
+    const size_t rows16 = sizeof(double) * 16 * (size_t)(H + Hprime + Hprime * Hprime);
+    *stage16 = 1;
+    size_t sh16 = fixed + sizeof(double) * (size_t)Kt + rows16;
+    if (sh16 > 40 * 1024) {
+        *stage16 = 0;
+        sh16 = fixed + rows16;
+    }
+    return sh16 <= 40 * 1024 ? sh16 : 0;
+#endif
+}
+
+// Every launch decision of pm_dsc_estep_f64, pm_dsc_estep_mstats_f64 and pm_dsc_mstep_rows_cutp_f64: the launchers switch on
+// this struct and pm_dsc_plan exports it, so a test that asks for the plan sees the path the launch takes.
+struct DscPlan {
+    int family, maxhp, vpl, km, stage, nt, fast_off;
+    size_t lds;
+    unsigned grid;
+};
+
+static int dsc_plan(int which, int64_t H, int64_t Hprime, int64_t S, int64_t K, int flags, int64_t N, DscPlan *p) {
+    if (which < PM_DSC_PLAN_ESTEP || which > PM_DSC_PLAN_MSTEP_ROWS || H <= 0 || Hprime <= 0 || S < 0 || N < 1 || K < 2 ||
+        K > PM_DSC_MAX_K)
+        return PM_EINVAL;
+    if (Hprime > PM_MAX_HPRIME || Hprime > H || H > 65536) return PM_ERANGE;
+    const int64_t Kn = K - 1;
+    const int64_t Kt = (flags & PM_DSC_TABLE_ONLY) ? S : 1 + Kn * H + S;
+    *p = DscPlan{};
+    p->maxhp = Hprime <= 8 ? 8 : PM_MAX_HPRIME;
+    const int64_t blocks16 = (N + 15) / 16;
+    if (which == PM_DSC_PLAN_ESTEP_MSTATS) {
+        p->lds = dsc_estep_ms_lds(H, Hprime, S, Kt, Kn, &p->stage, &p->nt);
+        if (!p->lds) return PM_ERANGE;
+        const int per_cu = (Hprime <= 8 && H <= 128) ? PM_DSC_MS_WPE : 2;
+        p->family = PM_DSC_PLAN_LANES16;
+        p->vpl = H <= 128 ? 8 : 16;
+        p->km = K <= 4 ? 4 : PM_DSC_MAX_K;
+        p->grid = (unsigned)(blocks16 < 256 * per_cu ? blocks16 : 256 * per_cu);
+        return PM_OK;
+    }
+    if (which == PM_DSC_PLAN_MSTEP_ROWS) {
+        // sixteen lanes per datapoint where the layout fits four workgroups per CU
+        p->km = PM_DSC_MAX_K;
+        p->lds = dsc_rows16_lds(H, Hprime, S, Kt, &p->stage);
+        if (p->lds) {
+            p->family = PM_DSC_PLAN_LANES16;
+            p->vpl = H <= 128 ? 8 : 16;
+            p->grid = (unsigned)(blocks16 < 256 * 4 ? blocks16 : 256 * 4);
+            return PM_OK;
+        }
+        size_t shmem = sizeof(double) * (H + PM_DSC_MAX_K + 4 + WAVES * (H + Hprime + Hprime * Hprime)) +
+                       align8((size_t)S * Hprime);
+        if (shmem > 150 * 1024) return PM_ERANGE;
+        p->stage = shmem + sizeof(double) * (size_t)Kt <= 36 * 1024 ? 1 : 0;     // four workgroups per CU stay
+        if (p->stage) shmem += sizeof(double) * (size_t)Kt;
+        p->family = PM_DSC_PLAN_WAVE;
+        p->lds = shmem;
+        p->grid = row_grid(N, p->maxhp <= 8 ? 4 : 3);
+        return PM_OK;
+    }
+#ifndef PM_DSC_WAVE64
+    {
+        // sixteen lanes per datapoint where its LDS layout fits four workgroups per CU
+        int64_t NT16 = 1 + Hprime * Kn + Hprime * (Hprime - 1) / 2 * Kn * Kn;
+        if (NT16 > 256 || S == 0) NT16 = 0;
+        if (S * Hprime < (1 << 20) && Kt < (1 << 20)) {
+            int stage16 = 1;
+            Lay16 L = dsc_lay16((int)H, (int)Hprime, (int)S, (int)Kt, (int)NT16, stage16);
+            if (L.bytes > 40 * 1024) {
+                stage16 = 0;
+                L = dsc_lay16((int)H, (int)Hprime, (int)S, (int)Kt, (int)NT16, stage16);
+            }
+            if (L.bytes <= 40 * 1024 && H <= 256) {
+                p->family = PM_DSC_PLAN_LANES16;
+                p->vpl = H <= 128 ? 8 : 16;
+                p->stage = stage16;
+                p->nt = (int)NT16;
+                p->lds = (size_t)L.bytes;
+                p->grid = (unsigned)(blocks16 < 256 * 4 ? blocks16 : 256 * 4);
+                return PM_OK;
+            }
+        }
+    }
+#endif
+    size_t shmem = sizeof(double) * (H + WAVES * (Hprime + Hprime * Hprime)) + align8((size_t)S * Hprime);
+    if (shmem > 150 * 1024) return PM_ERANGE;
+    const size_t staged = shmem + sizeof(double) * (size_t)(WAVES + 1) * (size_t)Kt;
+    p->stage = staged <= 30 * 1024 ? 1 : 0;       // keep five workgroups per CU
+    if (p->stage) shmem = staged;
+    // the energy-term tables (see the kernel): where they fit beside the rest
+    int64_t NT = 1 + Hprime * Kn + Hprime * (Hprime - 1) / 2 * Kn * Kn;
+    const size_t fast_off = align8(shmem);
+    const size_t fast_bytes = (size_t)S * 8 + 2 * (size_t)((NT + 7) & ~7) + sizeof(double) * (size_t)NT * (2 + WAVES);
+    if (NT > 256 || S == 0 || fast_off + fast_bytes > 40 * 1024) NT = 0;
+    else shmem = fast_off + fast_bytes;
+    p->family = PM_DSC_PLAN_WAVE;
+    p->nt = (int)NT;
+    p->fast_off = (int)fast_off;
+    p->lds = shmem;
+    p->grid = row_grid(N, p->maxhp <= 8 ? 5 : 4);
+    return PM_OK;
+}
+
+extern "C" int pm_dsc_plan(int which, int64_t H, int64_t Hprime, int64_t S, int64_t K, int flags, int64_t N, int32_t *out) {
+    if (!out) return PM_EINVAL;
+    DscPlan p;
+    if (int e = dsc_plan(which, H, Hprime, S, K, flags, N, &p)) return e;
+    out[0] = p.family;
+    out[1] = p.maxhp;
+    out[2] = p.vpl;
+    out[3] = p.km;
+    out[4] = p.stage;
+    out[5] = p.nt;
+    out[6] = (int32_t)p.lds;
+    out[7] = (int32_t)p.grid;
+    return PM_OK;
+}
+
+// the four sixteen-lane instantiations <MAXHP 8|16, VPL 8|16> of a plan
+#define PM_DSC_DISPATCH16(plan, LAUNCH)                                 \
+    do {                                                                \
+        if ((plan).maxhp == 8 && (plan).vpl == 8) LAUNCH(8, 8);         \
+        else if ((plan).maxhp == 8) LAUNCH(8, 16);                      \
+        else if ((plan).vpl == 8) LAUNCH(PM_MAX_HPRIME, 8);             \
+        else LAUNCH(PM_MAX_HPRIME, 16);                                 \
+    } while (0)
+
+extern "C" int pm_dsc_estep_f64(const double *scores, int64_t lds, const double *gram, const double *ynorm2,
+                                const int32_t *cand, const uint8_t *state_idx, int64_t S, const double *prior,
+                                const pm_dsc_params *params_host, int64_t N, int64_t H, int64_t Hprime, double *logpj,
+                                int64_t ldl, double *lse, void *stream) {
+    if (N == 0) return PM_OK;
+    if (!scores || !gram || !ynorm2 || !cand || !prior || !logpj || !lse || N < 0 || H <= 0 || Hprime <= 0 || S < 0 ||
+        lds < H || bad_params(params_host) || (S > 0 && !state_idx))
+        return PM_EINVAL;
+    if (ldl < ((params_host->flags & PM_DSC_TABLE_ONLY) ? S : 1 + (params_host->K - 1) * H + S)) return PM_EINVAL;
+    DscPlan pl;
+    if (int e = dsc_plan(PM_DSC_PLAN_ESTEP, H, Hprime, S, params_host->K, params_host->flags, N, &pl)) return e;
+    if (pl.family == PM_DSC_PLAN_LANES16) {
+#define PM_LAUNCH16(M, V)                                                                                              \
+    do {                                                                                                               \
+        if (int e = allow_lds_dsc(reinterpret_cast<const void *>(dsc_estep16_kernel<M, V>), pl.lds)) return e;         \
+        hipLaunchKernelGGL((dsc_estep16_kernel<M, V>), dim3(pl.grid), dim3(256), pl.lds,                               \
+                           static_cast<hipStream_t>(stream), scores, lds, gram, ynorm2, cand, state_idx, (int)S, prior, \
+                           *params_host, N, (int)H, (int)Hprime, logpj, ldl, lse, pl.stage, pl.nt);                    \
+    } while (0)
+        PM_DSC_DISPATCH16(pl, PM_LAUNCH16);
+#undef PM_LAUNCH16
+        return (int)hipGetLastError();
+    }
+#define PM_LAUNCH(M)                                                                                                 \
+    do {                                                                                                             \
+        if (int e = allow_lds_dsc(reinterpret_cast<const void *>(dsc_estep_kernel<M>), pl.lds)) return e;            \
+        hipLaunchKernelGGL(dsc_estep_kernel<M>, dim3(pl.grid), dim3(64 * WAVES), pl.lds,                             \
+                           static_cast<hipStream_t>(stream), scores, lds, gram, ynorm2, cand, state_idx, (int)S, prior, \
+                           *params_host, N, (int)H, (int)Hprime, logpj, ldl, lse, pl.stage, pl.fast_off, pl.nt);     \
+    } while (0)
+    if (pl.maxhp == 8) PM_LAUNCH(8);
+    else PM_LAUNCH(PM_MAX_HPRIME);
+#undef PM_LAUNCH
+    return (int)hipGetLastError();
+}
+
 extern "C" int pm_dsc_estep_mstats_supported(int64_t H, int64_t Hprime, int64_t S, int64_t K, int flags) {
     if (H <= 0 || Hprime <= 0 || Hprime > PM_MAX_HPRIME || Hprime > H || S < 0 || K < 2 || K > PM_DSC_MAX_K) return 0;
     int st = 0, nt = 0;
@@ -1297,54 +1397,28 @@ extern "C" int pm_dsc_estep_mstats_f64(const double *scores, int64_t lds, const 
         return PM_EINVAL;
     const int64_t Kt = (params_host->flags & PM_DSC_TABLE_ONLY) ? S : 1 + (params_host->K - 1) * H + S;
     if (ldl < Kt) return PM_EINVAL;
-    if (Hprime > PM_MAX_HPRIME || Hprime > H) return PM_ERANGE;
-    int stage16 = 0, NT16 = 0;
-    const size_t shmem = dsc_estep_ms_lds(H, Hprime, S, Kt, params_host->K - 1, &stage16, &NT16);
-    if (!shmem) return PM_ERANGE;
-    const int64_t blocks16 = (N + 15) / 16;
-    const int per_cu = (Hprime <= 8 && H <= 128) ? PM_DSC_MS_WPE : 2;
-    const unsigned grid16 = (unsigned)(blocks16 < 256 * per_cu ? blocks16 : 256 * per_cu);
+    DscPlan pl;
+    if (int e = dsc_plan(PM_DSC_PLAN_ESTEP_MSTATS, H, Hprime, S, params_host->K, params_host->flags, N, &pl)) return e;
 #define PM_LAUNCH16K(M, V, KMV)                                                                                        \
     do {                                                                                                               \
-        if (int e = allow_lds_dsc(reinterpret_cast<const void *>(dsc_estep16_ms_kernel<M, V, KMV>), shmem)) return e;  \
-        hipLaunchKernelGGL((dsc_estep16_ms_kernel<M, V, KMV>), dim3(grid16), dim3(256), shmem,                         \
+        if (int e = allow_lds_dsc(reinterpret_cast<const void *>(dsc_estep16_ms_kernel<M, V, KMV>), pl.lds)) return e; \
+        hipLaunchKernelGGL((dsc_estep16_ms_kernel<M, V, KMV>), dim3(pl.grid), dim3(256), pl.lds,                       \
                            static_cast<hipStream_t>(stream), scores, lds, gram, ynorm2, cand, state_idx, (int)S, prior, \
-                           *params_host, N, (int)H, (int)D, (int)Hprime, logpj, ldl, lse, stage16, NT16, expect, lde,   \
+                           *params_host, N, (int)H, (int)D, (int)Hprime, logpj, ldl, lse, pl.stage, pl.nt, expect, lde, \
                            stats, nz_idx, nz_val);                                                                     \
     } while (0)
 #define PM_LAUNCH16(M, V)                        \
     do {                                         \
-        if (params_host->K <= 4) {               \
+        if (pl.km == 4) {                        \
             PM_LAUNCH16K(M, V, 4);               \
         } else {                                 \
             PM_LAUNCH16K(M, V, PM_DSC_MAX_K);    \
         }                                        \
     } while (0)
-    if (Hprime <= 8 && H <= 128) PM_LAUNCH16(8, 8);
-    else if (Hprime <= 8) PM_LAUNCH16(8, 16);
-    else if (H <= 128) PM_LAUNCH16(PM_MAX_HPRIME, 8);
-    else PM_LAUNCH16(PM_MAX_HPRIME, 16);
+    PM_DSC_DISPATCH16(pl, PM_LAUNCH16);
 #undef PM_LAUNCH16
 #undef PM_LAUNCH16K
     return (int)hipGetLastError();
-}
-
-// the launch geometry of dsc_mstep_rows16_kernel, or 0 bytes where it does not apply
-static size_t dsc_rows16_lds(int64_t H, int64_t Hprime, int64_t S, int64_t Kt, int *stage16) {
-#ifdef PM_DSC_WAVE64
-    return 0;
-#else
-    if (!(H <= 256 && S * Hprime < (1 << 20) && Kt < (1 << 20))) return 0;
-    const size_t fixed = sizeof(double) * (H + PM_DSC_MAX_K + 4) + align8((size_t)S * Hprime);
-    const size_t rows16 = sizeof(double) * 16 * (size_t)(H + Hprime + Hprime * Hprime);
-    *stage16 = 1;
-    size_t sh16 = fixed + sizeof(double) * (size_t)Kt + rows16;
-    if (sh16 > 40 * 1024) {
-        *stage16 = 0;
-        sh16 = fixed + rows16;
-    }
-    return sh16 <= 40 * 1024 ? sh16 : 0;
-#endif
 }
 
 extern "C" int pm_dsc_rows16_supported(int64_t H, int64_t Hprime, int64_t S, int64_t K, int flags) {
@@ -1383,45 +1457,30 @@ extern "C" int pm_dsc_mstep_rows_cutp_f64(const double *logpj, int64_t ldl, cons
     if (ldl < ((params_host->flags & PM_DSC_TABLE_ONLY) ? S : 1 + (params_host->K - 1) * H + S) ||
         params_host->ecoef == 0.0)
         return PM_EINVAL;
-    if (Hprime > PM_MAX_HPRIME || Hprime > H || H > 65536) return PM_ERANGE;
-    const int64_t Kt = (params_host->flags & PM_DSC_TABLE_ONLY) ? S : 1 + (params_host->K - 1) * H + S;
-    {
-        // sixteen lanes per datapoint where the layout fits four workgroups per CU
-        int stage16 = 0;
-        const size_t sh16 = dsc_rows16_lds(H, Hprime, S, Kt, &stage16);
-        if (sh16) {
-            const int64_t blocks16 = (N + 15) / 16;
-            const unsigned grid16 = (unsigned)(blocks16 < 256 * 4 ? blocks16 : 256 * 4);
+    DscPlan pl;
+    if (int e = dsc_plan(PM_DSC_PLAN_MSTEP_ROWS, H, Hprime, S, params_host->K, params_host->flags, N, &pl)) return e;
+    if (pl.family == PM_DSC_PLAN_LANES16) {
 #define PM_LAUNCH16(M, V)                                                                                              \
     do {                                                                                                               \
-        if (int e = allow_lds_dsc(reinterpret_cast<const void *>(dsc_mstep_rows16_kernel<M, V>), sh16)) return e;      \
-        hipLaunchKernelGGL((dsc_mstep_rows16_kernel<M, V>), dim3(grid16), dim3(256), sh16,                             \
+        if (int e = allow_lds_dsc(reinterpret_cast<const void *>(dsc_mstep_rows16_kernel<M, V>), pl.lds)) return e;    \
+        hipLaunchKernelGGL((dsc_mstep_rows16_kernel<M, V>), dim3(pl.grid), dim3(256), pl.lds,                          \
                            static_cast<hipStream_t>(stream), logpj, ldl, lse, lse_cut, cand, state_idx, (int)S, prior, \
-                           *params_host, N, (int)H, (int)D, (int)Hprime, expect, lde, stats, stage16, nz_idx, nz_val,  \
+                           *params_host, N, (int)H, (int)D, (int)Hprime, expect, lde, stats, pl.stage, nz_idx, nz_val, \
                            cut_dev);                                                                                   \
     } while (0)
-            if (Hprime <= 8 && H <= 128) PM_LAUNCH16(8, 8);
-            else if (Hprime <= 8) PM_LAUNCH16(8, 16);
-            else if (H <= 128) PM_LAUNCH16(PM_MAX_HPRIME, 8);
-            else PM_LAUNCH16(PM_MAX_HPRIME, 16);
+        PM_DSC_DISPATCH16(pl, PM_LAUNCH16);
 #undef PM_LAUNCH16
-            return (int)hipGetLastError();
-        }
+        return (int)hipGetLastError();
     }
     if (nz_idx) return PM_ERANGE;       // (lists come from the sixteen-lane kernel only: pm_dsc_rows16_supported)
-    size_t shmem = sizeof(double) * (H + PM_DSC_MAX_K + 4 + WAVES * (H + Hprime + Hprime * Hprime)) +
-                   align8((size_t)S * Hprime);
-    if (shmem > 150 * 1024) return PM_ERANGE;
-    const int stage = shmem + sizeof(double) * (size_t)Kt <= 36 * 1024 ? 1 : 0;     // four workgroups per CU stay
-    if (stage) shmem += sizeof(double) * (size_t)Kt;
 #define PM_LAUNCH(M)                                                                                                 \
     do {                                                                                                             \
-        if (int e = allow_lds_dsc(reinterpret_cast<const void *>(dsc_mstep_rows_kernel<M>), shmem)) return e;        \
-        hipLaunchKernelGGL(dsc_mstep_rows_kernel<M>, dim3(row_grid(N, M <= 8 ? 4 : 3)), dim3(64 * WAVES), shmem,       \
+        if (int e = allow_lds_dsc(reinterpret_cast<const void *>(dsc_mstep_rows_kernel<M>), pl.lds)) return e;       \
+        hipLaunchKernelGGL(dsc_mstep_rows_kernel<M>, dim3(pl.grid), dim3(64 * WAVES), pl.lds,                        \
                            static_cast<hipStream_t>(stream), logpj, ldl, lse, lse_cut, cand, state_idx, (int)S, prior, \
-                           *params_host, N, (int)H, (int)D, (int)Hprime, expect, lde, stats, stage, cut_dev);        \
+                           *params_host, N, (int)H, (int)D, (int)Hprime, expect, lde, stats, pl.stage, cut_dev);     \
     } while (0)
-    if (Hprime <= 8) PM_LAUNCH(8);
+    if (pl.maxhp == 8) PM_LAUNCH(8);
     else PM_LAUNCH(PM_MAX_HPRIME);
 #undef PM_LAUNCH
     return (int)hipGetLastError();
