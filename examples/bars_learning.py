@@ -93,7 +93,8 @@ def main():
                     "datapoint under the learned parameters and under the ground-truth ones (DESIGN 4.12)")
     ap.add_argument("--exact", action="store_true",
                     help="with --heldout: also the exact held-out log-likelihood of the learned parameters, summed over "
-                    "every latent state (DESIGN 4.13), next to the truncated bound and their difference per datapoint")
+                    "every latent state (DESIGN 4.13), next to the truncated bound and their difference per datapoint; "
+                    "with --reconstruct: also the mean squared error of the exact posterior mean (DESIGN 4.18)")
     ap.add_argument("--reconstruct", action="store_true",
                     help="with --heldout: denoise the held-out datapoints (reconstruct, DESIGN 4.14) and print the mean squared "
                     "error of the noisy data and of the reconstruction against the noiseless data, for the learned and for "
@@ -172,6 +173,15 @@ def main():
                 print("held-out mean squared error against the noiseless data (%d datapoints): noisy data %.4f, reconstruction "
                       "with the learned parameters %.4f, with the generating parameters %.4f"
                       % (a.heldout, sums[0] / sums[3], sums[1] / sums[3], sums[2] / sums[3]))
+            if a.exact:
+                # the quantity the truncated reconstruction approximates: the posterior mean over EVERY state;
+                # with the generating parameters it is the minimum-mean-square estimate of the noiseless data
+                ex = comm.allreduce(np.array([sq(rmodel.reconstruct(dict(em.lparams), heldout, exact=True)),
+                                              sq(rmodel.reconstruct(dict(gt), heldout, exact=True))]))
+                if comm.rank == 0:
+                    print("held-out mean squared error with the learned parameters: noisy data %.4f, truncated reconstruction "
+                          "%.4f, exact reconstruction %.4f (generating parameters: truncated %.4f, exact %.4f)"
+                          % (sums[0] / sums[3], sums[1] / sums[3], ex[0] / sums[3], sums[2] / sums[3], ex[1] / sums[3]))
 
 
 if __name__ == "__main__":

@@ -930,6 +930,42 @@ int pm_loglik_exact_gsc_f64(const double *Y, int64_t ldy, const double *P, const
                             int64_t D, int64_t H, double *rows_out, double *work, double *total, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Exact posterior-mean reconstruction (recon_exact.hip)
+ * ---------------------------------------------------------------------------------------
+ * The posterior expectation sum_{all s} q_n(s) f(s), q_n(s) = p(s, y_n) / sum_{all s'} p(s', y_n), over the model's WHOLE
+ * state space by enumeration on the device, with the models, arguments and log-joints of pm_loglik_exact_* (row constants
+ * cancel in q and are not taken).  Two sweeps over the states: the first forms v_n = log sum_s exp l_n(s), the second the
+ * sums weighted by exp(l_n(s) - v_n).  The state index space is cut into R ranges, R a function of the state count alone
+ * (never of N); a workgroup owns one (row or row tile, range) and writes one partial, and the partials are merged in range
+ * order.  No atomics: a row of the result is a function of that row of Y and of the parameters alone -- the same bits on
+ * every run, in both builds, under a row permutation and in any shard.  A NaN in y_n makes that row NaN and no other; a
+ * state of zero prior carries weight 0.
+ *
+ * `work`: pm_recon_exact_work_len(N, H, D) doubles, enough for any of the three entries.  The entries walk N in row blocks
+ * of a fixed size (256 rows; MCA 64), so the length is bounded in N, does not depend on the state count and is at most
+ * min(N, 256) (H + 1 + 256 max(H, 2)) or min(N, 64) (1 + 64 max(D, 2)), whichever is larger (-1 for N < 0, H < 1 or D < 1).
+ * Every entry checks its arguments before it touches a device: PM_EINVAL for a null pointer, N < 0, D < 1, H < 1, ldy < D,
+ * an output leading dimension below the row width or a bad K; PM_ERANGE past the bounds of pm_loglik_exact_* (K^H <= 2^32
+ * and H <= 32; GSC H <= 16) and, for MCA / MMCA, D > 1024.  N == 0 launches nothing and returns PM_OK. */
+int64_t pm_recon_exact_work_len(int64_t N, int64_t H, int64_t D);
+/* BSC, TSC, DSC: E (N x H, row stride lde >= H) receives E_n[s]_h = sum_s q_n(s) values[k_h]; Y, ymu, P, G, logp, values and
+ * K as for pm_loglik_exact_lin_f64.  Columns of E past H are not written. */
+int pm_recon_exact_lin_f64(const double *Y, int64_t ldy, const double *ymu, const double *P, const double *G,
+                           const double *logp, const double *values, int64_t K, int64_t N, int64_t D, int64_t H, double *E,
+                           int64_t lde, double *work, void *stream);
+/* MCA (signed_w = 0) and MMCA (signed_w = 1): Yhat (N x D, row stride ldo >= D) receives sum_s q_n(s) Wbar_d(s); Wrho,
+ * inv_rho, lp1, lp0 and inv_s2 as for pm_loglik_exact_mca_f64.  One wavefront per state, lanes over the dimensions. */
+int pm_recon_exact_mca_f64(const double *Y, int64_t ldy, const double *Wrho, double inv_rho, int signed_w, double lp1,
+                           double lp0, double inv_s2, int64_t N, int64_t D, int64_t H, double *Yhat, int64_t ldo,
+                           double *work, void *stream);
+/* GSC: E (N x H, row stride lde >= H) receives E_n[s o z]_h = sum_s q_n(s) kappa_s(y_n)_h (0 for h outside s), kappa_s =
+ * mu_s + A_s^T (A_s beta_{n,s}) = E[z_s | s, y_n] in the notation of pm_loglik_exact_gsc_f64; P, M, Psi, mu and logp as
+ * there (y^T Sigma^-1 y is a row constant and not needed). */
+int pm_recon_exact_gsc_f64(const double *Y, int64_t ldy, const double *P, const double *M, const double *Psi,
+                           const double *mu, const double *logp, int64_t N, int64_t D, int64_t H, double *E, int64_t lde,
+                           double *work, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Posterior-mean reconstruction (reconstruct_kernels.hip)
  * ---------------------------------------------------------------------------------------
  * yhat_n = sum_{s in K_n} q_n(s) ybar(s), q_n(s) = exp(a logpj[n,s] + o_s - lse_n), over exactly the states whose log-joints

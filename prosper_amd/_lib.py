@@ -189,6 +189,11 @@ SIGNATURES = {
                                           C.c_double, i64, i64, i64, c_dp, c_dp, c_dp, c_dp]),
     "pm_loglik_exact_gsc_f64": (C.c_int, [c_dp, i64, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.c_double, i64, i64, i64,
                                           c_dp, c_dp, c_dp, c_dp]),
+    "pm_recon_exact_work_len": (i64, [i64, i64, i64]),
+    "pm_recon_exact_lin_f64": (C.c_int, [c_dp, i64, c_dp, c_dp, c_dp, c_dp, c_dp, i64, i64, i64, i64, c_dp, i64, c_dp, c_dp]),
+    "pm_recon_exact_mca_f64": (C.c_int, [c_dp, i64, c_dp, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, i64, i64,
+                                         i64, c_dp, i64, c_dp, c_dp]),
+    "pm_recon_exact_gsc_f64": (C.c_int, [c_dp, i64, c_dp, c_dp, c_dp, c_dp, c_dp, i64, i64, i64, c_dp, i64, c_dp, c_dp]),
     "pm_gemm_nt_rows_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, i64, i64, i64, i64, c_dp]),
     "pm_recon_expect_f64": (C.c_int, [c_dp, i64, c_dp, C.c_double, c_dp, c_dp, c_dp, c_dp, i64, i64, i64, i64, i64, i64, i64,
                                       i64, c_dp, i64, i64, i64, c_dp]),
@@ -219,7 +224,7 @@ class HipError(RuntimeError):
     pass
 
 
-MIN_VERSION = 1022
+MIN_VERSION = 1023
 _lib = None
 _lib_det = None
 LIB_PATH_DET = os.path.join(os.path.dirname(LIB_PATH), "libprosper_hip_det.so")

@@ -1146,7 +1146,7 @@ class DeviceCAModel(CAModel):
                        self.Hprime, self.no_states, _ptr(Yhat), self.D, self._stream())
         return Yhat
 
-    def reconstruct(self, model_params, my_data, device=False):
+    def reconstruct(self, model_params, my_data, device=False, exact=False):
         """Posterior-mean denoising: yhat_n = sum_{s in K_n} q_n(s) ybar(s; Theta), q_n(s) = p(s, y_n | Theta) / sum_{s' in K_n}
         p(s', y_n | Theta), for ``my_data['y']`` (host array, torch tensor or DeviceArray): the model's estimate of the
         noiseless data.  K_n and p are exactly those of ``log_likelihood``: the state set the E-step scores
@@ -1166,12 +1166,19 @@ class DeviceCAModel(CAModel):
         ``my_data['mask']`` (N, D; non-zero = observed; NumPy, torch or DeviceArray of any numeric type; BSC,
         MCA and MMCA): q_n comes from the joint of the observed dimensions alone, yhat_n still covers all D -- the missing
         ones are inpainted.  Whatever an unobserved entry holds changes no bit; a row's bits depend on that row of ``y``,
-        that row of the mask and the parameters alone.  Other models raise ``NotImplementedError`` before any launch."""
+        that row of the mask and the parameters alone.  Other models raise ``NotImplementedError`` before any launch.
+
+        ``exact=True``: yhat_n = sum_{all s} p(s | y_n, Theta) ybar(s) over the model's WHOLE state space by enumeration on
+        the device (pm_recon_exact_*), the same generative model, parameters and ybar(s): no candidates, no
+        state table, no E-step, and a result independent of Hprime, gamma and the annealing state.  A row's bits depend on
+        that row of ``y`` and the parameters alone.  The state count is bounded as for ``log_likelihood(exact=True)`` (MCA /
+        MMCA also D <= 1024): past the bound this raises ``HipError``.  Together with ``my_data['mask']`` it raises
+        ``NotImplementedError``."""
         y = my_data['y']
         N = int(y.shape[0])
         mask = my_data.get('mask')
         if mask is not None:
-            self._masked_admit(y, mask)
+            self._masked_admit(y, mask, exact, what="reconstruct")
         if N == 0:
             return DeviceArray(torch.empty((0, self.D), dtype=torch.float64, device=self.device)) if device \
                 else np.empty((0, self.D))
@@ -1182,6 +1189,8 @@ class DeviceCAModel(CAModel):
             self._par, self._rows_gemm = {}, True
             if mask is not None:
                 Yhat = self._reconstruct_masked(dict(model_params), y, mask, N)
+            elif exact:
+                Yhat = self._reconstruct_exact(dict(model_params), y, N)
             else:
                 Yhat = self._reconstruct(dict(model_params), {'y': y}, N)
             return DeviceArray(Yhat) if device else Yhat.cpu().numpy()
@@ -1198,13 +1207,13 @@ class DeviceCAModel(CAModel):
         raise NotImplementedError("%s: missing values (my_data['mask']) are not built for this model; BSC_ET, MCA_ET and "
                                   "MMCA_ET have the masked E-step" % type(self).__name__)
 
-    def _masked_admit(self, y, mask, exact=False):
+    def _masked_admit(self, y, mask, exact=False, what="log_likelihood"):
         """Everything that refuses a masked call, before any launch: the model, ``exact=True``, the mask's shape, H'."""
         if type(self)._masked_estep is DeviceCAModel._masked_estep:
             self._masked_estep(None, None, None)
         if exact:
-            raise NotImplementedError("%s.log_likelihood: exact=True with a mask is not built (the enumeration kernels "
-                                      "read every dimension)" % type(self).__name__)
+            raise NotImplementedError("%s.%s: exact=True with a mask is not built (the enumeration kernels "
+                                      "read every dimension)" % (type(self).__name__, what))
         shape = tuple(getattr(mask, "tensor", mask).shape) if hasattr(getattr(mask, "tensor", mask), "shape") \
             else np.asarray(mask).shape
         if len(shape) != 2:
@@ -1333,3 +1342,48 @@ class DeviceCAModel(CAModel):
         finally:
             self._eval_end(saved)
         return self._sum_over_ranks(local)
+
+    def _reconstruct_exact(self, model_params, y, N):
+        """The (N, D) device tensor of ``reconstruct(exact=True)``, from the ``_loglik_exact`` hook's ``(kind,
+        arrays, scalars)``: 'lin' -- E[s] by pm_recon_exact_lin_f64, then mu + E[s] W^T through ``_recon_product``; 'gsc' --
+        E[s o z] by pm_recon_exact_gsc_f64 and the same product with W; 'mca' -- Yhat itself by pm_recon_exact_mca_f64."""
+        D, H = self.D, self.H
+        kind, arrays, sc = self._loglik_exact(model_params)
+        dev = {k: (torch.from_numpy(np.array(v, dtype=np.float64, order="C")).to(self.device) if v is not None else None)
+               for k, v in arrays.items()}
+        dbl = ctypes.c_double
+        mu = arrays.get("mu") if kind == "lin" else None
+        if mu is not None and not np.any(mu):
+            mu = None
+        Kp = D if kind == "mca" else (H + (1 if mu is not None else 0) + 7) // 8 * 8
+
+        def entry(call, Yp, ld, n, out, work):
+            if kind == "lin":
+                call("pm_recon_exact_lin_f64", Yp, ld, _ptr(dev.get("mu")), _ptr(dev["P"]), _ptr(dev["G"]), _ptr(dev["logp"]),
+                     _ptr(dev["values"]), int(arrays["values"].shape[0]), n, D, H, out, Kp, work, self._stream())
+            elif kind == "mca":
+                call("pm_recon_exact_mca_f64", Yp, ld, _ptr(dev["Wrho"]), dbl(sc["inv_rho"]), int(sc["signed"]), dbl(sc["lp1"]),
+                     dbl(sc["lp0"]), dbl(sc["inv_s2"]), n, D, H, out, Kp, work, self._stream())
+            else:
+                call("pm_recon_exact_gsc_f64", Yp, ld, _ptr(dev["P"]), _ptr(dev["M"]), _ptr(dev["Psi"]), _ptr(dev["mu"]),
+                     _ptr(dev["logp"]), n, D, H, out, Kp, work, self._stream())
+
+        # the limits first, before the data reaches the device or anything is launched: with no rows the entry checks its
+        # arguments (PM_ERANGE past a limit -> HipError) and returns
+        probe = torch.empty(1, dtype=torch.float64, device=self.device)
+        entry(lambda name, *a: _lib.call(name, *a, det=self.deterministic), None, D, 0, None, _ptr(probe))
+        res = self._resident(y)
+        Y = res["Y"]
+        lib = _lib.load(self.deterministic)
+        work = torch.empty(max(int(lib.pm_recon_exact_work_len(N, H, D)), 1), dtype=torch.float64, device=self.device)
+        ld = max(int(Y.stride(0)), D)
+        launch = lambda name, *a: self._call("recon_exact", name, *a)
+        if kind == "mca":
+            Yhat = torch.empty((N, D), dtype=torch.float64, device=self.device)
+            entry(launch, _ptr(Y), ld, N, _ptr(Yhat), _ptr(work))
+            return Yhat
+        es = torch.zeros((N, Kp), dtype=torch.float64, device=self.device)
+        if mu is not None:
+            es[:, H] = 1.0
+        entry(launch, _ptr(Y), ld, N, _ptr(es), _ptr(work))
+        return self._recon_product(es, Kp, Kp, model_params['W'], mu)

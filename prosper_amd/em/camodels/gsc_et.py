@@ -559,6 +559,15 @@ class GSC(DeviceCAModel):
                    _ptr(out), self.D, N, self.D, self.H, self._stream())
         return out
 
+    def _reconstruct_exact(self, model_params, y, N):
+        """reconstruct(exact=True): yhat_n = W E_n[s o z] over all 2^H supports, E_n[s o z] = sum_s q_n(s)
+        kappa_s(y_n) by pm_recon_exact_gsc_f64 from the whitened products of ``_loglik_exact`` (scalar, diagonal or full
+        Sigma).  A noise covariance that is not positive definite: every row NaN, as ``_reconstruct``."""
+        sig = np.asarray(model_params['sigma_sq'], dtype=np.float64)
+        if (np.linalg.eigvalsh(0.5 * (sig + sig.T)).min() <= 0) if sig.ndim == 2 else not np.all(sig > 0):
+            return torch.full((N, self.D), float("nan"), dtype=torch.float64, device=self.device)
+        return super()._reconstruct_exact(model_params, y, N)
+
     def _loglik_exact(self, model_params):
         """exact log_likelihood: supports {0,1}^H, log prior sum_h s_h log pi_h + (1 - s_h) log(1 - pi_h),
         y ~ N(W_s mu_s, Sigma + W_s Psi_s W_s^T).  The kernel takes the Sigma^-1-whitened products P = Sigma^-1 W and

@@ -56,7 +56,8 @@ class MixtureModel(Model):
     def reconstruct_image(self, model_params, image, mask=None, **kw):
         """Whole-image denoising by overlapping patches: ``utils.patches.denoise_image(self, model_params,
         image, **kw)`` -- every patch through ``reconstruct()``, the estimates averaged where they overlap.  Keywords:
-        ``patch``, ``stride``, ``center``, ``chunk``, ``device``.  ``mask`` (the image's shape, non-zero = observed pixel;
+        ``patch``, ``stride``, ``center``, ``chunk``, ``device``, ``exact`` (every patch through
+        ``reconstruct(exact=True)``).  ``mask`` (the image's shape, non-zero = observed pixel;
         DESIGN 4.16): the patches go through the masked ``reconstruct()`` -- inpainting."""
         from ...utils.patches import denoise_image
         return denoise_image(self, model_params, image, mask=mask, **kw)

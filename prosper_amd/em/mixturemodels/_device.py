@@ -196,7 +196,7 @@ class DeviceMixture(object):
                   float(t["coef"]), _ptr(lp_d), N, D, H, _ptr(logpj), _ptr(post), self._stream())
         return logpj
 
-    def reconstruct(self, model_params, my_data, device=False):
+    def reconstruct(self, model_params, my_data, device=False, exact=False):
         """Posterior-mean denoising: yhat_n = sum_h r_nh W_h with the responsibilities r_nh = pies_h p(y_n | h) / sum_h'
         pies_h' p(y_n | h') of the proper densities of ``log_likelihood`` (MoG with the 1/2; not the reference's E-step
         quirk), for ``my_data['y']`` (host array, torch tensor or DeviceArray).  MoP: in the units of the data its E-step
@@ -206,7 +206,10 @@ class DeviceMixture(object):
         device; no collective.  A NaN in a data row makes that row NaN and no other; a component with pies_h > 0 whose
         covariance is not positive definite makes every row NaN.  ``model_params`` and the training shard are left as they
         were.  The responsibilities are written as an (N, H) array by pm_recon_expect_f64 (a row softmax in a maximum and a
-        sum pass) and multiplied with W by pm_gemm_nt_rows_f64; H within pm_mix_scores_f64's bound for MoG diagonal / MoP."""
+        sum pass) and multiplied with W by pm_gemm_nt_rows_f64; H within pm_mix_scores_f64's bound for MoG diagonal / MoP.
+
+        ``exact`` is accepted for the component-analysis models' signature: a mixture's posterior mean is exact
+        either way, and ``exact=True`` returns the same bits."""
         self._refuse_mask(my_data)
         y = my_data['y']
         N, H, D = int(y.shape[0]), self.H, self.D

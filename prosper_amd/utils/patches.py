@@ -205,7 +205,8 @@ def _mask_image(mask, shape, dev):
     return _image_tensor((t.to(dev) != 0).to(torch.float64), dev)
 
 
-def denoise_image(model, model_params, image, patch=None, stride=1, center=False, chunk=None, device=False, mask=None):
+def denoise_image(model, model_params, image, patch=None, stride=1, center=False, chunk=None, device=False, mask=None,
+                  exact=False):
     """Denoise ``image`` ((H_i, W_i) or a stack (B, H_i, W_i); NumPy array, torch tensor -- a device tensor is used in place,
     without a host round trip -- or ``DeviceArray``) with ``model`` at ``model_params``: every overlapping patch on the grid of
     the module docstring is replaced by its posterior mean ``model.reconstruct()`` and every pixel by the average of the
@@ -229,6 +230,10 @@ def denoise_image(model, model_params, image, patch=None, stride=1, center=False
     there -- NaN included.  The overlap average is unchanged and covers every pixel.  ``center=True`` with a mask raises
     ``ValueError`` (a mean over the observed pixels only is not built); a model without the masked E-step raises
     ``NotImplementedError``.
+
+    ``exact=True``: every patch through ``model.reconstruct(..., exact=True)``, the posterior mean over the
+    model's whole state space; its limits apply, and with a mask it raises ``NotImplementedError``.  The keyword reaches
+    ``reconstruct()`` only when it is set.
     Returns the float64 image (the shape of ``image``) as a NumPy array, or with ``device=True`` as a ``DeviceArray``."""
     from ..em.camodels._device import DeviceArray
     if mask is not None and center:
@@ -250,11 +255,12 @@ def denoise_image(model, model_params, image, patch=None, stride=1, center=False
     elif int(chunk) != chunk or int(chunk) < 1:
         raise ValueError("chunk must be a positive number of patches, got %r" % (chunk,))
     rows = max(1, int(chunk) // nc)
+    extra = {'exact': True} if exact else {}
     if mask is not None:
         if _shape_of(mask) != tuple(shape):
             raise ValueError("mask has shape %r, the image %r" % (_shape_of(mask), tuple(shape)))
         # (an empty masked call: a model without the masked E-step refuses here, before anything reaches the device)
-        model.reconstruct(model_params, {'y': np.empty((0, D)), 'mask': np.empty((0, D), dtype=bool)})
+        model.reconstruct(model_params, {'y': np.empty((0, D)), 'mask': np.empty((0, D), dtype=bool)}, **extra)
     dev = _device(model)
     det = bool(getattr(model, "deterministic", False))
     img, ldi = _image_tensor(image, dev)
@@ -266,7 +272,7 @@ def denoise_image(model, model_params, image, patch=None, stride=1, center=False
         data = {'y': DeviceArray(Y)}
         if mimg is not None:
             data['mask'] = DeviceArray((_extract(mimg, ldmi, geo, n0, n, False, det)[0] != 0).view(torch.uint8))
-        est = model.reconstruct(model_params, data, device=True)
+        est = model.reconstruct(model_params, data, device=True, **extra)
         del Y, data
         if _shape_of(est) != (n, D):
             raise ValueError("reconstruct() returned %r for a chunk of (%d, %d)" % (_shape_of(est), n, D))
