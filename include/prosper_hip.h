@@ -527,8 +527,11 @@ int64_t pm_mca_stats_len(int64_t H, int64_t D);
  * G1 = q1^T.Y is then one pm_gemm_tn_acc_f64 into stats[0..H*D)), scatters the multi-cause
  * terms Aid (mca_et.py:309) into Wp_multi / Wq_multi, accumulates the scalars.  W_new = Wp/Wq is
  * an element-wise ratio, so only weights that underflow to 0 (as in the reference) are dropped.
- * Wrm1 = W^(rho-1) (H,D).  `stats` is zeroed by the caller once per EM step.  Hprime <= 12; any D
- * (the observed dimensions are walked in slabs of 512, one launch each). */
+ * Wrm1 = W^(rho-1) (H,D).  `stats` is accumulated into (the caller zeroes it once per EM step).  Hprime <= PM_MAX_HPRIME
+ * (16); any D up to 2^20: the observed dimensions are walked in slabs, one launch each, whose width follows the register
+ * tile of Hprime -- 512 at Hprime <= 8, 256 at Hprime 9..12, 128 at Hprime 13..16 (pm_mca_plan: PM_MCA_PLAN_MSTEP_ROWS).
+ * The slab that starts at dimension 0 writes q1 and adds q1sum and the scalars; every slab adds its columns of Wp_multi /
+ * Wq_multi. */
 int pm_mca_mstep_rows_f64(const double *logpj, int64_t ldl, const double *lse1, const double *lseb,
                           double lse_cut, const double *Y, int64_t ldy, const double *Wrho,
                           const double *Wrm1, const int32_t *cand, const uint16_t *state_masks, int64_t S,
@@ -575,6 +578,30 @@ int pm_mca_tables_f64(const double *wt, int64_t H, int64_t D, double rho, double
  * check_params (mca_et.py:44-55) makes of it at the top of the next step. */
 int pm_mca_w_update_f64(const double *stats, const double *wt, int64_t H, int64_t D, double w_tol, double *wt_new,
                         double *wt_clamped, void *stream);
+
+/* Host-only query (no device call): the launch that pm_mca_estep_f64 (`which` = PM_MCA_PLAN_ESTEP), pm_mca_mstep_rows_f64
+ * (PM_MCA_PLAN_MSTEP_ROWS), pm_mca_estep_mstats_f64 / pm_mca_estep_mstats_defer_f64 (PM_MCA_PLAN_FUSED; `defer`: records
+ * given) or pm_mca_defer_apply_f64 (PM_MCA_PLAN_DEFER_APPLY; S, signed_w, inv_rho, defer not read) would make for N >= 1
+ * datapoints; the launchers take every one of these decisions from the same function.  out[0..PM_MCA_PLAN_LEN):
+ *   0 DPL      observed dimensions per lane of the instantiation (M-step: of the first slab)
+ *   1 HP       height of the register tile V[HP][DPL] (4 / 8 / 12 / 16); E-step and deferred apply: Hprime
+ *   2 ROOT     21 / 6: the log / exp-free power of that rho, 0: the table (fused pass: uniform-exponent) power
+ *   3 paired   fused pass: 1 where the state loop takes two states per trip
+ *   4 wavefronts per workgroup    5 dynamic LDS bytes of a workgroup    6 grid (deferred apply: of the scatter kernel)
+ *   7 slab width, 8 slab count, 9 DPL of the last slab               (PM_MCA_PLAN_MSTEP_ROWS, else 0)
+ *  10 `defer` as given                                               (PM_MCA_PLAN_FUSED, else 0)
+ *  11 HR latent rows per scatter workgroup, 12 latent ranges, 13 datapoint groups, 14 grid of the q1 kernel
+ *                                                                    (PM_MCA_PLAN_DEFER_APPLY, else 0)
+ *  15 reserved (0)
+ * PM_EINVAL: out NULL, unknown `which`, a non-positive dimension, S < 0, N < 1.  PM_ERANGE exactly where the launcher
+ * returns it for the shape. */
+#define PM_MCA_PLAN_ESTEP 0
+#define PM_MCA_PLAN_MSTEP_ROWS 1
+#define PM_MCA_PLAN_FUSED 2
+#define PM_MCA_PLAN_DEFER_APPLY 3
+#define PM_MCA_PLAN_LEN 16
+int pm_mca_plan(int which, int64_t H, int64_t D, int64_t Hprime, int64_t S, int signed_w, double inv_rho, int64_t N,
+                int defer, int32_t *out);
 
 /* ---------------------------------------------------------------------------------------
  * Discrete Sparse Coding (prosper/em/camodels/dsc_et.py, DSC_ET): K-ary latents

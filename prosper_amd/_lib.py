@@ -123,6 +123,7 @@ SIGNATURES = {
     "pm_mca_defer_apply_work_len": (i64, [i64, i64]),
     "pm_mca_defer_apply_f64": (C.c_int, [c_dp, c_dp, c_dp, i64, c_dp, c_dp, c_dp, c_dp, i64, c_dp, c_dp, i64, i64, i64, i64,
                                          c_dp]),
+    "pm_mca_plan": (C.c_int, [C.c_int, i64, i64, i64, i64, C.c_int, C.c_double, i64, C.c_int, C.POINTER(C.c_int32)]),
     "pm_xsc_select_supported": (C.c_int, [i64, i64, C.c_int]),
     "pm_xsc_select_f64": (C.c_int, [c_dp, i64, c_dp, C.POINTER(DscParams), i64, i64, i64, c_dp, c_dp]),
     "pm_dsc_select_scores_f64": (C.c_int, [c_dp, i64, c_dp, C.POINTER(DscParams), i64, i64, c_dp, i64, c_dp]),
@@ -224,7 +225,7 @@ class HipError(RuntimeError):
     pass
 
 
-MIN_VERSION = 1023
+MIN_VERSION = 1024
 _lib = None
 _lib_det = None
 LIB_PATH_DET = os.path.join(os.path.dirname(LIB_PATH), "libprosper_hip_det.so")

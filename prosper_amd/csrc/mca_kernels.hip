@@ -53,6 +53,16 @@ __host__ __device__ static inline int64_t mca_stats_base(int64_t H, int64_t D) {
 
 namespace {
 
+// Launch decisions that a kernel and the host share (mca_plan below exports them through pm_mca_plan): written once.
+// rho of this launch is `rho` (the log / exp-free powers exist for 21 and 6).  A macro, #undef'd at the end of the file: as
+// an inline function the E-step and M-step kernels compile to other branches than the expression written out in them;
+// its argument is a plain double wherever it is used.
+#define MCA_RHO_IS(inv_rho, rho) ((inv_rho) > 0.0 && fabs(1.0 / (inv_rho) - (rho)) < 1e-9)
+// the fused pass walks its states two per trip (see PAIRED in mca_estep_fused_body)
+__host__ __device__ constexpr bool mca_fused_paired(int dpl, int hp, bool sgn) {
+    return (PM_MCA_PAIR == 1) || (PM_MCA_PAIR < 0 && sgn && dpl <= 4 && hp * dpl >= 24);
+}
+
 __device__ __forceinline__ void wave_sync_lds() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
@@ -177,8 +187,8 @@ __global__ __launch_bounds__(256) void mca_estep_kernel(const double *__restrict
     pm_load_powtab(s_tab, tid, blockDim.x);
     // rho = 21 (every temperature T <= 1.05), unsigned W: the log / exp-free power (pm_pow_m20_21)
     __shared__ __attribute__((aligned(16))) double s_rt[PM_ROOT21_LEN + 1];
-    const bool r21 = P.signed_w == 0.0 && P.inv_rho > 0.0 && fabs(1.0 / P.inv_rho - 21.0) < 1e-9;
-    const bool r6 = P.inv_rho > 0.0 && fabs(1.0 / P.inv_rho - 6.0) < 1e-9;       // (MMCA's steady rho; either sign of W)
+    const bool r21 = P.signed_w == 0.0 && MCA_RHO_IS(P.inv_rho, 21.0);
+    const bool r6 = MCA_RHO_IS(P.inv_rho, 6.0);       // (MMCA's steady rho; either sign of W)
     if (!PM_POW_HWSEED && r21) pm_load_root21(s_rt, pm_powtab_dev, tid, blockDim.x);       // (the table seed's tables: A/B builds)
     else if (!PM_POW_HWSEED && r6) pm_load_root6(s_rt, pm_powtab_dev, tid, blockDim.x);
     __syncthreads();
@@ -555,7 +565,7 @@ __device__ __forceinline__ void mca_estep_fused_body(const double *__restrict__ 
         // chains), stage B reduces, weighs and scatters states s and s + 1 -- their two wave reductions and exponentials
         // interleave.  Same operations per state in the same order: the bits of the one-state loop.  MMCA config-5 dimensions:
         // 10.67 -> 9.72 ms.  (At two wavefronts per SIMD the pair form needs 272 registers -- one wavefront, 9.0 against 6.65 ms.)
-        constexpr bool PAIRED = (PM_MCA_PAIR == 1) || (PM_MCA_PAIR < 0 && SIGNED && DPL <= 4 && HP * DPL >= 24);
+        constexpr bool PAIRED = mca_fused_paired(DPL, HP, SIGNED);
         if constexpr (PAIRED) {
         constexpr int NS = PM_MCA_NS;                 // states per trip
         auto mask_at = [&](int s) { return masks[s < S ? s : S - 1]; };
@@ -940,8 +950,8 @@ __global__ __launch_bounds__(256) void mca_mstep_rows_kernel(const double *__res
     double *s_wm = s_wr + HP * DS;   // SIGNED only: |W|^(rho-1)[cand]
     for (int h = tid; h < H; h += blockDim.x) s_q1sum[h] = 0.0;
     __shared__ __attribute__((aligned(16))) double s_rt[PM_ROOT21_LEN + 1];       // (see mca_estep_kernel)
-    const bool r21 = !SIGNED && P.inv_rho > 0.0 && fabs(1.0 / P.inv_rho - 21.0) < 1e-9;
-    const bool r6 = SIGNED && P.inv_rho > 0.0 && fabs(1.0 / P.inv_rho - 6.0) < 1e-9;
+    const bool r21 = !SIGNED && MCA_RHO_IS(P.inv_rho, 21.0);
+    const bool r6 = SIGNED && MCA_RHO_IS(P.inv_rho, 6.0);
     if (!PM_POW_HWSEED && r21) pm_load_root21(s_rt, pm_powtab_dev, tid, blockDim.x);       // (the table seed's tables: A/B builds)
     else if (!PM_POW_HWSEED && r6) pm_load_root6(s_rt, pm_powtab_dev, tid, blockDim.x);
     __syncthreads();
@@ -1172,7 +1182,134 @@ inline int64_t grid_waves(int64_t N, int waves) {
     return blocks < cap ? (blocks < 1 ? 1 : blocks) : cap;
 }
 
+constexpr int DEFER_GROUPS = 64;      // datapoint groups of the scatter kernel (workspace: one [Wp | Wq] partial per group)
+
+// Every launch decision of pm_mca_estep_f64, pm_mca_mstep_rows_f64, pm_mca_estep_mstats[_defer]_f64 and
+// pm_mca_defer_apply_f64: the launchers switch on this struct and pm_mca_plan exports it, so a test that asks for the plan
+// sees the instantiation the launch takes.
+struct McaPlan {
+    int dpl, hp, root, paired, waves;   // hp: the register tile's height (E-step: the rows staged, Hprime)
+    size_t lds;                         // dynamic LDS of a workgroup
+    unsigned grid;
+    int slab, nslabs, d0, dl;           // M-step: slab width and count; this slab's first dimension and width
+    int hr, nranges, groups;            // deferred statistics: latent rows per workgroup, latent ranges, datapoint groups
+    unsigned grid_q1;                   // ... and the grid of mca_defer_q1_kernel
+};
+
+// `slab_i`: the slab of the M-step's walk to plan (0 for the other entries)
+static int mca_plan(int which, int64_t H, int64_t D, int64_t Hprime, int64_t S, bool sgn, double inv_rho, int64_t N,
+                    int64_t slab_i, McaPlan *p) {
+    if (which < PM_MCA_PLAN_ESTEP || which > PM_MCA_PLAN_DEFER_APPLY || H <= 0 || D <= 0 || Hprime <= 0 || S < 0 || N < 1 ||
+        slab_i < 0)
+        return PM_EINVAL;
+    *p = McaPlan{};
+    if (which == PM_MCA_PLAN_ESTEP) {
+        if (D > 1024 || Hprime > PM_MAX_HPRIME || Hprime > H || S > 65535) return PM_ERANGE;
+        p->dpl = D <= 64 ? 1 : D <= 128 ? 2 : D <= 256 ? 4 : D <= 512 ? 8 : 16;
+        p->hp = (int)Hprime;
+        p->root = (!sgn && MCA_RHO_IS(inv_rho, 21.0)) ? 21 : MCA_RHO_IS(inv_rho, 6.0) ? 6 : 0;
+        const size_t per_wave = sizeof(double) * ((size_t)Hprime * 64 * p->dpl + S);
+        if (per_wave > 150 * 1024) return PM_ERANGE;
+        const size_t shared = sizeof(double) * PM_POWTAB_LEN;
+        p->waves = pick_waves(per_wave, shared);
+        p->lds = shared + per_wave * p->waves;
+        p->grid = (unsigned)grid_waves(N, p->waves);
+        return PM_OK;
+    }
+    if (which == PM_MCA_PLAN_MSTEP_ROWS) {
+        if (D > (1 << 20) || Hprime > PM_MAX_HPRIME || Hprime > H || S > 65535) return PM_ERANGE;
+        p->hp = Hprime <= 4 ? 4 : Hprime <= 8 ? 8 : Hprime <= 12 ? 12 : 16;
+        // observed dimensions are walked in slabs whose V[HP][DPL] register tile stays within 48 doubles per lane
+        const int dpl_max = p->hp == 16 ? 2 : p->hp == 12 ? 4 : 8;
+        p->slab = 64 * dpl_max;
+        p->nslabs = (int)((D + p->slab - 1) / p->slab);
+        if (slab_i >= p->nslabs) return PM_EINVAL;
+        p->d0 = (int)(slab_i * p->slab);
+        p->dl = (int)((D - p->d0) < p->slab ? (D - p->d0) : p->slab);
+        p->dpl = p->dl <= 64 ? 1 : p->dl <= 128 ? 2 : p->dl <= 256 ? 4 : 8;
+        p->root = (!sgn && MCA_RHO_IS(inv_rho, 21.0)) ? 21 : (sgn && MCA_RHO_IS(inv_rho, 6.0)) ? 6 : 0;
+        const size_t per_wave = sizeof(double) * ((size_t)p->hp * 64 * p->dpl) * (sgn ? 2 : 1);
+        const size_t shared = sizeof(double) * (PM_POWTAB_LEN + H + 16);
+        p->waves = pick_waves(per_wave, shared);
+        p->lds = shared + per_wave * p->waves;
+        if (p->lds > 150 * 1024) return PM_ERANGE;
+        p->grid = (unsigned)grid_waves(N, p->waves);
+        return PM_OK;
+    }
+    if (which == PM_MCA_PLAN_FUSED) {
+        if (D > 512 || Hprime > 12 || Hprime > H || S > 65535) return PM_ERANGE;
+        p->dpl = D <= 64 ? 1 : D <= 128 ? 2 : D <= 256 ? 4 : 8;
+        p->hp = Hprime <= 4 ? 4 : Hprime <= 8 ? 8 : 12;
+        if ((int64_t)p->dpl * p->hp > 48) return PM_ERANGE;  // V[HP][DPL] register tile
+        // Round 6: unsigned W takes the uniform-exponent power (pm_pow_uni, ROOT = 0) at EVERY rho -- 6.45 ms against 6.74 for the
+        // log / exp-free rho = 21 power at config 5 (scratch/mca_T_sweep.py; -DPM_MCA_ROOT21 brings that one back for A/B builds).
+        // Signed W (MMCA) keeps its rho = 6 power (pm_pow_m5_6: 9.65 against 10.48 ms, scratch/mmca_time.py -- that pass runs one
+        // wavefront per SIMD, where the uniform power's three LDS lookups are not hidden; -DPM_MCA_NO_ROOT6: A/B) and takes the
+        // uniform power at every other rho.
+#ifdef PM_MCA_ROOT21
+        if (!sgn && MCA_RHO_IS(inv_rho, 21.0)) p->root = 21;
+#endif
+#ifndef PM_MCA_NO_ROOT6
+        if (sgn && MCA_RHO_IS(inv_rho, 6.0)) p->root = 6;
+#endif
+        p->paired = mca_fused_paired(p->dpl, p->hp, sgn) ? 1 : 0;
+        const size_t per_wave = sizeof(double) * ((size_t)p->hp * 64 * p->dpl * (sgn ? 2 : 1) + S);
+        const size_t shared = sizeof(double) * (PM_POWTAB_LEN + PM_FUSED_RT_LEN + H + 16);
+        p->waves = pick_waves(per_wave, shared);
+        p->lds = shared + per_wave * p->waves;
+        if (p->lds > 150 * 1024) return PM_ERANGE;
+        p->grid = (unsigned)grid_waves(N, p->waves);
+        return PM_OK;
+    }
+    if (H > 512 || D > 512 || Hprime > 12) return PM_ERANGE;
+    p->hp = (int)Hprime;
+    p->dpl = D <= 64 ? 1 : D <= 128 ? 2 : D <= 256 ? 4 : 8;
+    p->hr = PM_SCATTER_LDS_DOUBLES / (2 * 64 * p->dpl);          // rows of Wp and Wq per workgroup: 32 at D <= 256
+    if (p->hr > H) p->hr = (int)H;
+    p->nranges = (int)((H + p->hr - 1) / p->hr);
+    int64_t groups = DEFER_GROUPS;
+    if (groups > (N + 255) / 256) groups = (N + 255) / 256;
+    p->groups = (int)groups;
+    p->waves = 16;
+    p->lds = (size_t)2 * p->hr * 64 * p->dpl * sizeof(double);
+    p->grid = (unsigned)(groups * p->nranges);
+    int64_t blocks = (N + 3) / 4;
+    if (blocks > 2048) blocks = 2048;
+    p->grid_q1 = (unsigned)blocks;
+    return PM_OK;
+}
+
 }  // namespace
+
+extern "C" int pm_mca_plan(int which, int64_t H, int64_t D, int64_t Hprime, int64_t S, int signed_w, double inv_rho, int64_t N,
+                           int defer, int32_t *out) {
+    if (!out) return PM_EINVAL;
+    McaPlan p;
+    if (int e = mca_plan(which, H, D, Hprime, S, signed_w != 0, inv_rho, N, 0, &p)) return e;
+    for (int i = 0; i < PM_MCA_PLAN_LEN; ++i) out[i] = 0;
+    out[0] = p.dpl;
+    out[1] = p.hp;
+    out[2] = p.root;
+    out[3] = p.paired;
+    out[4] = p.waves;
+    out[5] = (int32_t)p.lds;
+    out[6] = (int32_t)p.grid;
+    if (which == PM_MCA_PLAN_MSTEP_ROWS) {
+        McaPlan last;
+        if (int e = mca_plan(which, H, D, Hprime, S, signed_w != 0, inv_rho, N, p.nslabs - 1, &last)) return e;
+        out[7] = p.slab;
+        out[8] = p.nslabs;
+        out[9] = last.dpl;
+    }
+    if (which == PM_MCA_PLAN_FUSED) out[10] = defer ? 1 : 0;
+    if (which == PM_MCA_PLAN_DEFER_APPLY) {
+        out[11] = p.hr;
+        out[12] = p.nranges;
+        out[13] = p.groups;
+        out[14] = (int32_t)p.grid_q1;
+    }
+    return PM_OK;
+}
 
 extern "C" int64_t pm_mca_stats_len(int64_t H, int64_t D) {
     return mca_stats_base(H, D) + (PM_XCD_COPIES - 1) * 2 * H * D;
@@ -1206,14 +1343,12 @@ extern "C" int pm_mca_estep_f64(const double *scores, int64_t lds, const double 
     if (!scores || !wnorm2 || !ynorm2 || !Y || !Wrho || !cand || !params_host || !logpj || !lse1 || !lseb || N < 0 ||
         H <= 0 || D <= 0 || Hprime <= 0 || S < 0 || lds < H || ldy < D || ldl < 1 + H + S || (S > 0 && !state_masks))
         return PM_EINVAL;
-    if (D > 1024 || Hprime > PM_MAX_HPRIME || Hprime > H || S > 65535) return PM_ERANGE;
-    const int dpl = D <= 64 ? 1 : D <= 128 ? 2 : D <= 256 ? 4 : D <= 512 ? 8 : 16;
-    const size_t per_wave = sizeof(double) * ((size_t)Hprime * 64 * dpl + S);
-    if (per_wave > 150 * 1024) return PM_ERANGE;
-    const size_t shared = sizeof(double) * PM_POWTAB_LEN;
-    const int waves = pick_waves(per_wave, shared);
-    const size_t shmem = shared + per_wave * waves;
-    dim3 grid((unsigned)grid_waves(N, waves)), block(64 * waves);
+    McaPlan pl;
+    if (int e = mca_plan(PM_MCA_PLAN_ESTEP, H, D, Hprime, S, params_host->signed_w != 0.0, params_host->inv_rho, N, 0, &pl))
+        return e;
+    const int dpl = pl.dpl;
+    const size_t shmem = pl.lds;
+    dim3 grid(pl.grid), block(64 * pl.waves);
     hipStream_t s = static_cast<hipStream_t>(stream);
 #define PM_LAUNCH(V)                                                                                            \
     do {                                                                                                        \
@@ -1235,12 +1370,11 @@ extern "C" int pm_mca_estep_f64(const double *scores, int64_t lds, const double 
 
 namespace {
 template <int DPL, bool SIGNED>
-int launch_mstep_hp(int hp, dim3 grid, dim3 block, size_t shmem, hipStream_t s, const double *logpj, int64_t ldl,
+int launch_mstep_hp(int hp, int Hp, dim3 grid, dim3 block, size_t shmem, hipStream_t s, const double *logpj, int64_t ldl,
                     const double *lse1, const double *lseb, double lse_cut, const double *Y, int64_t ldy,
                     const double *Wrho, const double *Wrm1, const int32_t *cand, const uint16_t *masks, int S,
                     pm_mca_params P, int64_t N, int H, int D, int d0, int Dl, double *q1, int64_t ldq, double *stats) {
-    const int Hp = hp;
-    hp = hp <= 4 ? 4 : hp <= 8 ? 8 : hp <= 12 ? 12 : 16;
+    // hp: the register tile of the plan, Hp: the candidates
 #define PM_CASE(HPV)                                                                                              \
     case HPV: {                                                                                                   \
         if (int e = allow_lds_mca(reinterpret_cast<const void *>(mca_mstep_rows_kernel<DPL, HPV, SIGNED>), shmem)) return e; \
@@ -1273,26 +1407,18 @@ extern "C" int pm_mca_mstep_rows_f64(const double *logpj, int64_t ldl, const dou
     if (!logpj || !lse1 || !lseb || !Y || !Wrho || !Wrm1 || !cand || !params_host || !q1 || !stats || N < 0 ||
         H <= 0 || D <= 0 || Hprime <= 0 || S < 0 || ldl < 1 + H + S || ldy < D || ldq < H || (S > 0 && !state_masks))
         return PM_EINVAL;
-    if (D > (1 << 20) || Hprime > PM_MAX_HPRIME || Hprime > H || S > 65535) return PM_ERANGE;
-    const int hp_tile = Hprime <= 4 ? 4 : Hprime <= 8 ? 8 : Hprime <= 12 ? 12 : 16;
-    // observed dimensions are walked in slabs whose V[HP][DPL] register tile stays within 48 doubles per lane
-    const int dpl_max = hp_tile == 16 ? 2 : hp_tile == 12 ? 4 : 8;
-    const int slab = 64 * dpl_max;
     const bool sgn = params_host->signed_w != 0.0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    for (int64_t d0 = 0; d0 < D; d0 += slab) {
-        const int Dl = (int)((D - d0) < slab ? (D - d0) : slab);
-        const int dpl = Dl <= 64 ? 1 : Dl <= 128 ? 2 : Dl <= 256 ? 4 : 8;
-        const size_t per_wave = sizeof(double) * ((size_t)hp_tile * 64 * dpl) * (sgn ? 2 : 1);
-        const size_t shared = sizeof(double) * (PM_POWTAB_LEN + H + 16);
-        const int waves = pick_waves(per_wave, shared);
-        const size_t shmem = shared + per_wave * waves;
-        if (shmem > 150 * 1024) return PM_ERANGE;
-        dim3 grid((unsigned)grid_waves(N, waves)), block(64 * waves);
-#define PM_ARGS (int)Hprime, grid, block, shmem, s, logpj, ldl, lse1, lseb, lse_cut, Y, ldy, Wrho, Wrm1, cand, state_masks, \
-                (int)S, *params_host, N, (int)H, (int)D, (int)d0, Dl, q1, ldq, stats
+    for (int i = 0, nslabs = 1; i < nslabs; ++i) {
+        McaPlan pl;
+        if (int e = mca_plan(PM_MCA_PLAN_MSTEP_ROWS, H, D, Hprime, S, sgn, params_host->inv_rho, N, i, &pl)) return e;
+        nslabs = pl.nslabs;
+        const size_t shmem = pl.lds;
+        dim3 grid(pl.grid), block(64 * pl.waves);
+#define PM_ARGS pl.hp, (int)Hprime, grid, block, shmem, s, logpj, ldl, lse1, lseb, lse_cut, Y, ldy, Wrho, Wrm1, cand, state_masks, \
+                (int)S, *params_host, N, (int)H, (int)D, pl.d0, pl.dl, q1, ldq, stats
         int rc;
-        switch (dpl) {
+        switch (pl.dpl) {
             case 1: rc = sgn ? launch_mstep_hp<1, true>(PM_ARGS) : launch_mstep_hp<1, false>(PM_ARGS); break;
             case 2: rc = sgn ? launch_mstep_hp<2, true>(PM_ARGS) : launch_mstep_hp<2, false>(PM_ARGS); break;
             case 4: rc = sgn ? launch_mstep_hp<4, true>(PM_ARGS) : launch_mstep_hp<4, false>(PM_ARGS); break;
@@ -1307,27 +1433,13 @@ extern "C" int pm_mca_mstep_rows_f64(const double *logpj, int64_t ldl, const dou
 
 namespace {
 template <int DPL, bool SIGNED>
-int launch_fused_hp(int Hp, dim3 grid, dim3 block, size_t shmem, hipStream_t s, const double *scores, int64_t lds,
+int launch_fused_hp(int hp, int root, int Hp, dim3 grid, dim3 block, size_t shmem, hipStream_t s, const double *scores, int64_t lds,
                     const double *wnorm2, const double *ynorm2, const double *Y, int64_t ldy, const double *Wrho,
                     const double *Wrm1, const int32_t *cand, const uint16_t *masks, int S, pm_mca_params P, int64_t N,
                     int H, int D, double *logpj, int64_t ldl, double *lse1, double *lseb, double *q1, int64_t ldq,
                     double *stats, double *defer_rec, double *defer_sc) {
-    const int hp = Hp <= 4 ? 4 : Hp <= 8 ? 8 : 12;
-    // Round 6: unsigned W takes the uniform-exponent power (pm_pow_uni, ROOT = 0) at EVERY rho -- 6.45 ms against 6.74 for the
-    // log / exp-free rho = 21 power at config 5 (scratch/mca_T_sweep.py; -DPM_MCA_ROOT21 brings that one back for A/B builds).
-    // Signed W (MMCA) keeps its rho = 6 power (pm_pow_m5_6: 9.65 against 10.48 ms, scratch/mmca_time.py -- that pass runs one
-    // wavefront per SIMD, where the uniform power's three LDS lookups are not hidden; -DPM_MCA_NO_ROOT6: A/B) and takes the
-    // uniform power at every other rho.
-#ifdef PM_MCA_ROOT21
-    const bool rho21 = !SIGNED && P.inv_rho > 0.0 && fabs(1.0 / P.inv_rho - 21.0) < 1e-9;
-#else
-    const bool rho21 = false;
-#endif
-#ifndef PM_MCA_NO_ROOT6
-    const bool rho6 = SIGNED && P.inv_rho > 0.0 && fabs(1.0 / P.inv_rho - 6.0) < 1e-9;
-#else
-    const bool rho6 = false;
-#endif
+    // hp, root: the register tile and the power of the plan (mca_plan); Hp: the candidates
+    const bool rho21 = !SIGNED && root == 21, rho6 = SIGNED && root == 6;
 #define PM_LAUNCH_F(HPV, SG, RT, DF)                                                                                  \
     do {                                                                                                              \
         if (DF) {                                                                                                     \
@@ -1461,8 +1573,6 @@ __global__ __launch_bounds__(256) void mca_defer_q1_kernel(const double *__restr
     }
 }
 
-constexpr int DEFER_GROUPS = 64;      // datapoint groups of the scatter kernel (workspace: one [Wp | Wq] partial per group)
-
 // A workgroup of sixteen wavefronts owns HR rows (latents) of Wp and Wq -- all D observed dimensions of them, in LDS -- for
 // 1/G of the datapoints.  [First form: slices of 64 observed dimensions of ALL latents per workgroup -- every 2 KB record row
 // was then read in four 512-byte pieces by four workgroups at four different times, and the kernel ran at 2 TB/s; a
@@ -1586,23 +1696,18 @@ extern "C" int pm_mca_defer_apply_f64(const double *lseb, const double *cut, con
     if (!lseb || !cut || !Y || !cand || !records || !scalars || !q1 || !stats || !work || N < 0 || H <= 0 || D <= 0 ||
         Hprime <= 0 || ldy < D || ldq < H)
         return PM_EINVAL;
-    if (H > 512 || D > 512 || Hprime > 12) return PM_ERANGE;
+    McaPlan pl;
+    if (int e = mca_plan(PM_MCA_PLAN_DEFER_APPLY, H, D, Hprime, 0, false, 0.0, N, 0, &pl)) return e;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int64_t blocks = (N + 3) / 4;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(mca_defer_q1_kernel, dim3((unsigned)blocks), dim3(256), 0, s, lseb, cut, scalars, q1, ldq, stats, N,
+    hipLaunchKernelGGL(mca_defer_q1_kernel, dim3(pl.grid_q1), dim3(256), 0, s, lseb, cut, scalars, q1, ldq, stats, N,
                        (int)H, (int)D);
-    const int dpl = D <= 64 ? 1 : D <= 128 ? 2 : D <= 256 ? 4 : 8;
-    int hr = PM_SCATTER_LDS_DOUBLES / (2 * 64 * dpl);          // rows of Wp and Wq per workgroup: 32 at D <= 256
-    if (hr > H) hr = (int)H;
-    const int nranges = (int)((H + hr - 1) / hr);
-    int64_t groups = DEFER_GROUPS;
-    if (groups > (N + 255) / 256) groups = (N + 255) / 256;
-    const size_t shmem = (size_t)2 * hr * 64 * dpl * sizeof(double);
+    const int dpl = pl.dpl, hr = pl.hr, nranges = pl.nranges;
+    const int64_t groups = pl.groups;
+    const size_t shmem = pl.lds;
 #define PM_SCATTER(DPLV)                                                                                                  \
     do {                                                                                                                  \
         if (int e = allow_lds_mca(reinterpret_cast<const void *>(mca_defer_scatter_kernel<DPLV>), shmem)) return e;       \
-        hipLaunchKernelGGL((mca_defer_scatter_kernel<DPLV>), dim3((unsigned)(groups * nranges)), dim3(1024), shmem, s, lseb, cut, \
+        hipLaunchKernelGGL((mca_defer_scatter_kernel<DPLV>), dim3(pl.grid), dim3(1024), shmem, s, lseb, cut, \
                            Y, ldy, cand, records, work, N, (int)H, (int)D, (int)Hprime, hr, nranges);                     \
     } while (0)
     if (dpl == 1) PM_SCATTER(1);
@@ -1629,19 +1734,14 @@ extern "C" int pm_mca_estep_mstats_defer_f64(const double *scores, int64_t lds, 
         !q1 || !stats || N < 0 || H <= 0 || D <= 0 || Hprime <= 0 || S < 0 || lds < H || ldy < D ||
         ldl < 1 + H + S || ldq < H || (S > 0 && !state_masks))
         return PM_EINVAL;
-    if (D > 512 || Hprime > 12 || Hprime > H || S > 65535) return PM_ERANGE;
-    const int dpl = D <= 64 ? 1 : D <= 128 ? 2 : D <= 256 ? 4 : 8;
-    const int hp_tile = Hprime <= 4 ? 4 : Hprime <= 8 ? 8 : 12;
-    if ((int64_t)dpl * hp_tile > 48) return PM_ERANGE;  // V[HP][DPL] register tile
     const bool sgn = params_host->signed_w != 0.0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t per_wave = sizeof(double) * ((size_t)hp_tile * 64 * dpl * (sgn ? 2 : 1) + S);
-    const size_t shared = sizeof(double) * (PM_POWTAB_LEN + PM_FUSED_RT_LEN + H + 16);
-    const int waves = pick_waves(per_wave, shared);
-    const size_t shmem = shared + per_wave * waves;
-    if (shmem > 150 * 1024) return PM_ERANGE;
-    dim3 grid((unsigned)grid_waves(N, waves)), block(64 * waves);
-#define PM_ARGS (int)Hprime, grid, block, shmem, s, scores, lds, wnorm2, ynorm2, Y, ldy, Wrho, Wrm1, cand, state_masks, \
+    McaPlan pl;
+    if (int e = mca_plan(PM_MCA_PLAN_FUSED, H, D, Hprime, S, sgn, params_host->inv_rho, N, 0, &pl)) return e;
+    const int dpl = pl.dpl;
+    const size_t shmem = pl.lds;
+    dim3 grid(pl.grid), block(64 * pl.waves);
+#define PM_ARGS pl.hp, pl.root, (int)Hprime, grid, block, shmem, s, scores, lds, wnorm2, ynorm2, Y, ldy, Wrho, Wrm1, cand, state_masks, \
                 (int)S, *params_host, N, (int)H, (int)D, logpj, ldl, lse1, lseb, q1, ldq, stats, defer_rec, defer_sc
     int rc;
     switch (dpl) {
@@ -1731,3 +1831,4 @@ extern "C" int pm_mca_w_update_f64(const double *stats, const double *wt, int64_
 }
 
 PM_DET_SETTER(mca)
+#undef MCA_RHO_IS
