@@ -733,6 +733,46 @@ int pm_dsc_plan(int which, int64_t H, int64_t Hprime, int64_t S, int64_t K, int 
 /* Shapes the GSC kernel covers: H <= 512, gamma <= 8 (g x g systems solved in registers; instantiated for 2, 3, 4, 6, 8). */
 int pm_gsc_supported(int64_t H, int64_t Hprime, int64_t gamma);
 
+/* Host-only query (no device call): the launch that pm_gsc_estep_f64 and its siblings (`which` = PM_GSC_PLAN_ESTEP; `flags`:
+ * PM_GSC_PLAN_LPJ for pm_gsc_estep_lpj_f64, PM_GSC_PLAN_LPJ | PM_GSC_PLAN_BLOCKS for pm_gsc_estep_lpj_blocks_f64,
+ * PM_GSC_PLAN_LISTS for pm_gsc_estep_lists_f64), pm_gsc_list_pairs_f64 (PM_GSC_PLAN_LIST_PAIRS: H and N are read),
+ * pm_gsc_pack_stats_f64 (PM_GSC_PLAN_PACK: H) or pm_gsc_component_scores_f64 (PM_GSC_PLAN_COMPONENT_SCORES: H, N) would make
+ * for N >= 1 datapoints; the launchers take every one of these decisions from the same function.  `S`: the length of the
+ * state table handed in (it may be a prefix of the full table of Hprime and gamma).  `cus`: compute units of the device,
+ * <= 0 for the 256 the launcher assumes when it cannot ask.  `D` is read with PM_GSC_PLAN_LISTS only: > 0 adds what
+ * pm_gsc_lists_supported asks of the M-step's contraction ((D + 2 H) % 128 == 0, H % 128 == 0), <= 0 plans the launch alone.
+ * out[0..PM_GSC_PLAN_LEN):
+ *   0 VPL          latents per lane of gsc_estep_kernel: 1, 2, 4, 8, 16, 32 (H <= 16, 32, 64, 128, 256, 512; LIST: 8 or 16)
+ *   1 GMAX         size of the g x g systems in registers: 2, 3, 4, 6, 8 (gamma <= 2, 3, 4, 5..6, 7..8)
+ *   2 form         PM_GSC_FORM_PLAIN (column sums by gsc_colsum_kernel, singleton diagonal in registers), _LACC (column sums
+ *                  and the whole diagonal of sum xpt_szsz in LDS accumulators: where that layout is <= 53 KB), _LPJ
+ *                  (log-joints written; statistics as PLAIN), _LIST (LACC + the row lists)
+ *   3 LDS bytes    dynamic shared memory of the launch
+ *   4 grid         workgroups (E-step: min(ceil(N / 16), 3 cus), LIST: at least ceil(N / 512))
+ *   5 trips        E-step: groups of sixteen datapoints a workgroup walks at most, ceil(ceil(N / 16) / grid); list pairs:
+ *                  trips of 512 datapoints per group; else 1
+ *   6 colsum       1: gsc_colsum_kernel follows the E-step (PLAIN, LPJ)
+ *   7 rows_c, 8 nchunks, 9 groups, 10 rows_per_group     (PM_GSC_PLAN_LIST_PAIRS, else 0): a workgroup owns rows_c rows of
+ *                  one of the two products -- the largest divisor of H with rows_c * H <= 16384 -- and rows_per_group datapoints
+ * Returns PM_OK, PM_EINVAL (null `out`, unknown `which` or flag, BLOCKS without LPJ, LISTS with LPJ, H < 1, N < 1, E-step:
+ * Hprime < 1, S < 0) or PM_ERANGE exactly where the launcher returns it: !pm_gsc_supported, a state table whose LDS layout
+ * exceeds 64 KB; LISTS: the LACC layout does not fit, gamma > 3, H <= 64, H > 256 (and the conditions on D above); list
+ * pairs: H > 256 or H % 64 != 0; pack: H > 512; component scores: more than INT32_MAX workgroups. */
+#define PM_GSC_PLAN_ESTEP 0
+#define PM_GSC_PLAN_LIST_PAIRS 1
+#define PM_GSC_PLAN_PACK 2
+#define PM_GSC_PLAN_COMPONENT_SCORES 3
+#define PM_GSC_PLAN_LPJ 1
+#define PM_GSC_PLAN_BLOCKS 2
+#define PM_GSC_PLAN_LISTS 4
+#define PM_GSC_FORM_PLAIN 0
+#define PM_GSC_FORM_LACC 1
+#define PM_GSC_FORM_LPJ 2
+#define PM_GSC_FORM_LIST 3
+#define PM_GSC_PLAN_LEN 12
+int pm_gsc_plan(int which, int64_t H, int64_t Hprime, int64_t S, int64_t gamma, int64_t D, int flags, int64_t N, int cus,
+                int32_t *out);
+
 /* stats (float64): [ sum_n xpt_ss, STRICT upper triangle, multi-cause part (H*H; its diagonal is sum_n xpt_s and is not formed here) |
  *                    sum_n xpt_szsz, both triangles as they are, multi-cause part (H*H) |
  *                    sum_n xpt_s (H) | sum_n xpt_sz (H) | diagonal of sum_n xpt_szsz that is not in the block above (H): the
@@ -770,7 +810,12 @@ int pm_gsc_mstep_finish_f64(const double *xs_xsz, const double *xsz_xsz, const d
  *   sigma_sq == 0: `tables` has a ninth row whose first entry is 1/sigma_sq (left on the device by
  *     pm_gsc_mstep_finish_f64).
  * Outputs: xpt_s, xpt_sz (N,H) and the sums over datapoints accumulated into `stats`
- * (zeroed by the caller).  The (N,H,H) moments of the reference are never materialised. */
+ * (zeroed by the caller).  The (N,H,H) moments of the reference are never materialised.
+ * The selection contract: the candidates are the Hprime largest component scores (pm_gsc_component_scores_f64, clamps
+ * included), RANKED ON THE SCORE WITH ITS LOW 10 MANTISSA BITS DROPPED -- the kernel carries the latent index in those bits.
+ * Equal ranking values resolve towards the larger latent index (the reference's argsort does the same on equal scores).
+ * So the selected set equals the reference's whenever the Hprime-th and the (Hprime + 1)-th largest scores differ in the
+ * upper 43 bits of the mantissa (or in sign or exponent); scores closer than that may be taken in index order instead. */
 int pm_gsc_estep_f64(const double *scores, int64_t lds, const double *gram, const double *psi_sq,
                      const double *ynorm2, const double *tables, const uint16_t *state_masks, int64_t S,
                      int64_t gamma, double beta, double sigma_sq, int64_t N, int64_t H, int64_t Hprime,
@@ -821,7 +866,9 @@ int pm_gsc_estep_lpj_blocks_f64(const double *scores, int64_t lds, const double 
                                 double *logpj, int64_t ldl, double *blocks, int64_t ldb, void *stream);
 
 /* GSC.component_scores (gsc_et.py:752-809): singleton log-posteriors without the prior, clamped as the reference
- * clamps them (NaN / below -DBL_MAX -> -DBL_MAX, +-inf -> 0), out (N, ldo >= H).  `scores`, `ynorm2`, `tables`
+ * clamps them, in the reference's order (gsc_et.py:802-804): NaN and everything below -DBL_MAX -- so -inf too -- become
+ * -DBL_MAX, then +inf becomes 0; the E-step kernel's selection applies the same two steps in the same order.
+ * out (N, ldo >= H).  `scores`, `ynorm2`, `tables`
  * (rows c0, c1, gm, il are read), `sigma_sq` (> 0) as for pm_gsc_estep_f64. */
 int pm_gsc_component_scores_f64(const double *scores, int64_t lds, const double *ynorm2, const double *tables,
                                 double sigma_sq, int64_t N, int64_t H, double *out, int64_t ldo, void *stream);

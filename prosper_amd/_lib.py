@@ -145,6 +145,7 @@ SIGNATURES = {
     "pm_wp_sparse_f64": (C.c_int, [c_dp, c_dp, c_dp, i64, c_dp, i64, c_dp, i64, i64, i64, c_dp]),
     "pm_wp_sparse_t_f64": (C.c_int, [c_dp, c_dp, c_dp, i64, c_dp, i64, i64, i64, i64, c_dp]),
     "pm_gsc_supported": (C.c_int, [i64, i64, i64]),
+    "pm_gsc_plan": (C.c_int, [C.c_int, i64, i64, i64, i64, i64, C.c_int, i64, C.c_int, C.POINTER(C.c_int32)]),
     "pm_gsc_stats_len": (i64, [i64]),
     "pm_gsc_pack_stats_f64": (C.c_int, [c_dp, i64, c_dp, c_dp, c_dp]),
     "pm_gsc_mstep_finish_f64": (C.c_int, [c_dp] * 10 + [C.c_double, i64, i64, C.c_int, c_dp, c_dp, c_dp]),
@@ -225,7 +226,7 @@ class HipError(RuntimeError):
     pass
 
 
-MIN_VERSION = 1024
+MIN_VERSION = 1025
 _lib = None
 _lib_det = None
 LIB_PATH_DET = os.path.join(os.path.dirname(LIB_PATH), "libprosper_hip_det.so")

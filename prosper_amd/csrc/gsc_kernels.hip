@@ -763,15 +763,126 @@ static size_t gsc_shmem(int64_t H, int64_t Hprime, int64_t S) {
 static size_t gsc_shmem_lacc(int64_t H, int64_t Hprime, int64_t S) {
     return gsc_shmem(H, Hprime, S) + sizeof(double) * (3 * 4 * H + 1);
 }
-
-extern "C" int pm_gsc_supported(int64_t H, int64_t Hprime, int64_t gamma) {
-    if (H <= 0 || H > 512 || Hprime <= 0 || Hprime > PM_MAX_HPRIME || Hprime > H || gamma < 1 || gamma > 8) return 0;
-    int64_t S = 0, c = Hprime;                       // multi-cause states: sum_{g=2..gamma} C(H', g)
+// multi-cause states of the full table: sum_{g=2..gamma} C(H', g)
+static int64_t gsc_full_states(int64_t Hprime, int64_t gamma) {
+    int64_t S = 0, c = Hprime;
     for (int64_t g = 2; g <= gamma && g <= Hprime; ++g) {
         c = c * (Hprime - g + 1) / g;
         S += c;
     }
-    return gsc_shmem(H, Hprime, S) <= 64 * 1024 ? 1 : 0;
+    return S;
+}
+
+extern "C" int pm_gsc_supported(int64_t H, int64_t Hprime, int64_t gamma) {
+    if (H <= 0 || H > 512 || Hprime <= 0 || Hprime > PM_MAX_HPRIME || Hprime > H || gamma < 1 || gamma > 8) return 0;
+    return gsc_shmem(H, Hprime, gsc_full_states(Hprime, gamma)) <= 64 * 1024 ? 1 : 0;
+}
+
+#ifndef PM_PAIRS_WGS
+#define PM_PAIRS_WGS 256
+#endif
+// Every launch decision of gsc_estep_launch (pm_gsc_estep_f64, _lists_f64, _lpj_f64, _lpj_blocks_f64), pm_gsc_list_pairs_f64,
+// pm_gsc_pack_stats_f64 and pm_gsc_component_scores_f64: the launchers switch on this struct and pm_gsc_plan exports it, so a
+// test that asks for the plan sees the instantiation the launch takes.
+struct GscPlan {
+    int vpl, gmax, form;                // gsc_estep_kernel<VPL, GMAX, ...>, PM_GSC_FORM_*
+    bool lacc;                          // the LACC layout fits (it also sizes the LDS of the LPJ form)
+    bool colsum;                        // gsc_colsum_kernel follows
+    size_t lds;                         // dynamic LDS of a workgroup
+    int64_t grid, trips;                // workgroups; datapoint groups of sixteen a workgroup walks at most
+    int rows_c, nchunks;                // list pairs: rows of a product per workgroup, chunks of rows
+    int64_t groups, rpg;                // ... datapoint groups and datapoints per group
+};
+
+// `D` is read with PM_GSC_PLAN_LISTS only: > 0 adds the conditions of pm_gsc_lists_supported on the M-step's contraction
+static int gsc_plan(int which, int64_t H, int64_t Hprime, int64_t S, int64_t gamma, int64_t D, int flags, int64_t N, int cus,
+                    GscPlan *p) {
+    *p = GscPlan{};
+    if (which < PM_GSC_PLAN_ESTEP || which > PM_GSC_PLAN_COMPONENT_SCORES || H <= 0 || N < 1) return PM_EINVAL;
+    if (which == PM_GSC_PLAN_LIST_PAIRS) {
+        if (H > 256 || H % 64 != 0) return PM_ERANGE;
+        // rows_c x H doubles <= 128 KB: the largest divisor of H that fits (64: 64, 128: 128, 192: 64, 256: 64)
+        int rows_c = (int)(16384 / H < H ? 16384 / H : H);
+        while (H % rows_c != 0) --rows_c;
+        p->rows_c = rows_c;
+        p->nchunks = (int)(H / rows_c);
+        int64_t groups = PM_PAIRS_WGS / (2 * p->nchunks);
+        if (groups < 1) groups = 1;
+        int64_t rpg = (N + groups - 1) / groups;
+        rpg = (rpg + 63) / 64 * 64;
+        p->rpg = rpg;
+        p->groups = (N + rpg - 1) / rpg;
+        p->lds = sizeof(double) * (size_t)rows_c * (size_t)H;
+        p->grid = 2 * p->nchunks * p->groups;
+        p->trips = (rpg + 64 * 8 - 1) / (64 * 8);
+        return PM_OK;
+    }
+    if (which == PM_GSC_PLAN_PACK) {
+        if (H > 512) return PM_ERANGE;
+        p->grid = (H * H + 255) / 256;
+        p->trips = 1;
+        return PM_OK;
+    }
+    if (which == PM_GSC_PLAN_COMPONENT_SCORES) {
+        if (N > INT64_MAX / H) return PM_ERANGE;
+        p->grid = (N * H + 255) / 256;
+        if (p->grid > INT32_MAX) return PM_ERANGE;
+        p->trips = 1;
+        return PM_OK;
+    }
+    const bool lpj = flags & PM_GSC_PLAN_LPJ, blocks = flags & PM_GSC_PLAN_BLOCKS, lists = flags & PM_GSC_PLAN_LISTS;
+    if (Hprime <= 0 || S < 0 || (flags & ~(PM_GSC_PLAN_LPJ | PM_GSC_PLAN_BLOCKS | PM_GSC_PLAN_LISTS)) || (blocks && !lpj) ||
+        (lists && lpj))
+        return PM_EINVAL;
+    if (!pm_gsc_supported(H, Hprime, gamma)) return PM_ERANGE;
+    if (gsc_shmem(H, Hprime, S) > 64 * 1024) return PM_ERANGE;
+    p->lacc = gsc_shmem_lacc(H, Hprime, S) <= 53 * 1024;
+    p->lds = p->lacc ? gsc_shmem_lacc(H, Hprime, S) : gsc_shmem(H, Hprime, S);
+    // ONE resident round of workgroups (three per CU for the tuned instantiations), each walking its share of the
+    // datapoints: 2048 workgroups -- 2.7 rounds, the last one two thirds full, and 2048 table loads / accumulator flushes --
+    // ran 0.717 ms at config 4, 768 run 0.677 (1536: 0.70, 3072: 0.71)
+    if (cus <= 0) cus = 256;
+    const int64_t dgroups = (N + ROWS - 1) / ROWS;
+    int64_t grid = dgroups;
+    if (grid > 3 * (int64_t)cus) grid = 3 * (int64_t)cus;
+    p->gmax = gamma <= 2 ? 2 : gamma == 3 ? 3 : gamma == 4 ? 4 : gamma <= 6 ? 6 : 8;
+    if (lists) {      // LIST: a workgroup's dense rows wait in GSC_DENSE_CAP slots of LDS
+        if (!p->lacc || gamma > 3 || H <= 64 || H > 256) return PM_ERANGE;
+        // (the sparse product needs H <= 256, the gathered GEMM whole 128 x 128 tiles of the (D + 2 H) x H output)
+        if (D > 0 && ((D + 2 * H) % 128 != 0 || H % 128 != 0)) return PM_ERANGE;
+        const int64_t per_wg = GSC_DENSE_CAP / ROWS, need = (dgroups + per_wg - 1) / per_wg;
+        if (grid < need) grid = need;
+        if (grid > INT32_MAX) return PM_ERANGE;
+        p->vpl = H <= 128 ? 8 : 16;
+        p->form = PM_GSC_FORM_LIST;
+    } else {
+        p->vpl = H <= 16 ? 1 : H <= 32 ? 2 : H <= 64 ? 4 : H <= 128 ? 8 : H <= 256 ? 16 : 32;
+        p->form = lpj ? PM_GSC_FORM_LPJ : p->lacc ? PM_GSC_FORM_LACC : PM_GSC_FORM_PLAIN;
+    }
+    p->grid = grid;
+    p->trips = (dgroups + grid - 1) / grid;
+    p->colsum = p->form == PM_GSC_FORM_PLAIN || p->form == PM_GSC_FORM_LPJ;
+    return PM_OK;
+}
+
+extern "C" int pm_gsc_plan(int which, int64_t H, int64_t Hprime, int64_t S, int64_t gamma, int64_t D, int flags, int64_t N,
+                           int cus, int32_t *out) {
+    if (!out) return PM_EINVAL;
+    GscPlan p;
+    if (int e = gsc_plan(which, H, Hprime, S, gamma, D, flags, N, cus, &p)) return e;
+    for (int i = 0; i < PM_GSC_PLAN_LEN; ++i) out[i] = 0;
+    out[0] = p.vpl;
+    out[1] = p.gmax;
+    out[2] = p.form;
+    out[3] = (int32_t)p.lds;
+    out[4] = (int32_t)p.grid;
+    out[5] = (int32_t)(p.trips > INT32_MAX ? INT32_MAX : p.trips);
+    out[6] = p.colsum ? 1 : 0;
+    out[7] = p.rows_c;
+    out[8] = p.nchunks;
+    out[9] = (int32_t)p.groups;
+    out[10] = (int32_t)(p.rpg > INT32_MAX ? INT32_MAX : p.rpg);
+    return PM_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -899,27 +1010,18 @@ static int gsc_estep_launch(const double *scores, int64_t lds, const double *gra
     if (!scores || !gram || !psi_sq || !ynorm2 || !tables || !cand || !xpt_s || !xpt_sz || !stats || N < 0 || H <= 0 ||
         Hprime <= 0 || S < 0 || lds < H || ldx < H || (S > 0 && !state_masks) || !(sigma_sq >= 0.0))
         return PM_EINVAL;
-    if (!pm_gsc_supported(H, Hprime, gamma)) return PM_ERANGE;
+    int dev = 0, cus = 0;                 // (the one value the plan cannot know: 0 = the 256 it assumes)
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    GscPlan pl;
+    if (nz_idx && (!nz_val || !dense_rows || !dense_count)) return PM_ERANGE;
+    if (int e = gsc_plan(PM_GSC_PLAN_ESTEP, H, Hprime, S, gamma, 0,
+                         nz_idx ? PM_GSC_PLAN_LISTS : blocks ? PM_GSC_PLAN_LPJ | PM_GSC_PLAN_BLOCKS : logpj ? PM_GSC_PLAN_LPJ : 0,
+                         N, cus, &pl))
+        return e;
     GscTables T{tables, tables + H, tables + 2 * H, tables + 3 * H, tables + 4 * H, tables + 5 * H, tables + 6 * H,
                 tables + 7 * H};
-    const bool lacc = gsc_shmem_lacc(H, Hprime, S) <= 53 * 1024;
-    const size_t shmem = lacc ? gsc_shmem_lacc(H, Hprime, S) : gsc_shmem(H, Hprime, S);
-    if (gsc_shmem(H, Hprime, S) > 64 * 1024) return PM_ERANGE;
-    // ONE resident round of workgroups (three per CU for the tuned instantiations), each walking its share of the
-    // datapoints: 2048 workgroups -- 2.7 rounds, the last one two thirds full, and 2048 table loads / accumulator flushes --
-    // ran 0.717 ms at config 4, 768 run 0.677 (1536: 0.70, 3072: 0.71)
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-    int64_t groups = (N + ROWS - 1) / ROWS;
-    if (groups > 3 * (int64_t)cus) groups = 3 * (int64_t)cus;
-    if (nz_idx) {      // LIST: a workgroup's dense rows wait in GSC_DENSE_CAP slots of LDS
-        if (!lacc || logpj || gamma > 3 || H <= 64 || H > 256 || !nz_val || !dense_rows || !dense_count) return PM_ERANGE;
-        const int64_t per_wg = GSC_DENSE_CAP / ROWS, need = ((N + ROWS - 1) / ROWS + per_wg - 1) / per_wg;
-        if (groups < need) groups = need;
-        if (groups > INT32_MAX) return PM_ERANGE;
-    }
-    dim3 grid((unsigned)groups), block(256);
+    const size_t shmem = pl.lds;
+    dim3 grid((unsigned)pl.grid), block(256);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const double inv_s2 = sigma_sq > 0.0 ? 1.0 / sigma_sq : 0.0;   // 0: tables[8 H] holds it (pm_gsc_mstep_finish_f64)
 #define PM_LAUNCH_LA(V, G, L, A)                                                                                        \
@@ -938,38 +1040,44 @@ static int gsc_estep_launch(const double *scores, int64_t lds, const double *gra
                            cand, xpt_s, xpt_sz, ldx, stats, logpj, ldl, nz_idx, nz_val, dense_rows, dense_count,       \
                            nullptr, 0);                                                                                \
     } while (0)
-#define PM_LAUNCH(V, G)                         \
-    do {                                        \
-        if (logpj) {                            \
-            PM_LAUNCH_LA(V, G, true, false);    \
-        } else if (lacc) {                      \
-            PM_LAUNCH_LA(V, G, false, true);    \
-        } else {                                \
-            PM_LAUNCH_LA(V, G, false, false);   \
-        }                                       \
+#define PM_LAUNCH(V, G)                                        \
+    do {                                                       \
+        if (pl.form == PM_GSC_FORM_LPJ) {                      \
+            PM_LAUNCH_LA(V, G, true, false);                   \
+        } else if (pl.form == PM_GSC_FORM_LACC) {              \
+            PM_LAUNCH_LA(V, G, false, true);                   \
+        } else {                                               \
+            PM_LAUNCH_LA(V, G, false, false);                  \
+        }                                                      \
     } while (0)
-#define PM_BY_G(V)                            \
-    do {                                      \
-        if (gamma <= 2) PM_LAUNCH(V, 2);      \
-        else if (gamma == 3) PM_LAUNCH(V, 3); \
-        else if (gamma == 4) PM_LAUNCH(V, 4); \
-        else if (gamma <= 6) PM_LAUNCH(V, 6); \
-        else PM_LAUNCH(V, 8);                 \
+#define PM_BY_G(V)                                             \
+    do {                                                       \
+        switch (pl.gmax) {                                     \
+            case 2: PM_LAUNCH(V, 2); break;                    \
+            case 3: PM_LAUNCH(V, 3); break;                    \
+            case 4: PM_LAUNCH(V, 4); break;                    \
+            case 6: PM_LAUNCH(V, 6); break;                    \
+            default: PM_LAUNCH(V, 8); break;                   \
+        }                                                      \
     } while (0)
-    if (nz_idx) {
-        if (H <= 128) {
-            if (gamma <= 2) PM_LAUNCH_LIST(8, 2);
+    if (pl.form == PM_GSC_FORM_LIST) {
+        if (pl.vpl == 8) {
+            if (pl.gmax == 2) PM_LAUNCH_LIST(8, 2);
             else PM_LAUNCH_LIST(8, 3);
         } else {
-            if (gamma <= 2) PM_LAUNCH_LIST(16, 2);
+            if (pl.gmax == 2) PM_LAUNCH_LIST(16, 2);
             else PM_LAUNCH_LIST(16, 3);
         }
-    } else if (H <= 16) PM_BY_G(1);
-    else if (H <= 32) PM_BY_G(2);
-    else if (H <= 64) PM_BY_G(4);
-    else if (H <= 128) PM_BY_G(8);
-    else if (H <= 256) PM_BY_G(16);
-    else PM_BY_G(32);
+    } else {
+        switch (pl.vpl) {
+            case 1: PM_BY_G(1); break;
+            case 2: PM_BY_G(2); break;
+            case 4: PM_BY_G(4); break;
+            case 8: PM_BY_G(8); break;
+            case 16: PM_BY_G(16); break;
+            default: PM_BY_G(32); break;
+        }
+    }
 #undef PM_BY_G
 #undef PM_LAUNCH
 #undef PM_LAUNCH_LA
@@ -981,7 +1089,7 @@ static int gsc_estep_launch(const double *scores, int64_t lds, const double *gra
         const int64_t HH2 = 2 * H * H;
         hipLaunchKernelGGL(pm_fold_copies_kernel, dim3((unsigned)((HH2 + 255) / 256)), dim3(256), 0, s, stats,
                            stats + HH2 + 3 * H, HH2);
-        if (!lacc || logpj)
+        if (pl.colsum)
             hipLaunchKernelGGL(gsc_colsum_kernel, dim3((unsigned)blocks), dim3(256), 0, s, xpt_s, xpt_sz, ldx, N, (int)H,
                                rows_per_block, g_cs, g_cs + H);
     }
@@ -1013,9 +1121,9 @@ __global__ __launch_bounds__(256) void gsc_pack_kernel(const double *__restrict_
 
 extern "C" int pm_gsc_pack_stats_f64(const double *stats, int64_t H, const double *sum_ynorm2, double *out, void *stream) {
     if (!stats || !sum_ynorm2 || !out || H <= 0) return PM_EINVAL;
-    if (H > 512) return PM_ERANGE;
-    const int64_t HH = H * H;
-    hipLaunchKernelGGL(gsc_pack_kernel, dim3((unsigned)((HH + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+    GscPlan pl;
+    if (int e = gsc_plan(PM_GSC_PLAN_PACK, H, 0, 0, 0, 0, 0, 1, 0, &pl)) return e;
+    hipLaunchKernelGGL(gsc_pack_kernel, dim3((unsigned)pl.grid), dim3(256), 0, static_cast<hipStream_t>(stream),
                        stats, (int)H, sum_ynorm2, out);
     return (int)hipGetLastError();
 }
@@ -1033,14 +1141,10 @@ extern "C" int pm_gsc_estep_f64(const double *scores, int64_t lds, const double 
 // (gsc_estep_kernel, LIST).  `tables` must carry the threshold in tables[8 H + 1] (pm_gsc_mstep_finish_f64 writes it; 0 =
 // every row dense); *dense_count must be 0 at launch; nz_idx / nz_val (N x PM_BSC_NZ_MAX), dense_rows (N).
 extern "C" int pm_gsc_lists_supported(int64_t H, int64_t Hprime, int64_t gamma, int64_t D) {
-    if (!pm_gsc_supported(H, Hprime, gamma) || gamma > 3 || H <= 64 || H > 256) return 0;
-    int64_t S = 0, c = Hprime;
-    for (int64_t g = 2; g <= gamma && g <= Hprime; ++g) {
-        c = c * (Hprime - g + 1) / g;
-        S += c;
-    }
-    // (the sparse product needs H <= 256, the gathered GEMM whole 128 x 128 tiles of the (D + 2 H) x H output)
-    return (gsc_shmem_lacc(H, Hprime, S) <= 53 * 1024 && (D + 2 * H) % 128 == 0 && H % 128 == 0) ? 1 : 0;
+    GscPlan pl;
+    if (D <= 0) return 0;
+    return gsc_plan(PM_GSC_PLAN_ESTEP, H, Hprime, gsc_full_states(Hprime, gamma), gamma, D, PM_GSC_PLAN_LISTS, 1, 0, &pl) == PM_OK
+               ? 1 : 0;
 }
 
 extern "C" int pm_gsc_estep_lists_f64(const double *scores, int64_t lds, const double *gram, const double *psi_sq,
@@ -1132,24 +1236,15 @@ __global__ __launch_bounds__(1024) void gsc_list_pairs_kernel(const uint16_t *__
 extern "C" int pm_gsc_list_pairs_f64(const uint16_t *nz_idx, const double *nz_val_s, const double *nz_val, int64_t N,
                                      int64_t H, double *out, void *stream) {
     if (!nz_idx || !nz_val_s || !nz_val || !out || N < 0 || H <= 0) return PM_EINVAL;
-    if (H > 256 || H % 64 != 0) return PM_ERANGE;
+    GscPlan pl;
+    if (int e = gsc_plan(PM_GSC_PLAN_LIST_PAIRS, H, 0, 0, 0, 0, 0, N > 0 ? N : 1, 0, &pl)) return e;
     if (N == 0) return PM_OK;
-    const int rows_c = (int)(H <= 128 ? H : 16384 / H), nchunks = (int)(H / rows_c);      // rows_c x H doubles <= 128 KB
-    if (H % rows_c != 0) return PM_ERANGE;
-#ifndef PM_PAIRS_WGS
-#define PM_PAIRS_WGS 256
-#endif
-    int64_t groups = PM_PAIRS_WGS / (2 * nchunks);
-    if (groups < 1) groups = 1;
-    int64_t rpg = (N + groups - 1) / groups;
-    rpg = (rpg + 63) / 64 * 64;
-    groups = (N + rpg - 1) / rpg;
-    const size_t shmem = sizeof(double) * (size_t)rows_c * (size_t)H;
+    const size_t shmem = pl.lds;
     if (int e = (int)hipFuncSetAttribute(reinterpret_cast<const void *>(gsc_list_pairs_kernel),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem))
         return e;
-    hipLaunchKernelGGL(gsc_list_pairs_kernel, dim3((unsigned)(2 * nchunks * groups)), dim3(1024), shmem,
-                       static_cast<hipStream_t>(stream), nz_idx, nz_val_s, nz_val, N, (int)H, rows_c, nchunks, rpg, out);
+    hipLaunchKernelGGL(gsc_list_pairs_kernel, dim3((unsigned)pl.grid), dim3(1024), shmem,
+                       static_cast<hipStream_t>(stream), nz_idx, nz_val_s, nz_val, N, (int)H, pl.rows_c, pl.nchunks, pl.rpg, out);
     return (int)hipGetLastError();
 }
 
@@ -1181,7 +1276,8 @@ extern "C" int pm_gsc_estep_lpj_blocks_f64(const double *scores, int64_t lds, co
 }
 
 // component_scores (gsc_et.py:752-809): the singleton log-posterior of every latent WITHOUT the prior, with the
-// reference's clamps (NaN and values below the smallest double -> that double, +-inf -> 0), from the scores a = W^T y
+// reference's clamps (NaN and values below -DBL_MAX, -inf among them, -> -DBL_MAX; then +inf -> 0: the order of gsc_et.py:802-804
+// and of gsc_estep_kernel's selection keys), from the scores a = W^T y
 // (or (Sigma^-1 W)^T y for diagonal / full noise, as pm_gsc_estep_f64 takes them).
 namespace {
 __global__ __launch_bounds__(256) void gsc_component_scores_kernel(const double *__restrict__ scores, int64_t lds,
@@ -1208,9 +1304,9 @@ extern "C" int pm_gsc_component_scores_f64(const double *scores, int64_t lds, co
                                            void *stream) {
     if (N == 0) return PM_OK;
     if (!scores || !ynorm2 || !tables || !out || N < 0 || H <= 0 || lds < H || ldo < H || !(sigma_sq > 0.0)) return PM_EINVAL;
-    const int64_t blocks = (N * H + 255) / 256;
-    if (blocks > INT32_MAX) return PM_ERANGE;
-    hipLaunchKernelGGL(gsc_component_scores_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+    GscPlan pl;
+    if (int e = gsc_plan(PM_GSC_PLAN_COMPONENT_SCORES, H, 0, 0, 0, 0, 0, N, 0, &pl)) return e;
+    hipLaunchKernelGGL(gsc_component_scores_kernel, dim3((unsigned)pl.grid), dim3(256), 0, static_cast<hipStream_t>(stream),
                        scores, lds, ynorm2, tables, 1.0 / sigma_sq, N, (int)H, out, ldo);
     return (int)hipGetLastError();
 }
