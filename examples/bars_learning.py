@@ -99,6 +99,10 @@ def main():
                     help="with --heldout: denoise the held-out datapoints (reconstruct, DESIGN 4.14) and print the mean squared "
                     "error of the noisy data and of the reconstruction against the noiseless data, for the learned and for "
                     "the generating parameters")
+    ap.add_argument("--variance", action="store_true",
+                    help="with --heldout --reconstruct: also the posterior variance V of every estimate (reconstruct(variance=True), "
+                    "DESIGN 4.19) and the calibration ratio sum (yhat - clean)^2 / sum V: 1 in expectation for a model that "
+                    "is as sure as it should be, above 1 for an overconfident one")
     a = ap.parse_args()
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         import torch
@@ -173,6 +177,17 @@ def main():
                 print("held-out mean squared error against the noiseless data (%d datapoints): noisy data %.4f, reconstruction "
                       "with the learned parameters %.4f, with the generating parameters %.4f"
                       % (a.heldout, sums[0] / sums[3], sums[1] / sums[3], sums[2] / sums[3]))
+            if a.variance:
+                # how sure the model is of these estimates: the summed posterior variance against the summed squared error
+                cal = []
+                for params in (em.lparams, gt):
+                    yh, V = rmodel.reconstruct(dict(params), heldout, variance=True)
+                    cal += [sq(yh), float(np.asarray(V).sum())]
+                cal = comm.allreduce(np.array(cal))
+                if comm.rank == 0:
+                    print("held-out calibration sum (yhat - clean)^2 / sum V: learned parameters %.4f, generating parameters %.4f "
+                          "(mean posterior variance %.4f and %.4f)"
+                          % (cal[0] / cal[1], cal[2] / cal[3], cal[1] / sums[3], cal[3] / sums[3]))
             if a.exact:
                 # the quantity the truncated reconstruction approximates: the posterior mean over EVERY state;
                 # with the generating parameters it is the minimum-mean-square estimate of the noiseless data

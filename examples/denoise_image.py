@@ -2,7 +2,7 @@
 """Whole-image denoising by overlapping patches on an image the models are correctly specified for.
 
     python examples/denoise_image.py [bsc|mca] [--size 128] [--p 5] [--stride 1] [--steps 50] [--missing FRACTION]
-                                     [--train-missing]
+                                     [--train-missing] [--variance]
 
 No file is read.  The script draws a *bars image*: row indicators r_i and column indicators c_j ~ Bernoulli(pi),
 clean[i, j] = a (r_i + c_j) (MCA: a max(r_i, c_j)), plus Gaussian noise of standard deviation sigma.  Every p x p patch of
@@ -20,7 +20,12 @@ dropped pixels hold NaN), and the MSE is printed separately over the observed pi
 incomplete image's own patches.  The mask image goes through ``extract_patches`` on the same grid and travels as
 ``my_data['mask']`` through EM; ``Ncut_factor`` stays 0 (data truncation is not defined across rows with different numbers
 of observed pixels); the start parameters come from the image with its holes filled by the observed mean.  The same
-observed / missing MSE lines are printed."""
+observed / missing MSE lines are printed.
+
+``--variance``: ``reconstruct_image(..., variance=True)`` also returns ``var_map``, the overlap average of the
+patches' posterior variances of the noiseless value -- an upper bound on the variance of the averaged estimate.  Its mean is
+printed beside the actual MSE against the clean image (with ``--missing``: separately over the observed and over the missing
+pixels)."""
 import argparse
 import os
 import sys
@@ -77,6 +82,8 @@ def main():
                     help="share of pixels dropped after the noise; the reconstruction runs with the mask")
     ap.add_argument("--train-missing", action="store_true",
                     help="bsc with --missing: train on the incomplete image's own patches (my_data['mask'])")
+    ap.add_argument("--variance", action="store_true",
+                    help="also print the mean of var_map (the posterior variance the model reports) beside the MSE")
     a = ap.parse_args()
     if a.train_missing and (a.model != "bsc" or not 0.0 < a.missing < 1.0):
         ap.error("--train-missing needs the bsc model and --missing FRACTION in (0, 1)")
@@ -114,6 +121,7 @@ def main():
     # denoise over a wider truncated state set than training uses (as examples/bars_learning.py --reconstruct)
     rmodel = build(a.model, a.p, min(H, 7), min(H, 5))
     peak = float(clean.max()) or 1.0
+    kw = {'variance': True} if a.variance else {}
     print("%s, %d x %d bars image (a = %g, sigma = %g, pi = %g), %d x %d patches at stride %d, %d patches trained on, %d EM steps"
           % (a.model.upper(), a.size, a.size, a.a, a.sigma, a.pi, a.p, a.p, a.stride, len(Y), a.steps))
     if a.missing > 0.0:
@@ -129,12 +137,19 @@ def main():
         print("  %-44s MSE observed %.4f   missing %.4f (filled with the observed mean)"
               % ("noisy image", mse(noisy, mask), mse(np.full_like(clean, noisy[mask].mean()), ~mask)))
         for tag, params in (("learned", learned), ("generating", gt)):
-            out = rmodel.reconstruct_image(params, holes, mask=mask, stride=a.stride)
+            out = rmodel.reconstruct_image(params, holes, mask=mask, stride=a.stride, **kw)
+            out, var = out if a.variance else (out, None)
             print("  %-44s MSE observed %.4f   missing %.4f" % ("reconstructed, %s parameters" % tag, mse(out, mask), mse(out, ~mask)))
+            if a.variance:
+                print("  %-44s     observed %.4f   missing %.4f" % ("  mean of var_map", var[mask].mean(), var[~mask].mean()))
         return
     report("noisy image", noisy, clean, peak)
-    report("denoised, learned parameters", rmodel.reconstruct_image(learned, noisy, stride=a.stride), clean, peak)
-    report("denoised, generating parameters", rmodel.reconstruct_image(gt, noisy, stride=a.stride), clean, peak)
+    for tag, params in (("learned", learned), ("generating", gt)):
+        out = rmodel.reconstruct_image(params, noisy, stride=a.stride, **kw)
+        out, var = out if a.variance else (out, None)
+        report("denoised, %s parameters" % tag, out, clean, peak)
+        if a.variance:
+            print("  %-44s     %.4f (mean of var_map: the posterior variance the model reports)" % ("", var.mean()))
     print("  learned pi %.4f (generating %.4f), sigma %.4f (generating %.4f)"
           % (float(np.asarray(learned['pi'])), a.pi, float(np.asarray(learned['sigma'])), a.sigma))
 

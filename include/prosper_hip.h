@@ -1075,6 +1075,54 @@ int pm_recon_mca_f64(const double *logpj, int64_t ld, const double *lse, const i
                      int64_t S, double *Yhat, int64_t ldy, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Posterior variance of the reconstruction (recon_var.hip)
+ * ---------------------------------------------------------------------------------------
+ * V_nd = E_q[ybar_d(s)^2] - yhat_nd^2 over exactly the states and weights of the entries above.  For ybar = mu + W u the second
+ * moment is E[((W u)_d)^2] = sum_h m2[n,h] W_dh^2 + 2 sum_{i<j} p[n,(i,j)] W_d,c_i W_d,c_j: two latents co-occur only among a
+ * row's candidates c = cand[n, :].  No atomics and no branch on the build; every output element is written once by one lane,
+ * and every sum runs in an order fixed by H, Hprime, S and D alone (a lane adds its states in ascending state number and its
+ * pairs in ascending pair number): both builds return the same bits and a row's bits depend on that row alone.  Every entry
+ * checks its arguments before it touches a device, at N == 0 too: PM_EINVAL for a null pointer, a negative size, a short
+ * leading dimension or an inconsistent layout, PM_ERANGE past a limit; N == 0 launches nothing.
+ *
+ * pm_recon_moments2_f64: logpj, ld, lse, a, col_offset, cand, state_vals, block_values_host, N, H, Hprime, K, single_off,
+ * nblocks, multi_off, S exactly as pm_recon_expect_f64.  m2 (N, ldm >= out_cols >= H): m2[n, h] = sum_c value_c^2 q(block c, h)
+ * + sum over the table states of q(s) v_j^2 at every candidate position j that holds h (a latent held by two positions (TSC)
+ * receives both), 0 in the columns [H, out_cols) (the K padding of the product that follows).  p (N, ldp >= Hprime (Hprime -
+ * 1) / 2): p[n, (i,j)] = sum over the table states of q(s) v_i v_j, pairs of POSITIONS in the order (0,1), (0,2), ...,
+ * (Hprime-2, Hprime-1), the order of pm_bsc_mtrain_rows_f64; p may be NULL when there are no pairs or no table states (Hprime
+ * <= 1 or S == 0) and is written (zeros for S == 0) whenever it is given.  With S = 0 and one block of value 1, m2 is the row
+ * softmax of a X + o.  Hprime <= PM_MAX_HPRIME, nblocks <= 8. */
+int pm_recon_moments2_f64(const double *logpj, int64_t ld, const double *lse, double a, const double *col_offset,
+                          const int32_t *cand, const double *state_vals, const double *block_values_host, int64_t N,
+                          int64_t H, int64_t Hprime, int64_t K, int64_t single_off, int64_t nblocks, int64_t multi_off,
+                          int64_t S, double *m2, int64_t ldm, int64_t out_cols, double *p, int64_t ldp, void *stream);
+/* GSC: m2 and p (layout and pair order as above) of u = s o z, E[u u^T] = sum_s q(s) (kappa_s kappa_s^T + Lambda_s^-1), from one
+ * pass of pm_gsc_estep_lpj_blocks_f64 at the same beta: logpj (N, ldl >= 1 + H + S), blocks (N, ldb >= 2 Hprime^2 + 2 Hprime + 1;
+ * NULL: no multi-cause states, S == 0), the scores (N, lds >= H) and tables (8 H) that pass was given, and cand (N, Hprime).
+ * The weights are the E-step's own: exp(beta lp) floored at DBL_MIN for every state but the null state, normalised by 1 / (Z
+ * + DBL_MIN).  m2[n,h] = q_h (kappa_h^2 + 1 / lambda_h) + the diagonal of the candidate block at the position that holds h;
+ * p[n,(i,j)] = the mean of the block's (i,j) and (j,i) entries.  Hprime <= PM_MAX_HPRIME. */
+int pm_recon_gsc_moments2_f64(const double *logpj, int64_t ldl, const double *blocks, int64_t ldb, const double *scores,
+                              int64_t lds, const double *tables, const int32_t *cand, double beta, int64_t N, int64_t H,
+                              int64_t Hprime, int64_t S, double *m2, int64_t ldm, int64_t out_cols, double *p, int64_t ldp,
+                              void *stream);
+/* V (N, ldv >= D) arrives holding sum_h m2[n,h] W_dh^2 (pm_gemm_nt_rows_f64 of m2 against W o W) and leaves as
+ *   V[n,d] = max(V[n,d] + 2 sum_{i<j} p[n,(i,j)] Wt[c_i, d] Wt[c_j, d] - (Yhat[n,d] - mu[d])^2, 0)
+ * (mu NULL: 0; a NaN stays NaN), Wt (H, ldw >= D) the transpose of W, Yhat (N, ldy >= D) the posterior mean.  A candidate
+ * outside [0, H) is clamped into it.  p NULL or Hprime <= 1: no pair term, and cand and Wt are not read and may be NULL (the
+ * mixtures, MCA / MMCA, Hprime = 1).  Any D; Hprime <= PM_MAX_HPRIME. */
+int pm_recon_var_finish_f64(double *V, int64_t ldv, const double *Yhat, int64_t ldy, const double *mu, const double *p,
+                            int64_t ldp, const int32_t *cand, const double *Wt, int64_t ldw, int64_t N, int64_t H, int64_t D,
+                            int64_t Hprime, void *stream);
+/* MCA (signed_w = 0) / MMCA (1): V[n, d] += sum_s q_n(s) Wbar_d(s)^2 over the S multi-cause states, arguments, Wbar, power
+ * functions and limits of pm_recon_mca_f64.  The one-cause part of E[ybar^2] is pm_recon_moments2_f64 (one block of value 1, S =
+ * 0) + pm_gemm_nt_rows_f64 against W o W; pm_recon_var_finish_f64 without pairs follows.  D <= 1024, Hprime <= PM_MAX_HPRIME. */
+int pm_recon_mca_var_f64(const double *logpj, int64_t ld, const double *lse, const int32_t *cand, const uint16_t *state_masks,
+                         const double *Wrho, double inv_rho, int signed_w, int64_t N, int64_t H, int64_t D, int64_t Hprime,
+                         int64_t S, double *V, int64_t ldv, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Whole-image denoising by overlapping patches (patch_kernels.hip)
  * ---------------------------------------------------------------------------------------
  * The patch grid.  Along an axis of length L, patches of length p at stride s >= 1 start at 0, s, 2s, ... while start + p <=

@@ -120,8 +120,9 @@ class CAModel(Model):
         """Whole-image denoising by overlapping patches: ``utils.patches.denoise_image(self, model_params,
         image, **kw)`` -- every patch through ``reconstruct()``, the estimates averaged where they overlap.  Keywords:
         ``patch``, ``stride``, ``center``, ``chunk``, ``device``, ``exact`` (every patch through
-        ``reconstruct(exact=True)``).  ``mask`` (the image's shape, non-zero = observed pixel;
-        DESIGN 4.16): the patches go through the masked ``reconstruct()`` -- inpainting."""
+        ``reconstruct(exact=True)``), ``variance`` (returns ``(image, var_map)``, var_map the overlap average of
+        the patches' posterior variances -- an upper bound on the variance of the averaged estimate).  ``mask`` (the image's
+        shape, non-zero = observed pixel): the patches go through the masked ``reconstruct()`` -- inpainting."""
         from ...utils.patches import denoise_image
         return denoise_image(self, model_params, image, mask=mask, **kw)
 

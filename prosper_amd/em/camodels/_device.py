@@ -1077,6 +1077,8 @@ class DeviceCAModel(CAModel):
         return out
 
     # ---- posterior-mean reconstruction --------------------------------------------------------------------
+    _recon_var_max_D = 2 ** 30        # (MCA / MMCA: 1024, the lanes-over-dimensions kernels)
+
     def _recon_layout(self, model_params):
         """Per model: what ``reconstruct`` needs beside the E-step's log-joints -- ``params`` (the parameters the E-step is
         run with), ``blocks`` (the latent value of every block of H one-cause columns, starting at column ``soff``),
@@ -1118,8 +1120,55 @@ class DeviceCAModel(CAModel):
                    self._stream())
         return out
 
-    def _reconstruct(self, model_params, my_data, N):
-        """The (N, D) device tensor of ``reconstruct`` for the models whose E-step leaves (N, K) log-joints."""
+    def _recon_variance(self, lp, K, N, cand, lay, Yhat, mu, par=None):
+        """The (N, D) device tensor V of ``reconstruct(variance=True)`` from the log-joints, candidates and
+        layout ``Yhat`` was formed from: m2 and p by pm_recon_moments2_f64, sum_h m2 W_dh^2 as one pm_gemm_nt_rows_f64
+        against W o W, MCA / MMCA's multi-cause squares by pm_recon_mca_var_f64, then pm_recon_var_finish_f64."""
+        H, D, Hp = self.H, self.D, self.Hprime
+        table, blocks = lay.get("table"), lay["blocks"]
+        S = 0 if table is None else int(table.shape[0])
+        npair = Hp * (Hp - 1) // 2 if S else 0
+        Kp = (H + 7) // 8 * 8
+        m2 = self._buf("recon_m2", (N, Kp))
+        p2 = self._buf("recon_p2", (N, npair)) if npair else None
+        tab_d = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float64)).to(self.device) if S else None
+        bv = (ctypes.c_double * 8)(*([float(v) for v in blocks] + [0.0] * (8 - len(blocks))))
+        ld = lp.stride(0) if N > 1 else max(int(lp.stride(0)), K)
+        self._call("recon_var", "pm_recon_moments2_f64", _ptr(lp), ld, None, ctypes.c_double(1.0), None,
+                   _ptr(cand) if S else None, _ptr(tab_d), bv, N, H, Hp if S else 0, K, lay["soff"], len(blocks), lay["moff"],
+                   S, _ptr(m2), Kp, Kp, _ptr(p2), max(npair, 1), self._stream())
+        mca = None
+        if lay.get("mca") and self.no_states:
+            mca = lambda V: self._call("recon_var", "pm_recon_mca_var_f64", _ptr(lp), ld, None, _ptr(cand), _ptr(self._masks()),
+                                       _ptr(par["Wrho"]), ctypes.c_double(1. / par["rho"]), int(bool(self.signed_w)), N, H, D,
+                                       Hp, self.no_states, _ptr(V), D, self._stream())
+        return self._recon_var_product(m2, p2, cand, lay["W"], mu, Yhat, more=mca)
+
+    def _recon_var_product(self, m2, p2, cand, W, mu, Yhat, more=None):
+        """V (N, D) from the second moments: sum_h m2 W_dh^2 as one pm_gemm_nt_rows_f64 of ``m2`` (N, Kp; zero past H) against
+        W o W, ``more(V)`` (MCA / MMCA: the multi-cause squares), then pm_recon_var_finish_f64 with the pairs ``p2`` (N,
+        H'(H'-1)/2; None: no pair term) over ``cand``, ``Yhat`` and ``mu`` (None: 0)."""
+        N, Kp = m2.shape
+        H, D, Hp = self.H, self.D, self.Hprime
+        npair = 0 if p2 is None else int(p2.shape[1])
+        W = np.asarray(W, dtype=np.float64)
+        W2 = np.zeros((D, Kp))
+        W2[:, :H] = W * W
+        W2d = torch.from_numpy(W2).to(self.device)
+        V = torch.empty((N, D), dtype=torch.float64, device=self.device)
+        self._call("recon_var", "pm_gemm_nt_rows_f64", _ptr(m2), Kp, _ptr(W2d), Kp, _ptr(V), D, N, D, Kp, self._stream())
+        if more is not None:
+            more(V)
+        Wt = torch.from_numpy(np.ascontiguousarray(W.T)).to(self.device) if npair else None
+        mu_d = torch.from_numpy(np.ascontiguousarray(mu, dtype=np.float64).reshape(-1)).to(self.device) if mu is not None \
+            else None
+        self._call("recon_var", "pm_recon_var_finish_f64", _ptr(V), D, _ptr(Yhat), D, _ptr(mu_d), _ptr(p2), max(npair, 1),
+                   _ptr(cand) if npair else None, _ptr(Wt), D, N, H, D, Hp if npair else 0, self._stream())
+        return V
+
+    def _reconstruct(self, model_params, my_data, N, variance=False):
+        """The (N, D) device tensor of ``reconstruct`` for the models whose E-step leaves (N, K) log-joints; with
+        ``variance`` the pair (Yhat, V)."""
         lay = self._recon_layout(model_params)
         mp = lay["params"]
         data = self.select_Hprimes(mp, my_data)
@@ -1138,15 +1187,18 @@ class DeviceCAModel(CAModel):
         es = self._recon_expect(lp, K, N, lse=lse, cand=cand, table=lay.get("table"), blocks=lay["blocks"],
                                 soff=lay["soff"], moff=lay["moff"], ones=mu is not None)
         Yhat = self._recon_product(es, es.shape[1], es.shape[1], lay["W"], mu)
+        par = None
         if mca and self.no_states:
             par = self._tables_for(mp['W'], 1.0, self._resident(my_data['y']))
             ld = lp.stride(0) if N > 1 else max(int(lp.stride(0)), K)
             self._call("recon_mca", "pm_recon_mca_f64", _ptr(lp), ld, None, _ptr(cand), _ptr(self._masks()),
                        _ptr(par["Wrho"]), ctypes.c_double(1. / par["rho"]), int(bool(self.signed_w)), N, self.H, self.D,
                        self.Hprime, self.no_states, _ptr(Yhat), self.D, self._stream())
+        if variance:
+            return Yhat, self._recon_variance(lp, K, N, cand, lay, Yhat, mu, par)
         return Yhat
 
-    def reconstruct(self, model_params, my_data, device=False, exact=False):
+    def reconstruct(self, model_params, my_data, device=False, exact=False, variance=False):
         """Posterior-mean denoising: yhat_n = sum_{s in K_n} q_n(s) ybar(s; Theta), q_n(s) = p(s, y_n | Theta) / sum_{s' in K_n}
         p(s', y_n | Theta), for ``my_data['y']`` (host array, torch tensor or DeviceArray): the model's estimate of the
         noiseless data.  K_n and p are exactly those of ``log_likelihood``: the state set the E-step scores
@@ -1173,26 +1225,49 @@ class DeviceCAModel(CAModel):
         state table, no E-step, and a result independent of Hprime, gamma and the annealing state.  A row's bits depend on
         that row of ``y`` and the parameters alone.  The state count is bounded as for ``log_likelihood(exact=True)`` (MCA /
         MMCA also D <= 1024): past the bound this raises ``HipError``.  Together with ``my_data['mask']`` it raises
-        ``NotImplementedError``."""
+        ``NotImplementedError``.
+
+        ``variance=True``: returns ``(Yhat, V)``, both NumPy arrays or both ``DeviceArray``, V_nd = E_q[(ybar_d(s) -
+        yhat_nd)^2] = E_q[ybar_d^2] - yhat_nd^2 under the same q_n over the same K_n (GSC: over z | s, y_n too): the posterior
+        variance of the NOISELESS value -- the predictive variance of a new observation is V + sigma^2 (GSC: + Sigma_dd), which
+        the caller adds.  ``Yhat`` has the bits of the call without the keyword.  At H' = gamma = H it is the exact posterior
+        variance; with ``my_data['mask']`` the variance given the observed dimensions, at every dimension.  A value rounding
+        takes below 0 is returned as 0; a NaN data row gives a NaN row of V and touches no other.  Together with
+        ``exact=True`` it raises ``NotImplementedError`` before any launch (the enumeration kernels keep no second
+        moments).  Runs pm_recon_moments2_f64, pm_recon_mca_var_f64, pm_recon_var_finish_f64 and one more
+        pm_gemm_nt_rows_f64."""
         y = my_data['y']
         N = int(y.shape[0])
         mask = my_data.get('mask')
         if mask is not None:
             self._masked_admit(y, mask, exact, what="reconstruct")
+        if variance and exact:
+            raise NotImplementedError("%s.reconstruct: variance=True with exact=True is not built (the enumeration kernels "
+                                      "keep no second moments)" % type(self).__name__)
+        if variance and self.Hprime > 16:
+            raise _lib.HipError("%s.reconstruct: variance=True holds H' <= 16 candidates, got %d"
+                                % (type(self).__name__, self.Hprime))
+        if variance and self.D > self._recon_var_max_D:
+            raise _lib.HipError("%s.reconstruct: variance=True holds D <= %d (pm_recon_mca_var_f64), got %d"
+                                % (type(self).__name__, self._recon_var_max_D, self.D))
         if N == 0:
-            return DeviceArray(torch.empty((0, self.D), dtype=torch.float64, device=self.device)) if device \
+            empty = lambda: DeviceArray(torch.empty((0, self.D), dtype=torch.float64, device=self.device)) if device \
                 else np.empty((0, self.D))
+            return (empty(), empty()) if variance else empty()
         saved = self._eval_begin()
         try:
             # every product of the pass through the one-kernel GEMM, on parameter products of its own: a row of the result
             # is a function of that row of the data and of the parameters alone (attributes of the evaluation only)
             self._par, self._rows_gemm = {}, True
+            kw = {"variance": True} if variance else {}
             if mask is not None:
-                Yhat = self._reconstruct_masked(dict(model_params), y, mask, N)
+                Yhat = self._reconstruct_masked(dict(model_params), y, mask, N, **kw)
             elif exact:
                 Yhat = self._reconstruct_exact(dict(model_params), y, N)
             else:
-                Yhat = self._reconstruct(dict(model_params), {'y': y}, N)
+                Yhat = self._reconstruct(dict(model_params), {'y': y}, N, **kw)
+            if variance:
+                return tuple(DeviceArray(t) if device else t.cpu().numpy() for t in Yhat)
             return DeviceArray(Yhat) if device else Yhat.cpu().numpy()
         finally:
             self._par = {}
@@ -1257,9 +1332,9 @@ class DeviceCAModel(CAModel):
         g = self._gemm_nt(Mf, (Wt * Wt).contiguous(), self._buf("mask_g", (N, H)), "masked_gemm")
         return b, g
 
-    def _reconstruct_masked(self, model_params, y, mask, N):
+    def _reconstruct_masked(self, model_params, y, mask, N, variance=False):
         """``_reconstruct`` from the masked E-step's log-joints: the expectation and product kernels are the unmasked ones,
-        so the estimate covers all D dimensions."""
+        so the estimate (and with ``variance`` its variance given the observed dimensions) covers all D dimensions."""
         out = self._masked_estep(model_params, y, mask)
         lay, lp, cand = out["lay"], out["logpj"], out["cand"]
         K = lp.shape[1]
@@ -1275,6 +1350,8 @@ class DeviceCAModel(CAModel):
             self._call("recon_mca", "pm_recon_mca_f64", _ptr(lp), ld, None, _ptr(cand), _ptr(self._masks()),
                        _ptr(par["Wrho"]), ctypes.c_double(1. / par["rho"]), int(bool(self.signed_w)), N, self.H, self.D,
                        self.Hprime, self.no_states, _ptr(Yhat), self.D, self._stream())
+        if variance:
+            return Yhat, self._recon_variance(lp, K, N, cand, lay, Yhat, mu, out.get("par"))
         return Yhat
 
     def _log_likelihood_masked(self, model_params, my_data, per_datapoint, exact):

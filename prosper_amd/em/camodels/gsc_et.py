@@ -381,6 +381,7 @@ class GSC(DeviceCAModel):
             par["scores"] = None
             if A is None:
                 A = self._gemm_nt(Y, par["Wst"], self._buf("scores", (N, H)), "scores_gemm")
+        self._scores_used = A                # (reconstruct(variance=True) hands them to its second pass)
         return self._launch_estep(res, A, par["G"], par["psi_d"], par["yn"], par["tables"], par["s2"], anneal_T, cand_in,
                                   logpj)
 
@@ -538,26 +539,58 @@ class GSC(DeviceCAModel):
         c = float(np.log(1. - pi).sum()) - 0.5 * self.D * np.log(2 * np.pi) - 0.5 * logdet
         return logpj.tensor, 0.5, c
 
-    def _reconstruct(self, model_params, my_data, N):
+    def _reconstruct(self, model_params, my_data, N, variance=False):
         """reconstruct: yhat_n = W E[s z | y_n] = sum_s q_n(s) W_s kappa_s(y_n), kappa_s = mu_s + Lambda_s^-1
         W_s^T Sigma^-1 (y_n - W_s mu_s) = E[z_s | s, y_n].  The E-step pass returns xpt_sz = sum_s w_n(s) kappa_s with the
         reference's weights exp(beta (lp + prior)), lp carrying the Gaussian terms WITHOUT the 1/2 (gsc_et.py:341-354): at
         beta = 1/2 with every logit doubled (``_lpi_scale``, as ``_loglik_terms``) the weight is exp(lp / 2 + prior), the
         generative model's, and kappa_s does not depend on beta.  Then Yhat = xpt_sz W^T.  The pass floors every state's
         weight at DBL_MIN as the reference does (:355-356): visible only in a row whose weights all underflow.  A noise
-        covariance that is not positive definite: every row NaN."""
+        covariance that is not positive definite: every row NaN.  ``variance``: the pair (Yhat, V), ``_recon_variance_gsc``."""
         sig = np.asarray(model_params['sigma_sq'], dtype=np.float64)
         if (np.linalg.eigvalsh(0.5 * (sig + sig.T)).min() <= 0) if sig.ndim == 2 else not np.all(sig > 0):
-            return torch.full((N, self.D), float("nan"), dtype=torch.float64, device=self.device)
+            nan = lambda: torch.full((N, self.D), float("nan"), dtype=torch.float64, device=self.device)
+            return (nan(), nan()) if variance else nan()
         self._lpi_scale = 2.0          # (an attribute of the evaluation only: _eval_end restores the model's)
         self._require_scalar()
         res = self._resident(my_data['y'])
-        _, _, xsz, _ = self._run(2.0, model_params, res, None)
+        cand, _, xsz, _ = self._run(2.0, model_params, res, None)
         W = torch.from_numpy(np.ascontiguousarray(model_params['W'], dtype=np.float64)).to(self.device)
         out = torch.empty((N, self.D), dtype=torch.float64, device=self.device)
         self._call("recon_gemm", "pm_gemm_nt_rows_f64", _ptr(xsz), max(int(xsz.stride(0)), self.H), _ptr(W), self.H,
                    _ptr(out), self.D, N, self.D, self.H, self._stream())
+        if variance:
+            return out, self._recon_variance_gsc(model_params, res, cand, out, N)
         return out
+
+    def _recon_variance_gsc(self, model_params, res, cand, Yhat, N):
+        """V of ``reconstruct(variance=True)``: V_nd = sum_s q_n(s) (W_s (kappa_s kappa_s^T + Lambda_s^-1) W_s^T)_dd -
+        yhat_nd^2, the variance over s and z | s, y_n.  A second E-step pass on the candidates of the first (handed in, so the
+        pass that formed ``Yhat`` is the one ``reconstruct()`` runs, bit for bit) at the same beta = 1/2 and doubled logits
+        leaves the log-joints and every row's un-normalised multi-cause sums (pm_gsc_estep_lpj_blocks_f64);
+        pm_recon_gsc_moments2_f64 adds the null and one-cause states with the E-step's weights, floor and normaliser, and the
+        linear family's product and finish follow."""
+        H, Hp, S = self.H, self.Hprime, self.no_states
+        dev = self.device
+        par = self._tables_for(model_params, res)
+        A = self._scores_used               # (the scores Y . Sigma^-1 W of the pass ``_run`` has just made)
+        ldb = 2 * Hp * Hp + 2 * Hp + 1
+        blocks = self._buf("recon_blocks", (N, ldb))
+        logpj = self._buf("recon_gsc_lpj", (N, 1 + H + S))
+        both = self._buf("recon_gsc_xpt", (N, 2 * H))
+        stats = torch.zeros(int(_lib.load().pm_gsc_stats_len(H)), dtype=torch.float64, device=dev)
+        self._call("estep", "pm_gsc_estep_lpj_blocks_f64", _ptr(A), H, _ptr(par["G"]), _ptr(par["psi_d"]), _ptr(par["yn"]),
+                   _ptr(par["tables"]), _ptr(self._masks()), S, self.gamma, ctypes.c_double(0.5), ctypes.c_double(par["s2"]),
+                   N, H, Hp, 0, _ptr(cand), _ptr(both), ctypes.c_void_p(both.data_ptr() + 8 * H), 2 * H, _ptr(stats),
+                   _ptr(logpj), logpj.stride(0), _ptr(blocks), ldb, self._stream())
+        npair = Hp * (Hp - 1) // 2
+        Kp = (H + 7) // 8 * 8
+        m2 = self._buf("recon_m2", (N, Kp))
+        p2 = self._buf("recon_p2", (N, npair)) if npair else None
+        self._call("recon_var", "pm_recon_gsc_moments2_f64", _ptr(logpj), logpj.stride(0), _ptr(blocks), ldb, _ptr(A), H,
+                   _ptr(par["tables"]), _ptr(cand), ctypes.c_double(0.5), N, H, Hp, S, _ptr(m2), Kp, Kp, _ptr(p2),
+                   max(npair, 1), self._stream())
+        return self._recon_var_product(m2, p2, cand, model_params['W'], None, Yhat)
 
     def _reconstruct_exact(self, model_params, y, N):
         """reconstruct(exact=True): yhat_n = W E_n[s o z] over all 2^H supports, E_n[s o z] = sum_s q_n(s)

@@ -261,6 +261,8 @@ class MCA_ET(DeviceCAModel):
         c = self.H * np.log(1. - pies) - 0.5 * self.D * np.log(2 * _PI * sigma ** 2)
         return self._loglik_estep(model_params, my_data), 1.0, c
 
+    _recon_var_max_D = 1024
+
     def _recon_layout(self, model_params):
         """reconstruct: the mean of ``_loglik_terms``' model -- W_h for a one-cause state (the E-step's energy
         uses W itself there), the rho-combination Wbar(s) at T = 1 for a multi-cause state (pm_recon_mca_f64), 0 for the null

@@ -196,7 +196,7 @@ class DeviceMixture(object):
                   float(t["coef"]), _ptr(lp_d), N, D, H, _ptr(logpj), _ptr(post), self._stream())
         return logpj
 
-    def reconstruct(self, model_params, my_data, device=False, exact=False):
+    def reconstruct(self, model_params, my_data, device=False, exact=False, variance=False):
         """Posterior-mean denoising: yhat_n = sum_h r_nh W_h with the responsibilities r_nh = pies_h p(y_n | h) / sum_h'
         pies_h' p(y_n | h') of the proper densities of ``log_likelihood`` (MoG with the 1/2; not the reference's E-step
         quirk), for ``my_data['y']`` (host array, torch tensor or DeviceArray).  MoP: in the units of the data its E-step
@@ -209,12 +209,23 @@ class DeviceMixture(object):
         sum pass) and multiplied with W by pm_gemm_nt_rows_f64; H within pm_mix_scores_f64's bound for MoG diagonal / MoP.
 
         ``exact`` is accepted for the component-analysis models' signature: a mixture's posterior mean is exact
-        either way, and ``exact=True`` returns the same bits."""
+        either way, and ``exact=True`` returns the same bits.
+
+        ``variance=True``: returns ``(Yhat, V)``, both NumPy arrays or both ``DeviceArray``, V_nd = sum_h r_nh
+        W_dh^2 - yhat_nd^2: the posterior variance of the component mean, the NOISELESS value (the predictive variance of a
+        new observation adds the components' own noise, which the caller adds).  ``Yhat`` has the bits of the call without
+        the keyword; a value rounding takes below 0 is returned as 0; a NaN row of the data gives a NaN row of V.  One more
+        pm_gemm_nt_rows_f64 of the responsibilities against W o W, then pm_recon_var_finish_f64.  Together with
+        ``exact=True`` it raises ``NotImplementedError``, as the component-analysis models do."""
         self._refuse_mask(my_data)
+        if variance and exact:
+            raise NotImplementedError("%s.reconstruct: variance=True with exact=True is not built" % type(self).__name__)
         y = my_data['y']
         N, H, D = int(y.shape[0]), self.H, self.D
         if N == 0:
-            return DeviceArray(torch.empty((0, D), dtype=torch.float64, device=self.device)) if device else np.empty((0, D))
+            empty = lambda: DeviceArray(torch.empty((0, D), dtype=torch.float64, device=self.device)) if device \
+                else np.empty((0, D))
+            return (empty(), empty()) if variance else empty()
         saved = dict(self.__dict__)
         slot = saved.get("_eval_slot") or {"_data": {}, "_ws": {}}
         self._data, self._ws = slot["_data"], slot["_ws"]
@@ -232,6 +243,13 @@ class DeviceMixture(object):
             W_d = self._dev(Wp)
             out = torch.empty((N, D), dtype=torch.float64, device=self.device)
             _lib.call("pm_gemm_nt_rows_f64", _ptr(r), Kp, _ptr(W_d), Kp, _ptr(out), D, N, D, Kp, st)
+            if variance:
+                # (the second moment per component is the responsibility itself: pm_recon_moments2_f64 with one block of
+                # value 1 and no table would write ``r`` again)
+                V = torch.empty((N, D), dtype=torch.float64, device=self.device)
+                _lib.call("pm_gemm_nt_rows_f64", _ptr(r), Kp, _ptr(self._dev(Wp * Wp)), Kp, _ptr(V), D, N, D, Kp, st)
+                _lib.call("pm_recon_var_finish_f64", _ptr(V), D, _ptr(out), D, None, None, 1, None, None, D, N, H, D, 0, st)
+                return (DeviceArray(out), DeviceArray(V)) if device else (out.cpu().numpy(), V.cpu().numpy())
             return DeviceArray(out) if device else out.cpu().numpy()
         finally:
             slot = {"_data": self._data, "_ws": self._ws}

@@ -206,7 +206,7 @@ def _mask_image(mask, shape, dev):
 
 
 def denoise_image(model, model_params, image, patch=None, stride=1, center=False, chunk=None, device=False, mask=None,
-                  exact=False):
+                  exact=False, variance=False):
     """Denoise ``image`` ((H_i, W_i) or a stack (B, H_i, W_i); NumPy array, torch tensor -- a device tensor is used in place,
     without a host round trip -- or ``DeviceArray``) with ``model`` at ``model_params``: every overlapping patch on the grid of
     the module docstring is replaced by its posterior mean ``model.reconstruct()`` and every pixel by the average of the
@@ -234,6 +234,14 @@ def denoise_image(model, model_params, image, patch=None, stride=1, center=False
     ``exact=True``: every patch through ``model.reconstruct(..., exact=True)``, the posterior mean over the
     model's whole state space; its limits apply, and with a mask it raises ``NotImplementedError``.  The keyword reaches
     ``reconstruct()`` only when it is set.
+
+    ``variance=True``: every patch through ``model.reconstruct(..., variance=True)`` and the result is ``(image,
+    var_map)``; the image has the bits of the call without the keyword.  ``var_map`` is the overlap average of the patches'
+    posterior variances V through the same accumulate / finish kernels (the same bits for every ``chunk``): the MEAN OF THE
+    COVERING PATCHES' VARIANCES.  Whatever the correlation between the patches' estimates, Var(mean) <= mean Var, so it is an
+    upper bound on the variance of the averaged estimate, not that variance itself.  It is the variance of the noiseless
+    value; ``center=True`` leaves V unchanged (the patch mean is a constant to the model).  The keyword reaches
+    ``reconstruct()`` only when it is set.
     Returns the float64 image (the shape of ``image``) as a NumPy array, or with ``device=True`` as a ``DeviceArray``."""
     from ..em.camodels._device import DeviceArray
     if mask is not None and center:
@@ -256,16 +264,22 @@ def denoise_image(model, model_params, image, patch=None, stride=1, center=False
         raise ValueError("chunk must be a positive number of patches, got %r" % (chunk,))
     rows = max(1, int(chunk) // nc)
     extra = {'exact': True} if exact else {}
+    if variance:
+        extra['variance'] = True
     if mask is not None:
         if _shape_of(mask) != tuple(shape):
             raise ValueError("mask has shape %r, the image %r" % (_shape_of(mask), tuple(shape)))
         # (an empty masked call: a model without the masked E-step refuses here, before anything reaches the device)
         model.reconstruct(model_params, {'y': np.empty((0, D)), 'mask': np.empty((0, D), dtype=bool)}, **extra)
+    if variance and exact:
+        raise NotImplementedError("denoise_image: variance=True with exact=True is not built (the enumeration kernels keep no "
+                                  "second moments)")
     dev = _device(model)
     det = bool(getattr(model, "deterministic", False))
     img, ldi = _image_tensor(image, dev)
     mimg, ldmi = _mask_image(mask, shape, dev) if mask is not None else (None, 0)
     acc = torch.zeros((B, Hi, Wi), dtype=torch.float64, device=dev)
+    vacc = torch.zeros((B, Hi, Wi), dtype=torch.float64, device=dev) if variance else None
     for R0 in range(0, B * nr, rows):
         n0, n = R0 * nc, min(rows, B * nr - R0) * nc
         Y, means = _extract(img, ldi, geo, n0, n, center, det)
@@ -274,9 +288,19 @@ def denoise_image(model, model_params, image, patch=None, stride=1, center=False
             data['mask'] = DeviceArray((_extract(mimg, ldmi, geo, n0, n, False, det)[0] != 0).view(torch.uint8))
         est = model.reconstruct(model_params, data, device=True, **extra)
         del Y, data
+        if variance:
+            est, var = est
+            if _shape_of(var) != (n, D):
+                raise ValueError("reconstruct() returned a variance of %r for a chunk of (%d, %d)" % (_shape_of(var), n, D))
+            var, ldv = _rows_tensor(var, D, dev, "reconstruct()'s variance")
+            _accumulate(vacc, var, ldv, None, geo, n0, n, det)
+            del var
         if _shape_of(est) != (n, D):
             raise ValueError("reconstruct() returned %r for a chunk of (%d, %d)" % (_shape_of(est), n, D))
         est, lde = _rows_tensor(est, D, dev, "reconstruct()'s result")
         _accumulate(acc, est, lde, means, geo, n0, n, det)
         del est, means
-    return _hand_back(_finish(acc, geo, det), len(shape) == 2, device)
+    out = _hand_back(_finish(acc, geo, det), len(shape) == 2, device)
+    if variance:
+        return out, _hand_back(_finish(vacc, geo, det), len(shape) == 2, device)
+    return out
