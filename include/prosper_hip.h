@@ -1246,6 +1246,67 @@ int pm_bsc_mtrain_solve_f64(const double *A, const double *Ainv, const double *p
                             const double *Wt_old, int64_t ldw, int64_t D, int64_t H, double *Wt_new, int64_t ldo,
                             int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Posterior draws of the noiseless data (posterior_sample.hip)
+ * ---------------------------------------------------------------------------------------
+ * ybar(s) for s ~ q_n(s) = exp(a logpj[n,s] + o_s - lse_n) over exactly the states and weights of the reconstruction entries
+ * above.  No atomics and no branch on the build: every output element is written once by one lane, both builds
+ * return the same bits and a row's values depend on that row's inputs alone.  Every entry checks its arguments before it
+ * touches a device (PM_EINVAL: null pointer, negative size, short leading dimension, inconsistent layout; PM_ERANGE: past a
+ * limit); N == 0 launches nothing.
+ *
+ * pm_sample_states_f64: the categorical draws.  logpj (N, ld >= K), a, col_offset as pm_recon_expect_f64; lse NULL: the rows'
+ * log-sum-exp of a logpj + o by a maximum pass and a sum pass, else the caller's normaliser (N values, with any a and o; zeros
+ * leave the weights un-normalised, as GSC's E-step forms them).  The weight of column k is w_k = exp(a logpj[n,k] + o_k -
+ * lse_n), raised to weight_floor (>= 0; GSC: DBL_MIN) in every column but null_col (-1: in every column).  U (N, ldu >= M): the uniforms; idx (N, M) int32: for each, the column drawn.  With c the running sum of w in the
+ * order below and C its last value, the draw for u is the smallest k with fl(u C) < c_k.  Order: lane l of the row's wavefront
+ * owns the columns [l seg, (l + 1) seg), seg = ceil(K / 64) | 1; p_k = the lane's weights added in ascending k; base_l = the
+ * lanes' totals added in ascending lane order; c_k = base_l + p_k (every + one rounded f64 addition).  c is non-decreasing and
+ * stays put over a column of weight 0 by construction, so whatever U holds: 0 <= idx < K, a column of weight 0 is never
+ * returned, u = 0 gives the first column of positive weight and the largest double below 1 the last one; a u that is NaN or
+ * outside [0, 1) is clamped into [0, 1 - 2^-53].  A row with a NaN weight (a NaN log-joint), or whose weights do not sum to a
+ * positive finite value, returns -1 for every sample and touches no other row.  K <= pm_sample_states_max_cols() (the CDF of a row
+ * lives in the LDS of its wavefront). */
+int64_t pm_sample_states_max_cols(void);
+int pm_sample_states_f64(const double *logpj, int64_t ld, const double *lse, double a, const double *col_offset,
+                         double weight_floor, int64_t null_col, const double *U, int64_t ldu, int64_t N, int64_t K, int64_t M,
+                         int32_t *idx, void *stream);
+/* idx (N, M) -> the active list of each draw: act_idx (N, M, A) int32 the latents, act_val (N, M, A) their values, in ascending
+ * candidate position; the column layout (single_off, nblocks, block_values_host, multi_off, S, state_vals, cand, Hprime) is
+ * pm_recon_expect_f64's.  A one-cause column gives one entry, a table state one entry per position of non-zero value (a latent
+ * held by two positions (TSC) appears twice; entries past A are dropped: A >= the table's largest support), any other column
+ * (the null state) none.  Unused slots: index -1, value 0.  A draw of -1: index -1 and value NaN in every slot.  A candidate
+ * outside [0, H) is clamped into it.  1 <= A <= PM_MAX_HPRIME, Hprime <= PM_MAX_HPRIME, nblocks <= 8. */
+int pm_sample_active_f64(const int32_t *idx, const int32_t *cand, const double *state_vals, const double *block_values_host,
+                         int64_t N, int64_t M, int64_t H, int64_t Hprime, int64_t K, int64_t single_off, int64_t nblocks,
+                         int64_t multi_off, int64_t S, int64_t A, int32_t *act_idx, double *act_val, void *stream);
+/* GSC: the same list format with the values z | s, y_n ~ N(kappa_s, Lambda_s^-1) of the DRAWN state alone.  idx (N, M) over the
+ * columns [null ; H singletons ; S multi-cause states] (state_masks over the candidate positions as pm_gsc_estep_f64), cand
+ * (N, Hprime), and what the E-step pass was given: scores (N, lds >= H) = Y Sigma^-1 W, G (H, H) = W^T Sigma^-1 W, psi_sq (H,
+ * H), tables (8 H) and s2 (> 0).  E (N, M, lde >= gamma): the standard normals of each draw.  Singleton h: z = kappa_h + E[n,m,0]
+ * / sqrt(lambda_h) from the tables.  Multi-cause state on the candidates a (ascending position, g <= gamma of them): Lambda =
+ * G_aa / s2 + (psi_aa)^-1, kappa = mu_a + Lambda^-1 (scores_a - G_aa mu_a) / s2, z = kappa + L E[n,m,0..g), L the lower Cholesky
+ * factor of Lambda^-1: at most 8 x 8 per (row, sample), one lane each, sums in ascending index.  A matrix that is not positive
+ * definite gives NaN values; a draw of -1 the list of pm_sample_active_f64.  gamma <= 8, gamma <= A <= PM_MAX_HPRIME. */
+int pm_sample_gsc_f64(const int32_t *idx, const int32_t *cand, const uint16_t *state_masks, const double *scores, int64_t lds,
+                      const double *G, const double *psi_sq, const double *tables, double s2, const double *E, int64_t lde,
+                      int64_t N, int64_t M, int64_t H, int64_t Hprime, int64_t S, int64_t gamma, int64_t A, int32_t *act_idx,
+                      double *act_val, void *stream);
+/* out[n ld_row + m ld_sample + d] = mu[d] + sum_j act_val[n,m,j] Wt[act_idx[n,m,j], d], d < D: one fma per entry in ascending
+ * j, starting from mu[d] (NULL: 0); Wt (H, ldw >= D) the transpose of W.  A gather of at most A rows, not a dense product.  A
+ * slot of index -1 adds nothing unless its value is NaN (a draw of -1), which makes the whole output row NaN.  Both output
+ * strides are the caller's (>= D; (M, N, D): ld_row = D, ld_sample = N D).  Any D; A <= PM_MAX_HPRIME. */
+int pm_sample_decode_lin_f64(const int32_t *act_idx, const double *act_val, int64_t A, const double *Wt, int64_t ldw,
+                             const double *mu, int64_t N, int64_t M, int64_t H, int64_t D, double *out, int64_t ld_row,
+                             int64_t ld_sample, void *stream);
+/* MCA (signed_w = 0) / MMCA (1), columns [null ; H one-cause ; S multi-cause] as pm_recon_mca_f64: out[n, m, :] = 0 for the null
+ * state, Wt[h, :] for a one-cause state (Wt (H, D), leading dimension D), Wbar(s) = (sum_{j in s} Wrho[cand[n,j], :])^inv_rho
+ * (signed: sign(t) |t|^inv_rho) for a multi-cause state, the sum in ascending position and the power functions of
+ * pm_recon_mca_f64; NaN for a draw of -1.  Output strides as above.  D <= 1024, Hprime <= PM_MAX_HPRIME. */
+int pm_sample_decode_mca_f64(const int32_t *idx, const int32_t *cand, const uint16_t *state_masks, const double *Wt,
+                             const double *Wrho, double inv_rho, int signed_w, int64_t N, int64_t M, int64_t H, int64_t D,
+                             int64_t Hprime, int64_t S, double *out, int64_t ld_row, int64_t ld_sample, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1273,6 +1273,204 @@ class DeviceCAModel(CAModel):
             self._par = {}
             self._eval_end(saved)
 
+    # ---- posterior draws ----------------------------------------------------------------------------------
+    sample_chunk_bytes = 1 << 26      # bound of the workspace beside the result (indices and active lists of one row chunk)
+    sample_chunk_rows = None          # rows per chunk when set (tests): the draws do not depend on it
+
+    @staticmethod
+    def _sample_check(N, n_samples, uniforms, normals, n_normals=0):
+        """The refusals of ``sample_posterior`` that need no device: ``ValueError`` for n_samples < 1, a wrongly shaped
+        ``uniforms`` / ``normals`` and a host ``uniforms`` with a value outside [0, 1) or NaN.  Returns n_samples as an int."""
+        M = int(n_samples)
+        if M != n_samples or M < 1:
+            raise ValueError("sample_posterior: n_samples must be an integer >= 1, got %r" % (n_samples,))
+        for name, arr, want in (("uniforms", uniforms, (N, M)), ("normals", normals, (N, M, n_normals))):
+            if arr is None:
+                continue
+            t = getattr(arr, "tensor", arr)
+            shape = tuple(t.shape) if hasattr(t, "shape") else np.asarray(t).shape
+            if name == "normals" and not n_normals:
+                continue                     # (only GSC draws z: the other models ignore the argument's values)
+            if shape != want:
+                raise ValueError("sample_posterior: %s has shape %r, expected %r" % (name, shape, want))
+        if uniforms is not None:
+            t = getattr(uniforms, "tensor", uniforms)
+            if not (torch is not None and torch.is_tensor(t) and t.is_cuda):
+                h = t.numpy() if (torch is not None and torch.is_tensor(t)) else np.asarray(t)
+                if h.size and not bool(np.all((h >= 0.0) & (h < 1.0))):
+                    raise ValueError("sample_posterior: uniforms must lie in [0, 1) (a NaN or a value outside it was given)")
+        return M
+
+    def _sample_randoms(self, N, M, seed, uniforms, normals, n_normals):
+        """(U (N, M), E (N, M, n_normals) or None) float64 on the device: the caller's arrays, or ``torch.rand`` and then
+        ``torch.randn`` from ONE generator on the device seeded with ``seed`` (it fills the whole arrays: with ``seed`` alone a
+        row's draws depend on (N, M))."""
+        g = self._gen(seed) if (uniforms is None or (n_normals and normals is None)) else None
+
+        def given(arr):
+            t = getattr(arr, "tensor", arr)
+            if not torch.is_tensor(t):
+                t = torch.from_numpy(np.ascontiguousarray(np.asarray(t), dtype=np.float64))
+            return t.to(device=self.device, dtype=torch.float64).contiguous()
+        U = given(uniforms) if uniforms is not None else \
+            torch.rand((N, M), generator=g, device=self.device, dtype=torch.float64)
+        E = None
+        if n_normals:
+            E = given(normals) if normals is not None else \
+                torch.randn((N, M, n_normals), generator=g, device=self.device, dtype=torch.float64)
+        return U, E
+
+    _sample_n_normals = 0             # standard normals per draw (GSC: gamma, its draw of z)
+
+    def _sample_rows(self, N, M, A):
+        """Rows per chunk: idx (4 bytes) and the active list (12 A bytes) per (row, sample) within ``sample_chunk_bytes``."""
+        if self.sample_chunk_rows:
+            return max(1, int(self.sample_chunk_rows))
+        return max(1, min(N, int(self.sample_chunk_bytes) // (M * (4 + 12 * A))))
+
+    def _sample_states(self, X, K, n0, n, U, M, a=1.0, off=None, floor=0.0, null_col=-1):
+        """pm_sample_states_f64 on rows [n0, n0 + n) of the log-joints ``X`` and of ``U``: idx (n, M) int32."""
+        idx = self._buf("sample_idx", (n, M), torch.int32)
+        ld = X.stride(0) if X.shape[0] > 1 else max(int(X.stride(0)), K)
+        self._call("sample_states", "pm_sample_states_f64", ctypes.c_void_p(X.data_ptr() + 8 * n0 * ld), ld, None,
+                   ctypes.c_double(a), _ptr(off), ctypes.c_double(floor), null_col,
+                   ctypes.c_void_p(U.data_ptr() + 8 * n0 * M), M, n, K, M, _ptr(idx), self._stream())
+        return idx
+
+    def _sample_active(self, idx, cand_rows, n, M, K, A, table_d, S, blocks, soff, moff):
+        """pm_sample_active_f64: (act_idx (n, M, A) int32, act_val (n, M, A))."""
+        ai = self._buf("sample_act_idx", (n, M, A), torch.int32)
+        av = self._buf("sample_act_val", (n, M, A))
+        bv = (ctypes.c_double * 8)(*([float(v) for v in blocks] + [0.0] * (8 - len(blocks))))
+        self._call("sample_active", "pm_sample_active_f64", _ptr(idx), cand_rows if S else None, _ptr(table_d) if S else None, bv,
+                   n, M, self.H, self.Hprime if S else 0, K, soff, len(blocks), moff, S, A, _ptr(ai), _ptr(av), self._stream())
+        return ai, av
+
+    @staticmethod
+    def _sample_scatter(idx, ai, av, H):
+        """The active lists as latent values (M, n, H): a latent held by two positions (TSC) receives both values, a draw of
+        -1 (a NaN row) gives NaN."""
+        n, M, A = ai.shape
+        ii = ai.long()
+        ii = torch.where(ii < 0, torch.full_like(ii, H), ii)
+        buf = torch.zeros((n, M, H + 1), dtype=torch.float64, device=ai.device)
+        buf.scatter_add_(2, ii, av)
+        s = buf[:, :, :H]
+        s[idx < 0] = float("nan")
+        return s.permute(1, 0, 2)
+
+    def _sample(self, model_params, y, mask, N, M, U, latents, E=None):
+        """The (M, N, D) device tensor of ``sample_posterior`` (and with ``latents`` the (M, N, H) one) for the models whose
+        E-step leaves (N, K) log-joints: the E-step of ``reconstruct``, then per row chunk pm_sample_states_f64, the active
+        list and the decode kernel, written in place."""
+        H, D, Hp = self.H, self.D, self.Hprime
+        par = None
+        if mask is not None:
+            out = self._masked_estep(model_params, y, mask)
+            lay, lp, cand, par = out["lay"], out["logpj"], out["cand"], out.get("par")
+        else:
+            lay = self._recon_layout(model_params)
+            mp = lay["params"]
+            data = self.select_Hprimes(mp, {'y': y})
+            lp = self.E_step(LoglikPoint(), mp, data)['logpj'].tensor
+            cand = self._device_candidates(data['candidates'], N)
+        K = lp.shape[1]
+        mca = bool(lay.get("mca"))
+        table, blocks = lay.get("table"), lay["blocks"]
+        if mca:
+            if par is None:
+                par = self._tables_for(lay["params"]['W'], 1.0, self._resident(y))
+            table = self.state_matrix if self.no_states else None
+        S = 0 if table is None else int(table.shape[0])
+        A = max(1, int((np.asarray(table) != 0).sum(axis=1).max())) if S else 1
+        table_d = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float64)).to(self.device) if S else None
+        mu = lay.get("mu")
+        mu_d = torch.from_numpy(np.ascontiguousarray(mu, dtype=np.float64).reshape(-1)).to(self.device) \
+            if (mu is not None and np.any(np.asarray(mu))) else None
+        Wt = par["Wt"] if mca else \
+            torch.from_numpy(np.ascontiguousarray(np.asarray(lay["W"], dtype=np.float64).T)).to(self.device)
+        Ys = torch.empty((M, N, D), dtype=torch.float64, device=self.device)
+        Sl = torch.empty((M, N, H), dtype=torch.float64, device=self.device) if latents else None
+        rows = self._sample_rows(N, M, A)
+        for n0 in range(0, N, rows):
+            n = min(rows, N - n0)
+            idx = self._sample_states(lp, K, n0, n, U, M)
+            cand_rows = ctypes.c_void_p(cand.data_ptr() + 4 * n0 * Hp)
+            out_p = ctypes.c_void_p(Ys.data_ptr() + 8 * n0 * D)
+            if mca:
+                self._call("sample_decode", "pm_sample_decode_mca_f64", _ptr(idx), cand_rows, _ptr(self._masks()), _ptr(Wt),
+                           _ptr(par["Wrho"]), ctypes.c_double(1. / par["rho"]), int(bool(self.signed_w)), n, M, H, D, Hp,
+                           self.no_states, out_p, D, N * D, self._stream())
+            if latents or not mca:
+                ai, av = self._sample_active(idx, cand_rows, n, M, K, A, table_d, S, blocks, lay["soff"], lay["moff"])
+                if not mca:
+                    self._call("sample_decode", "pm_sample_decode_lin_f64", _ptr(ai), _ptr(av), A, _ptr(Wt), D, _ptr(mu_d), n,
+                               M, H, D, out_p, D, N * D, self._stream())
+                if latents:
+                    Sl[:, n0:n0 + n] = self._sample_scatter(idx, ai, av, H)
+        return Ys, Sl
+
+    def sample_posterior(self, model_params, my_data, n_samples=1, seed=None, latents=False, device=False, uniforms=None,
+                         normals=None):
+        """Posterior draws of the noiseless data: ``Ys`` (n_samples, my_N, D) float64 with Ys[m, n] = ybar(s),
+        s ~ q_n(s) -- the states K_n, the weights q_n and the per-state mean ybar(s) are exactly those ``reconstruct``
+        without keywords averages (mu + W s for BSC / DSC / TSC; W_h, the rho-combination at T = 1 or 0 for MCA / MMCA), so
+        the mean of many draws tends to ``reconstruct``'s estimate and their variance to ``variance=True``'s.  Observation
+        noise is NOT added: for a predictive draw the caller adds sigma eps, as V + sigma^2.  ``latents=True`` returns ``(Ys,
+        S)``, S (n_samples, my_N, H) float64 the latent values of each draw (0 / 1, the DSC / TSC value; a TSC latent that two
+        candidate positions hold carries the sum of both).  NumPy arrays, or with ``device=True`` ``DeviceArray`` handles
+        left on the device; no collective.  ``model_params``, the training state and Hprime / gamma stay as they were, the
+        result does not depend on ``deterministic``; the call runs in the evaluation slot.
+
+        Randomness: U = torch.rand((my_N, n_samples)) from a ``torch.Generator`` on the device seeded with ``seed``, or the
+        caller's ``uniforms`` of that shape (NumPy, torch or DeviceArray) -- then the result is a pure function of its
+        inputs: a row's draws depend on that row of the data, the parameters and that row of U alone, with the same bits from
+        both libraries, under a row permutation that permutes U along, in a shard and for every internal chunking.  With
+        ``seed`` alone the draws depend on (my_N, n_samples): the generator fills the whole array, so a shard of the data
+        does not reproduce the rows of the whole call -- pass ``uniforms`` (GSC: and ``normals``) for that.  ``normals`` is
+        GSC's (its draw of z); the other models ignore it.  Draw m of row n is the smallest column k of the row's log-joints with u C < c_k, c the
+        running sum of the weights in pm_sample_states_f64's order: a state of weight 0 is never drawn.
+
+        ``my_data['mask']`` (BSC, MCA, MMCA): the draw comes from the posterior given the observed dimensions
+        and covers all D -- an imputation; whatever an unobserved entry holds changes no bit.  Other models raise
+        ``NotImplementedError`` before any launch.  A NaN in a data row makes that row's draws NaN and no other's.
+
+        Raises ``ValueError`` for n_samples < 1, wrongly shaped ``uniforms`` / ``normals`` and host ``uniforms`` outside [0, 1),
+        ``HipError`` for H' > 16 and for MCA / MMCA with D > 1024 -- all before any launch.  There is no ``exact=``.  Runs
+        the E-step kernels and pm_sample_*.
+
+        GSC: ybar = W_s z with z | s, y_n ~ N(kappa_s, Lambda_s^-1) drawn as kappa_s + L eps (pm_sample_gsc_f64), L the lower
+        Cholesky factor of Lambda_s^-1 with the positions in ascending candidate order and eps the first |s| of the draw's
+        gamma standard normals E[n, m, :] -- ``torch.randn((my_N, n_samples, gamma))`` from the same generator, after U, or the
+        caller's ``normals`` of that shape; the state weights are the E-step's floored ones (pm_recon_gsc_moments2_f64).
+        ``S`` holds s o z."""
+        y = my_data['y']
+        N = int(y.shape[0])
+        nn = int(self._sample_n_normals)
+        M = self._sample_check(N, n_samples, uniforms, normals, nn)
+        mask = my_data.get('mask')
+        if mask is not None:
+            self._masked_admit(y, mask, what="sample_posterior")
+        if self.Hprime > 16:
+            raise _lib.HipError("%s.sample_posterior holds H' <= 16 candidates, got %d" % (type(self).__name__, self.Hprime))
+        if self.D > self._recon_var_max_D:
+            raise _lib.HipError("%s.sample_posterior holds D <= %d (pm_sample_decode_mca_f64), got %d"
+                                % (type(self).__name__, self._recon_var_max_D, self.D))
+        wrap = (lambda t: DeviceArray(t)) if device else (lambda t: t.cpu().numpy())
+        if N == 0:
+            z = lambda c: DeviceArray(torch.empty((M, 0, c), dtype=torch.float64, device=self.device)) if device \
+                else np.empty((M, 0, c))
+            return (z(self.D), z(self.H)) if latents else z(self.D)
+        saved = self._eval_begin()
+        try:
+            self._par, self._rows_gemm = {}, True
+            U, E = self._sample_randoms(N, M, seed, uniforms, normals, nn)
+            Ys, Sl = self._sample(dict(model_params), y, mask, N, M, U, latents, E)
+            return (wrap(Ys), wrap(Sl)) if latents else wrap(Ys)
+        finally:
+            self._par = {}
+            self._eval_end(saved)
+
     # ---- missing values (DESIGN 4.16) -----------------------------------------------------------------------------------
     def _masked_estep(self, model_params, y, mask):
         """Per model: selection and T = 1 E-step of ``y`` over the dimensions its ``mask`` marks as observed (non-zero), run

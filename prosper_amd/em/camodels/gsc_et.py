@@ -592,6 +592,57 @@ class GSC(DeviceCAModel):
                    max(npair, 1), self._stream())
         return self._recon_var_product(m2, p2, cand, model_params['W'], None, Yhat)
 
+    @property
+    def _sample_n_normals(self):
+        return int(self.gamma)
+
+    def _sample(self, model_params, y, mask, N, M, U, latents, E=None):
+        """sample_posterior: the pass of ``reconstruct`` (beta = 1/2, doubled logits) with every state's
+        log-joint written beside it; the state by pm_sample_states_f64 with the E-step's own weights -- exp(lp / 2), floored
+        at DBL_MIN for every state but the null one, not normalised --, z | s, y_n by pm_sample_gsc_f64 from the scores, Gram
+        matrix, psi_sq and tables that pass was given, then the gather of pm_sample_decode_lin_f64 against W^T.  A noise
+        covariance that is not positive definite: every draw NaN, as ``reconstruct``."""
+        H, D, Hp, S, gamma = self.H, self.D, self.Hprime, self.no_states, int(self.gamma)
+        dev = self.device
+        Ys = torch.empty((M, N, D), dtype=torch.float64, device=dev)
+        Sl = torch.empty((M, N, H), dtype=torch.float64, device=dev) if latents else None
+        sig = np.asarray(model_params['sigma_sq'], dtype=np.float64)
+        if (np.linalg.eigvalsh(0.5 * (sig + sig.T)).min() <= 0) if sig.ndim == 2 else not np.all(sig > 0):
+            Ys.fill_(float("nan"))
+            if latents:
+                Sl.fill_(float("nan"))
+            return Ys, Sl
+        self._lpi_scale = 2.0          # (an attribute of the evaluation only: _eval_end restores the model's)
+        res = self._resident(y)
+        K = 1 + H + S
+        lp = self._buf("sample_gsc_lpj", (N, K))
+        cand, _, _, _ = self._run(2.0, model_params, res, None, logpj=lp)
+        par = self._tables_for(model_params, res)
+        scores = self._scores_used
+        Wt = torch.from_numpy(np.ascontiguousarray(np.asarray(model_params['W'], dtype=np.float64).T)).to(dev)
+        zeros = torch.zeros(N, dtype=torch.float64, device=dev)
+        A = max(gamma, 1)
+        rows = self._sample_rows(N, M, A)
+        tiny = 2.2250738585072014e-308
+        for n0 in range(0, N, rows):
+            n = min(rows, N - n0)
+            idx = self._buf("sample_idx", (n, M), torch.int32)
+            self._call("sample_states", "pm_sample_states_f64", ctypes.c_void_p(lp.data_ptr() + 8 * n0 * K), K,
+                       ctypes.c_void_p(zeros.data_ptr() + 8 * n0), ctypes.c_double(0.5), None, ctypes.c_double(tiny), 0,
+                       ctypes.c_void_p(U.data_ptr() + 8 * n0 * M), M, n, K, M, _ptr(idx), self._stream())
+            ai = self._buf("sample_act_idx", (n, M, A), torch.int32)
+            av = self._buf("sample_act_val", (n, M, A))
+            self._call("sample_gsc", "pm_sample_gsc_f64", _ptr(idx), ctypes.c_void_p(cand.data_ptr() + 4 * n0 * Hp),
+                       _ptr(self._masks()), ctypes.c_void_p(scores.data_ptr() + 8 * n0 * scores.stride(0)),
+                       max(int(scores.stride(0)), H), _ptr(par["G"]), _ptr(par["psi_d"]), _ptr(par["tables"]),
+                       ctypes.c_double(par["s2"]), ctypes.c_void_p(E.data_ptr() + 8 * n0 * M * gamma), gamma, n, M, H, Hp, S,
+                       gamma, A, _ptr(ai), _ptr(av), self._stream())
+            self._call("sample_decode", "pm_sample_decode_lin_f64", _ptr(ai), _ptr(av), A, _ptr(Wt), D, None, n, M, H, D,
+                       ctypes.c_void_p(Ys.data_ptr() + 8 * n0 * D), D, N * D, self._stream())
+            if latents:
+                Sl[:, n0:n0 + n] = self._sample_scatter(idx, ai, av, H)
+        return Ys, Sl
+
     def _reconstruct_exact(self, model_params, y, N):
         """reconstruct(exact=True): yhat_n = W E_n[s o z] over all 2^H supports, E_n[s o z] = sum_s q_n(s)
         kappa_s(y_n) by pm_recon_exact_gsc_f64 from the whitened products of ``_loglik_exact`` (scalar, diagonal or full

@@ -63,6 +63,26 @@ class MixtureModel(Model):
         from ...utils.patches import denoise_image
         return denoise_image(self, model_params, image, mask=mask, **kw)
 
+    def sample_posterior(self, model_params, my_data, n_samples=1, seed=None, latents=False, device=False, uniforms=None,
+                         normals=None):
+        """Posterior draws of the noiseless data: ``Ys`` (n_samples, my_N, D) float64, Ys[m, n] = W_h with h ~
+        r_nh, the responsibilities ``reconstruct`` averages with (the proper densities of ``log_likelihood``); the
+        components' own noise is not added.  ``latents=True`` returns ``(Ys, S)``, S (n_samples, my_N, H) one-hot.  NumPy
+        arrays, or ``DeviceArray`` handles with ``device=True``; no collective; ``model_params`` and the training shard are
+        left as they were.
+
+        U = torch.rand((my_N, n_samples)) from a ``torch.Generator`` on the device seeded with ``seed``, or the caller's
+        ``uniforms`` of that shape (NumPy, torch or DeviceArray): then a row's draws depend on that row, the parameters and
+        that row of U alone -- the same bits under a row permutation that permutes U along, in a shard and for every
+        internal chunking.  With ``seed`` alone the draws depend on (my_N, n_samples): the generator fills the whole array.
+        ``normals`` is accepted for the component-analysis models' signature and ignored.  Draw m of row n is the smallest h
+        with u C < c_h, c the running sum of the responsibilities in pm_sample_states_f64's order: a component of weight 0 is
+        never drawn; a NaN data row gives NaN draws and touches no other row.
+
+        Raises ``ValueError`` for n_samples < 1, a wrongly shaped ``uniforms`` and host ``uniforms`` outside [0, 1),
+        ``NotImplementedError`` for ``my_data['mask']`` -- before any launch."""
+        return self._sample_posterior(model_params, my_data, n_samples, seed, latents, device, uniforms, normals)
+
     @tracing.traced
     def generate_data(self, model_params, my_N):
         """Component labels from ``scipy.stats.rv_discrete(values=(arange(H), pies)).rvs(size=my_N)`` (the reference's

@@ -257,6 +257,66 @@ class DeviceMixture(object):
             self.__dict__.update(saved)
             self._eval_slot = slot
 
+    # ---- posterior draws --------------------------------------------------------------------------------
+    sample_chunk_bytes = 1 << 26      # bound of the workspace beside the result (indices and lists of one row chunk)
+    sample_chunk_rows = None          # rows per chunk when set (tests): the draws do not depend on it
+
+    def _sample_posterior(self, model_params, my_data, n_samples, seed, latents, device, uniforms, normals):
+        """``MixtureModel.sample_posterior``: the scores of ``reconstruct`` (``_recon_scores``), then per row chunk
+        pm_sample_states_f64 (h ~ softmax(a X + o)), pm_sample_active_f64 (one block of value 1, no table) and
+        pm_sample_decode_lin_f64 against W^T, written in place."""
+        from ..camodels._device import DeviceCAModel
+        y = my_data['y']
+        N, H, D = int(y.shape[0]), self.H, self.D
+        M = DeviceCAModel._sample_check(N, n_samples, uniforms, None)
+        self._refuse_mask(my_data)
+        wrap = (lambda t: DeviceArray(t)) if device else (lambda t: t.cpu().numpy())
+        if N == 0:
+            z = lambda c: DeviceArray(torch.empty((M, 0, c), dtype=torch.float64, device=self.device)) if device \
+                else np.empty((M, 0, c))
+            return (z(D), z(H)) if latents else z(D)
+        saved = dict(self.__dict__)
+        slot = saved.get("_eval_slot") or {"_data": {}, "_ws": {}}
+        self._data, self._ws = slot["_data"], slot["_ws"]
+        try:
+            res = self._resident(y)
+            X, a, off_d = self._recon_scores(dict(model_params), res)
+            if uniforms is None:
+                g = torch.Generator(device=self.device)
+                g.manual_seed(int(seed)) if seed is not None else g.seed()
+                U = torch.rand((N, M), generator=g, device=self.device, dtype=torch.float64)
+            else:
+                U = getattr(uniforms, "tensor", uniforms)
+                if not torch.is_tensor(U):
+                    U = torch.from_numpy(np.ascontiguousarray(np.asarray(U), dtype=np.float64))
+                U = U.to(device=self.device, dtype=torch.float64).contiguous()
+            Wt = self._dev(np.asarray(model_params['W'], dtype=np.float64).T)
+            Ys = torch.empty((M, N, D), dtype=torch.float64, device=self.device)
+            Sl = torch.empty((M, N, H), dtype=torch.float64, device=self.device) if latents else None
+            one = (ctypes.c_double * 8)(1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+            st = self._stream()
+            rows = max(1, int(self.sample_chunk_rows)) if self.sample_chunk_rows else \
+                max(1, min(N, int(self.sample_chunk_bytes) // (M * 16)))
+            for n0 in range(0, N, rows):
+                n = min(rows, N - n0)
+                idx = torch.empty((n, M), dtype=torch.int32, device=self.device)
+                ai = torch.empty((n, M, 1), dtype=torch.int32, device=self.device)
+                av = torch.empty((n, M, 1), dtype=torch.float64, device=self.device)
+                _lib.call("pm_sample_states_f64", ctypes.c_void_p(X.data_ptr() + 8 * n0 * H), H, None, ctypes.c_double(a),
+                          _ptr(off_d), ctypes.c_double(0.0), -1, ctypes.c_void_p(U.data_ptr() + 8 * n0 * M), M, n, H, M,
+                          _ptr(idx), st)
+                _lib.call("pm_sample_active_f64", _ptr(idx), None, None, one, n, M, H, 0, H, 0, 1, 0, 0, 1, _ptr(ai), _ptr(av), st)
+                _lib.call("pm_sample_decode_lin_f64", _ptr(ai), _ptr(av), 1, _ptr(Wt), D, None, n, M, H, D,
+                          ctypes.c_void_p(Ys.data_ptr() + 8 * n0 * D), D, N * D, st)
+                if latents:
+                    Sl[:, n0:n0 + n] = DeviceCAModel._sample_scatter(idx, ai, av, H)
+            return (wrap(Ys), wrap(Sl)) if latents else wrap(Ys)
+        finally:
+            slot = {"_data": self._data, "_ws": self._ws}
+            self.__dict__.clear()
+            self.__dict__.update(saved)
+            self._eval_slot = slot
+
     # ---- E-step -------------------------------------------------------------------------------------------------------
     def _full_factors(self, sig):
         """The full covariances (H, D, D) factored on the device (pm_mix_chol_f64): returns (B, mode, logdet) for
