@@ -11,24 +11,21 @@
 // R (ranges per tile) depends on N and the state count alone, the ranges are fixed slices of the state index space, and
 // nothing is added by atomics: the result is a function of the input bits (every run, both library builds).  States are decoded from their
 // index; every per-state quantity is recomputed directly from its digits (no incremental updates), so the accuracy does
-// not depend on how far a range reaches.
+// not depend on how far a range reaches.  What recon_exact.hip must form the same way -- the log-sum-exp, the bounds, the state
+// count and its L / CH split, MCA's Wbar_d(s), GSC's staging and per-support factorisation -- lives in pm_exact.h.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <stdint.h>
 
 #include "prosper_hip.h"
+#include "pm_exact.h"
 
 namespace {
 
-constexpr int EX_THREADS = 256;
+constexpr int EX_THREADS = PMX_THREADS;
 constexpr int64_t EX_BLOCKS = 4096;          // 16 workgroups per CU on 256 CUs, split between tiles and ranges
 constexpr int64_t EX_MAX_RANGES = 4096;
-constexpr uint64_t EX_MAX_STATES = 1ull << 32;
-constexpr int EX_LIN_MAX_K = 8;
-constexpr int EX_MAX_H = 32;
-constexpr int EX_GSC_MAX_H = 16;
-constexpr int EX_GSC_TN = 64;                // GSC: one lane per datapoint of the tile
 constexpr int EX_MCA_TN = 4;
 
 int ex_lin_tn(int64_t N) { return N >= 64 ? 8 : 1; }
@@ -57,7 +54,7 @@ constexpr uint64_t EX_GSC_MIN_STATES = 32;     // supports per range at least: 8
 
 int64_t ex_part_len(int64_t N) {
     int64_t m = ex_ranges(N, ex_lin_tn(N));
-    const int64_t a = ex_ranges(N, ex_mca_tn(N)), b = ex_ranges(N, EX_GSC_TN);
+    const int64_t a = ex_ranges(N, ex_mca_tn(N)), b = ex_ranges(N, PMX_GSC_TN);
     if (a > m) m = a;
     if (b > m) m = b;
     return 2 * N * m;
@@ -77,35 +74,6 @@ ExWork ex_work(double *work, int64_t N, int64_t H) {
     return w;
 }
 
-// The online log-sum-exp step.  A -inf term (a state of zero prior) changes nothing and never meets another -inf in a
-// difference; a NaN term makes the sum NaN.
-__device__ __forceinline__ void lse_add(double &m, double &s, double z) {
-    if (z == -INFINITY) return;
-    const double d = z - m;                    // +inf while m is still -inf
-    const double e = exp(-fabs(d));
-    if (d > 0.0) {
-        s = s * e + 1.0;
-        m = z;
-    } else {
-        s += e;                                // NaN d: s becomes NaN
-    }
-}
-
-// (m, s) += (m2, s2)
-__device__ __forceinline__ void lse_merge(double &m, double &s, double m2, double s2) {
-    if (s2 != s2) {
-        s = s2;
-        return;
-    }
-    if (m2 == -INFINITY) return;
-    if (m2 > m) {
-        s = s * exp(m - m2) + s2;
-        m = m2;
-    } else {
-        s += s2 * exp(m2 - m);
-    }
-}
-
 // With x_n = y_n - ymu (ymu NULL: 0): B[n,h] = sum_d x_nd P[d,h] (h < H); q[n] = sum_d wdiag_d x_nd^2 (wdiag NULL: 1), or
 // |Lw x_n|^2 with Lw lower (D x D)
 __global__ void __launch_bounds__(EX_THREADS) ex_prep_kernel(const double *__restrict__ Y, int64_t ldy,
@@ -120,8 +88,7 @@ __global__ void __launch_bounds__(EX_THREADS) ex_prep_kernel(const double *__res
     const double *y = Y + n * ldy;
     double acc = 0.0;
     if (P && h < H) {
-        for (int64_t d = 0; d < D; ++d) acc = fma(y[d] - (ymu ? ymu[d] : 0.0), P[d * H + h], acc);
-        B[n * H + h] = acc;
+        B[n * H + h] = pmx_prep_dot(y, ymu, D, P, H, h);
         return;
     }
     if (Lw) {
@@ -148,14 +115,13 @@ __global__ void __launch_bounds__(EX_THREADS) ex_combine_kernel(const double *__
     const int64_t n = (int64_t)blockIdx.x * (EX_THREADS / 64) + (threadIdx.x >> 6);
     if (n >= N) return;                        // (wave-uniform)
     double m = -INFINITY, s = 0.0;
-    for (int64_t r = lane; r < R; r += 64) lse_merge(m, s, part[2 * (r * N + n)], part[2 * (r * N + n) + 1]);
+    for (int64_t r = lane; r < R; r += 64) pmx_lse_merge(m, s, part[2 * (r * N + n)], part[2 * (r * N + n) + 1]);
     for (int o = 32; o > 0; o >>= 1) {
         const double m2 = __shfl_down(m, o), s2 = __shfl_down(s, o);
-        if (lane < o) lse_merge(m, s, m2, s2);
+        if (lane < o) pmx_lse_merge(m, s, m2, s2);
     }
     if (lane == 0) {
-        const double v = (s != s) ? (double)NAN : (m == -INFINITY ? -INFINITY : m + log(s));
-        rows[n] = v + cst + qcoef * q[n];
+        rows[n] = pmx_lse_value(m, s) + cst + qcoef * q[n];
     }
 }
 
@@ -192,7 +158,7 @@ __device__ void block_partials(const double (&m)[TN], const double (&s)[TN], dou
 #pragma unroll
             for (int i = 0; i < TN; ++i) {
                 double mm = red[(2 * i) * EX_THREADS + t], ss = red[(2 * i + 1) * EX_THREADS + t];
-                lse_merge(mm, ss, red[(2 * i) * EX_THREADS + t + o], red[(2 * i + 1) * EX_THREADS + t + o]);
+                pmx_lse_merge(mm, ss, red[(2 * i) * EX_THREADS + t + o], red[(2 * i + 1) * EX_THREADS + t + o]);
                 red[(2 * i) * EX_THREADS + t] = mm;
                 red[(2 * i + 1) * EX_THREADS + t] = ss;
             }
@@ -207,16 +173,8 @@ __device__ void block_partials(const double (&m)[TN], const double (&s)[TN], dou
 }
 
 // ---- linear models: BSC, TSC, DSC ----------------------------------------------------------------------------------------
-// log p(s, y_n) = sum_h logp[h, k_h] - 1/2 s^T G s + s^T B_n + (row constant), s_h = values[k_h], G = W^T W / sigma^2,
-// B_n = W^T y_n / sigma^2.  The state index is sum_h k_h K^h.  Its L low digits (lo, CH = K^L states) are fixed per thread;
-// a workgroup walks chunks of fixed high digits (hi).  With s = s_lo + s_hi:
-//   l(s) = [prior_lo - 1/2 s_lo^T G_ll s_lo]          (per lo, once per workgroup, in registers)
-//        + [prior_hi - 1/2 s_hi^T G_hh s_hi]          (per chunk, shared)
-//        - s_lo^T (G_lh s_hi)                          (per chunk a table g[h][k] = values[k] (G_lh s_hi)_h, L lookups)
-//   s^T B_n = s_lo^T B_n,lo (per lo and datapoint, registers) + s_hi^T B_n,hi (per chunk and datapoint, shared)
-// so a (state, datapoint) costs two adds and one exp.
-constexpr int LIN_MAX_J = 4;              // lo states per thread (CH <= 1024)
-
+// l(s) in the decomposition pm_exact.h describes (lo digits per thread, chunks of hi digits); a workgroup walks the chunks
+// of its range for the TN datapoints of its tile.
 struct LinArgs {
     const double *G;        // H x H
     const double *logp;     // H x K
@@ -235,12 +193,12 @@ __global__ void __launch_bounds__(EX_THREADS) ex_lin_kernel(LinArgs a) {
     double *sG = lds;                          // H*H
     double *sLogp = sG + H * H;                // H*K
     double *sVal = sLogp + H * K;              // 8
-    double *sB = sVal + EX_LIN_MAX_K;          // TN*H
+    double *sB = sVal + PMX_LIN_MAX_K;          // TN*H
     double *sGv = sB + TN * H;                 // L*K   - values[k] (G_lh s_hi)_h
-    double *sHv = sGv + EX_MAX_H * EX_LIN_MAX_K;  // NH: prior_hi + (-1/2 s_i (G_hh s_hi)_i) per hi latent
-    double *sBh = sHv + EX_MAX_H;              // TN
+    double *sHv = sGv + PMX_MAX_H * PMX_LIN_MAX_K;  // NH: prior_hi + (-1/2 s_i (G_hh s_hi)_i) per hi latent
+    double *sBh = sHv + PMX_MAX_H;              // TN
     int *sDig = (int *)(sBh + TN);             // H-L hi digits of the current chunk
-    double *red = sBh + TN + EX_MAX_H;         // 2*TN*256 (block_partials), overlaps nothing used after the loop
+    double *red = sBh + TN + PMX_MAX_H;         // 2*TN*256 (block_partials), overlaps nothing used after the loop
 
     const int64_t R = a.R, tile = blockIdx.x / R, r = blockIdx.x % R, n0 = tile * TN;
     for (int i = threadIdx.x; i < H * H; i += EX_THREADS) sG[i] = a.G[i];
@@ -261,10 +219,10 @@ __global__ void __launch_bounds__(EX_THREADS) ex_lin_kernel(LinArgs a) {
     __syncthreads();
 
     // per lo state of this thread: its packed digits (3 bits each), prior_lo - 1/2 s_lo^T G_ll s_lo and s_lo^T B_n,lo
-    uint32_t code[LIN_MAX_J];
-    double plo[LIN_MAX_J], blo[LIN_MAX_J][TN];
+    uint32_t code[PMX_LIN_MAX_J];
+    double plo[PMX_LIN_MAX_J], blo[PMX_LIN_MAX_J][TN];
 #pragma unroll
-    for (int j = 0; j < LIN_MAX_J; ++j) {
+    for (int j = 0; j < PMX_LIN_MAX_J; ++j) {
         const int lo = threadIdx.x + j * EX_THREADS;
         code[j] = 0;
         plo[j] = -INFINITY;
@@ -311,8 +269,8 @@ __global__ void __launch_bounds__(EX_THREADS) ex_lin_kernel(LinArgs a) {
             if (si != 0.0)
                 for (int l = 0; l < NH; ++l) g = fma(sG[t * H + L + l], sVal[sDig[l]], g);
             sHv[i] = sLogp[t * K + sDig[i]] - 0.5 * si * g;
-        } else if (t >= EX_MAX_H && t < EX_MAX_H + TN) {  // s_hi^T B_n,hi
-            const int i = t - EX_MAX_H;
+        } else if (t >= PMX_MAX_H && t < PMX_MAX_H + TN) {  // s_hi^T B_n,hi
+            const int i = t - PMX_MAX_H;
             double b = 0.0;
             for (int l = 0; l < NH; ++l) b = fma(sVal[sDig[l]], sB[i * H + L + l], b);
             sBh[i] = b;
@@ -324,13 +282,13 @@ __global__ void __launch_bounds__(EX_THREADS) ex_lin_kernel(LinArgs a) {
 #pragma unroll
         for (int i = 0; i < TN; ++i) bh[i] = sBh[i];
 #pragma unroll
-        for (int j = 0; j < LIN_MAX_J; ++j) {
+        for (int j = 0; j < PMX_LIN_MAX_J; ++j) {
             if (threadIdx.x + j * EX_THREADS >= (unsigned)CH) break;
             double cross = 0.0;
             for (int h = 0; h < L; ++h) cross += sGv[h * K + ((code[j] >> (3 * h)) & 7)];
             const double l = (plo[j] + lhi) + cross;
 #pragma unroll
-            for (int i = 0; i < TN; ++i) lse_add(m[i], s[i], l + (blo[j][i] + bh[i]));
+            for (int i = 0; i < TN; ++i) pmx_lse_add(m[i], s[i], l + (blo[j][i] + bh[i]));
         }
         if (threadIdx.x == 0) {                             // odometer: the next chunk's hi digits
             for (int i = 0; i < NH; ++i) {
@@ -344,8 +302,8 @@ __global__ void __launch_bounds__(EX_THREADS) ex_lin_kernel(LinArgs a) {
 }
 
 // ---- MCA / MMCA ----------------------------------------------------------------------------------------------------------
-// log p(s, y_n) = |s| lp1 + (H - |s|) lp0 + inv_s2 (y_n^T Wbar(s) - 1/2 |Wbar(s)|^2) + (row constant), Wbar_d(s) =
-// (sum_{h in s} Wrho[h,d])^(1/rho) (signed: sign(t) |t|^(1/rho)), Wbar(0) = 0; the state index is the bit mask of s.
+// log p(s, y_n) = |s| lp1 + (H - |s|) lp0 + inv_s2 (y_n^T Wbar(s) - 1/2 |Wbar(s)|^2) + (row constant), Wbar_d(s) from
+// pmx_mca_wbar (pm_exact.h); the state index is the bit mask of s.
 // Every thread owns the states r0 + t, r0 + t + 256, ... of the workgroup's range and forms Wbar(s) one dimension at a time.
 struct McaArgs {
     const double *Y;
@@ -381,29 +339,21 @@ __global__ void __launch_bounds__(EX_THREADS) ex_mca_kernel(McaArgs a) {
         for (int i = 0; i < TN; ++i) dot[i] = 0.0;
         if (st) {
             for (int64_t d = 0; d < a.D; ++d) {
-                double t = 0.0;
-                for (uint64_t b = st; b; b &= b - 1) t += a.Wrho[(int64_t)__builtin_ctzll(b) * a.D + d];
-                const double w = a.signed_w ? copysign(pow(fabs(t), a.inv_rho), t) : pow(t, a.inv_rho);
+                const double w = pmx_mca_wbar(a.Wrho, a.D, d, st, a.inv_rho, a.signed_w);
                 nrm = fma(w, w, nrm);
 #pragma unroll
                 for (int i = 0; i < TN; ++i) dot[i] = fma(yrow[i][d], w, dot[i]);
             }
         }
 #pragma unroll
-        for (int i = 0; i < TN; ++i) lse_add(m[i], s[i], lp + a.inv_s2 * (dot[i] - 0.5 * nrm));
+        for (int i = 0; i < TN; ++i) pmx_lse_add(m[i], s[i], lp + a.inv_s2 * (dot[i] - 0.5 * nrm));
     }
     block_partials<TN>(m, s, red, n0, a.N, r, a.part);
 }
 
 // ---- GSC -----------------------------------------------------------------------------------------------------------------
-// Given the support s (k latents), y ~ N(W_s mu_s, C_s), C_s = Sigma + W_s Psi_s W_s^T.  With Psi_s = Lp Lp^T,
-// M = W^T Sigma^-1 W, K_s = I + Lp^T M_ss Lp = Lk Lk^T and A_s = Lk^-1 Lp^T (determinant lemma and Woodbury):
-//   log det C_s = log det Sigma + 2 sum log diag Lk,   r^T C_s^-1 r = r^T Sigma^-1 r - |A_s beta|^2,
-//   beta = W_s^T Sigma^-1 r = u_n,s - M_ss mu_s  (u_n = W^T Sigma^-1 y_n, the rows of B),
-//   r^T Sigma^-1 r = q_n - 2 mu_s^T u_n,s + mu_s^T M_ss mu_s.
-// So log p(s, y_n) = kappa_s + mu_s^T u_n,s + 1/2 |A_s (u_n,s - m_s)|^2 + (row constant), m_s = M_ss mu_s and
-// kappa_s = log prior(s) - sum log diag Lk - 1/2 mu_s^T m_s.  A wavefront factors one support at a time in its own LDS
-// (k <= 16), then every lane -- one datapoint of the tile -- applies it.
+// l(s) = kappa_s + mu_s^T u_n,s + 1/2 |A_s (u_n,s - m_s)|^2 (pm_exact.h).  A wavefront factors one support at a time in its
+// own LDS (k <= 16), then every lane -- one datapoint of the tile -- applies it.
 struct GscArgs {
     const double *M, *Psi, *mu, *logp;   // H x H, H x H, H, H x 2 (log(1 - pi_h), log pi_h)
     const double *B;                     // N x H
@@ -413,118 +363,37 @@ struct GscArgs {
     int H;
 };
 
-constexpr int GS = EX_GSC_MAX_H;
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// In-place lower Cholesky factor of the k x k matrix X (row stride GS) by one wavefront; the upper triangle is left alone.
-__device__ void wave_cholesky(double *X, int k, int lane) {
-    for (int j = 0; j < k; ++j) {
-        const double d = sqrt(X[j * GS + j]);
-        wave_sync();
-        for (int i = j + 1 + lane; i < k; i += 64) X[i * GS + j] /= d;
-        if (lane == 0) X[j * GS + j] = d;
-        wave_sync();
-        const int n = k - j - 1;
-        for (int e = lane; e < n * n; e += 64) {
-            const int i = j + 1 + e / n, l = j + 1 + e % n;
-            if (l <= i) X[i * GS + l] -= X[i * GS + j] * X[l * GS + j];
-        }
-        wave_sync();
-    }
-}
-
 __global__ void __launch_bounds__(EX_THREADS) ex_gsc_kernel(GscArgs a) {
     constexpr int WAVES = EX_THREADS / 64;
-    __shared__ double sM[GS * GS], sPsi[GS * GS], sMu[GS], sLp[2 * GS];
-    __shared__ double sU[EX_GSC_TN * GS];
-    __shared__ double sX[WAVES][3][GS * GS];     // Lp | T, then A | Lk
-    __shared__ double sV[WAVES][GS];             // m_s
-    __shared__ int sIdx[WAVES][GS];              // the support's latents, ascending
+    __shared__ double sM[PMX_GS * PMX_GS], sPsi[PMX_GS * PMX_GS], sMu[PMX_GS], sLp[2 * PMX_GS];
+    __shared__ double sU[PMX_GSC_TN * PMX_GS];
+    __shared__ double sX[WAVES][3][PMX_GS * PMX_GS];     // Lp | T, then A | Lk
+    __shared__ double sV[WAVES][PMX_GS];             // m_s
+    __shared__ int sIdx[WAVES][PMX_GS];              // the support's latents, ascending
     __shared__ double red[2][WAVES][64];
     const int H = a.H, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t R = a.R, tile = blockIdx.x / R, r = blockIdx.x % R, n0 = tile * EX_GSC_TN;
-    for (int i = threadIdx.x; i < H * H; i += EX_THREADS) {
-        sM[(i / H) * GS + i % H] = a.M[i];
-        sPsi[(i / H) * GS + i % H] = a.Psi[i];
-    }
-    if ((int)threadIdx.x < H) {
-        sMu[threadIdx.x] = a.mu[threadIdx.x];
-        sLp[2 * threadIdx.x] = a.logp[2 * threadIdx.x];
-        sLp[2 * threadIdx.x + 1] = a.logp[2 * threadIdx.x + 1];
-    }
-    for (int i = threadIdx.x; i < EX_GSC_TN * H; i += EX_THREADS) {
-        const int64_t n = n0 + i / H;
-        sU[(i / H) * GS + i % H] = n < a.N ? a.B[n * H + i % H] : 0.0;
-    }
+    const int64_t R = a.R, tile = blockIdx.x / R, r = blockIdx.x % R, n0 = tile * PMX_GSC_TN;
+    pmx_gsc_stage(sM, sPsi, sMu, sLp, sU, a.M, a.Psi, a.mu, a.logp, a.B, n0, a.N, H);
     __syncthreads();
     const uint64_t s0 = a.nstates * (uint64_t)r / (uint64_t)R, s1 = a.nstates * (uint64_t)(r + 1) / (uint64_t)R;
     double *Lp = sX[w][0], *T = sX[w][1], *X = sX[w][2];
     double *mv = sV[w];
     const int *idx = sIdx[w];
-    const double *u = sU + lane * GS;
+    const double *u = sU + lane * PMX_GS;
     double m = -INFINITY, s = 0.0;
     for (uint64_t st = s0 + w; st < s1; st += WAVES) {
         const int k = __popcll(st);
-        double lp = 0.0;
-        for (int h = 0; h < H; ++h) lp += sLp[2 * h + (int)((st >> h) & 1)];
+        const double lp = pmx_gsc_prior(sLp, st, H);
         if (lp == -INFINITY) continue;
         if (lane < H && ((st >> lane) & 1)) sIdx[w][__popcll(st & ((1ull << lane) - 1))] = lane;
-        wave_sync();
+        pm_wave_sync();
         double kappa = lp, lin = 0.0, quad = 0.0;
         if (k) {
-            // Lp = chol(Psi_ss)
-            for (int e = lane; e < k * k; e += 64) Lp[(e / k) * GS + e % k] = sPsi[idx[e / k] * GS + idx[e % k]];
-            wave_sync();
-            wave_cholesky(Lp, k, lane);
-            // T = M_ss Lp (Lp lower: rows p >= l)
-            for (int e = lane; e < k * k; e += 64) {
-                const int i = e / k, l = e % k;
-                double t = 0.0;
-                for (int p = l; p < k; ++p) t = fma(sM[idx[i] * GS + idx[p]], Lp[p * GS + l], t);
-                T[i * GS + l] = t;
-            }
-            // m_s = M_ss mu_s
-            if (lane < k) {
-                double t = 0.0;
-                for (int p = 0; p < k; ++p) t = fma(sM[idx[lane] * GS + idx[p]], sMu[idx[p]], t);
-                mv[lane] = t;
-            }
-            wave_sync();
-            // X = I + Lp^T T (lower triangle)
-            for (int e = lane; e < k * k; e += 64) {
-                const int i = e / k, l = e % k;
-                if (l > i) continue;
-                double t = (i == l) ? 1.0 : 0.0;
-                for (int p = i; p < k; ++p) t = fma(Lp[p * GS + i], T[p * GS + l], t);
-                X[i * GS + l] = t;
-            }
-            wave_sync();
-            wave_cholesky(X, k, lane);
-            // A = Lk^-1 Lp^T, column l by lane l (into T)
-            if (lane < k) {
-                const int l = lane;
-                for (int i = 0; i < k; ++i) {
-                    double t = (i <= l) ? Lp[l * GS + i] : 0.0;
-                    for (int p = 0; p < i; ++p) t = fma(-X[i * GS + p], T[p * GS + l], t);
-                    T[i * GS + l] = t / X[i * GS + i];
-                }
-            }
-            wave_sync();
-            double ld = 0.0, mm = 0.0;
-            for (int i = 0; i < k; ++i) {
-                ld += log(X[i * GS + i]);
-                mm = fma(sMu[idx[i]], mv[i], mm);
-            }
-            kappa = lp - ld - 0.5 * mm;
+            kappa = pmx_gsc_factor_support(sM, sPsi, sMu, idx, k, lane, lp, Lp, T, X, mv);
             // per datapoint: beta = u_s - m_s, z = A beta
-            double beta[GS];
+            double beta[PMX_GS];
 #pragma unroll
-            for (int i = 0; i < GS; ++i) {
+            for (int i = 0; i < PMX_GS; ++i) {
                 if (i < k) {
                     const double ui = u[idx[i]];
                     lin = fma(sMu[idx[i]], ui, lin);
@@ -532,25 +401,25 @@ __global__ void __launch_bounds__(EX_THREADS) ex_gsc_kernel(GscArgs a) {
                 }
             }
 #pragma unroll
-            for (int i = 0; i < GS; ++i) {
+            for (int i = 0; i < PMX_GS; ++i) {
                 if (i < k) {
                     double z = 0.0;
 #pragma unroll
-                    for (int l = 0; l < GS; ++l)
-                        if (l < k) z = fma(T[i * GS + l], beta[l], z);
+                    for (int l = 0; l < PMX_GS; ++l)
+                        if (l < k) z = fma(T[i * PMX_GS + l], beta[l], z);
                     quad = fma(z, z, quad);
                 }
             }
-            wave_sync();                          // (the next support overwrites this wave's LDS)
+            pm_wave_sync();                          // (the next support overwrites this wave's LDS)
         }
-        lse_add(m, s, kappa + lin + 0.5 * quad);
+        pmx_lse_add(m, s, kappa + lin + 0.5 * quad);
     }
     red[0][w][lane] = m;
     red[1][w][lane] = s;
     __syncthreads();
     if (w == 0 && n0 + lane < a.N) {
         double mm = -INFINITY, ss = 0.0;
-        for (int v = 0; v < WAVES; ++v) lse_merge(mm, ss, red[0][v][lane], red[1][v][lane]);
+        for (int v = 0; v < WAVES; ++v) pmx_lse_merge(mm, ss, red[0][v][lane], red[1][v][lane]);
         const int64_t n = n0 + lane;
         a.part[2 * (r * a.N + n)] = mm;
         a.part[2 * (r * a.N + n) + 1] = ss;
@@ -580,16 +449,6 @@ int ex_finish(int64_t N, int64_t R, double cst, double qcoef, const ExWork &w, d
     return (int)hipGetLastError();
 }
 
-// K^H, or 0 past the bound
-uint64_t ex_state_count(int64_t K, int64_t H) {
-    uint64_t c = 1;
-    for (int64_t h = 0; h < H; ++h) {
-        c *= (uint64_t)K;
-        if (c > EX_MAX_STATES) return 0;
-    }
-    return c;
-}
-
 }  // namespace
 
 extern "C" int64_t pm_loglik_exact_work_len(int64_t N, int64_t H) {
@@ -602,19 +461,16 @@ extern "C" int pm_loglik_exact_lin_f64(const double *Y, int64_t ldy, const doubl
                                        const double *logp, const double *values, int64_t K, double cst, double qcoef,
                                        int64_t N, int64_t D, int64_t H, double *rows_out, double *work, double *total,
                                        void *stream) {
-    if (N < 0 || D < 1 || H < 1 || K < 2 || K > EX_LIN_MAX_K || ldy < D || !P || !G || !logp || !values || !work || !total ||
+    if (N < 0 || D < 1 || H < 1 || K < 2 || K > PMX_LIN_MAX_K || ldy < D || !P || !G || !logp || !values || !work || !total ||
         (N > 0 && !Y))
         return PM_EINVAL;
-    const uint64_t S = ex_state_count(K, H);
-    if (H > EX_MAX_H || S == 0) return PM_ERANGE;
+    const uint64_t S = pmx_state_count(K, H);
+    if (H > PMX_MAX_H || S == 0) return PM_ERANGE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const ExWork w = ex_work(work, N, H);
     const int tn = ex_lin_tn(N);
-    int L = 0, CH = 1;
-    while (L < H && CH * K <= LIN_MAX_J * EX_THREADS) {
-        CH *= (int)K;
-        ++L;
-    }
+    int L, CH;
+    pmx_lin_split(K, H, L, CH);
     const uint64_t nchunks = S / (uint64_t)CH;
     const int64_t R = ex_ranges_for(N, tn, nchunks);
     if (N > 0) {
@@ -633,8 +489,8 @@ extern "C" int pm_loglik_exact_lin_f64(const double *Y, int64_t ldy, const doubl
         a.L = L;
         a.CH = CH;
         a.nchunks = nchunks;
-        const size_t lds = sizeof(double) * ((size_t)H * H + H * K + EX_LIN_MAX_K + (size_t)tn * H + EX_MAX_H * EX_LIN_MAX_K +
-                                             EX_MAX_H + tn + EX_MAX_H + 2 * (size_t)tn * EX_THREADS);
+        const size_t lds = sizeof(double) * ((size_t)H * H + H * K + PMX_LIN_MAX_K + (size_t)tn * H + PMX_MAX_H * PMX_LIN_MAX_K +
+                                             PMX_MAX_H + tn + PMX_MAX_H + 2 * (size_t)tn * EX_THREADS);
         const dim3 grid((unsigned)(ex_tiles(N, tn) * R));
         if (tn == 8)
             hipLaunchKernelGGL(ex_lin_kernel<8>, grid, dim3(EX_THREADS), lds, st, a);
@@ -650,7 +506,7 @@ extern "C" int pm_loglik_exact_mca_f64(const double *Y, int64_t ldy, const doubl
                                        double lp1, double lp0, double inv_s2, double cst, int64_t N, int64_t D, int64_t H,
                                        double *rows_out, double *work, double *total, void *stream) {
     if (N < 0 || D < 1 || H < 1 || ldy < D || !Wrho || !work || !total || (N > 0 && !Y)) return PM_EINVAL;
-    if (H > EX_MAX_H) return PM_ERANGE;
+    if (H > PMX_MAX_H) return PM_ERANGE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const ExWork w = ex_work(work, N, H);
     const int tn = ex_mca_tn(N);
@@ -691,10 +547,10 @@ extern "C" int pm_loglik_exact_gsc_f64(const double *Y, int64_t ldy, const doubl
     if (N < 0 || D < 1 || H < 1 || ldy < D || !P || !M || !Psi || !mu || !logp || !work || !total || (N > 0 && !Y) ||
         (wdiag && Lw))
         return PM_EINVAL;
-    if (H > EX_GSC_MAX_H) return PM_ERANGE;
+    if (H > PMX_GSC_MAX_H) return PM_ERANGE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const ExWork w = ex_work(work, N, H);
-    const int64_t R = ex_ranges_for(N, EX_GSC_TN, ((1ull << H) + EX_GSC_MIN_STATES - 1) / EX_GSC_MIN_STATES);
+    const int64_t R = ex_ranges_for(N, PMX_GSC_TN, ((1ull << H) + EX_GSC_MIN_STATES - 1) / EX_GSC_MIN_STATES);
     if (N > 0) {
         int err = ex_prep(Y, ldy, nullptr, N, D, P, H, wdiag, Lw, w, st);
         if (err) return err;
@@ -709,7 +565,7 @@ extern "C" int pm_loglik_exact_gsc_f64(const double *Y, int64_t ldy, const doubl
         a.R = R;
         a.nstates = 1ull << H;
         a.H = (int)H;
-        hipLaunchKernelGGL(ex_gsc_kernel, dim3((unsigned)(ex_tiles(N, EX_GSC_TN) * R)), dim3(EX_THREADS), 0, st, a);
+        hipLaunchKernelGGL(ex_gsc_kernel, dim3((unsigned)(ex_tiles(N, PMX_GSC_TN) * R)), dim3(EX_THREADS), 0, st, a);
         err = (int)hipGetLastError();
         if (err) return err;
     }

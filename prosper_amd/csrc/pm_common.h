@@ -89,6 +89,41 @@ __device__ __forceinline__ double pm_wave_max(double v) {
     return v;
 }
 
+// The lanes of ONE wavefront hand values to each other through their own LDS region: release / barrier / acquire at wavefront
+// scope orders the accesses for the compiler and the hardware without a workgroup barrier (the wavefronts of a workgroup
+// walk different rows or supports).
+__device__ __forceinline__ void pm_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// log sum_k exp(a x_k + o_k) of one row by a maximum pass and a sum pass (as rows_lse_kernel), the row LSE of every posterior
+// read-out (reconstruct(), its variance, sample_posterior()): NaN for a NaN entry, the maximum itself when it is infinite.
+// Wave-uniform.
+__device__ __forceinline__ double pm_row_lse(const double *__restrict__ x, int K, double a, const double *__restrict__ off,
+                                             int lane) {
+    double m = -INFINITY;
+    int bad = 0;
+    for (int k = lane; k < K; k += 64) {
+        const double z = a * x[k] + (off ? off[k] : 0.0);
+        bad |= (z != z);
+        m = fmax(m, z);
+    }
+    m = pm_wave_max(m);
+    if (__any(bad)) return NAN;
+    if (isinf(m)) return m;
+    double s = 0.0;
+    for (int k = lane; k < K; k += 64) s += exp(a * x[k] + (off ? off[k] : 0.0) - m);
+    return m + log(pm_wave_sum(s));
+}
+
+// The values of the one-cause state blocks of a log-joint row (DSC: K - 1 <= 7), passed to the read-out kernels by value.
+#define PM_MAX_BLOCKVALS 8
+struct pm_blockvals {
+    double v[PM_MAX_BLOCKVALS];
+};
+
 // Wave-wide sum without the LDS crossbar: DPP butterflies inside each 16-lane row (quad_perm xor 1 / xor 2,
 // row_half_mirror, row_mirror), then the four row totals through v_readlane.  Result is wave-uniform.
 template <int CTRL>
@@ -344,6 +379,28 @@ __device__ __forceinline__ double pm_pow_m5_6(double x, const double *rt) {
     // * 2^(-5 (q - 175))
     return __hiloint2double(__double2hiint(v) + (int)((875u - 5u * q) << 20), __double2loint(v));
 #endif
+}
+
+// The MCA / MMCA read-outs (reconstruct(), its variance, sample_posterior()) form Wbar_d(s) = sign(T) |T|^(1/rho), T the sum
+// of the state's rows of W^rho, with the power functions above.  pm_mca_pow_setup fills the workgroup's tables (s_tab:
+// PM_POWTAB_LEN doubles, s_rt: PM_ROOT21_LEN + 1) and picks the path for this rho -- r21: rho = 21 (MCA, unsigned), r6: rho = 6,
+// the root functions; neither: pm_pow_tab.  The caller's __syncthreads() follows it.
+__device__ __forceinline__ void pm_mca_pow_setup(double *s_tab, double *s_rt, double inv_rho, int signed_w, int tid,
+                                                 int nthreads, bool &r21, bool &r6) {
+    pm_load_powtab(s_tab, tid, nthreads);
+    r21 = !signed_w && inv_rho > 0.0 && fabs(1.0 / inv_rho - 21.0) < 1e-9;
+    r6 = inv_rho > 0.0 && fabs(1.0 / inv_rho - 6.0) < 1e-9;
+    if (!PM_POW_HWSEED && r21) pm_load_root21(s_rt, pm_powtab_dev, tid, nthreads);
+    else if (!PM_POW_HWSEED && r6) pm_load_root6(s_rt, pm_powtab_dev, tid, nthreads);
+}
+__device__ __forceinline__ double pm_mca_wbar(double T, double inv_rho, bool r21, bool r6, const double *s_tab,
+                                              const double *s_rt) {
+    const double aT = fabs(T);
+    double wbar = 0.0;
+    if (aT > 0.0)
+        wbar = r21 ? aT * pm_pow_m20_21(aT, s_rt)
+                   : r6 ? copysign(aT * pm_pow_m5_6(aT, s_rt), T) : copysign(pm_pow_tab(aT, inv_rho, s_tab), T);
+    return wbar;
 }
 
 // x^c for NORMAL x > 0 and an exponent c that is UNIFORM over the launch (round 6: MCA / MMCA's state power at any

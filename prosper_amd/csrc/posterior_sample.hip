@@ -37,41 +37,10 @@ namespace {
 constexpr int SMP_THREADS = 256;
 constexpr int64_t SMP_MAX_BLOCKS = 8192;       // decode kernels: a wavefront per (row, sample)
 constexpr int64_t SMP_ROW_BLOCKS = 2048;       // the other kernels: 8192 wavefronts fill the device; more rows take another trip
-constexpr int SMP_MAX_BLOCKVALS = 8;
 constexpr int SMP_LDS_DOUBLES = 8192;          // 64 KB: one wavefront's CDF at the largest K, four at K <= 1984
 constexpr int SMP_MAX_ACTIVE = PM_MAX_HPRIME;
 
-struct smp_blockvals {
-    double v[SMP_MAX_BLOCKVALS];
-};
-
 __host__ __device__ inline int smp_seg(int64_t K) { return (int)((K + 63) / 64) | 1; }
-
-// The lanes of ONE wavefront hand values to each other through their own LDS region: order the accesses for the compiler and
-// the hardware without a workgroup barrier (the wavefronts of a workgroup walk different rows).
-__device__ __forceinline__ void smp_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// As rec_row_lse (reconstruct_kernels.hip): NaN for a row with a NaN entry, the maximum itself when it is infinite.
-__device__ __forceinline__ double smp_row_lse(const double *__restrict__ x, int K, double a, const double *__restrict__ off,
-                                              int lane) {
-    double m = -INFINITY;
-    int bad = 0;
-    for (int k = lane; k < K; k += 64) {
-        const double z = a * x[k] + (off ? off[k] : 0.0);
-        bad |= (z != z);
-        m = fmax(m, z);
-    }
-    m = pm_wave_max(m);
-    if (__any(bad)) return NAN;
-    if (isinf(m)) return m;
-    double s = 0.0;
-    for (int k = lane; k < K; k += 64) s += exp(a * x[k] + (off ? off[k] : 0.0) - m);
-    return m + log(pm_wave_sum(s));
-}
 
 // blockDim.x = 64 * waves; dynamic LDS: waves * 64 * seg doubles.
 __global__ __launch_bounds__(SMP_THREADS) void sample_states_kernel(
@@ -85,7 +54,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_states_kernel(
     const int64_t wave0 = (int64_t)blockIdx.x * waves + wave, nwaves = (int64_t)gridDim.x * waves;
     for (int64_t n = wave0; n < N; n += nwaves) {
         const double *row = X + n * ld;
-        const double lse = lse_in ? lse_in[n] : smp_row_lse(row, K, a, off, lane);
+        const double lse = lse_in ? lse_in[n] : pm_row_lse(row, K, a, off, lane);
         // ---- weights, column k at cdf[k] (coalesced reads of the row); a NaN weight marks the row
         int bad = (lse != lse);
         for (int k = lane; k < Kpad; k += 64) {
@@ -98,7 +67,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_states_kernel(
             cdf[k] = w;
         }
         bad = __any(bad);
-        smp_wave_sync();
+        pm_wave_sync();
         // ---- the lane's running sums, then the bases in ascending lane order, then c in place
         double *mine = cdf + lane * seg;
         double p = 0.0;
@@ -112,7 +81,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_states_kernel(
             run += __shfl(p, l, 64);
         }
         for (int i = 0; i < seg; ++i) mine[i] = base + mine[i];
-        smp_wave_sync();
+        pm_wave_sync();
         const double C = run;
         bad |= !(C > 0.0) || !(C < INFINITY);
         // ---- the draws: the row's CDF serves every uniform (the wave's own LDS region: no barrier)
@@ -134,7 +103,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_states_kernel(
             }
             irow[m] = k;
         }
-        smp_wave_sync();          // (the next row's weights overwrite the CDF)
+        pm_wave_sync();          // (the next row's weights overwrite the CDF)
     }
 }
 
@@ -142,7 +111,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_states_kernel(
 // in every slot.
 __global__ __launch_bounds__(SMP_THREADS) void sample_active_kernel(const int32_t *__restrict__ idx, const int32_t *__restrict__ cand,
                                                                     const double *__restrict__ tab, int64_t N, int M, int H,
-                                                                    int Hp, int K, int soff, int nblk, smp_blockvals bv, int moff,
+                                                                    int Hp, int K, int soff, int nblk, pm_blockvals bv, int moff,
                                                                     int S, int A, int32_t *__restrict__ act_idx,
                                                                     double *__restrict__ act_val) {
     const int64_t total = N * (int64_t)M;
@@ -345,11 +314,8 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_decode_mca_kernel(const in
     __shared__ __attribute__((aligned(16))) double s_tab[PM_POWTAB_LEN];
     __shared__ __attribute__((aligned(16))) double s_rt[PM_ROOT21_LEN + 1];
     const int tid = threadIdx.x, lane = tid & 63;
-    pm_load_powtab(s_tab, tid, blockDim.x);
-    const bool r21 = !signed_w && inv_rho > 0.0 && fabs(1.0 / inv_rho - 21.0) < 1e-9;
-    const bool r6 = inv_rho > 0.0 && fabs(1.0 / inv_rho - 6.0) < 1e-9;
-    if (!PM_POW_HWSEED && r21) pm_load_root21(s_rt, pm_powtab_dev, tid, blockDim.x);
-    else if (!PM_POW_HWSEED && r6) pm_load_root6(s_rt, pm_powtab_dev, tid, blockDim.x);
+    bool r21, r6;
+    pm_mca_pow_setup(s_tab, s_rt, inv_rho, signed_w, tid, blockDim.x, r21, r6);
     __syncthreads();
     const int64_t total = N * (int64_t)M;
     const int64_t wave0 = (int64_t)blockIdx.x * (SMP_THREADS / 64) + (tid >> 6);
@@ -379,13 +345,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_decode_mca_kernel(const in
 #pragma unroll
                 for (int j = 0; j < PM_MAX_HPRIME; ++j)
                     if ((mk >> j) & 1u) T += Wrho[coff[j] + d];   // uniform
-                const double aT = fabs(T);
-                double wbar = 0.0;
-                if (aT > 0.0)
-                    wbar = r21 ? aT * pm_pow_m20_21(aT, s_rt)
-                               : r6 ? copysign(aT * pm_pow_m5_6(aT, s_rt), T)
-                                    : copysign(pm_pow_tab(aT, inv_rho, s_tab), T);
-                orow[d] = wbar;
+                orow[d] = pm_mca_wbar(T, inv_rho, r21, r6, s_tab, s_rt);
             }
         }
     }
@@ -426,15 +386,15 @@ extern "C" int pm_sample_active_f64(const int32_t *idx, const int32_t *cand, con
     if (N < 0 || M <= 0 || H <= 0 || K <= 0 || single_off < 0 || nblocks < 0 || multi_off < 0 || S < 0 || Hprime < 0 ||
         (S > 0 && Hprime == 0) || A < 1)
         return PM_EINVAL;
-    if (Hprime > PM_MAX_HPRIME || A > SMP_MAX_ACTIVE || nblocks > SMP_MAX_BLOCKVALS || K > INT32_MAX / 2 ||
+    if (Hprime > PM_MAX_HPRIME || A > SMP_MAX_ACTIVE || nblocks > PM_MAX_BLOCKVALS || K > INT32_MAX / 2 ||
         H > INT32_MAX / 16 || M > INT32_MAX / 2)
         return PM_ERANGE;
     if (single_off + nblocks * H > K || multi_off + S > K) return PM_EINVAL;
     if (!idx || !act_idx || !act_val || (nblocks > 0 && !block_values_host) || (S > 0 && (!cand || !state_vals)))
         return PM_EINVAL;
     if (N == 0) return PM_OK;
-    smp_blockvals bv;
-    for (int c = 0; c < SMP_MAX_BLOCKVALS; ++c) bv.v[c] = c < nblocks ? block_values_host[c] : 0.0;
+    pm_blockvals bv;
+    for (int c = 0; c < PM_MAX_BLOCKVALS; ++c) bv.v[c] = c < nblocks ? block_values_host[c] : 0.0;
     hipLaunchKernelGGL(sample_active_kernel, dim3(smp_grid(N * M, SMP_THREADS, SMP_ROW_BLOCKS)), dim3(SMP_THREADS), 0,
                        static_cast<hipStream_t>(stream), idx, cand, state_vals, N, (int)M, (int)H, (int)Hprime, (int)K,
                        (int)single_off, (int)nblocks, bv, (int)multi_off, (int)S, (int)A, act_idx, act_val);

@@ -13,23 +13,20 @@
 // R, the ranges themselves, the assignment of states to threads and every merge order are functions of the state count (and
 // H, K, D) alone, never of N, and a workgroup handles its rows independently of one another: a row of the result is a
 // function of that row of Y and of the parameters.  Nothing is added by atomics and nothing depends on PM_DETERMINISTIC.
-// States are decoded from their index; every per-state quantity is recomputed from its digits, as in loglik_exact.hip.
+// States are decoded from their index; every per-state quantity is recomputed from its digits.  The pieces of l_n(s) shared
+// with loglik_exact.hip are the single definitions of pm_exact.h.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <stdint.h>
 
 #include "prosper_hip.h"
+#include "pm_exact.h"
 
 namespace {
 
-constexpr int RX_THREADS = 256;
+constexpr int RX_THREADS = PMX_THREADS;
 constexpr int RX_WAVES = RX_THREADS / 64;
-constexpr uint64_t RX_MAX_STATES = 1ull << 32;
-constexpr int RX_LIN_MAX_K = 8;
-constexpr int RX_MAX_H = 32;
-constexpr int RX_GSC_MAX_H = 16;
-constexpr int RX_GSC_TN = 64;                 // GSC: one lane per datapoint of the tile
 constexpr int RX_MCA_MAX_D = 1024;
 constexpr int RX_MCA_SLABS = RX_MCA_MAX_D / 64;
 constexpr int64_t RX_ROWS = 256;              // rows per block of the host walk: linear models, GSC
@@ -47,38 +44,6 @@ int64_t rx_ranges(uint64_t units, uint64_t per, int64_t cap) {
     return r > (uint64_t)cap ? cap : (int64_t)r;
 }
 
-// The online log-sum-exp step (loglik_exact.hip).  A -inf term changes nothing; a NaN term makes the sum NaN.
-__device__ __forceinline__ void lse_add(double &m, double &s, double z) {
-    if (z == -INFINITY) return;
-    const double d = z - m;                    // +inf while m is still -inf
-    const double e = exp(-fabs(d));
-    if (d > 0.0) {
-        s = s * e + 1.0;
-        m = z;
-    } else {
-        s += e;                                // NaN d: s becomes NaN
-    }
-}
-
-// (m, s) += (m2, s2)
-__device__ __forceinline__ void lse_merge(double &m, double &s, double m2, double s2) {
-    if (s2 != s2) {
-        s = s2;
-        return;
-    }
-    if (m2 == -INFINITY) return;
-    if (m2 > m) {
-        s = s * exp(m - m2) + s2;
-        m = m2;
-    } else {
-        s += s2 * exp(m2 - m);
-    }
-}
-
-__device__ __forceinline__ double lse_value(double m, double s) {
-    return (s != s) ? (double)NAN : (m == -INFINITY ? -INFINITY : m + log(s));
-}
-
 // The 256 threads' values added in a fixed order: lane l takes lane l + o for o = 32, 16, ..., 1, then the four wavefronts'
 // sums as (0 + 1) + (2 + 3).  Every thread calls it; thread 0 holds the result.  `red`: RX_WAVES doubles.
 __device__ double block_sum(double v, double *red) {
@@ -93,7 +58,7 @@ __device__ double block_sum(double v, double *red) {
 __device__ void block_lse(double &m, double &s, double *red) {
     for (int o = 32; o > 0; o >>= 1) {
         const double m2 = __shfl_down(m, o), s2 = __shfl_down(s, o);
-        if ((int)(threadIdx.x & 63) < o) lse_merge(m, s, m2, s2);
+        if ((int)(threadIdx.x & 63) < o) pmx_lse_merge(m, s, m2, s2);
     }
     __syncthreads();
     if ((threadIdx.x & 63) == 0) {
@@ -102,7 +67,7 @@ __device__ void block_lse(double &m, double &s, double *red) {
     }
     __syncthreads();
     if (threadIdx.x == 0)
-        for (int w = 1; w < RX_WAVES; ++w) lse_merge(m, s, red[2 * w], red[2 * w + 1]);
+        for (int w = 1; w < RX_WAVES; ++w) pmx_lse_merge(m, s, red[2 * w], red[2 * w + 1]);
 }
 
 // B[n,h] = sum_d (y_nd - ymu_d) P[d,h] (ymu NULL: 0), one thread per output
@@ -114,9 +79,7 @@ __global__ void __launch_bounds__(RX_THREADS) rx_prep_kernel(const double *__res
     if (i >= N * H) return;
     const int64_t n = i / H, h = i % H;
     const double *y = Y + n * ldy;
-    double acc = 0.0;
-    for (int64_t d = 0; d < D; ++d) acc = fma(y[d] - (ymu ? ymu[d] : 0.0), P[d * H + h], acc);
-    B[i] = acc;
+    B[i] = pmx_prep_dot(y, ymu, D, P, H, h);
 }
 
 // v[n] = log sum exp of the row's R partials part[2 (r nb + n)], merged in range order: one thread per row
@@ -125,8 +88,8 @@ __global__ void __launch_bounds__(RX_THREADS) rx_combine_lse_kernel(const double
     const int64_t n = (int64_t)blockIdx.x * RX_THREADS + threadIdx.x;
     if (n >= nb) return;
     double m = -INFINITY, s = 0.0;
-    for (int64_t r = 0; r < R; ++r) lse_merge(m, s, part[2 * (r * nb + n)], part[2 * (r * nb + n) + 1]);
-    v[n] = lse_value(m, s);
+    for (int64_t r = 0; r < R; ++r) pmx_lse_merge(m, s, part[2 * (r * nb + n)], part[2 * (r * nb + n) + 1]);
+    v[n] = pmx_lse_value(m, s);
 }
 
 // out[n, j] = sum_r part[(r nb + n) width + j] in range order: one thread per output
@@ -141,13 +104,11 @@ __global__ void __launch_bounds__(RX_THREADS) rx_combine_sum_kernel(const double
 }
 
 // ---- linear models: BSC, TSC, DSC ----------------------------------------------------------------------------------------
-// l(s) as ex_lin_kernel (loglik_exact.hip) forms it: the state index is sum_h k_h K^h, its L low digits (lo, CH = K^L
-// states, up to four per thread) are fixed per thread, a workgroup walks the chunks (values of the NH = H - L high digits) of
-// its range for ONE datapoint.  Sweep 2 keeps no accumulator per latent and state visit: a thread adds the weight of a
+// l(s) in the decomposition pm_exact.h describes (lo digits per thread, chunks of hi digits); a workgroup walks the chunks
+// of its range for ONE datapoint.  Sweep 2 keeps no accumulator per latent and state visit: a thread adds the weight of a
 // state to the mass of its lo state (one add), the chunk's mass (one add per state) to the NH high-digit sums weighted by
 // the chunk's own digit values (NH fmas per chunk, i.e. per up to four states), and turns the lo masses into the low
 // latents' sums once, after the loop.  E[s]_h = sum over threads of these sums, by block_sum's fixed tree.
-constexpr int LIN_MAX_J = 4;              // lo states per thread (CH <= 1024)
 constexpr int LIN_MAX_NH = 24;            // high digits at most (K = 2, H = 32: 22)
 
 struct LinArgs {
@@ -164,12 +125,12 @@ struct LinArgs {
 
 template <int SWEEP>
 __global__ void __launch_bounds__(RX_THREADS) rx_lin_kernel(LinArgs a) {
-    __shared__ double sG[RX_MAX_H * RX_MAX_H], sLogp[RX_MAX_H * RX_LIN_MAX_K], sVal[RX_LIN_MAX_K], sB[RX_MAX_H];
-    __shared__ double sGv[RX_MAX_H * RX_LIN_MAX_K];   // -values[k] (G_lh s_hi)_h
-    __shared__ double sHv[RX_MAX_H];                   // prior_hi - 1/2 s_i (G_hh s_hi)_i per hi latent
-    __shared__ double sSv[RX_MAX_H];                   // s_i of the chunk's hi digits
+    __shared__ double sG[PMX_MAX_H * PMX_MAX_H], sLogp[PMX_MAX_H * PMX_LIN_MAX_K], sVal[PMX_LIN_MAX_K], sB[PMX_MAX_H];
+    __shared__ double sGv[PMX_MAX_H * PMX_LIN_MAX_K];   // -values[k] (G_lh s_hi)_h
+    __shared__ double sHv[PMX_MAX_H];                   // prior_hi - 1/2 s_i (G_hh s_hi)_i per hi latent
+    __shared__ double sSv[PMX_MAX_H];                   // s_i of the chunk's hi digits
     __shared__ double sBh[1];
-    __shared__ int sDig[RX_MAX_H];
+    __shared__ int sDig[PMX_MAX_H];
     __shared__ double red[2 * RX_WAVES];
     const int H = a.H, K = a.K, L = a.L, CH = a.CH, NH = H - L;
     const int64_t R = a.R, n = blockIdx.x / R, r = blockIdx.x % R;
@@ -188,10 +149,10 @@ __global__ void __launch_bounds__(RX_THREADS) rx_lin_kernel(LinArgs a) {
     __syncthreads();
 
     // per lo state of this thread: its packed digits (3 bits each), prior_lo - 1/2 s_lo^T G_ll s_lo and s_lo^T B_n,lo
-    uint32_t code[LIN_MAX_J];
-    double plo[LIN_MAX_J], blo[LIN_MAX_J];
+    uint32_t code[PMX_LIN_MAX_J];
+    double plo[PMX_LIN_MAX_J], blo[PMX_LIN_MAX_J];
 #pragma unroll
-    for (int j = 0; j < LIN_MAX_J; ++j) {
+    for (int j = 0; j < PMX_LIN_MAX_J; ++j) {
         const int lo = threadIdx.x + j * RX_THREADS;
         code[j] = 0;
         plo[j] = -INFINITY;
@@ -219,9 +180,9 @@ __global__ void __launch_bounds__(RX_THREADS) rx_lin_kernel(LinArgs a) {
 
     const double vn = SWEEP == 2 ? a.v[n] : 0.0;
     double m = -INFINITY, s = 0.0;             // sweep 1
-    double mlo[LIN_MAX_J], ehi[LIN_MAX_NH];    // sweep 2
+    double mlo[PMX_LIN_MAX_J], ehi[LIN_MAX_NH];    // sweep 2
 #pragma unroll
-    for (int j = 0; j < LIN_MAX_J; ++j) mlo[j] = 0.0;
+    for (int j = 0; j < PMX_LIN_MAX_J; ++j) mlo[j] = 0.0;
 #pragma unroll
     for (int i = 0; i < LIN_MAX_NH; ++i) ehi[i] = 0.0;
     for (uint64_t c = c0; c < c1; ++c) {
@@ -239,7 +200,7 @@ __global__ void __launch_bounds__(RX_THREADS) rx_lin_kernel(LinArgs a) {
                 for (int l = 0; l < NH; ++l) g = fma(sG[t * H + L + l], sVal[sDig[l]], g);
             sHv[i] = sLogp[t * K + sDig[i]] - 0.5 * si * g;
             sSv[i] = si;
-        } else if (t == RX_MAX_H) {                         // s_hi^T B_n,hi
+        } else if (t == PMX_MAX_H) {                         // s_hi^T B_n,hi
             double b = 0.0;
             for (int l = 0; l < NH; ++l) b = fma(sVal[sDig[l]], sB[L + l], b);
             sBh[0] = b;
@@ -250,13 +211,13 @@ __global__ void __launch_bounds__(RX_THREADS) rx_lin_kernel(LinArgs a) {
         const double bh = sBh[0];
         double cm = 0.0;
 #pragma unroll
-        for (int j = 0; j < LIN_MAX_J; ++j) {
+        for (int j = 0; j < PMX_LIN_MAX_J; ++j) {
             if (threadIdx.x + j * RX_THREADS >= (unsigned)CH) break;
             double cross = 0.0;
             for (int h = 0; h < L; ++h) cross += sGv[h * K + ((code[j] >> (3 * h)) & 7)];
             const double l = ((plo[j] + lhi) + cross) + (blo[j] + bh);
             if (SWEEP == 1) {
-                lse_add(m, s, l);
+                pmx_lse_add(m, s, l);
             } else {
                 const double q = exp(l - vn);              // (-inf - v: 0, a state of zero prior)
                 mlo[j] += q;
@@ -288,7 +249,7 @@ __global__ void __launch_bounds__(RX_THREADS) rx_lin_kernel(LinArgs a) {
     for (int h = 0; h < L; ++h) {                           // the low latents from the lo masses
         double e = 0.0;
 #pragma unroll
-        for (int j = 0; j < LIN_MAX_J; ++j)
+        for (int j = 0; j < PMX_LIN_MAX_J; ++j)
             if (threadIdx.x + j * RX_THREADS < (unsigned)CH) e = fma(sVal[(code[j] >> (3 * h)) & 7], mlo[j], e);
         e = block_sum(e, red);
         if (threadIdx.x == 0) out[h] = e;
@@ -303,7 +264,7 @@ __global__ void __launch_bounds__(RX_THREADS) rx_lin_kernel(LinArgs a) {
 }
 
 // ---- MCA / MMCA ----------------------------------------------------------------------------------------------------------
-// l(s) = |s| lp1 + (H - |s|) lp0 + inv_s2 sum_d (y_d Wbar_d(s) - 1/2 Wbar_d(s)^2), Wbar as ex_mca_kernel forms it; the state
+// l(s) = |s| lp1 + (H - |s|) lp0 + inv_s2 sum_d (y_d Wbar_d(s) - 1/2 Wbar_d(s)^2), Wbar_d(s) from pmx_mca_wbar; the state
 // index is the bit mask of s.  A workgroup owns one (datapoint, range); wavefront w takes the states s0 + w, s0 + w + 4, ...
 // with its lanes over the dimensions d = lane + 64 i (i < 16: D <= 1024), forms Wbar_d(s) once per state and sweep, sums
 // the energy over the lanes by a butterfly (every lane holds the same bits) and, in sweep 2, adds q Wbar_d to its own
@@ -348,9 +309,7 @@ __global__ void __launch_bounds__(RX_THREADS) rx_mca_kernel(McaArgs a) {
             if (i < nsl) {
                 const int64_t d = lane + 64 * i;
                 if (d < D && st) {
-                    double t = 0.0;
-                    for (uint64_t b = st; b; b &= b - 1) t += a.Wrho[(int64_t)__builtin_ctzll(b) * D + d];
-                    wv[i] = a.signed_w ? copysign(pow(fabs(t), a.inv_rho), t) : pow(t, a.inv_rho);
+                    wv[i] = pmx_mca_wbar(a.Wrho, D, d, st, a.inv_rho, a.signed_w);
                 }
                 e = fma(wv[i], y[i] - 0.5 * wv[i], e);
             }
@@ -358,7 +317,7 @@ __global__ void __launch_bounds__(RX_THREADS) rx_mca_kernel(McaArgs a) {
         for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
         const double l = lp + a.inv_s2 * e;
         if (SWEEP == 1) {
-            lse_add(m, s, l);
+            pmx_lse_add(m, s, l);
         } else {
             const double q = exp(l - vn);
 #pragma unroll
@@ -373,7 +332,7 @@ __global__ void __launch_bounds__(RX_THREADS) rx_mca_kernel(McaArgs a) {
         }
         __syncthreads();
         if (threadIdx.x == 0) {
-            for (int u = 1; u < RX_WAVES; ++u) lse_merge(m, s, red[2 * u], red[2 * u + 1]);
+            for (int u = 1; u < RX_WAVES; ++u) pmx_lse_merge(m, s, red[2 * u], red[2 * u + 1]);
             a.part[2 * (r * a.nb + n)] = m;
             a.part[2 * (r * a.nb + n) + 1] = s;
         }
@@ -389,7 +348,7 @@ __global__ void __launch_bounds__(RX_THREADS) rx_mca_kernel(McaArgs a) {
 }
 
 // ---- GSC -----------------------------------------------------------------------------------------------------------------
-// l(s) = kappa_s + mu_s^T u_n,s + 1/2 |A_s beta_n,s|^2 with the per-support factorisation of ex_gsc_kernel (loglik_exact.hip):
+// l(s) = kappa_s + mu_s^T u_n,s + 1/2 |A_s beta_n,s|^2 with pmx_gsc_factor_support's per-support factorisation (pm_exact.h):
 // a wavefront factors one support at a time in its own LDS, then every lane -- one datapoint of the 64-row tile -- applies
 // it.  Sweep 2 keeps z = A_s beta and adds q (mu_h + (A_s^T z)_pos) to the accumulator of every latent h of the support
 // (pos its rank in the support): 16 accumulators per lane, indexed statically.  The wavefronts 1, 2, 3 hand theirs to
@@ -404,126 +363,45 @@ struct GscArgs {
     int H;
 };
 
-constexpr int GS = RX_GSC_MAX_H;
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// In-place lower Cholesky factor of the k x k matrix X (row stride GS) by one wavefront; the upper triangle is left alone.
-__device__ void wave_cholesky(double *X, int k, int lane) {
-    for (int j = 0; j < k; ++j) {
-        const double d = sqrt(X[j * GS + j]);
-        wave_sync();
-        for (int i = j + 1 + lane; i < k; i += 64) X[i * GS + j] /= d;
-        if (lane == 0) X[j * GS + j] = d;
-        wave_sync();
-        const int n = k - j - 1;
-        for (int e = lane; e < n * n; e += 64) {
-            const int i = j + 1 + e / n, l = j + 1 + e % n;
-            if (l <= i) X[i * GS + l] -= X[i * GS + j] * X[l * GS + j];
-        }
-        wave_sync();
-    }
-}
-
 template <int SWEEP>
 __global__ void __launch_bounds__(RX_THREADS) rx_gsc_kernel(GscArgs a) {
-    __shared__ double sM[GS * GS], sPsi[GS * GS], sMu[GS], sLp[2 * GS];
-    __shared__ double sU[RX_GSC_TN * GS];
-    __shared__ double sX[RX_WAVES][3][GS * GS];  // Lp | T, then A | Lk; after the loop (RX_WAVES - 1) x GS x 64 accumulators
-    __shared__ double sV[RX_WAVES][GS];          // m_s
-    __shared__ int sIdx[RX_WAVES][GS];           // the support's latents, ascending
+    __shared__ double sM[PMX_GS * PMX_GS], sPsi[PMX_GS * PMX_GS], sMu[PMX_GS], sLp[2 * PMX_GS];
+    __shared__ double sU[PMX_GSC_TN * PMX_GS];
+    __shared__ double sX[RX_WAVES][3][PMX_GS * PMX_GS];  // Lp | T, then A | Lk; after the loop (RX_WAVES - 1) x PMX_GS x 64 accumulators
+    __shared__ double sV[RX_WAVES][PMX_GS];          // m_s
+    __shared__ int sIdx[RX_WAVES][PMX_GS];           // the support's latents, ascending
     __shared__ double red[2][RX_WAVES][64];
-    static_assert((RX_WAVES - 1) * GS * 64 <= RX_WAVES * 3 * GS * GS, "the accumulators fit the factorisation's LDS");
+    static_assert((RX_WAVES - 1) * PMX_GS * 64 <= RX_WAVES * 3 * PMX_GS * PMX_GS, "the accumulators fit the factorisation's LDS");
     const int H = a.H, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t R = a.R, tile = blockIdx.x / R, r = blockIdx.x % R, n0 = tile * RX_GSC_TN;
-    for (int i = threadIdx.x; i < H * H; i += RX_THREADS) {
-        sM[(i / H) * GS + i % H] = a.M[i];
-        sPsi[(i / H) * GS + i % H] = a.Psi[i];
-    }
-    if ((int)threadIdx.x < H) {
-        sMu[threadIdx.x] = a.mu[threadIdx.x];
-        sLp[2 * threadIdx.x] = a.logp[2 * threadIdx.x];
-        sLp[2 * threadIdx.x + 1] = a.logp[2 * threadIdx.x + 1];
-    }
-    for (int i = threadIdx.x; i < RX_GSC_TN * H; i += RX_THREADS) {
-        const int64_t n = n0 + i / H;
-        sU[(i / H) * GS + i % H] = n < a.nb ? a.B[n * H + i % H] : 0.0;
-    }
+    const int64_t R = a.R, tile = blockIdx.x / R, r = blockIdx.x % R, n0 = tile * PMX_GSC_TN;
+    pmx_gsc_stage(sM, sPsi, sMu, sLp, sU, a.M, a.Psi, a.mu, a.logp, a.B, n0, a.nb, H);
     __syncthreads();
     const uint64_t s0 = a.nstates * (uint64_t)r / (uint64_t)R, s1 = a.nstates * (uint64_t)(r + 1) / (uint64_t)R;
     double *Lp = sX[w][0], *T = sX[w][1], *X = sX[w][2];
     double *mv = sV[w];
     const int *idx = sIdx[w];
-    const double *u = sU + lane * GS;
+    const double *u = sU + lane * PMX_GS;
     const double vn = (SWEEP == 2 && n0 + lane < a.nb) ? a.v[n0 + lane] : 0.0;
     double m = -INFINITY, s = 0.0;
-    double acc[GS];
+    double acc[PMX_GS];
 #pragma unroll
-    for (int i = 0; i < GS; ++i) acc[i] = 0.0;
+    for (int i = 0; i < PMX_GS; ++i) acc[i] = 0.0;
     for (uint64_t st = s0 + w; st < s1; st += RX_WAVES) {
         const int k = __popcll(st);
-        double lp = 0.0;
-        for (int h = 0; h < H; ++h) lp += sLp[2 * h + (int)((st >> h) & 1)];
+        const double lp = pmx_gsc_prior(sLp, st, H);
         if (lp == -INFINITY) continue;
         if (lane < H && ((st >> lane) & 1)) sIdx[w][__popcll(st & ((1ull << lane) - 1))] = lane;
-        wave_sync();
+        pm_wave_sync();
         double kappa = lp, lin = 0.0, quad = 0.0;
-        double z[GS];
+        double z[PMX_GS];
 #pragma unroll
-        for (int i = 0; i < GS; ++i) z[i] = 0.0;
+        for (int i = 0; i < PMX_GS; ++i) z[i] = 0.0;
         if (k) {
-            // Lp = chol(Psi_ss)
-            for (int e = lane; e < k * k; e += 64) Lp[(e / k) * GS + e % k] = sPsi[idx[e / k] * GS + idx[e % k]];
-            wave_sync();
-            wave_cholesky(Lp, k, lane);
-            // T = M_ss Lp (Lp lower: rows p >= l)
-            for (int e = lane; e < k * k; e += 64) {
-                const int i = e / k, l = e % k;
-                double t = 0.0;
-                for (int p = l; p < k; ++p) t = fma(sM[idx[i] * GS + idx[p]], Lp[p * GS + l], t);
-                T[i * GS + l] = t;
-            }
-            // m_s = M_ss mu_s
-            if (lane < k) {
-                double t = 0.0;
-                for (int p = 0; p < k; ++p) t = fma(sM[idx[lane] * GS + idx[p]], sMu[idx[p]], t);
-                mv[lane] = t;
-            }
-            wave_sync();
-            // X = I + Lp^T T (lower triangle)
-            for (int e = lane; e < k * k; e += 64) {
-                const int i = e / k, l = e % k;
-                if (l > i) continue;
-                double t = (i == l) ? 1.0 : 0.0;
-                for (int p = i; p < k; ++p) t = fma(Lp[p * GS + i], T[p * GS + l], t);
-                X[i * GS + l] = t;
-            }
-            wave_sync();
-            wave_cholesky(X, k, lane);
-            // A = Lk^-1 Lp^T, column l by lane l (into T)
-            if (lane < k) {
-                const int l = lane;
-                for (int i = 0; i < k; ++i) {
-                    double t = (i <= l) ? Lp[l * GS + i] : 0.0;
-                    for (int p = 0; p < i; ++p) t = fma(-X[i * GS + p], T[p * GS + l], t);
-                    T[i * GS + l] = t / X[i * GS + i];
-                }
-            }
-            wave_sync();
-            double ld = 0.0, mm = 0.0;
-            for (int i = 0; i < k; ++i) {
-                ld += log(X[i * GS + i]);
-                mm = fma(sMu[idx[i]], mv[i], mm);
-            }
-            kappa = lp - ld - 0.5 * mm;
+            kappa = pmx_gsc_factor_support(sM, sPsi, sMu, idx, k, lane, lp, Lp, T, X, mv);
             // per datapoint: beta = u_s - m_s, z = A beta
-            double beta[GS];
+            double beta[PMX_GS];
 #pragma unroll
-            for (int i = 0; i < GS; ++i) {
+            for (int i = 0; i < PMX_GS; ++i) {
                 beta[i] = 0.0;
                 if (i < k) {
                     const double ui = u[idx[i]];
@@ -532,12 +410,12 @@ __global__ void __launch_bounds__(RX_THREADS) rx_gsc_kernel(GscArgs a) {
                 }
             }
 #pragma unroll
-            for (int i = 0; i < GS; ++i) {
+            for (int i = 0; i < PMX_GS; ++i) {
                 if (i < k) {
                     double zi = 0.0;
 #pragma unroll
-                    for (int l = 0; l < GS; ++l)
-                        if (l < k) zi = fma(T[i * GS + l], beta[l], zi);
+                    for (int l = 0; l < PMX_GS; ++l)
+                        if (l < k) zi = fma(T[i * PMX_GS + l], beta[l], zi);
                     quad = fma(zi, zi, quad);
                     z[i] = zi;
                 }
@@ -545,23 +423,23 @@ __global__ void __launch_bounds__(RX_THREADS) rx_gsc_kernel(GscArgs a) {
         }
         const double l = kappa + lin + 0.5 * quad;
         if (SWEEP == 1) {
-            lse_add(m, s, l);
+            pmx_lse_add(m, s, l);
         } else if (k) {
             const double q = exp(l - vn);
             int pos = 0;                          // (uniform: the rank of latent h in the support)
 #pragma unroll
-            for (int h = 0; h < GS; ++h) {
+            for (int h = 0; h < PMX_GS; ++h) {
                 if ((st >> h) & 1) {
                     double kap = sMu[h];
 #pragma unroll
-                    for (int i = 0; i < GS; ++i)
-                        if (i < k) kap = fma(T[i * GS + pos], z[i], kap);
+                    for (int i = 0; i < PMX_GS; ++i)
+                        if (i < k) kap = fma(T[i * PMX_GS + pos], z[i], kap);
                     acc[h] = fma(q, kap, acc[h]);
                     ++pos;
                 }
             }
         }
-        wave_sync();                              // (the next support overwrites this wave's LDS)
+        pm_wave_sync();                              // (the next support overwrites this wave's LDS)
     }
     if (SWEEP == 1) {
         red[0][w][lane] = m;
@@ -569,7 +447,7 @@ __global__ void __launch_bounds__(RX_THREADS) rx_gsc_kernel(GscArgs a) {
         __syncthreads();
         if (w == 0 && n0 + lane < a.nb) {
             double mm = -INFINITY, ss = 0.0;
-            for (int v = 0; v < RX_WAVES; ++v) lse_merge(mm, ss, red[0][v][lane], red[1][v][lane]);
+            for (int v = 0; v < RX_WAVES; ++v) pmx_lse_merge(mm, ss, red[0][v][lane], red[1][v][lane]);
             const int64_t n = n0 + lane;
             a.part[2 * (r * a.nb + n)] = mm;
             a.part[2 * (r * a.nb + n) + 1] = ss;
@@ -580,16 +458,16 @@ __global__ void __launch_bounds__(RX_THREADS) rx_gsc_kernel(GscArgs a) {
     double *sR = &sX[0][0][0];
     if (w > 0) {
 #pragma unroll
-        for (int h = 0; h < GS; ++h) sR[((w - 1) * GS + h) * 64 + lane] = acc[h];
+        for (int h = 0; h < PMX_GS; ++h) sR[((w - 1) * PMX_GS + h) * 64 + lane] = acc[h];
     }
     __syncthreads();
     if (w == 0 && n0 + lane < a.nb) {
         double *out = a.part + (r * a.nb + n0 + lane) * H;
 #pragma unroll
-        for (int h = 0; h < GS; ++h) {
+        for (int h = 0; h < PMX_GS; ++h) {
             if (h < H) {
                 double e = acc[h];
-                for (int u2 = 0; u2 < RX_WAVES - 1; ++u2) e += sR[(u2 * GS + h) * 64 + lane];
+                for (int u2 = 0; u2 < RX_WAVES - 1; ++u2) e += sR[(u2 * PMX_GS + h) * 64 + lane];
                 out[h] = e;
             }
         }
@@ -598,16 +476,6 @@ __global__ void __launch_bounds__(RX_THREADS) rx_gsc_kernel(GscArgs a) {
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
 inline unsigned rx_blocks(int64_t items) { return (unsigned)((items + RX_THREADS - 1) / RX_THREADS); }
-
-// K^H, or 0 past the bound
-uint64_t rx_state_count(int64_t K, int64_t H) {
-    uint64_t c = 1;
-    for (int64_t h = 0; h < H; ++h) {
-        c *= (uint64_t)K;
-        if (c > RX_MAX_STATES) return 0;
-    }
-    return c;
-}
 
 int rx_combine_lse(const double *part, int64_t nb, int64_t R, double *v, hipStream_t st) {
     hipLaunchKernelGGL(rx_combine_lse_kernel, dim3(rx_blocks(nb)), dim3(RX_THREADS), 0, st, part, nb, R, v);
@@ -635,16 +503,13 @@ extern "C" int64_t pm_recon_exact_work_len(int64_t N, int64_t H, int64_t D) {
 extern "C" int pm_recon_exact_lin_f64(const double *Y, int64_t ldy, const double *ymu, const double *P, const double *G,
                                       const double *logp, const double *values, int64_t K, int64_t N, int64_t D, int64_t H,
                                       double *E, int64_t lde, double *work, void *stream) {
-    if (N < 0 || D < 1 || H < 1 || K < 2 || K > RX_LIN_MAX_K || ldy < D || lde < H || !P || !G || !logp || !values || !work ||
+    if (N < 0 || D < 1 || H < 1 || K < 2 || K > PMX_LIN_MAX_K || ldy < D || lde < H || !P || !G || !logp || !values || !work ||
         (N > 0 && (!Y || !E)))
         return PM_EINVAL;
-    const uint64_t S = rx_state_count(K, H);
-    if (H > RX_MAX_H || S == 0) return PM_ERANGE;
-    int L = 0, CH = 1;
-    while (L < H && CH * K <= LIN_MAX_J * RX_THREADS) {
-        CH *= (int)K;
-        ++L;
-    }
+    const uint64_t S = pmx_state_count(K, H);
+    if (H > PMX_MAX_H || S == 0) return PM_ERANGE;
+    int L, CH;
+    pmx_lin_split(K, H, L, CH);
     if (H - L > LIN_MAX_NH) return PM_ERANGE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     LinArgs a;
@@ -683,7 +548,7 @@ extern "C" int pm_recon_exact_mca_f64(const double *Y, int64_t ldy, const double
                                       double lp1, double lp0, double inv_s2, int64_t N, int64_t D, int64_t H, double *Yhat,
                                       int64_t ldo, double *work, void *stream) {
     if (N < 0 || D < 1 || H < 1 || ldy < D || ldo < D || !Wrho || !work || (N > 0 && (!Y || !Yhat))) return PM_EINVAL;
-    if (H > RX_MAX_H || D > RX_MCA_MAX_D) return PM_ERANGE;
+    if (H > PMX_MAX_H || D > RX_MCA_MAX_D) return PM_ERANGE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     McaArgs a;
     a.ldy = ldy;
@@ -721,7 +586,7 @@ extern "C" int pm_recon_exact_gsc_f64(const double *Y, int64_t ldy, const double
                                       int64_t lde, double *work, void *stream) {
     if (N < 0 || D < 1 || H < 1 || ldy < D || lde < H || !P || !M || !Psi || !mu || !logp || !work || (N > 0 && (!Y || !E)))
         return PM_EINVAL;
-    if (H > RX_GSC_MAX_H) return PM_ERANGE;
+    if (H > PMX_GSC_MAX_H) return PM_ERANGE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     GscArgs a;
     a.M = M;
@@ -742,7 +607,7 @@ extern "C" int pm_recon_exact_gsc_f64(const double *Y, int64_t ldy, const double
         a.v = v;
         a.part = part;
         a.nb = nb;
-        const dim3 grid((unsigned)(((nb + RX_GSC_TN - 1) / RX_GSC_TN) * a.R));
+        const dim3 grid((unsigned)(((nb + PMX_GSC_TN - 1) / PMX_GSC_TN) * a.R));
         hipLaunchKernelGGL(rx_gsc_kernel<1>, grid, dim3(RX_THREADS), 0, st, a);
         if ((err = (int)hipGetLastError())) return err;
         if ((err = rx_combine_lse(part, nb, a.R, v, st))) return err;

@@ -8,7 +8,8 @@
 //   recon_gsc_moments2_kernel  GSC: the same m2 and p of u = s o z, assembled from the E-step pass's log-joints, its
 //                           un-normalised multi-cause sums (pm_gsc_estep_lpj_blocks_f64) and the per-latent tables.
 //   recon_var_finish_kernel V (holding the product) += 2 sum_p p W_d,c_i W_d,c_j, -= (yhat - mu)^2, clamped at 0.
-//   recon_mca_var_kernel    MCA / MMCA: V += sum_{multi-cause s} q(s) Wbar_d(s)^2, Wbar with the E-step's own powers.
+//   recon_mca_kernel<DPL, true> (recon_mca.h)  MCA / MMCA: V += sum_{multi-cause s} q(s) Wbar_d(s)^2, reconstruct()'s kernel
+//                           with the square.
 //
 // One wavefront per datapoint in all four.  No atomics and no branch on the build; every output element is written once by
 // one lane, and every sum runs in an order fixed by the shapes (H, H', S, D) alone: a lane adds its states in ascending
@@ -20,42 +21,20 @@
 
 #include "prosper_hip.h"
 #include "pm_common.h"
+#include "recon_mca.h"
 
 namespace {
 
 constexpr int RV_WAVES = 4;               // wavefronts per workgroup, one row each
 constexpr int RV_THREADS = 64 * RV_WAVES;
+static_assert(RV_WAVES == RMCA_WAVES, "rv_grid sizes recon_mca_kernel's grid: one row per wavefront");
 constexpr int RV_CHUNK = 256;             // table states per LDS chunk of a wavefront
 constexpr int64_t RV_MAX_BLOCKS = 2048;   // 8 workgroups per CU, grid-stride beyond: the second trip starts at row 8192
-constexpr int RV_MAX_BLOCKVALS = 8;       // value blocks of one-cause states (DSC: K - 1 <= 7)
 constexpr int RV_MAX_PAIRS = PM_MAX_HPRIME * (PM_MAX_HPRIME - 1) / 2;
-
-struct rv_blockvals {
-    double v[RV_MAX_BLOCKVALS];
-};
 
 __device__ __forceinline__ void rv_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
-}
-
-// log sum_k exp(a x_k + o_k) of one row by a maximum pass and a sum pass, in the order of pm_recon_expect_f64's own: NaN for
-// a NaN entry, the maximum itself when it is infinite.  Wave-uniform.
-__device__ __forceinline__ double rv_row_lse(const double *__restrict__ x, int K, double a, const double *__restrict__ off,
-                                             int lane) {
-    double m = -INFINITY;
-    int bad = 0;
-    for (int k = lane; k < K; k += 64) {
-        const double z = a * x[k] + (off ? off[k] : 0.0);
-        bad |= (z != z);
-        m = fmax(m, z);
-    }
-    m = pm_wave_max(m);
-    if (__any(bad)) return NAN;
-    if (isinf(m)) return m;
-    double s = 0.0;
-    for (int k = lane; k < K; k += 64) s += exp(a * x[k] + (off ? off[k] : 0.0) - m);
-    return m + log(pm_wave_sum(s));
 }
 
 unsigned rv_grid(int64_t N) {
@@ -71,7 +50,7 @@ unsigned rv_grid(int64_t N) {
 __global__ __launch_bounds__(RV_THREADS) void recon_moments2_kernel(
     const double *__restrict__ X, int64_t ld, const double *__restrict__ lse_in, double a, const double *__restrict__ off,
     const int32_t *__restrict__ cand, const double *__restrict__ tab, int64_t N, int H, int Hp, int K, int soff, int nblk,
-    rv_blockvals bv, int moff, int S, double *__restrict__ m2, int64_t ldm, int out_cols, double *__restrict__ p,
+    pm_blockvals bv, int moff, int S, double *__restrict__ m2, int64_t ldm, int out_cols, double *__restrict__ p,
     int64_t ldp) {
     __shared__ double s_q[RV_WAVES][RV_CHUNK];
     __shared__ double s_m[RV_WAVES][PM_MAX_HPRIME];
@@ -94,7 +73,7 @@ __global__ __launch_bounds__(RV_THREADS) void recon_moments2_kernel(
     const int64_t wave0 = (int64_t)blockIdx.x * RV_WAVES + wave, nwaves = (int64_t)gridDim.x * RV_WAVES;
     for (int64_t n = wave0; n < N; n += nwaves) {
         const double *row = X + n * ld;
-        const double lse = lse_in ? lse_in[n] : rv_row_lse(row, K, a, off, lane);
+        const double lse = lse_in ? lse_in[n] : pm_row_lse(row, K, a, off, lane);
         double a0 = 0.0, a1 = 0.0, am = 0.0;
         for (int s0 = 0; s0 < S; s0 += RV_CHUNK) {
             const int cnt = min(RV_CHUNK, S - s0);
@@ -250,78 +229,6 @@ __global__ __launch_bounds__(RV_THREADS) void recon_gsc_moments2_kernel(
     }
 }
 
-// MCA / MMCA: V[n, d] += sum_s q_n(s) Wbar_d(s)^2 over the S multi-cause states: recon_mca_kernel (reconstruct_kernels.hip)
-// with the square of the same Wbar -- the sum over a state's candidates in ascending position order, the power functions
-// of mca_estep_kernel.  Lane l holds dimensions l, l + 64, ...: D <= 64 DPL.
-template <int DPL>
-__global__ __launch_bounds__(RV_THREADS) void recon_mca_var_kernel(const double *__restrict__ X, int64_t ld,
-                                                                   const double *__restrict__ lse_in,
-                                                                   const int32_t *__restrict__ cand,
-                                                                   const uint16_t *__restrict__ masks,
-                                                                   const double *__restrict__ Wrho, double inv_rho,
-                                                                   int signed_w, int64_t N, int H, int D, int Hp, int S,
-                                                                   double *__restrict__ V, int64_t ldv) {
-    __shared__ __attribute__((aligned(16))) double s_tab[PM_POWTAB_LEN];
-    __shared__ __attribute__((aligned(16))) double s_rt[PM_ROOT21_LEN + 1];
-    const int tid = threadIdx.x, lane = tid & 63;
-    pm_load_powtab(s_tab, tid, blockDim.x);
-    const bool r21 = !signed_w && inv_rho > 0.0 && fabs(1.0 / inv_rho - 21.0) < 1e-9;
-    const bool r6 = inv_rho > 0.0 && fabs(1.0 / inv_rho - 6.0) < 1e-9;
-    if (!PM_POW_HWSEED && r21) pm_load_root21(s_rt, pm_powtab_dev, tid, blockDim.x);
-    else if (!PM_POW_HWSEED && r6) pm_load_root6(s_rt, pm_powtab_dev, tid, blockDim.x);
-    __syncthreads();
-    const int K = 1 + H + S;
-    const int64_t wave0 = (int64_t)blockIdx.x * RV_WAVES + (tid >> 6), nwaves = (int64_t)gridDim.x * RV_WAVES;
-    for (int64_t n = wave0; n < N; n += nwaves) {
-        const double *row = X + n * ld;
-        const double lse = lse_in ? lse_in[n] : rv_row_lse(row, K, 1.0, nullptr, lane);
-        int64_t coff[PM_MAX_HPRIME];
-#pragma unroll
-        for (int j = 0; j < PM_MAX_HPRIME; ++j) {
-            int c = (j < Hp) ? cand[n * Hp + j] : 0;
-            c = c < 0 ? 0 : (c >= H ? H - 1 : c);
-            coff[j] = (int64_t)c * D;
-        }
-        double acc[DPL];
-#pragma unroll
-        for (int i = 0; i < DPL; ++i) acc[i] = 0.0;
-        for (int s = 0; s < S; ++s) {
-            const unsigned m = masks[s];
-            const double q = exp(row[1 + H + s] - lse);
-            double T[DPL];
-#pragma unroll
-            for (int i = 0; i < DPL; ++i) T[i] = 0.0;
-#pragma unroll
-            for (int j = 0; j < PM_MAX_HPRIME; ++j) {
-                if ((m >> j) & 1u) {          // uniform
-                    const double *src = Wrho + coff[j];
-#pragma unroll
-                    for (int i = 0; i < DPL; ++i) {
-                        const int d = lane + 64 * i;
-                        T[i] += (d < D) ? src[d] : 0.0;
-                    }
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < DPL; ++i) {
-                const double aT = fabs(T[i]);
-                double wbar = 0.0;
-                if (aT > 0.0)
-                    wbar = r21 ? aT * pm_pow_m20_21(aT, s_rt)
-                               : r6 ? copysign(aT * pm_pow_m5_6(aT, s_rt), T[i])
-                                    : copysign(pm_pow_tab(aT, inv_rho, s_tab), T[i]);
-                acc[i] = fma(q, wbar * wbar, acc[i]);
-            }
-        }
-        double *vrow = V + n * ldv;
-#pragma unroll
-        for (int i = 0; i < DPL; ++i) {
-            const int d = lane + 64 * i;
-            if (d < D) vrow[d] += acc[i];
-        }
-    }
-}
-
 }  // namespace
 
 extern "C" int pm_recon_moments2_f64(const double *logpj, int64_t ld, const double *lse, double a, const double *col_offset,
@@ -332,7 +239,7 @@ extern "C" int pm_recon_moments2_f64(const double *logpj, int64_t ld, const doub
     if (N < 0 || H <= 0 || K <= 0 || ld < K || out_cols < H || ldm < out_cols || single_off < 0 || nblocks < 0 ||
         multi_off < 0 || S < 0 || Hprime < 0 || (S > 0 && Hprime == 0))
         return PM_EINVAL;
-    if (Hprime > PM_MAX_HPRIME || nblocks > RV_MAX_BLOCKVALS || K > INT32_MAX / 2 || H > INT32_MAX / 16 ||
+    if (Hprime > PM_MAX_HPRIME || nblocks > PM_MAX_BLOCKVALS || K > INT32_MAX / 2 || H > INT32_MAX / 16 ||
         out_cols > INT32_MAX / 2)
         return PM_ERANGE;
     const int64_t npair = Hprime * (Hprime - 1) / 2;
@@ -341,8 +248,8 @@ extern "C" int pm_recon_moments2_f64(const double *logpj, int64_t ld, const doub
         return PM_EINVAL;
     if (single_off + nblocks * H > K || multi_off + S > K) return PM_EINVAL;
     if (N == 0) return PM_OK;
-    rv_blockvals bv;
-    for (int c = 0; c < RV_MAX_BLOCKVALS; ++c) bv.v[c] = c < nblocks ? block_values_host[c] : 0.0;
+    pm_blockvals bv;
+    for (int c = 0; c < PM_MAX_BLOCKVALS; ++c) bv.v[c] = c < nblocks ? block_values_host[c] : 0.0;
     hipLaunchKernelGGL(recon_moments2_kernel, dim3(rv_grid(N)), dim3(RV_THREADS), 0, static_cast<hipStream_t>(stream), logpj,
                        ld, lse, a, col_offset, cand, state_vals, N, (int)H, (int)Hprime, (int)K, (int)single_off,
                        (int)nblocks, bv, (int)multi_off, (int)S, m2, ldm, (int)out_cols, p, ldp);
@@ -390,16 +297,6 @@ extern "C" int pm_recon_mca_var_f64(const double *logpj, int64_t ld, const doubl
     if (D > 1024 || Hprime > PM_MAX_HPRIME || H > INT32_MAX / 2048 || S > INT32_MAX / 2) return PM_ERANGE;
     if (!logpj || !cand || !state_masks || !Wrho || !V) return PM_EINVAL;
     if (N == 0 || S == 0) return PM_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid(rv_grid(N)), block(RV_THREADS);
-#define PM_RV_MCA(DPL)                                                                                                       \
-    hipLaunchKernelGGL(recon_mca_var_kernel<DPL>, grid, block, 0, st, logpj, ld, lse, cand, state_masks, Wrho, inv_rho,       \
-                       signed_w, N, (int)H, (int)D, (int)Hprime, (int)S, V, ldv)
-    if (D <= 64) PM_RV_MCA(1);
-    else if (D <= 128) PM_RV_MCA(2);
-    else if (D <= 256) PM_RV_MCA(4);
-    else if (D <= 512) PM_RV_MCA(8);
-    else PM_RV_MCA(16);
-#undef PM_RV_MCA
-    return (int)hipGetLastError();
+    return recon_mca_launch<true>(rv_grid(N), logpj, ld, lse, cand, state_masks, Wrho, inv_rho, signed_w, N, H, D, Hprime, S, V,
+                                  ldv, stream);
 }

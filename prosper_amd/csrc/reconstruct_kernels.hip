@@ -6,7 +6,8 @@
 //                         normalised weights of the leading H states themselves: MCA / MMCA's one-cause weights, a mixture's
 //                         responsibilities (softmax of a X + o).  Yhat = E[s] W^T (+ mu: a column of ones) is then one launch
 //                         of pm_gemm_nt_rows_f64.
-//   recon_mca_kernel      MCA / MMCA: Yhat_nd += sum_{multi-cause s} q_n(s) Wbar_d(s), Wbar with the E-step's own powers.
+//   recon_mca_kernel      (recon_mca.h, shared with the variance) MCA / MMCA: Yhat_nd += sum_{multi-cause s} q_n(s) Wbar_d(s),
+//                         Wbar with the E-step's own powers.
 //
 // One wavefront per datapoint in both; the sums over a row's states run in a fixed order (lane-strided partial sums, xor
 // butterflies) and every output element is written by one lane: no atomics, the same bits in both library builds and whatever
@@ -18,36 +19,14 @@
 
 #include "prosper_hip.h"
 #include "pm_common.h"
+#include "recon_mca.h"
 
 namespace {
 
 constexpr int REC_THREADS = 256;
 constexpr int REC_WAVES = REC_THREADS / 64;
+static_assert(REC_WAVES == RMCA_WAVES, "rec_grid sizes recon_mca_kernel's grid: one row per wavefront");
 constexpr int64_t REC_MAX_BLOCKS = 8192;
-constexpr int REC_MAX_BLOCKVALS = 8;      // value blocks of one-cause states (DSC: K - 1 <= 7)
-
-struct rec_blockvals {
-    double v[REC_MAX_BLOCKVALS];
-};
-
-// log sum_k exp(a x_k + o_k) of one row by a maximum pass and a sum pass (as rows_lse_kernel): NaN for a NaN entry, the
-// maximum itself when it is infinite.  Wave-uniform.
-__device__ __forceinline__ double rec_row_lse(const double *__restrict__ x, int K, double a, const double *__restrict__ off,
-                                              int lane) {
-    double m = -INFINITY;
-    int bad = 0;
-    for (int k = lane; k < K; k += 64) {
-        const double z = a * x[k] + (off ? off[k] : 0.0);
-        bad |= (z != z);
-        m = fmax(m, z);
-    }
-    m = pm_wave_max(m);
-    if (__any(bad)) return NAN;
-    if (isinf(m)) return m;
-    double s = 0.0;
-    for (int k = lane; k < K; k += 64) s += exp(a * x[k] + (off ? off[k] : 0.0) - m);
-    return m + log(pm_wave_sum(s));
-}
 
 // Columns of a row: [soff, soff + nblk H) one-cause blocks (block c: latent h takes the value bv.v[c]), [moff, moff + S) the
 // table states (state s: the latent at candidate position j takes tab[s, j]); every other column (the null state) carries
@@ -56,12 +35,12 @@ __device__ __forceinline__ double rec_row_lse(const double *__restrict__ x, int 
 __global__ __launch_bounds__(REC_THREADS) void recon_expect_kernel(
     const double *__restrict__ X, int64_t ld, const double *__restrict__ lse_in, double a, const double *__restrict__ off,
     const int32_t *__restrict__ cand, const double *__restrict__ tab, int64_t N, int H, int Hp, int K, int soff, int nblk,
-    rec_blockvals bv, int moff, int S, double *__restrict__ out, int64_t ldo, int out_cols, int ones_col) {
+    pm_blockvals bv, int moff, int S, double *__restrict__ out, int64_t ldo, int out_cols, int ones_col) {
     const int lane = threadIdx.x & 63;
     const int64_t wave0 = (int64_t)blockIdx.x * REC_WAVES + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * REC_WAVES;
     for (int64_t n = wave0; n < N; n += nwaves) {
         const double *row = X + n * ld;
-        const double lse = lse_in ? lse_in[n] : rec_row_lse(row, K, a, off, lane);
+        const double lse = lse_in ? lse_in[n] : pm_row_lse(row, K, a, off, lane);
         // ---- table states: per candidate position, sum_s q_s tab[s, j]
         double t[PM_MAX_HPRIME];
         int cj[PM_MAX_HPRIME];
@@ -102,78 +81,6 @@ __global__ __launch_bounds__(REC_THREADS) void recon_expect_kernel(
     }
 }
 
-// MCA / MMCA: Yhat[n, d] += sum_s q_n(s) Wbar_d(s) over the S multi-cause states, q = exp(lpj[n, 1 + H + s] - lse_n),
-// Wbar_d(s) = (sum_{j in s} Wrho[c_j, d])^(1/rho) (MMCA: signed) with the sum in ascending position order and the power
-// functions of mca_estep_kernel, so that Wbar is the E-step's.  Lane l holds dimensions l, l + 64, ...: D <= 64 DPL.
-template <int DPL>
-__global__ __launch_bounds__(REC_THREADS) void recon_mca_kernel(const double *__restrict__ X, int64_t ld,
-                                                                const double *__restrict__ lse_in,
-                                                                const int32_t *__restrict__ cand,
-                                                                const uint16_t *__restrict__ masks,
-                                                                const double *__restrict__ Wrho, double inv_rho, int signed_w,
-                                                                int64_t N, int H, int D, int Hp, int S,
-                                                                double *__restrict__ Yhat, int64_t ldy) {
-    __shared__ __attribute__((aligned(16))) double s_tab[PM_POWTAB_LEN];
-    __shared__ __attribute__((aligned(16))) double s_rt[PM_ROOT21_LEN + 1];
-    const int tid = threadIdx.x, lane = tid & 63;
-    pm_load_powtab(s_tab, tid, blockDim.x);
-    const bool r21 = !signed_w && inv_rho > 0.0 && fabs(1.0 / inv_rho - 21.0) < 1e-9;
-    const bool r6 = inv_rho > 0.0 && fabs(1.0 / inv_rho - 6.0) < 1e-9;
-    if (!PM_POW_HWSEED && r21) pm_load_root21(s_rt, pm_powtab_dev, tid, blockDim.x);
-    else if (!PM_POW_HWSEED && r6) pm_load_root6(s_rt, pm_powtab_dev, tid, blockDim.x);
-    __syncthreads();
-    const int K = 1 + H + S;
-    const int64_t wave0 = (int64_t)blockIdx.x * REC_WAVES + (tid >> 6), nwaves = (int64_t)gridDim.x * REC_WAVES;
-    for (int64_t n = wave0; n < N; n += nwaves) {
-        const double *row = X + n * ld;
-        const double lse = lse_in ? lse_in[n] : rec_row_lse(row, K, 1.0, nullptr, lane);
-        int64_t coff[PM_MAX_HPRIME];
-#pragma unroll
-        for (int j = 0; j < PM_MAX_HPRIME; ++j) {
-            int c = (j < Hp) ? cand[n * Hp + j] : 0;
-            c = c < 0 ? 0 : (c >= H ? H - 1 : c);
-            coff[j] = (int64_t)c * D;
-        }
-        double acc[DPL];
-#pragma unroll
-        for (int i = 0; i < DPL; ++i) acc[i] = 0.0;
-        for (int s = 0; s < S; ++s) {
-            const unsigned m = masks[s];
-            const double q = exp(row[1 + H + s] - lse);
-            double T[DPL];
-#pragma unroll
-            for (int i = 0; i < DPL; ++i) T[i] = 0.0;
-#pragma unroll
-            for (int j = 0; j < PM_MAX_HPRIME; ++j) {
-                if ((m >> j) & 1u) {          // uniform
-                    const double *src = Wrho + coff[j];
-#pragma unroll
-                    for (int i = 0; i < DPL; ++i) {
-                        const int d = lane + 64 * i;
-                        T[i] += (d < D) ? src[d] : 0.0;
-                    }
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < DPL; ++i) {
-                const double aT = fabs(T[i]);
-                double wbar = 0.0;
-                if (aT > 0.0)
-                    wbar = r21 ? aT * pm_pow_m20_21(aT, s_rt)
-                               : r6 ? copysign(aT * pm_pow_m5_6(aT, s_rt), T[i])
-                                    : copysign(pm_pow_tab(aT, inv_rho, s_tab), T[i]);
-                acc[i] = fma(q, wbar, acc[i]);
-            }
-        }
-        double *yrow = Yhat + n * ldy;
-#pragma unroll
-        for (int i = 0; i < DPL; ++i) {
-            const int d = lane + 64 * i;
-            if (d < D) yrow[d] += acc[i];
-        }
-    }
-}
-
 unsigned rec_grid(int64_t N) {
     int64_t nb = (N + REC_WAVES - 1) / REC_WAVES;
     if (nb > REC_MAX_BLOCKS) nb = REC_MAX_BLOCKS;
@@ -193,12 +100,12 @@ extern "C" int pm_recon_expect_f64(const double *logpj, int64_t ld, const double
     if (!logpj || !out || (nblocks > 0 && !block_values_host) || (S > 0 && (!cand || !state_vals)) ||
         (lse && (a != 1.0 || col_offset)))
         return PM_EINVAL;
-    if (Hprime > PM_MAX_HPRIME || nblocks > REC_MAX_BLOCKVALS || K > INT32_MAX / 2 || H > INT32_MAX / 16 ||
+    if (Hprime > PM_MAX_HPRIME || nblocks > PM_MAX_BLOCKVALS || K > INT32_MAX / 2 || H > INT32_MAX / 16 ||
         out_cols > INT32_MAX / 2)
         return PM_ERANGE;
     if (single_off + nblocks * H > K || multi_off + S > K) return PM_EINVAL;
-    rec_blockvals bv;
-    for (int c = 0; c < REC_MAX_BLOCKVALS; ++c) bv.v[c] = c < nblocks ? block_values_host[c] : 0.0;
+    pm_blockvals bv;
+    for (int c = 0; c < PM_MAX_BLOCKVALS; ++c) bv.v[c] = c < nblocks ? block_values_host[c] : 0.0;
     hipLaunchKernelGGL(recon_expect_kernel, dim3(rec_grid(N)), dim3(REC_THREADS), 0, static_cast<hipStream_t>(stream), logpj,
                        ld, lse, a, col_offset, cand, state_vals, N, (int)H, (int)Hprime, (int)K, (int)single_off,
                        (int)nblocks, bv, (int)multi_off, (int)S, out, ldo, (int)out_cols, (int)ones_col);
@@ -212,16 +119,6 @@ extern "C" int pm_recon_mca_f64(const double *logpj, int64_t ld, const double *l
     if (D > 1024 || Hprime > PM_MAX_HPRIME || H > INT32_MAX / 2048 || S > INT32_MAX / 2) return PM_ERANGE;
     if (N == 0 || S == 0) return PM_OK;
     if (!logpj || !cand || !state_masks || !Wrho || !Yhat) return PM_EINVAL;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid(rec_grid(N)), block(REC_THREADS);
-#define PM_REC_MCA(DPL)                                                                                                      \
-    hipLaunchKernelGGL(recon_mca_kernel<DPL>, grid, block, 0, st, logpj, ld, lse, cand, state_masks, Wrho, inv_rho, signed_w, \
-                       N, (int)H, (int)D, (int)Hprime, (int)S, Yhat, ldy)
-    if (D <= 64) PM_REC_MCA(1);
-    else if (D <= 128) PM_REC_MCA(2);
-    else if (D <= 256) PM_REC_MCA(4);
-    else if (D <= 512) PM_REC_MCA(8);
-    else PM_REC_MCA(16);
-#undef PM_REC_MCA
-    return (int)hipGetLastError();
+    return recon_mca_launch<false>(rec_grid(N), logpj, ld, lse, cand, state_masks, Wrho, inv_rho, signed_w, N, H, D, Hprime, S,
+                                   Yhat, ldy, stream);
 }
