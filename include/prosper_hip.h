@@ -476,12 +476,67 @@ int pm_bsc_mstep_rows16_f64(const double *logpj, int64_t ldl, const double *lse,
                             const pm_bsc_estep_params *params_host, int64_t N, int64_t H, int64_t D,
                             int64_t Hprime, double *expect, int64_t lde, double *stats, void *stream);
 /* ... that also leaves the non-zeros of every E[s] row as a list (format of pm_bsc_estep_fused8_nz_f64; rows with more
- * than PM_BSC_NZ_MAX non-zeros count in scalars[3]).  The M-step after a data-truncation step. */
+ * than PM_BSC_NZ_MAX non-zeros count in scalars[3]).  The M-step after a data-truncation step.  Unlike that entry, this one
+ * ALWAYS stores the dense row in `expect` and never writes PM_BSC_NZ_OVERFLOW into slot 0: the list of a row with more than
+ * PM_BSC_NZ_MAX non-zeros holds its first PM_BSC_NZ_MAX.  Follow it with pm_bsc_wp_sparse_f64 (gated on scalars[3]) and the dense
+ * product on `expect`, never with pm_bsc_wp_sparse_expand_f64 / pm_bsc_expand_lists_gated_f64, which would rebuild such a row
+ * from its truncated list.  A cut datapoint gets a zero row and an empty list. */
 int pm_bsc_mstep_rows16_nz_f64(const double *logpj, int64_t ldl, const double *lse, double lse_cut,
                                const int32_t *cand, const uint16_t *state_masks, int64_t S,
                                const pm_bsc_estep_params *params_host, int64_t N, int64_t H, int64_t D,
                                int64_t Hprime, double *expect, int64_t lde, double *stats, uint16_t *nz_idx,
                                double *nz_val, void *stream);
+
+/* Host-only query (no device call, except for the compute units of the current device when `cus` <= 0 under
+ * PM_BSC_PLAN_FUSED8): the launch that a Binary Sparse Coding entry point would make for N >= 1 datapoints of this shape; the
+ * launchers, the *_supported predicates and pm_bsc_fused8_main_rows take every one of these decisions from the same functions.
+ * `which`: PM_BSC_PLAN_SELECT (pm_bsc_select_f64), _ESTEP (pm_bsc_estep_f64), _MSTEP_ROWS (pm_bsc_mstep_rows_f64),
+ * _SELECT_ESTEP (pm_bsc_select_estep_f64), _MSTEP_ROWS16 (pm_bsc_mstep_rows16_f64; with PM_BSC_PLAN_LISTS _nz_f64), _FUSED
+ * (pm_bsc_estep_fused_f64), _FUSED8 (pm_bsc_estep_fused8_f64; with PM_BSC_PLAN_LISTS _nz_f64 and _defer_f64).
+ * `flags`: the entry's `mode` argument in bits 0..4 (SELECT_ESTEP, FUSED, FUSED8: at least one of bits 0 and 1),
+ * PM_BSC_PLAN_STATS (`stats` given: FUSED, FUSED8), PM_BSC_PLAN_LISTS (`nz_idx` given: MSTEP_ROWS16, FUSED8).
+ * `S`: the length of the state table handed in.  `gamma` is read where the entry takes it (SELECT_ESTEP, FUSED, FUSED8), and
+ * by MSTEP_ROWS for the length of the pair lists: sum_g C(Hprime, g) g^2 when S is the complete state set of sizes
+ * 2 .. gamma, else the upper bound S gamma^2.  `D` is read by FUSED and FUSED8 (the K dimension).  `cus`: compute units for
+ * the FUSED8 split, <= 0: those of the current device (256 when there is none).
+ * out[0..PM_BSC_PLAN_LEN):
+ *   0 family       PM_BSC_FAMILY_WAVE (one wavefront per datapoint: bsc_kernels.hip), _LANES16 (sixteen lanes per datapoint:
+ *                  bsc_rows16.hip), _FUSED (bsc_fused.hip), _FUSED8 (bsc_fused8.hip)
+ *   1 VPL          latents per lane: SELECT 1, 2, 4, 8, 16 (H <= 64, 128, 256, 512, 1024); LANES16 1, 2, 4, 8, 16, 32
+ *                  (H <= 16, 32, 64, 128, 256, 512); else 0
+ *   2 NJ           16-latent column blocks per wavefront: FUSED 8 (H <= 128) or 16, FUSED8 8; else 0
+ *   3 HP, 4 GAMMA  FUSED8: the instantiation (5 .. 8; 3 or 4); else 0
+ *   5 FULL         FUSED: H == 16 NJ; FUSED8: H == 256 (no shadow rows of W); else 0
+ *   6 MSTATS       FUSED, FUSED8: statistics in the same pass; SELECT_ESTEP: the E-step instantiation (mode bit 1);
+ *                  MSTEP_ROWS16: the list-writing instantiation
+ *   7 LDS bytes    dynamic shared memory of the launch (FUSED8: of the main launch)
+ *   8 grid         workgroups (FUSED8: of both launches together)
+ *   9 main rows, 10 main grid, 11 TAIL rows, 12 TAIL grid, 13 TAIL LDS bytes      FUSED8 only (else 0): the leading rows the
+ *                  128-row main launch takes -- whole rounds of `cus` workgroups; everything when the ragged round is at
+ *                  least 70 % full or exceeds two rounds of 16-row TAIL workgroups (2 cus 16 rows) -- and the rest
+ * Returns PM_OK, PM_EINVAL (null `out`, unknown `which` or flag, H, Hprime or N < 1, S < 0; D < 1 where D is read; no mode
+ * bit 0 or 1, gamma outside 1 .. Hprime with mode bit 1, STATS without mode bit 1, LISTS without STATS) or PM_ERANGE exactly
+ * where the launcher returns it for the shape: Hprime > H, H > PM_MAX_H, Hprime > PM_MAX_HPRIME, S > 65535 or the LDS layout
+ * above 160 KB (WAVE); !pm_bsc_rows16_supported, lists with !pm_bsc_rows16_nz_supported (LANES16); !pm_bsc_fused_supported,
+ * mode bits above 1, STATS with Hprime > 8 (FUSED); !pm_bsc_fused8_supported, !pm_bsc_fused8_whole_shard, mode bits above 1
+ * (FUSED8); a value of out[] beyond INT32_MAX (a shard of more than 2^31 rows). */
+#define PM_BSC_PLAN_SELECT 0
+#define PM_BSC_PLAN_ESTEP 1
+#define PM_BSC_PLAN_MSTEP_ROWS 2
+#define PM_BSC_PLAN_SELECT_ESTEP 3
+#define PM_BSC_PLAN_MSTEP_ROWS16 4
+#define PM_BSC_PLAN_FUSED 5
+#define PM_BSC_PLAN_FUSED8 6
+#define PM_BSC_PLAN_MODE 31
+#define PM_BSC_PLAN_STATS 32
+#define PM_BSC_PLAN_LISTS 64
+#define PM_BSC_FAMILY_WAVE 1
+#define PM_BSC_FAMILY_LANES16 2
+#define PM_BSC_FAMILY_FUSED 3
+#define PM_BSC_FAMILY_FUSED8 4
+#define PM_BSC_PLAN_LEN 14
+int pm_bsc_plan(int which, int64_t H, int64_t D, int64_t Hprime, int64_t S, int64_t gamma, int flags, int64_t N, int cus,
+                int32_t *out);
 
 /* ---------------------------------------------------------------------------------------
  * Maximal Causes Analysis (prosper/em/camodels/mca_et.py)

@@ -101,6 +101,7 @@ SIGNATURES = {
     "pm_bsc_wp_sparse_expand_f64": (C.c_int, [c_dp, c_dp, c_dp, i64, c_dp, c_dp, i64, i64, i64, i64, c_dp]),
     "pm_gemm_tn_acc_gated_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, i64, i64, i64, i64, c_dp, c_dp]),
     "pm_gemm_tn_acc_rows_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, i64, i64, i64, c_dp, c_dp, i64, i64, c_dp]),
+    "pm_bsc_plan": (C.c_int, [C.c_int, i64, i64, i64, i64, i64, C.c_int, i64, C.c_int, C.POINTER(C.c_int32)]),
     "pm_bsc_mstep_rows16_f64": (C.c_int, [c_dp, i64, c_dp, C.c_double, c_dp, c_dp, i64,
                                           C.POINTER(EStepParams), i64, i64, i64, i64, c_dp, i64, c_dp, c_dp]),
     "pm_bsc_mstep_rows16_nz_f64": (C.c_int, [c_dp, i64, c_dp, C.c_double, c_dp, c_dp, i64,
@@ -243,7 +244,7 @@ class HipError(RuntimeError):
     pass
 
 
-MIN_VERSION = 1027
+MIN_VERSION = 1028
 _lib = None
 _lib_det = None
 LIB_PATH_DET = os.path.join(os.path.dirname(LIB_PATH), "libprosper_hip_det.so")

@@ -20,6 +20,7 @@
 #include "prosper_hip.h"
 #include "pm_common.h"
 #include "bsc_rows16_body.h"
+#include "bsc_plan.h"
 
 namespace {
 
@@ -320,12 +321,34 @@ size_t fused_lds_bytes(int64_t H, int64_t Hp, int64_t S) {
 
 }  // namespace
 
-// The fused kernel covers H <= 256 latents (16 accumulator tiles per wavefront), D a multiple of 8, 16-byte aligned
-// rows, and whatever pm_bsc_rows16_supported admits for the row passes.
+// Launch decisions of the fused kernel (bsc_plan.h): the launcher and the two predicates below switch on this, and
+// pm_bsc_plan exports it.  The fused kernel covers H <= 256 latents (16 accumulator tiles per wavefront), D a multiple of 8,
+// 16-byte aligned rows, and whatever pm_bsc_rows16_supported admits for the row passes, with the epilogue's layout within
+// 80 KB (two workgroups per CU).  `flags`: mode bits and PM_BSC_PLAN_STATS; flags = 1 asks for the shape alone.
+int pm_bsc::plan_fused(int64_t H, int64_t D, int64_t Hprime, int64_t S, int flags, int64_t N, Plan *p) {
+    const int mode = flags & PM_BSC_PLAN_MODE;
+    const bool stats = flags & PM_BSC_PLAN_STATS;
+    if (H <= 0 || D <= 0 || Hprime <= 0 || S < 0 || N < 1 || !(mode & 3) || (stats && !(mode & 2))) return PM_EINVAL;
+    if (H > 256 || D < DK || D % DK != 0) return PM_ERANGE;
+    if (!pm_bsc_rows16_supported(H, Hprime, S)) return PM_ERANGE;
+    if (make_layout((int)H, (int)Hprime, (int)S, 1).bytes > 80 * 1024) return PM_ERANGE;
+    if (mode & ~3) return PM_ERANGE;                  // (BSC's own ranking only)
+    if (stats && Hprime > 8) return PM_ERANGE;        // (the M-statistics ride on the three-phase row passes)
+    const int64_t tiles = (N + AROWS - 1) / AROWS;
+    if (tiles > INT32_MAX) return PM_ERANGE;
+    *p = Plan{};
+    p->family = PM_BSC_FAMILY_FUSED;
+    p->nj = H <= 128 ? 8 : 16;
+    p->full = H == 16 * p->nj ? 1 : 0;
+    p->mstats = stats ? 1 : 0;
+    p->lds = p->nj == 8 ? fused_lds_bytes<8, 4>(H, Hprime, S) : fused_lds_bytes<16, 4>(H, Hprime, S);
+    p->grid = tiles;
+    return PM_OK;
+}
+
 extern "C" int pm_bsc_fused_supported(int64_t H, int64_t D, int64_t Hprime, int64_t S) {
-    if (H <= 0 || H > 256 || D < DK || D % DK != 0) return 0;
-    if (!pm_bsc_rows16_supported(H, Hprime, S)) return 0;
-    return make_layout((int)H, (int)Hprime, (int)S, 1).bytes <= 80 * 1024 ? 1 : 0;   // two workgroups per CU
+    pm_bsc::Plan pl;
+    return pm_bsc::plan_fused(H, D, Hprime, S, 1, 1, &pl) == PM_OK ? 1 : 0;
 }
 
 #ifdef PM_FUSED_STAMPS
@@ -337,19 +360,20 @@ extern "C" int pm_fused_read_stamps(unsigned long long *host, int n) {
 // Workgroups of the fused kernel one CU holds at once for this shape (LDS- and register-limited; 2 is the design
 // point: one in its K-loop on the matrix pipe while the other runs its row passes).  <= 0: not supported / error.
 extern "C" int pm_bsc_fused_occupancy(int64_t H, int64_t D, int64_t Hprime, int64_t S) {
-    if (!pm_bsc_fused_supported(H, D, Hprime, S)) return 0;
+    pm_bsc::Plan pl;
+    if (pm_bsc::plan_fused(H, D, Hprime, S, 1, 1, &pl) != PM_OK) return 0;
     int n = 0;
     hipError_t e;
 #define PM_OCC(NJ, ST)                                                                                                 \
     do {                                                                                                               \
-        const size_t shmem = fused_lds_bytes<NJ, ST>(H, Hprime, S);                                                       \
+        const size_t shmem = pl.lds;                                                                                   \
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(bsc_estep_fused_kernel<NJ, ST, false, false>),          \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);                               \
         if (e == hipSuccess)                                                                                           \
             e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, bsc_estep_fused_kernel<NJ, ST, false, false>, 256,    \
                                                              shmem);                                                   \
     } while (0)
-    if (H <= 128) PM_OCC(8, 4);
+    if (pl.nj == 8) PM_OCC(8, 4);
     else PM_OCC(16, 4);
 #undef PM_OCC
     return e == hipSuccess ? n : -(int)e;
@@ -378,13 +402,14 @@ extern "C" int pm_bsc_estep_fused_f64(const double *Y, int64_t ldy, const double
     if ((mode & 2) && S > 0)
         for (int g = 0; g < gamma; ++g) so.off[g] = size_offsets_host[g];  // off[g-2] = first state of size g
     pm_bsc_estep_params P = params_host ? *params_host : pm_bsc_estep_params{0, 0, 0, 0};
-    const int64_t tiles = (N + AROWS - 1) / AROWS;
-    if (tiles > INT32_MAX) return PM_ERANGE;
-    dim3 grid((unsigned)tiles), block(256);
+    pm_bsc::Plan pl;
+    if (int e = pm_bsc::plan_fused(H, D, Hprime, S, (mode & PM_BSC_PLAN_MODE) | (stats ? PM_BSC_PLAN_STATS : 0), N, &pl))
+        return e;
+    dim3 grid((unsigned)pl.grid), block(256);
     hipStream_t s = static_cast<hipStream_t>(stream);
 #define PM_LAUNCH_FM(NJ, ST, F, M)                                                                                     \
     do {                                                                                                               \
-        const size_t shmem = fused_lds_bytes<NJ, ST>(H, Hprime, S);                                                    \
+        const size_t shmem = pl.lds;                                                                                   \
         if (int e = (int)hipFuncSetAttribute(reinterpret_cast<const void *>(bsc_estep_fused_kernel<NJ, ST, F, M>),     \
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem))                  \
             return e;                                                                                                  \
@@ -394,7 +419,7 @@ extern "C" int pm_bsc_estep_fused_f64(const double *Y, int64_t ldy, const double
     } while (0)
 #define PM_LAUNCH_F(NJ, ST, F)              \
     do {                                    \
-        if (stats) {                        \
+        if (pl.mstats) {                    \
             PM_LAUNCH_FM(NJ, ST, F, true);  \
         } else {                            \
             PM_LAUNCH_FM(NJ, ST, F, false); \
@@ -402,13 +427,13 @@ extern "C" int pm_bsc_estep_fused_f64(const double *Y, int64_t ldy, const double
     } while (0)
 #define PM_LAUNCH(NJ, ST)                  \
     do {                                   \
-        if (H == 16 * NJ) {                \
+        if (pl.full) {                     \
             PM_LAUNCH_F(NJ, ST, true);     \
         } else {                           \
             PM_LAUNCH_F(NJ, ST, false);    \
         }                                  \
     } while (0)
-    if (H <= 128) PM_LAUNCH(8, 4);
+    if (pl.nj == 8) PM_LAUNCH(8, 4);
     else PM_LAUNCH(16, 4);
 #undef PM_LAUNCH
 #undef PM_LAUNCH_F

@@ -18,6 +18,7 @@
 #include "prosper_hip.h"
 #include "pm_common.h"
 #include "bsc_rows16_body.h"
+#include "bsc_plan.h"
 
 namespace pm_fused8 {
 
@@ -1122,9 +1123,13 @@ static int fused8_states(int64_t hp, int64_t gamma) {
     return s;
 }
 
-extern "C" int pm_bsc_fused8_supported(int64_t H, int64_t D, int64_t Hprime, int64_t S) {
-    if (H <= 128 || H > 256 || D < DK || D % DK != 0 || Hprime < 5 || Hprime > 8) return 0;
-    return (S > 0 && (S == fused8_states(Hprime, 3) || S == fused8_states(Hprime, 4))) ? 1 : 0;
+// compute units the split of a shard is planned for: `cus` when positive, else those of the current device (256 without one)
+static int fused8_cus(int cus) {
+    if (cus > 0) return cus;
+    int dev = 0;
+    cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return cus > 0 ? cus : 256;
 }
 
 // pm_bsc_estep_fused8_f64 takes a WHOLE shard in one call -- whole rounds of 128-row tiles plus the TAIL kernel for a
@@ -1132,17 +1137,52 @@ extern "C" int pm_bsc_fused8_supported(int64_t H, int64_t D, int64_t Hprime, int
 // Leading rows of an N-row shard the main launch takes (the TAIL launch takes the rest): whole rounds of resident
 // workgroups (one per CU); everything when the ragged round is mostly full (>= 70 %) or too large for two rounds of 16-row
 // workgroups.
-extern "C" int64_t pm_bsc_fused8_main_rows(int64_t N, int64_t D) {
+static int64_t fused8_main_rows(int64_t N, int64_t D, int cus) {
     if (N <= 0) return 0;
     if (D % TAIL_DK != 0) return N;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-    const int64_t rnd = (int64_t)cus * 128;
+    const int64_t rnd = (int64_t)fused8_cus(cus) * 128;
     const int64_t main_rows = N / rnd * rnd, rest = N - main_rows;
-    if (rest * 10 >= rnd * 7 || rest > 2 * (int64_t)cus * TAIL_ROWS) return N;
+    if (rest * 10 >= rnd * 7 || rest > 2 * (rnd / 128) * TAIL_ROWS) return N;
     return main_rows;
 }
+
+// Launch decisions of the 16-wavefront kernel and its TAIL twin (bsc_plan.h): the launcher, the predicates and
+// pm_bsc_fused8_main_rows below switch on this, and pm_bsc_plan exports it.  `gamma` = -1: either complete state set (what
+// pm_bsc_fused8_supported asks); `flags`: mode bits, PM_BSC_PLAN_STATS, PM_BSC_PLAN_LISTS.
+int pm_bsc::plan_fused8(int64_t H, int64_t D, int64_t Hprime, int64_t S, int64_t gamma, int flags, int64_t N, int cus,
+                        Plan *p) {
+    const int mode = flags & PM_BSC_PLAN_MODE;
+    const bool stats = flags & PM_BSC_PLAN_STATS, lists = flags & PM_BSC_PLAN_LISTS;
+    if (H <= 0 || D <= 0 || Hprime <= 0 || S < 0 || N < 1 || !(mode & 3) || (stats && !(mode & 2)) || (lists && !stats))
+        return PM_EINVAL;
+    if ((mode & 2) && gamma != -1 && (gamma < 1 || gamma > Hprime)) return PM_EINVAL;
+    if (H <= 128 || H > 256 || D < DK || D % DK != 0 || Hprime < 5 || Hprime > 8) return PM_ERANGE;
+    if (S <= 0 || (S != fused8_states(Hprime, 3) && S != fused8_states(Hprime, 4))) return PM_ERANGE;
+    if (mode & ~3) return PM_ERANGE;
+    if (gamma != -1 && S != fused8_states(Hprime, gamma)) return PM_ERANGE;     // the complete state set of sizes 2 .. gamma
+    *p = Plan{};
+    p->family = PM_BSC_FAMILY_FUSED8;
+    p->nj = NJ;
+    p->hp = (int)Hprime;
+    p->gamma = S == fused8_states(Hprime, 4) ? 4 : 3;
+    p->full = H == HT ? 1 : 0;
+    p->mstats = stats ? 1 : 0;
+    p->main_rows = fused8_main_rows(N, D, cus);
+    p->tail_rows = N - p->main_rows;
+    p->grid = (p->main_rows + 127) / 128;
+    p->tail_grid = (p->tail_rows + TAIL_ROWS - 1) / TAIL_ROWS;
+    if (p->grid > INT32_MAX || p->tail_grid > INT32_MAX) return PM_ERANGE;
+    p->lds = (size_t)LEAN16_LDS_BYTES;      // (>= the ring: 4 stages x 24 KB)
+    p->lds_tail = (size_t)TAIL_RING_BYTES > (size_t)LEAN_LDS_BYTES ? (size_t)TAIL_RING_BYTES : (size_t)LEAN_LDS_BYTES;
+    return PM_OK;
+}
+
+extern "C" int pm_bsc_fused8_supported(int64_t H, int64_t D, int64_t Hprime, int64_t S) {
+    pm_bsc::Plan pl;
+    return pm_bsc::plan_fused8(H, D, Hprime, S, -1, 1, 1, 256, &pl) == PM_OK ? 1 : 0;
+}
+
+extern "C" int64_t pm_bsc_fused8_main_rows(int64_t N, int64_t D) { return fused8_main_rows(N, D, 0); }
 
 extern "C" int pm_bsc_fused8_whole_shard(int64_t H, int64_t Hprime, int64_t gamma, int64_t S) {
     if (H <= 128 || H > 256) return 0;
@@ -1223,7 +1263,11 @@ extern "C" int pm_bsc_estep_fused8_defer_f64(const double *Y, int64_t ldy, const
             off += c;
         }
     }
-    const size_t shmem_s = (size_t)LEAN16_LDS_BYTES;      // (>= the ring: 4 stages x 24 KB)
+    pm_bsc::Plan pl;
+    if (int e = pm_bsc::plan_fused8(H, D, Hprime, S, gamma,
+                                    (mode & PM_BSC_PLAN_MODE) | (stats ? PM_BSC_PLAN_STATS : 0) | (nz_idx ? PM_BSC_PLAN_LISTS : 0),
+                                    N, 0, &pl))
+        return e;
 #define PM_LAUNCH8SMTH(HPV, G, F, M, T, GRID, SH, NN, R0)                                                              \
     do {                                                                                                               \
         if (int e = (int)hipFuncSetAttribute(reinterpret_cast<const void *>(bsc_estep_fused8s_kernel<4, HPV, G, F, M, T>), \
@@ -1237,14 +1281,14 @@ extern "C" int pm_bsc_estep_fused8_defer_f64(const double *Y, int64_t ldy, const
     } while (0)
 #define PM_LAUNCH8SMT(G, F, M, T, GRID, SH, NN, R0)                                  \
     do {                                                                             \
-        if (Hprime == 8) PM_LAUNCH8SMTH(8, G, F, M, T, GRID, SH, NN, R0);            \
-        else if (Hprime == 7) PM_LAUNCH8SMTH(7, G, F, M, T, GRID, SH, NN, R0);       \
-        else if (Hprime == 6) PM_LAUNCH8SMTH(6, G, F, M, T, GRID, SH, NN, R0);       \
+        if (pl.hp == 8) PM_LAUNCH8SMTH(8, G, F, M, T, GRID, SH, NN, R0);             \
+        else if (pl.hp == 7) PM_LAUNCH8SMTH(7, G, F, M, T, GRID, SH, NN, R0);        \
+        else if (pl.hp == 6) PM_LAUNCH8SMTH(6, G, F, M, T, GRID, SH, NN, R0);        \
         else PM_LAUNCH8SMTH(5, G, F, M, T, GRID, SH, NN, R0);                        \
     } while (0)
 #define PM_LAUNCH8ST(G, F, T, GRID, SH, NN, R0)            \
     do {                                                    \
-        if (stats) {                                        \
+        if (pl.mstats) {                                    \
             PM_LAUNCH8SMT(G, F, true, T, GRID, SH, NN, R0); \
         } else {                                            \
             PM_LAUNCH8SMT(G, F, false, T, GRID, SH, NN, R0);\
@@ -1252,11 +1296,11 @@ extern "C" int pm_bsc_estep_fused8_defer_f64(const double *Y, int64_t ldy, const
     } while (0)
 #define PM_LAUNCH8SGF(T, GRID, SH, NN, R0)                             \
     do {                                                                \
-        if (gamma == 4) {                                               \
-            if (H == 256) PM_LAUNCH8ST(4, true, T, GRID, SH, NN, R0);   \
+        if (pl.gamma == 4) {                                            \
+            if (pl.full) PM_LAUNCH8ST(4, true, T, GRID, SH, NN, R0);    \
             else PM_LAUNCH8ST(4, false, T, GRID, SH, NN, R0);           \
         } else {                                                        \
-            if (H == 256) PM_LAUNCH8ST(3, true, T, GRID, SH, NN, R0);   \
+            if (pl.full) PM_LAUNCH8ST(3, true, T, GRID, SH, NN, R0);    \
             else PM_LAUNCH8ST(3, false, T, GRID, SH, NN, R0);           \
         }                                                               \
     } while (0)
@@ -1264,11 +1308,8 @@ extern "C" int pm_bsc_estep_fused8_defer_f64(const double *Y, int64_t ldy, const
         // Whole rounds of resident workgroups (one 128-row tile per CU) go to the main launch; a ragged last round that
         // fills most of a round stays with it; a small remainder (up to two rounds of 16-row workgroups) goes to the TAIL
         // kernel, whose workgroups split K four ways; anything in between is cheaper as a partial round of tiles.
-        const int64_t main_rows = pm_bsc_fused8_main_rows(N, D);
-        const int64_t rest = N - main_rows;
-        if (main_rows > 0 && part != 2) PM_LAUNCH8SGF(false, (main_rows + 127) / 128, shmem_s, main_rows, 0);
-        const size_t shmem_t = (size_t)TAIL_RING_BYTES > (size_t)LEAN_LDS_BYTES ? (size_t)TAIL_RING_BYTES : (size_t)LEAN_LDS_BYTES;
-        if (rest > 0 && part != 1) PM_LAUNCH8SGF(true, (rest + TAIL_ROWS - 1) / TAIL_ROWS, shmem_t, N, main_rows);
+        if (pl.main_rows > 0 && part != 2) PM_LAUNCH8SGF(false, pl.grid, pl.lds, pl.main_rows, 0);
+        if (pl.tail_rows > 0 && part != 1) PM_LAUNCH8SGF(true, pl.tail_grid, pl.lds_tail, N, pl.main_rows);
     }
 #undef PM_LAUNCH8SGF
 #undef PM_LAUNCH8ST

@@ -16,6 +16,7 @@
 
 #include "prosper_hip.h"
 #include "pm_common.h"
+#include "bsc_plan.h"
 
 namespace {
 
@@ -335,23 +336,92 @@ static int allow_lds(const void *kernel, size_t bytes) {
     return (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
+// Launch decisions of the three wavefront-per-datapoint kernels (bsc_plan.h): the launchers below switch on this, and
+// pm_bsc_plan exports it.
+int pm_bsc::plan_wave(int which, int64_t H, int64_t Hprime, int64_t S, int64_t pair_len, int64_t N, Plan *p) {
+    if (H <= 0 || Hprime <= 0 || S < 0 || pair_len < 0 || N < 1) return PM_EINVAL;
+    if (H > PM_MAX_H || Hprime > PM_MAX_HPRIME || Hprime > H) return PM_ERANGE;
+    *p = Plan{};
+    p->family = PM_BSC_FAMILY_WAVE;
+    p->grid = grid_for_rows(N);
+    if (which == PM_BSC_PLAN_SELECT) {
+        p->vpl = H <= 64 ? 1 : H <= 128 ? 2 : H <= 256 ? 4 : H <= 512 ? 8 : 16;
+        return PM_OK;
+    }
+    if (S > 65535) return PM_ERANGE;
+    if (which == PM_BSC_PLAN_ESTEP)
+        p->lds = sizeof(double) * (H + WAVES * (16 + 256)) + sizeof(uint16_t) * S;
+    else
+        p->lds = sizeof(double) * (2 * H + WAVES * (H + S) + 3 * WAVES) + sizeof(int32_t) * (Hprime * Hprime + 1) +
+                 sizeof(uint16_t) * (S + pair_len);
+    return p->lds > 160 * 1024 ? PM_ERANGE : PM_OK;
+}
+
+// entries of the pair lists of pm_bsc_mstep_rows_f64 (sum over the states of |s|^2): exact for the complete state set of
+// sizes 2 .. gamma, else the upper bound S gamma^2
+static int64_t plan_pair_len(int64_t Hprime, int64_t S, int64_t gamma) {
+    if (gamma < 2 || S <= 0) return 0;
+    int64_t states = 0, len = 0, c = Hprime;
+    for (int64_t g = 2; g <= gamma && g <= Hprime; ++g) {
+        c = c * (Hprime - g + 1) / g;              // C(Hprime, g) from C(Hprime, g - 1)
+        states += c;
+        len += c * g * g;
+    }
+    return states == S ? len : S * gamma * gamma;
+}
+
+extern "C" int pm_bsc_plan(int which, int64_t H, int64_t D, int64_t Hprime, int64_t S, int64_t gamma, int flags, int64_t N,
+                           int cus, int32_t *out) {
+    using namespace pm_bsc;
+    if (!out || which < PM_BSC_PLAN_SELECT || which > PM_BSC_PLAN_FUSED8) return PM_EINVAL;
+    const int allowed = which == PM_BSC_PLAN_SELECT_ESTEP ? PM_BSC_PLAN_MODE
+                      : which == PM_BSC_PLAN_MSTEP_ROWS16 ? PM_BSC_PLAN_LISTS
+                      : which == PM_BSC_PLAN_FUSED        ? PM_BSC_PLAN_MODE | PM_BSC_PLAN_STATS
+                      : which == PM_BSC_PLAN_FUSED8       ? PM_BSC_PLAN_MODE | PM_BSC_PLAN_STATS | PM_BSC_PLAN_LISTS
+                                                          : 0;
+    if (flags & ~allowed) return PM_EINVAL;
+    Plan p;
+    int e;
+    if (which <= PM_BSC_PLAN_MSTEP_ROWS)
+        e = plan_wave(which, H, Hprime, S, which == PM_BSC_PLAN_MSTEP_ROWS ? plan_pair_len(Hprime, S, gamma) : 0, N, &p);
+    else if (which <= PM_BSC_PLAN_MSTEP_ROWS16)
+        e = (which == PM_BSC_PLAN_SELECT_ESTEP && (flags & 2) && (gamma < 1 || gamma > Hprime))
+                ? PM_EINVAL
+                : plan_rows16(which, H, Hprime, S, flags, N, &p);
+    else if (which == PM_BSC_PLAN_FUSED)
+        e = ((flags & 2) && (gamma < 1 || gamma > Hprime)) ? PM_EINVAL : plan_fused(H, D, Hprime, S, flags, N, &p);
+    else
+        e = plan_fused8(H, D, Hprime, S, gamma < 0 ? 0 : gamma, flags, N, cus, &p);
+    if (e) return e;
+    const int64_t v[PM_BSC_PLAN_LEN] = {p.family, p.vpl, p.nj, p.hp, p.gamma, p.full, p.mstats, (int64_t)p.lds,
+                                        p.grid + p.tail_grid, p.main_rows, p.main_rows ? p.grid : 0, p.tail_rows, p.tail_grid,
+                                        (int64_t)p.lds_tail};
+    for (int i = 0; i < PM_BSC_PLAN_LEN; ++i)
+        if (v[i] > INT32_MAX) return PM_ERANGE;         // (rows of a shard beyond 2^31: not reportable, and not launchable)
+    for (int i = 0; i < PM_BSC_PLAN_LEN; ++i) out[i] = (int32_t)v[i];
+    return PM_OK;
+}
+
 extern "C" int pm_bsc_select_f64(const double *scores, int64_t lds, const double *wnorm2, int64_t wnorm2_stride,
                                  const double *ynorm2, int64_t N, int64_t H, int64_t Hprime, int32_t *cand,
                                  void *stream) {
     if (!scores || !wnorm2 || !ynorm2 || !cand || N < 0 || H <= 0 || Hprime <= 0 || lds < H || wnorm2_stride <= 0)
         return PM_EINVAL;
-    if (H > PM_MAX_H || Hprime > PM_MAX_HPRIME || Hprime > H) return PM_ERANGE;
+    pm_bsc::Plan pl;
+    if (int e = pm_bsc::plan_wave(PM_BSC_PLAN_SELECT, H, Hprime, 0, 0, N > 0 ? N : 1, &pl)) return e;
     if (N == 0) return PM_OK;
-    dim3 grid((unsigned)grid_for_rows(N)), block(256);
+    dim3 grid((unsigned)pl.grid), block(256);
     hipStream_t s = static_cast<hipStream_t>(stream);
 #define PM_SELECT(V)                                                                                              \
     hipLaunchKernelGGL(bsc_select_kernel<V>, grid, block, 0, s, scores, lds, wnorm2, wnorm2_stride, ynorm2, N, (int)H, \
                        (int)Hprime, cand)
-    if (H <= 64) PM_SELECT(1);
-    else if (H <= 128) PM_SELECT(2);
-    else if (H <= 256) PM_SELECT(4);
-    else if (H <= 512) PM_SELECT(8);
-    else PM_SELECT(16);
+    switch (pl.vpl) {
+        case 1: PM_SELECT(1); break;
+        case 2: PM_SELECT(2); break;
+        case 4: PM_SELECT(4); break;
+        case 8: PM_SELECT(8); break;
+        default: PM_SELECT(16); break;
+    }
 #undef PM_SELECT
     return (int)hipGetLastError();
 }
@@ -364,12 +434,15 @@ extern "C" int pm_bsc_estep_f64(const double *scores, int64_t lds, const double 
     if (!scores || !gram || !ynorm2 || !cand || !params_host || !logpj || N < 0 || H <= 0 || Hprime <= 0 || S < 0 ||
         lds < H || ldl < 1 + H + S || (S > 0 && !state_masks) || ((wmu == nullptr) != (ymu == nullptr)))
         return PM_EINVAL;
+    // (the range test of plan_wave, repeated in front of the N == 0 return: the plan needs N >= 1 and also judges the LDS
+    // layout, which an empty shard must not be refused for -- keep the two in step)
     if (H > PM_MAX_H || Hprime > PM_MAX_HPRIME || Hprime > H || S > 65535) return PM_ERANGE;
     if (N == 0) return PM_OK;
-    const size_t shmem = sizeof(double) * (H + WAVES * (16 + 256)) + sizeof(uint16_t) * S;
-    if (shmem > 160 * 1024) return PM_ERANGE;
+    pm_bsc::Plan pl;
+    if (int e = pm_bsc::plan_wave(PM_BSC_PLAN_ESTEP, H, Hprime, S, 0, N, &pl)) return e;
+    const size_t shmem = pl.lds;
     if (int e = allow_lds(reinterpret_cast<const void *>(bsc_estep_kernel), shmem)) return e;
-    hipLaunchKernelGGL(bsc_estep_kernel, dim3((unsigned)grid_for_rows(N)), dim3(256), shmem,
+    hipLaunchKernelGGL(bsc_estep_kernel, dim3((unsigned)pl.grid), dim3(256), shmem,
                        static_cast<hipStream_t>(stream), scores, lds, gram, ynorm2, wmu, ymu, cand, state_masks, (int)S,
                        *params_host, N, (int)H, (int)Hprime, logpj, ldl, lse);
     return (int)hipGetLastError();
@@ -384,13 +457,15 @@ extern "C" int pm_bsc_mstep_rows_f64(const double *logpj, int64_t ldl, const dou
         Hprime <= 0 || S < 0 || pair_len < 0 || ldl < 1 + H + S || lde < H ||
         (S > 0 && (!state_masks || !pair_states)))
         return PM_EINVAL;
+    // (the range test of plan_wave, repeated in front of the N == 0 return: the plan needs N >= 1 and also judges the LDS
+    // layout, which an empty shard must not be refused for -- keep the two in step)
     if (H > PM_MAX_H || Hprime > PM_MAX_HPRIME || Hprime > H || S > 65535) return PM_ERANGE;
     if (N == 0) return PM_OK;
-    const size_t shmem = sizeof(double) * (2 * H + WAVES * (H + S) + 3 * WAVES) +
-                         sizeof(int32_t) * (Hprime * Hprime + 1) + sizeof(uint16_t) * (S + pair_len);
-    if (shmem > 160 * 1024) return PM_ERANGE;
+    pm_bsc::Plan pl;
+    if (int e = pm_bsc::plan_wave(PM_BSC_PLAN_MSTEP_ROWS, H, Hprime, S, pair_len, N, &pl)) return e;
+    const size_t shmem = pl.lds;
     if (int e = allow_lds(reinterpret_cast<const void *>(bsc_mstep_rows_kernel), shmem)) return e;
-    hipLaunchKernelGGL(bsc_mstep_rows_kernel, dim3((unsigned)grid_for_rows(N)), dim3(256), shmem,
+    hipLaunchKernelGGL(bsc_mstep_rows_kernel, dim3((unsigned)pl.grid), dim3(256), shmem,
                        static_cast<hipStream_t>(stream), logpj, ldl, lse, lse_cut, cand, state_masks, (int)S, pair_ptr,
                        pair_states, *params_host, N, (int)H, (int)D, (int)Hprime, expect, lde, stats);
     return (int)hipGetLastError();

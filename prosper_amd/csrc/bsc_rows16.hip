@@ -20,6 +20,7 @@
 #include "prosper_hip.h"
 #include "pm_common.h"
 #include "bsc_rows16_body.h"
+#include "bsc_plan.h"
 
 namespace {
 
@@ -367,14 +368,6 @@ static int allow_lds16(const void *kernel, size_t bytes) {
 
 }  // namespace
 
-// The fast path covers H <= 512 (VPL <= 32 scores per lane) and states that fit the LDS areas.
-extern "C" int pm_bsc_rows16_supported(int64_t H, int64_t Hprime, int64_t S) {
-    if (H <= 0 || H > 512 || Hprime <= 0 || Hprime > PM_MAX_HPRIME || Hprime > H || S < 0 || S > 4096) return 0;
-    // (up to the CU's whole LDS less a margin for the kernels' static arrays: beyond 80 KB one workgroup per CU -- four wavefronts
-    // -- which still beats the generic two-launch path by a third at H = 256, H' = 10, gamma = 4: DESIGN.md, shape sweep)
-    return make_layout((int)H, (int)Hprime, (int)S, 0).bytes <= PM_ROWS16_LDS_MAX ? 1 : 0;
-}
-
 // The list-writing M-step pass needs one more score row per datapoint slot (ROWS * H doubles) than the plain one.
 static size_t mstep_rows16_lds(int64_t H, int64_t Hprime, int64_t S, bool lists) {
     size_t shmem = sizeof(double) * (2 * H + ROWS * Hprime * Hprime + 12) + sizeof(uint16_t) * S;
@@ -382,9 +375,41 @@ static size_t mstep_rows16_lds(int64_t H, int64_t Hprime, int64_t S, bool lists)
     return shmem;
 }
 
+// Launch decisions of the sixteen-lane kernels (bsc_plan.h): the launchers and the two predicates below switch on this, and
+// pm_bsc_plan exports it.  The fast path covers H <= 512 (VPL <= 32 scores per lane) and states that fit the LDS areas
+// (up to the CU's whole LDS less a margin for the kernels' static arrays: beyond 80 KB one workgroup per CU -- four wavefronts
+// -- which still beats the generic two-launch path by a third at H = 256, H' = 10, gamma = 4: DESIGN.md, shape sweep); list
+// indices are uint16 slots of <= 256 latents.
+int pm_bsc::plan_rows16(int which, int64_t H, int64_t Hprime, int64_t S, int flags, int64_t N, Plan *p) {
+    if (H <= 0 || Hprime <= 0 || S < 0 || N < 1) return PM_EINVAL;
+    if (which == PM_BSC_PLAN_SELECT_ESTEP && !(flags & 3)) return PM_EINVAL;
+    if (H > 512 || Hprime > PM_MAX_HPRIME || Hprime > H || S > 4096) return PM_ERANGE;
+    const size_t select_lds = (size_t)make_layout((int)H, (int)Hprime, (int)S, 0).bytes;
+    if (select_lds > PM_ROWS16_LDS_MAX) return PM_ERANGE;          // (pm_bsc_rows16_supported: asked of both entries)
+    *p = Plan{};
+    p->family = PM_BSC_FAMILY_LANES16;
+    p->vpl = H <= 16 ? 1 : H <= 32 ? 2 : H <= 64 ? 4 : H <= 128 ? 8 : H <= 256 ? 16 : 32;
+    p->grid = grid_groups(N);
+    if (which == PM_BSC_PLAN_SELECT_ESTEP) {
+        p->mstats = (flags & 2) ? 1 : 0;
+        p->lds = select_lds;
+        return PM_OK;
+    }
+    const bool lists = flags & PM_BSC_PLAN_LISTS;
+    if (lists && H > 256) return PM_ERANGE;
+    p->mstats = lists ? 1 : 0;
+    p->lds = mstep_rows16_lds(H, Hprime, S, lists);
+    return p->lds > PM_ROWS16_LDS_MAX ? PM_ERANGE : PM_OK;
+}
+
+extern "C" int pm_bsc_rows16_supported(int64_t H, int64_t Hprime, int64_t S) {
+    pm_bsc::Plan pl;
+    return pm_bsc::plan_rows16(PM_BSC_PLAN_SELECT_ESTEP, H, Hprime, S, 1, 1, &pl) == PM_OK ? 1 : 0;
+}
+
 extern "C" int pm_bsc_rows16_nz_supported(int64_t H, int64_t Hprime, int64_t S) {
-    if (!pm_bsc_rows16_supported(H, Hprime, S) || H > 256) return 0;       // (list indices are uint16 slots of <= 256 latents)
-    return mstep_rows16_lds(H, Hprime, S, true) <= PM_ROWS16_LDS_MAX ? 1 : 0;
+    pm_bsc::Plan pl;
+    return pm_bsc::plan_rows16(PM_BSC_PLAN_MSTEP_ROWS16, H, Hprime, S, PM_BSC_PLAN_LISTS, 1, &pl) == PM_OK ? 1 : 0;
 }
 
 extern "C" int pm_bsc_select_estep_f64(const double *scores, int64_t lds, const double *gram, const double *ynorm2,
@@ -406,8 +431,10 @@ extern "C" int pm_bsc_select_estep_f64(const double *scores, int64_t lds, const 
     if ((mode & 2) && S > 0)
         for (int g = 0; g < gamma; ++g) so.off[g] = size_offsets_host[g];  // off[g-2] = first state of size g
     pm_bsc_estep_params P = params_host ? *params_host : pm_bsc_estep_params{0, 0, 0, 0};
-    const size_t shmem = (size_t)make_layout((int)H, (int)Hprime, (int)S, 0).bytes;
-    dim3 grid((unsigned)grid_groups(N)), block(256);
+    pm_bsc::Plan pl;
+    if (int e = pm_bsc::plan_rows16(PM_BSC_PLAN_SELECT_ESTEP, H, Hprime, S, mode & PM_BSC_PLAN_MODE, N, &pl)) return e;
+    const size_t shmem = pl.lds;
+    dim3 grid((unsigned)pl.grid), block(256);
     hipStream_t s = static_cast<hipStream_t>(stream);
 #define PM_LAUNCH_E(V, E)                                                                                           \
     do {                                                                                                            \
@@ -418,18 +445,20 @@ extern "C" int pm_bsc_select_estep_f64(const double *scores, int64_t lds, const 
     } while (0)
 #define PM_LAUNCH(V)                \
     do {                            \
-        if (mode & 2) {             \
+        if (pl.mstats) {            \
             PM_LAUNCH_E(V, true);   \
         } else {                    \
             PM_LAUNCH_E(V, false);  \
         }                           \
     } while (0)
-    if (H <= 16) PM_LAUNCH(1);
-    else if (H <= 32) PM_LAUNCH(2);
-    else if (H <= 64) PM_LAUNCH(4);
-    else if (H <= 128) PM_LAUNCH(8);
-    else if (H <= 256) PM_LAUNCH(16);
-    else PM_LAUNCH(32);
+    switch (pl.vpl) {
+        case 1: PM_LAUNCH(1); break;
+        case 2: PM_LAUNCH(2); break;
+        case 4: PM_LAUNCH(4); break;
+        case 8: PM_LAUNCH(8); break;
+        case 16: PM_LAUNCH(16); break;
+        default: PM_LAUNCH(32); break;
+    }
 #undef PM_LAUNCH
 #undef PM_LAUNCH_E
     return (int)hipGetLastError();
@@ -499,16 +528,18 @@ extern "C" int pm_bsc_mstep_rows16_nz_f64(const double *logpj, int64_t ldl, cons
     if (!logpj || !lse || !cand || !params_host || !expect || !stats || N < 0 || H <= 0 || D <= 0 || Hprime <= 0 ||
         S < 0 || ldl < 1 + H + S || lde < H || (S > 0 && !state_masks))
         return PM_EINVAL;
+    // (the shape test of plan_rows16, in front of the N == 0 return: the plan needs N >= 1, and an empty shard is not refused
+    // for its lists -- keep the two in step)
     if (!pm_bsc_rows16_supported(H, Hprime, S)) return PM_ERANGE;
     if (N == 0) return PM_OK;
-    if (nz_idx && !pm_bsc_rows16_nz_supported(H, Hprime, S)) return PM_ERANGE;
-    const size_t shmem = mstep_rows16_lds(H, Hprime, S, nz_idx != nullptr);
-    if (shmem > PM_ROWS16_LDS_MAX) return PM_ERANGE;
-    dim3 grid((unsigned)grid_groups(N)), block(256);
+    pm_bsc::Plan pl;
+    if (int e = pm_bsc::plan_rows16(PM_BSC_PLAN_MSTEP_ROWS16, H, Hprime, S, nz_idx ? PM_BSC_PLAN_LISTS : 0, N, &pl)) return e;
+    const size_t shmem = pl.lds;
+    dim3 grid((unsigned)pl.grid), block(256);
     hipStream_t s = static_cast<hipStream_t>(stream);
 #define PM_LAUNCH(V)                                                                                               \
     do {                                                                                                           \
-        if (nz_idx) {                                                                                              \
+        if (pl.mstats) {                                                                                           \
             if (int e = allow_lds16(reinterpret_cast<const void *>(bsc_mstep_rows16_kernel<V, true>), shmem)) return e; \
             hipLaunchKernelGGL((bsc_mstep_rows16_kernel<V, true>), grid, block, shmem, s, logpj, ldl, lse, lse_cut, cand, \
                                state_masks, (int)S, *params_host, N, (int)H, (int)D, (int)Hprime, expect, lde, stats, \
@@ -520,12 +551,14 @@ extern "C" int pm_bsc_mstep_rows16_nz_f64(const double *logpj, int64_t ldl, cons
                                nz_idx, nz_val);                                                                    \
         }                                                                                                          \
     } while (0)
-    if (H <= 16) PM_LAUNCH(1);
-    else if (H <= 32) PM_LAUNCH(2);
-    else if (H <= 64) PM_LAUNCH(4);
-    else if (H <= 128) PM_LAUNCH(8);
-    else if (H <= 256) PM_LAUNCH(16);
-    else PM_LAUNCH(32);
+    switch (pl.vpl) {
+        case 1: PM_LAUNCH(1); break;
+        case 2: PM_LAUNCH(2); break;
+        case 4: PM_LAUNCH(4); break;
+        case 8: PM_LAUNCH(8); break;
+        case 16: PM_LAUNCH(16); break;
+        default: PM_LAUNCH(32); break;
+    }
 #undef PM_LAUNCH
     return (int)hipGetLastError();
 }
