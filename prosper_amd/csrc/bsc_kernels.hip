@@ -22,12 +22,6 @@ namespace {
 
 constexpr int WAVES = 4;  // wavefronts per workgroup
 
-// LDS traffic between lanes of ONE wavefront: order the accesses, no workgroup barrier needed.
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // ---------------------------------------------------------------------------------------------
 // select_Hprimes (bsc_et.py:98-115)
 // ---------------------------------------------------------------------------------------------
@@ -140,7 +134,7 @@ __global__ __launch_bounds__(256) void bsc_estep_kernel(const double *__restrict
             const int i = p / Hp, j = p - i * Hp;
             s_gc[p] = gram[(int64_t)cn[i] * H + cn[j]];
         }
-        wave_lds_sync();
+        pm_wave_lds_sync();
 
         double *out = logpj + n * ldl;
         LseAcc acc{-INFINITY, 0.0};
@@ -186,7 +180,7 @@ __global__ __launch_bounds__(256) void bsc_estep_kernel(const double *__restrict
             const double tot = pm_wave_sum(part);
             if (lane == 0) lse[n] = M + log(tot);
         }
-        wave_lds_sync();  // s_ac / s_gc are rewritten for the next datapoint
+        pm_wave_lds_sync();  // s_ac / s_gc are rewritten for the next datapoint
     }
 }
 
@@ -263,7 +257,7 @@ __global__ __launch_bounds__(256) void bsc_mstep_rows_kernel(const double *__res
             sig += q * ((fv - ppil * (double)__builtin_popcount((unsigned)s_masks[s])) * inv_ecoef);
             s_qs[s] = q;
         }
-        wave_lds_sync();
+        pm_wave_lds_sync();
 
         // second moments over candidate positions: m2[i][j] = sum_{s containing i and j} q_s
         for (int p = lane; p < npairs; p += 64) {
@@ -280,14 +274,14 @@ __global__ __launch_bounds__(256) void bsc_mstep_rows_kernel(const double *__res
                 pm_atomic_add(Wq + (int64_t)lo * H + hi, PM_Q(m2, 0));
             }
         }
-        wave_lds_sync();
+        pm_wave_lds_sync();
 
         for (int h = lane; h < H; h += 64) {
             const double v = s_es[h];
             erow[h] = v;
             atomicAdd(&s_mus[h], PM_Q(v, 0));
         }
-        wave_lds_sync();
+        pm_wave_lds_sync();
     }
 
     // workgroup reduction of the scalar statistics, then one atomic per workgroup and value
@@ -329,11 +323,6 @@ extern "C" int64_t pm_bsc_stats_offset_mus(int64_t H, int64_t D) { return pm_bsc
 extern "C" int64_t pm_bsc_stats_offset_scalars(int64_t H, int64_t D) { return pm_bsc_stats_offset_scalars_dev(H, D); }
 extern "C" int64_t pm_bsc_stats_len(int64_t H, int64_t D) {
     return pm_bsc_stats_offset_scalars_dev(H, D) + PM_BSC_NSCALARS;
-}
-
-static int allow_lds(const void *kernel, size_t bytes) {
-    if (bytes <= 48 * 1024) return 0;
-    return (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
 // Launch decisions of the three wavefront-per-datapoint kernels (bsc_plan.h): the launchers below switch on this, and
@@ -441,7 +430,7 @@ extern "C" int pm_bsc_estep_f64(const double *scores, int64_t lds, const double 
     pm_bsc::Plan pl;
     if (int e = pm_bsc::plan_wave(PM_BSC_PLAN_ESTEP, H, Hprime, S, 0, N, &pl)) return e;
     const size_t shmem = pl.lds;
-    if (int e = allow_lds(reinterpret_cast<const void *>(bsc_estep_kernel), shmem)) return e;
+    if (int e = pm_allow_lds(reinterpret_cast<const void *>(bsc_estep_kernel), shmem)) return e;
     hipLaunchKernelGGL(bsc_estep_kernel, dim3((unsigned)pl.grid), dim3(256), shmem,
                        static_cast<hipStream_t>(stream), scores, lds, gram, ynorm2, wmu, ymu, cand, state_masks, (int)S,
                        *params_host, N, (int)H, (int)Hprime, logpj, ldl, lse);
@@ -464,7 +453,7 @@ extern "C" int pm_bsc_mstep_rows_f64(const double *logpj, int64_t ldl, const dou
     pm_bsc::Plan pl;
     if (int e = pm_bsc::plan_wave(PM_BSC_PLAN_MSTEP_ROWS, H, Hprime, S, pair_len, N, &pl)) return e;
     const size_t shmem = pl.lds;
-    if (int e = allow_lds(reinterpret_cast<const void *>(bsc_mstep_rows_kernel), shmem)) return e;
+    if (int e = pm_allow_lds(reinterpret_cast<const void *>(bsc_mstep_rows_kernel), shmem)) return e;
     hipLaunchKernelGGL(bsc_mstep_rows_kernel, dim3((unsigned)pl.grid), dim3(256), shmem,
                        static_cast<hipStream_t>(stream), logpj, ldl, lse, lse_cut, cand, state_masks, (int)S, pair_ptr,
                        pair_states, *params_host, N, (int)H, (int)D, (int)Hprime, expect, lde, stats);

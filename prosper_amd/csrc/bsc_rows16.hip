@@ -361,11 +361,6 @@ inline int64_t grid_groups(int64_t N) {
     return groups < cap ? (groups < 1 ? 1 : groups) : cap;
 }
 
-static int allow_lds16(const void *kernel, size_t bytes) {
-    if (bytes <= 48 * 1024) return 0;
-    return (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 }  // namespace
 
 // The list-writing M-step pass needs one more score row per datapoint slot (ROWS * H doubles) than the plain one.
@@ -438,7 +433,7 @@ extern "C" int pm_bsc_select_estep_f64(const double *scores, int64_t lds, const 
     hipStream_t s = static_cast<hipStream_t>(stream);
 #define PM_LAUNCH_E(V, E)                                                                                           \
     do {                                                                                                            \
-        if (int e = allow_lds16(reinterpret_cast<const void *>(bsc_select_estep16_kernel<V, E>), shmem)) return e;  \
+        if (int e = pm_allow_lds(reinterpret_cast<const void *>(bsc_select_estep16_kernel<V, E>), shmem)) return e; \
         hipLaunchKernelGGL((bsc_select_estep16_kernel<V, E>), grid, block, shmem, s, scores, lds, gram, ynorm2, wmu,\
                            ymu, state_masks, state_parents, so, (int)S, (int)gamma, P, N, (int)H, (int)Hprime,     \
                            mode, cand, logpj, ldl, lse);                                                            \
@@ -489,7 +484,7 @@ extern "C" int pm_xsc_select_f64(const double *scores, int64_t lds, const double
     if (!tsc) P = *params_host;
 #define PM_LAUNCH_X(V, T)                                                                                    \
     do {                                                                                                     \
-        if (int e = allow_lds16(reinterpret_cast<const void *>(xsc_select16_kernel<V, T>), shmem)) return e; \
+        if (int e = pm_allow_lds(reinterpret_cast<const void *>(xsc_select16_kernel<V, T>), shmem)) return e;   \
         hipLaunchKernelGGL((xsc_select16_kernel<V, T>), grid, block, shmem, s, scores, lds, gram, P, N, (int)H, \
                            (int)Hprime, cand);                                                               \
     } while (0)
@@ -540,12 +535,12 @@ extern "C" int pm_bsc_mstep_rows16_nz_f64(const double *logpj, int64_t ldl, cons
 #define PM_LAUNCH(V)                                                                                               \
     do {                                                                                                           \
         if (pl.mstats) {                                                                                           \
-            if (int e = allow_lds16(reinterpret_cast<const void *>(bsc_mstep_rows16_kernel<V, true>), shmem)) return e; \
+            if (int e = pm_allow_lds(reinterpret_cast<const void *>(bsc_mstep_rows16_kernel<V, true>), shmem)) return e;  \
             hipLaunchKernelGGL((bsc_mstep_rows16_kernel<V, true>), grid, block, shmem, s, logpj, ldl, lse, lse_cut, cand, \
                                state_masks, (int)S, *params_host, N, (int)H, (int)D, (int)Hprime, expect, lde, stats, \
                                nz_idx, nz_val);                                                                    \
         } else {                                                                                                   \
-            if (int e = allow_lds16(reinterpret_cast<const void *>(bsc_mstep_rows16_kernel<V, false>), shmem)) return e; \
+            if (int e = pm_allow_lds(reinterpret_cast<const void *>(bsc_mstep_rows16_kernel<V, false>), shmem)) return e;  \
             hipLaunchKernelGGL((bsc_mstep_rows16_kernel<V, false>), grid, block, shmem, s, logpj, ldl, lse, lse_cut, cand, \
                                state_masks, (int)S, *params_host, N, (int)H, (int)D, (int)Hprime, expect, lde, stats, \
                                nz_idx, nz_val);                                                                    \

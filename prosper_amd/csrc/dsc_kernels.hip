@@ -30,11 +30,6 @@ constexpr int WAVES = 4;
                              // still wins (0.170 ms; 3 per SIMD, no spill: 0.200; scratch/dsc_ab.sh)
 #endif
 
-__device__ __forceinline__ void wave_sync_lds_dsc() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
 __global__ __launch_bounds__(256) void dsc_select_scores_kernel(const double *__restrict__ scores, int64_t lds,
                                                                  const double *__restrict__ gram, pm_dsc_params P,
                                                                  int64_t N, int H, double *__restrict__ R,
@@ -152,6 +147,171 @@ __device__ __forceinline__ bool dsc_build_energy_tables(const pm_dsc_params &P, 
     return __syncthreads_or(too_many);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// What the row kernels below must agree on bit for bit, written once.  `W` is the number of lanes that share a datapoint
+// (64: one wavefront; 16: a DPP row, `rowbase` the first lane of the row); lane `j` of the group holds candidate j in `myc`.
+// ---------------------------------------------------------------------------------------------------------------
+// Terms of a log-sum-exp below e^-37 of the row's largest are dropped: not evaluated, and no weight in the fused statistics
+// (e^-37 = 8.5e-17 is below 2^-53 of the largest term; a row of Kt columns loses at most Kt e^-37 of its sum).
+constexpr double DSC_TERM_CUT = -37.0;
+// Posterior weights below e^-60 of the evidence are dropped from the M-step's sums: they add nothing in f64.
+constexpr double DSC_WEIGHT_CUT = -60.0;
+
+// candidate `a` of this lane's datapoint
+template <int W>
+__device__ __forceinline__ int dsc_cand(int myc, int rowbase, int a) {
+    if constexpr (W == 64) return __shfl(myc, a);
+    else return __builtin_amdgcn_ds_bpermute((rowbase + a) << 2, myc);
+}
+
+// a state's energy from the term table: the six entries s_off names (unused slots name entry 0, an exact zero)
+__device__ __forceinline__ double dsc_table_energy(const uint8_t *s_off, const double *s_T, int st, double yn) {
+    const uint2 o = *reinterpret_cast<const uint2 *>(s_off + (size_t)st * 8);
+    return yn + s_T[o.x & 255u] + s_T[(o.x >> 8) & 255u] + s_T[(o.x >> 16) & 255u] + s_T[o.x >> 24] + s_T[o.y & 255u] +
+           s_T[(o.y >> 8) & 255u];
+}
+template <int MAXHP>
+__device__ __forceinline__ double dsc_state_e(bool fast, const uint8_t *s_off, const double *s_T, const uint8_t *s_tab, int st,
+                                              int Hp, const double *s_val, const double *s_a, const double *s_G, double yn) {
+    if (fast) return dsc_table_energy(s_off, s_T, st, yn);
+    return state_energy<MAXHP>(s_tab + st * Hp, Hp, s_val, s_a, s_G, yn);
+}
+
+// maximum / sum over a 16-lane row, in every lane of it.  (Not row_max_f64 / row_sum_f64 of bsc_rows16_body.h: those go
+// through ds_swizzle and vmax64, these through DPP and fmax -- other instructions.)
+__device__ __forceinline__ double dsc_row16_max(double m) {
+    m = fmax(m, pm_dpp_f64<0xB1>(m));
+    m = fmax(m, pm_dpp_f64<0x4E>(m));
+    m = fmax(m, pm_dpp_f64<0x141>(m));
+    m = fmax(m, pm_dpp_f64<0x140>(m));
+    return m;
+}
+__device__ __forceinline__ double dsc_row16_sum(double s) {
+    s += pm_dpp_f64<0xB1>(s);
+    s += pm_dpp_f64<0x4E>(s);
+    s += pm_dpp_f64<0x141>(s);
+    s += pm_dpp_f64<0x140>(s);
+    return s;
+}
+
+// Bit a set: candidate position a is the LAST occurrence of its latent and takes the latent's statistics (all positions
+// unless candidates repeat: TSC).  Every lane of the wavefront calls this.
+template <int W>
+__device__ __forceinline__ auto dsc_lastmask(int flags, int Hp, int j, int rowbase, int myc) {
+    bool mine_last = j < Hp;
+    for (int k = 1; k < Hp; ++k) {                          // uniform trip count
+        const int other = dsc_cand<W>(myc, rowbase, k);
+        if (k > j && other == myc) mine_last = false;
+    }
+    if constexpr (W == 64) {
+        return (flags & PM_DSC_LAST_POSITION) ? __ballot(mine_last) : ((1ull << Hp) - 1ull);
+    } else {
+        return (flags & PM_DSC_LAST_POSITION) ? (unsigned)((__ballot(mine_last) >> rowbase) & 0xFFFFull) : ((1u << Hp) - 1u);
+    }
+}
+
+// A state's share of the statistics, weight q: its value counts, s_m[a] += q v_a, and the upper triangle
+// s_B[a * Hp + k2] += q v_a v_k2 (a <= k2) over its non-zero positions.  The state's value indices and values are gathered
+// first (LDS lookups, static register indices), then scattered.  A macro: behind a function boundary the same text is
+// another kernel (dsc_mstep_rows16_kernel<8, 8>: 11023 -> 18524 instructions, 34 -> 43 spilled registers).
+// From the caller: Hp, P (K0), s_val, s_m, s_B.
+#define DSC_SCATTER_STATE(MAXHP_, KM_, srow, q, cnt)                                                                   \
+    do {                                                                                                               \
+        int ki[MAXHP_];                                                                                                \
+        double vv[MAXHP_];                                                                                             \
+        _Pragma("unroll") for (int a = 0; a < MAXHP_; ++a) {                                                           \
+            ki[a] = (a < Hp) ? (int)(srow)[a] : P.K0;                                                                  \
+            vv[a] = (a < Hp) ? s_val[ki[a]] : 0.0;                                                                     \
+        }                                                                                                              \
+        _Pragma("unroll") for (int a = 0; a < MAXHP_; ++a) {                                                           \
+            if (a < Hp && ki[a] != P.K0) {                                                                             \
+                _Pragma("unroll") for (int k = 0; k < KM_; ++k)                                                        \
+                    if (k == ki[a]) (cnt)[k] += (q);                                                                   \
+                atomicAdd(&s_m[a], (q) * vv[a]);                                                                       \
+                _Pragma("unroll") for (int k2 = a; k2 < MAXHP_; ++k2)                                                  \
+                    if (k2 < Hp && ki[k2] != P.K0) atomicAdd(&s_B[a * Hp + k2], (q) * vv[a] * vv[k2]);                 \
+            }                                                                                                          \
+        }                                                                                                              \
+    } while (0)
+
+// The three routines below are macros for the same reason: as functions each changed the instruction streams of 3 to 14 of
+// the 20 instantiations, and a stream that changes has to be measured again.  Each is one statement
+// (do ... while (0)) and declares nothing in its caller; the names it takes from the caller's scope are listed.
+
+// The non-zeros of an E[s] row as a list too (pm_wp_sparse_f64; format of the BSC statistics pass): PM_BSC_NZ_MAX slots in
+// ascending latent order, unused index slots 0xFFFF, rows with more non-zeros counted in `overflow`.  VAL: the row's value
+// at latent h = j + 16 i (an expression in i and h).  Sixteen-lane kernels.
+// From the caller: nz_idx, nz_val (null: nothing is written), nn, live, j, rowbase, H, VPL, overflow.
+#define DSC_ROW16_NZ_LIST(VAL)                                                                                         \
+    do {                                                                                                               \
+        if (nz_idx) {                                                                                                  \
+            uint16_t *nzi = nz_idx + nn * PM_BSC_NZ_MAX;                                                               \
+            double *nzv = nz_val + nn * PM_BSC_NZ_MAX;                                                                 \
+            uint32_t nzn = 0;                                                                                          \
+            _Pragma("unroll") for (int i = 0; i < VPL; ++i) {                                                          \
+                const int h = j + 16 * i;                                                                              \
+                const double v = h < H ? (VAL) : 0.0;                                                                  \
+                const uint32_t mine = (uint32_t)((__ballot(v != 0.0) >> rowbase) & 0xFFFFull);                         \
+                const uint32_t pos = nzn + __builtin_popcount(mine & ((1u << j) - 1u));                                \
+                if (v != 0.0 && pos < PM_BSC_NZ_MAX && live) {                                                         \
+                    nzi[pos] = (uint16_t)h;                                                                            \
+                    nzv[pos] = v;                                                                                      \
+                }                                                                                                      \
+                nzn += __builtin_popcount(mine);                                                                       \
+            }                                                                                                          \
+            if (live) {                                                                                                \
+                if ((uint32_t)j >= nzn) nzi[j] = 0xFFFFu;               /* (16 lanes = PM_BSC_NZ_MAX slots) */         \
+                if (j == 0 && nzn > PM_BSC_NZ_MAX) overflow += 1.0;                                                    \
+            }                                                                                                          \
+        }                                                                                                              \
+    } while (0)
+
+// Wq += SB over the upper triangle of the candidates' block, at (min, max) of the two latents (pm_spd_inverse_f64 layout);
+// only last occurrences count.  W lanes per datapoint, this one lane J of them (the first: ROWBASE); SB: the value of
+// s_B[p] (an expression in p).  From the caller: Hp, H, myc, lastmask, s_B (through SB), Wq.
+#define DSC_FLUSH_WQ(W, J, ROWBASE, SB)                                                                                \
+    do {                                                                                                               \
+        for (int p0 = 0; p0 < Hp * Hp; p0 += W) {          /* uniform trip count: every lane feeds the exchange */      \
+            const int p = p0 + J;                                                                                      \
+            const bool ok = p < Hp * Hp;                                                                               \
+            const int a = ok ? p / Hp : 0, k2 = ok ? p - a * Hp : 0;                                                   \
+            const int cj = dsc_cand<W>(myc, ROWBASE, a), ck = dsc_cand<W>(myc, ROWBASE, k2);                           \
+            if (!ok || k2 < a || !((lastmask >> a) & 1u) || !((lastmask >> k2) & 1u)) continue;                        \
+            const double v = (SB);                                                                                     \
+            if (v == 0.0) continue;                                                                                    \
+            const int r = cj < ck ? cj : ck, cc = cj < ck ? ck : cj;                                                   \
+            pm_atomic_add(Wq + (int64_t)r * H + cc, PM_Q(v, 0));                                                       \
+        }                                                                                                              \
+    } while (0)
+
+// End of a statistics kernel: the wavefronts' sums into the workgroup's LDS scalars (quantised, PM_Q), then the workgroup's
+// [ qdiag (H) | cnt (PM_DSC_MAX_K) | scal (4) ] block into the statistics buffer.  KM_: length of cnt; LISTS: the kernel
+// writes non-zero lists and counts their overflow (a constant).  Every thread of the workgroup reaches it.
+// From the caller: sig, fs, kept, overflow, cnt, tid, lane, s_scal, s_cnt, s_qdiag, stats, H, D.
+#define DSC_STATS_EPILOGUE(KM_, LISTS)                                                                                 \
+    do {                                                                                                               \
+        sig = pm_wave_sum(sig);                                                                                        \
+        fs = pm_wave_sum(fs);                                                                                          \
+        kept = pm_wave_sum(kept);                                                                                      \
+        if constexpr (LISTS) overflow = pm_wave_sum(overflow);                                                         \
+        _Pragma("unroll") for (int k = 0; k < KM_; ++k) cnt[k] = pm_wave_sum(cnt[k]);                                  \
+        if (lane == 0) {                                                                                               \
+            atomicAdd(&s_scal[0], PM_Q(sig, 1));                                                                       \
+            atomicAdd(&s_scal[1], PM_Q(fs, 2));                                                                        \
+            atomicAdd(&s_scal[2], kept);                                                                               \
+            if constexpr (LISTS)                                                                                       \
+                if (overflow != 0.0) atomicAdd(&s_scal[3], overflow);                                                  \
+            _Pragma("unroll") for (int k = 0; k < KM_; ++k)                                                            \
+                if (cnt[k] != 0.0) atomicAdd(&s_cnt[k], PM_Q(cnt[k], 0));                                              \
+        }                                                                                                              \
+        __syncthreads();                                                                                               \
+        double *g_qdiag = stats + (int64_t)H * D + (int64_t)H * H;                                                     \
+        for (int h = tid; h < H + PM_DSC_MAX_K + 4; h += blockDim.x) {                                                 \
+            const double v = s_qdiag[h];                                                                               \
+            if (v != 0.0) pm_atomic_add(g_qdiag + h, v);                                                               \
+        }                                                                                                              \
+    } while (0)
+
 template <int MAXHP>
 __global__ __launch_bounds__(64 * WAVES, 4) void dsc_estep_kernel(
     const double *__restrict__ scores, int64_t lds, const double *__restrict__ gram,
@@ -223,7 +383,7 @@ __global__ __launch_bounds__(64 * WAVES, 4) void dsc_estep_kernel(
             const int ci = __shfl(myc, ok ? p / Hp : 0), ck = __shfl(myc, ok ? p % Hp : 0);
             if (ok) s_G[p] = gram[(int64_t)ci * H + ck];
         }
-        wave_sync_lds_dsc();
+        pm_wave_lds_sync();
         if (fast) {
             for (int e = lane; e < NT; e += 64) {
                 const int j = s_dj[e];
@@ -253,16 +413,11 @@ __global__ __launch_bounds__(64 * WAVES, 4) void dsc_estep_kernel(
             }
             ++c;
         }
-        if (fast) wave_sync_lds_dsc();
+        if (fast) pm_wave_lds_sync();
         for (int s = lane; s < S; s += 64) {
-            double e;
-            if (fast) {
-                const uint2 o = *reinterpret_cast<const uint2 *>(s_off + (size_t)s * 8);
-                e = yn + s_T[o.x & 255u] + s_T[(o.x >> 8) & 255u] + s_T[(o.x >> 16) & 255u] + s_T[o.x >> 24] +
-                    s_T[o.y & 255u] + s_T[(o.y >> 8) & 255u];
-            } else {
-                e = state_energy<MAXHP>(s_tab + s * Hp, Hp, s_val, s_a, s_G, yn);
-            }
+            double e;      // (not dsc_state_e: behind it this kernel's stream moves)
+            if (fast) e = dsc_table_energy(s_off, s_T, s, yn);
+            else e = state_energy<MAXHP>(s_tab + s * Hp, Hp, s_val, s_a, s_G, yn);
             const double f = P.ecoef * e + P.pscale * prior[base + s];
             out[base + s] = f;
             if (stage) s_f[base + s] = f;
@@ -273,7 +428,7 @@ __global__ __launch_bounds__(64 * WAVES, 4) void dsc_estep_kernel(
         const double *src = stage ? s_f : out;
         double sum = 0.0;
         auto add = [&](double d, bool mine) {           // uniform trip counts: every lane reaches the __any
-            const bool need = mine && d > -37.0;
+            const bool need = mine && d > DSC_TERM_CUT;
             if (__any(need)) sum += need ? pm_exp_tab(d, etab) : 0.0;
         };
         if (!tab) add(lane == 0 ? src[0] - m : 0.0, lane == 0);
@@ -292,7 +447,7 @@ __global__ __launch_bounds__(64 * WAVES, 4) void dsc_estep_kernel(
         }
         sum = pm_wave_sum(sum);
         if (lane == 0) lse[n] = m + log(sum);
-        wave_sync_lds_dsc();
+        pm_wave_lds_sync();
     }
 }
 
@@ -386,13 +541,13 @@ __global__ __launch_bounds__(256, MAXHP <= 8 ? 4 : 2) void dsc_estep16_kernel(
             const int ck = __builtin_amdgcn_ds_bpermute((rowbase + pk) << 2, myc);
             if (ok) s_G[p] = gram[(int64_t)ci * H + ck];
         }
-        wave_sync_lds_dsc();
+        pm_wave_lds_sync();
         if (fast) {
             for (int e = j; e < NT; e += 16) {
                 const int dj = s_dj[e];
                 s_T[e] = fma(s_c1[e], s_G[dj * Hp + s_dk[e]], s_c2[e] * s_a[dj]);
             }
-            wave_sync_lds_dsc();
+            pm_wave_lds_sync();
         }
         double *out = logpj + nn * ldl;
         // every column of this lane, in a fixed order: fn(column, log-joint)
@@ -413,14 +568,7 @@ __global__ __launch_bounds__(256, MAXHP <= 8 ? 4 : 2) void dsc_estep16_kernel(
                 ++c;
             }
             for (int st = j; st < S; st += 16) {
-                double e;
-                if (fast) {
-                    const uint2 o = *reinterpret_cast<const uint2 *>(s_off + (size_t)st * 8);
-                    e = yn + s_T[o.x & 255u] + s_T[(o.x >> 8) & 255u] + s_T[(o.x >> 16) & 255u] + s_T[o.x >> 24] +
-                        s_T[o.y & 255u] + s_T[(o.y >> 8) & 255u];
-                } else {
-                    e = state_energy<MAXHP>(s_tab + st * Hp, Hp, s_val, s_a, s_G, yn);
-                }
+                const double e = dsc_state_e<MAXHP>(fast, s_off, s_T, s_tab, st, Hp, s_val, s_a, s_G, yn);
                 fn(base + st, P.ecoef * e + P.pscale * prior[base + st]);
             }
         };
@@ -429,21 +577,15 @@ __global__ __launch_bounds__(256, MAXHP <= 8 ? 4 : 2) void dsc_estep16_kernel(
             if (live) out[col] = f;
             m = fmax(m, f);
         });
-        m = fmax(m, pm_dpp_f64<0xB1>(m));
-        m = fmax(m, pm_dpp_f64<0x4E>(m));
-        m = fmax(m, pm_dpp_f64<0x141>(m));
-        m = fmax(m, pm_dpp_f64<0x140>(m));
+        m = dsc_row16_max(m);
         double sum = 0.0;
         visit([&](int, double f) {
             const double d = f - m;
-            sum += d > -37.0 ? pm_exp_tab(d, etab) : 0.0;
+            sum += d > DSC_TERM_CUT ? pm_exp_tab(d, etab) : 0.0;
         });
-        sum += pm_dpp_f64<0xB1>(sum);
-        sum += pm_dpp_f64<0x4E>(sum);
-        sum += pm_dpp_f64<0x141>(sum);
-        sum += pm_dpp_f64<0x140>(sum);
+        sum = dsc_row16_sum(sum);
         if (j == 0 && live) lse[n] = m + log(sum);
-        wave_sync_lds_dsc();
+        pm_wave_lds_sync();
     }
 }
 
@@ -545,32 +687,17 @@ __global__ __launch_bounds__(256, (MAXHP <= 8 && VPL <= 8) ? PM_DSC_MS_WPE : 2) 
             const int ck = __builtin_amdgcn_ds_bpermute((rowbase + pk) << 2, myc);
             if (ok) s_G[p] = gram[(int64_t)ci * H + ck];
         }
-        // positions that are the last occurrence of their latent (all of them unless candidates repeat: TSC)
-        bool mine_last = j < Hp;
-        for (int k = 1; k < Hp; ++k) {                          // uniform trip count
-            const int other = __builtin_amdgcn_ds_bpermute((rowbase + k) << 2, myc);
-            if (k > j && other == myc) mine_last = false;
-        }
-        const unsigned lastmask = (P.flags & PM_DSC_LAST_POSITION)
-                                      ? (unsigned)((__ballot(mine_last) >> rowbase) & 0xFFFFull)
-                                      : ((1u << Hp) - 1u);
-        wave_sync_lds_dsc();
+        const unsigned lastmask = dsc_lastmask<16>(P.flags, Hp, j, rowbase, myc);
+        pm_wave_lds_sync();
         if (fast) {
             for (int e = j; e < NT; e += 16) {
                 const int dj = s_dj[e];
                 s_T[e] = fma(s_c1[e], s_G[dj * Hp + s_dk[e]], s_c2[e] * s_a[dj]);
             }
-            wave_sync_lds_dsc();
+            pm_wave_lds_sync();
         }
         double *out = logpj + nn * ldl;
-        auto state_e = [&](int st) -> double {
-            if (fast) {
-                const uint2 o = *reinterpret_cast<const uint2 *>(s_off + (size_t)st * 8);
-                return yn + s_T[o.x & 255u] + s_T[(o.x >> 8) & 255u] + s_T[(o.x >> 16) & 255u] + s_T[o.x >> 24] +
-                       s_T[o.y & 255u] + s_T[(o.y >> 8) & 255u];
-            }
-            return state_energy<MAXHP>(s_tab + st * Hp, Hp, s_val, s_a, s_G, yn);
-        };
+        auto state_e = [&](int st) { return dsc_state_e<MAXHP>(fast, s_off, s_T, s_tab, st, Hp, s_val, s_a, s_G, yn); };
         // ---- pass 1: log-joints out, row maximum
         double m = -INFINITY;
         if (!tab && j == 0) {
@@ -601,10 +728,7 @@ __global__ __launch_bounds__(256, (MAXHP <= 8 && VPL <= 8) ? PM_DSC_MS_WPE : 2) 
             if (live) out[base + st] = f;
             m = fmax(m, f);
         }
-        m = fmax(m, pm_dpp_f64<0xB1>(m));
-        m = fmax(m, pm_dpp_f64<0x4E>(m));
-        m = fmax(m, pm_dpp_f64<0x141>(m));
-        m = fmax(m, pm_dpp_f64<0x140>(m));
+        m = dsc_row16_max(m);
         // ---- pass 2: exponentials relative to the maximum; the M-step's sums weighted by them (scaled by 1 / sum below)
         double sum = 0.0, sig_dp = 0.0;
         double cnt_dp[KM];
@@ -615,7 +739,7 @@ __global__ __launch_bounds__(256, (MAXHP <= 8 && VPL <= 8) ? PM_DSC_MS_WPE : 2) 
         for (int i = 0; i < VPL; ++i) rowv[i] = qd[i] = 0.0;
         if (!tab && j == 0) {
             const double d = (P.ecoef * yn + P.pscale * prior[0]) - m;
-            const double ex = d > -37.0 ? pm_exp_tab(d, etab) : 0.0;
+            const double ex = d > DSC_TERM_CUT ? pm_exp_tab(d, etab) : 0.0;
             sum += ex;
             sig_dp += ex * yn;
         }
@@ -631,7 +755,7 @@ __global__ __launch_bounds__(256, (MAXHP <= 8 && VPL <= 8) ? PM_DSC_MS_WPE : 2) 
                     if (h < H) {
                         const double e = v * v * s_w2[h] - 2.0 * v * ar[i] + yn;
                         const double d = (P.ecoef * e + P.pscale * prior[1 + c * H + h]) - m;
-                        const double ex = d > -37.0 ? pm_exp_tab(d, etab) : 0.0;
+                        const double ex = d > DSC_TERM_CUT ? pm_exp_tab(d, etab) : 0.0;
                         sum += ex;
                         rowv[i] += ex * v;
                         qd[i] += ex * v * v;
@@ -645,35 +769,13 @@ __global__ __launch_bounds__(256, (MAXHP <= 8 && VPL <= 8) ? PM_DSC_MS_WPE : 2) 
         for (int st = j; st < S; st += 16) {
             const double e = state_e(st);
             const double d = (P.ecoef * e + P.pscale * prior[base + st]) - m;
-            if (!(d > -37.0)) continue;
+            if (!(d > DSC_TERM_CUT)) continue;
             const double ex = pm_exp_tab(d, etab);
             sum += ex;
             sig_dp += ex * e;
-            const uint8_t *srow = s_tab + st * Hp;
-            int ki[MAXHP];
-            double vv[MAXHP];
-#pragma unroll
-            for (int a = 0; a < MAXHP; ++a) {
-                ki[a] = (a < Hp) ? (int)srow[a] : P.K0;
-                vv[a] = (a < Hp) ? s_val[ki[a]] : 0.0;
-            }
-#pragma unroll
-            for (int a = 0; a < MAXHP; ++a) {
-                if (a < Hp && ki[a] != P.K0) {
-#pragma unroll
-                    for (int k = 0; k < KM; ++k)
-                        if (k == ki[a]) cnt_dp[k] += ex;
-                    atomicAdd(&s_m[a], ex * vv[a]);
-#pragma unroll
-                    for (int k2 = a; k2 < MAXHP; ++k2)
-                        if (k2 < Hp && ki[k2] != P.K0) atomicAdd(&s_B[a * Hp + k2], ex * vv[a] * vv[k2]);
-                }
-            }
+            DSC_SCATTER_STATE(MAXHP, KM, s_tab + st * Hp, ex, cnt_dp);
         }
-        sum += pm_dpp_f64<0xB1>(sum);
-        sum += pm_dpp_f64<0x4E>(sum);
-        sum += pm_dpp_f64<0x141>(sum);
-        sum += pm_dpp_f64<0x140>(sum);
+        sum = dsc_row16_sum(sum);
         const double lse_n = m + log(sum);
         const double inv = live ? 1.0 / sum : 0.0;               // (shadow rows: every weight 0)
         if (j == 0 && live) {
@@ -693,7 +795,7 @@ __global__ __launch_bounds__(256, (MAXHP <= 8 && VPL <= 8) ? PM_DSC_MS_WPE : 2) 
                 if (q2 != 0.0) atomicAdd(&s_qdiag[h], PM_Q(q2, 0));
             }
         }
-        wave_sync_lds_dsc();
+        pm_wave_lds_sync();
         // the candidates' multi-cause share of E[s]: the lane that holds latent c_a takes s_m[a] (distinct latents)
         for (int a = 0; a < Hp; ++a) {                           // uniform trip count
             const int c = __builtin_amdgcn_ds_bpermute((rowbase + a) << 2, myc);
@@ -710,63 +812,12 @@ __global__ __launch_bounds__(256, (MAXHP <= 8 && VPL <= 8) ? PM_DSC_MS_WPE : 2) 
             for (int i = 0; i < VPL; ++i)
                 if (j + 16 * i < H) erow[j + 16 * i] = rowv[i];
         }
-        if (nz_idx) {      // the row's non-zeros as a list too (pm_wp_sparse_f64; format of the BSC statistics pass)
-            uint16_t *nzi = nz_idx + nn * PM_BSC_NZ_MAX;
-            double *nzv = nz_val + nn * PM_BSC_NZ_MAX;
-            uint32_t nzn = 0;
-#pragma unroll
-            for (int i = 0; i < VPL; ++i) {
-                const int h = j + 16 * i;
-                const double v = h < H ? rowv[i] : 0.0;
-                const uint32_t mine = (uint32_t)((__ballot(v != 0.0) >> rowbase) & 0xFFFFull);
-                const uint32_t pos = nzn + __builtin_popcount(mine & ((1u << j) - 1u));
-                if (v != 0.0 && pos < PM_BSC_NZ_MAX && live) {
-                    nzi[pos] = (uint16_t)h;
-                    nzv[pos] = v;
-                }
-                nzn += __builtin_popcount(mine);
-            }
-            if (live) {
-                if ((uint32_t)j >= nzn) nzi[j] = 0xFFFFu;               // (16 lanes = PM_BSC_NZ_MAX slots)
-                if (j == 0 && nzn > PM_BSC_NZ_MAX) overflow += 1.0;
-            }
-        }
-        for (int p0 = 0; p0 < Hp * Hp; p0 += 16) {              // uniform trip count: every lane feeds the permutes
-            const int p = p0 + j;
-            const bool ok = p < Hp * Hp;
-            const int a = ok ? p / Hp : 0, k2 = ok ? p - a * Hp : 0;
-            const int cj = __builtin_amdgcn_ds_bpermute((rowbase + a) << 2, myc);
-            const int ck = __builtin_amdgcn_ds_bpermute((rowbase + k2) << 2, myc);
-            if (!ok || k2 < a || !((lastmask >> a) & 1u) || !((lastmask >> k2) & 1u)) continue;
-            const double v = s_B[p] * inv;
-            if (v == 0.0) continue;
-            const int r = cj < ck ? cj : ck, cc = cj < ck ? ck : cj;
-            pm_atomic_add(Wq + (int64_t)r * H + cc, PM_Q(v, 0));          // upper triangle (pm_spd_inverse_f64 layout)
-        }
-        wave_sync_lds_dsc();
+        DSC_ROW16_NZ_LIST(rowv[i]);
+        DSC_FLUSH_WQ(16, j, rowbase, s_B[p] * inv);
+        pm_wave_lds_sync();
     }
 
-    sig = pm_wave_sum(sig);
-    fs = pm_wave_sum(fs);
-    kept = pm_wave_sum(kept);
-    overflow = pm_wave_sum(overflow);
-#pragma unroll
-    for (int k = 0; k < KM; ++k) cnt[k] = pm_wave_sum(cnt[k]);
-    if (lane == 0) {
-        atomicAdd(&s_scal[0], PM_Q(sig, 1));
-        atomicAdd(&s_scal[1], PM_Q(fs, 2));
-        atomicAdd(&s_scal[2], kept);
-        if (overflow != 0.0) atomicAdd(&s_scal[3], overflow);
-#pragma unroll
-        for (int k = 0; k < KM; ++k)
-            if (cnt[k] != 0.0) atomicAdd(&s_cnt[k], PM_Q(cnt[k], 0));
-    }
-    __syncthreads();
-    double *g_qdiag = stats + (int64_t)H * D + (int64_t)H * H;
-    for (int h = tid; h < H + PM_DSC_MAX_K + 4; h += blockDim.x) {
-        const double v = s_qdiag[h];
-        if (v != 0.0) pm_atomic_add(g_qdiag + h, v);
-    }
+    DSC_STATS_EPILOGUE(KM, true);
 }
 
 // one wave per datapoint and several dependent memory round trips per datapoint: latency-bound, so waves per SIMD
@@ -809,8 +860,8 @@ __global__ __launch_bounds__(64 * WAVES, MAXHP <= 8 ? 4 : 3) void dsc_mstep_rows
     }
     const double *prior = stage ? s_prior : prior_g;
     const double inv_ecoef = 1.0 / P.ecoef;
-    const double qcut = -60.0;     // multi-cause weights below e^-60 of the evidence add nothing in f64
-    double sig = 0.0, fs = 0.0, kept = 0.0;
+    constexpr double qcut = DSC_WEIGHT_CUT;
+    double sig = 0.0, fs = 0.0, kept = 0.0, overflow = 0.0;      // (overflow: this kernel writes no lists, it stays 0 and unread)
     double cnt[PM_DSC_MAX_K];
 #pragma unroll
     for (int k = 0; k < PM_DSC_MAX_K; ++k) cnt[k] = 0.0;
@@ -826,15 +877,8 @@ __global__ __launch_bounds__(64 * WAVES, MAXHP <= 8 ? 4 : 3) void dsc_mstep_rows
         const int32_t *cn = cand + n * Hp;
         if (lane < Hp) s_m[lane] = 0.0;
         for (int p = lane; p < Hp * Hp; p += 64) s_B[p] = 0.0;
-        // positions that are the last occurrence of their latent (all of them unless candidates repeat)
-        bool mine_last = lane < Hp;
         const int myc = lane < Hp ? cn[lane] : -1;       // ONE load of the candidates; the comparisons are shuffles
-        for (int k = 1; k < Hp; ++k) {                     // uniform trip count
-            const int other = __shfl(myc, k);
-            if (k > lane && other == myc) mine_last = false;
-        }
-        const unsigned long long lastmask =
-            (P.flags & PM_DSC_LAST_POSITION) ? __ballot(mine_last) : ((1ull << Hp) - 1ull);
+        const unsigned long long lastmask = dsc_lastmask<64>(P.flags, Hp, lane, 0, myc);
         if (lane == 0) {
             if (!tab) {
                 const double f0 = f[0];
@@ -862,73 +906,25 @@ __global__ __launch_bounds__(64 * WAVES, MAXHP <= 8 ? 4 : 3) void dsc_mstep_rows
             s_row[h] = row;
             if (qd != 0.0) atomicAdd(&s_qdiag[h], PM_Q(qd, 0));
         }
-        wave_sync_lds_dsc();
+        pm_wave_lds_sync();
         for (int s = lane; s < S; s += 64) {
             const double fsv = f[base + s];
             const double dl = fsv - l;
             if (!(dl > qcut)) continue;
             const double q = pm_exp_tab(dl, etab);
             sig += q * ((fsv - P.pscale * prior[base + s]) * inv_ecoef);
-            const uint8_t *row = s_tab + s * Hp;
-            // the state's value indices and values first (LDS lookups, static register indices), then the scatter
-            int ki[MAXHP];
-            double vv[MAXHP];
-#pragma unroll
-            for (int j = 0; j < MAXHP; ++j) {
-                ki[j] = (j < Hp) ? (int)row[j] : P.K0;
-                vv[j] = (j < Hp) ? s_val[ki[j]] : 0.0;
-            }
-#pragma unroll
-            for (int j = 0; j < MAXHP; ++j) {
-                if (j < Hp && ki[j] != P.K0) {
-#pragma unroll
-                    for (int k = 0; k < PM_DSC_MAX_K; ++k)
-                        if (k == ki[j]) cnt[k] += q;
-                    atomicAdd(&s_m[j], q * vv[j]);
-#pragma unroll
-                    for (int k2 = j; k2 < MAXHP; ++k2)
-                        if (k2 < Hp && ki[k2] != P.K0) atomicAdd(&s_B[j * Hp + k2], q * vv[j] * vv[k2]);
-                }
-            }
+            DSC_SCATTER_STATE(MAXHP, PM_DSC_MAX_K, s_tab + s * Hp, q, cnt);
         }
-        wave_sync_lds_dsc();
+        pm_wave_lds_sync();
         if (lane < Hp && ((lastmask >> lane) & 1ull)) s_row[myc] += s_m[lane];   // distinct latents
-        wave_sync_lds_dsc();
+        pm_wave_lds_sync();
         for (int h = lane; h < H; h += 64) erow[h] = s_row[h];
         double *Wq = stats + (int64_t)H * D;
-        for (int p0 = 0; p0 < Hp * Hp; p0 += 64) {          // uniform trip count: every lane feeds the shuffles
-            const int p = p0 + lane;
-            const bool ok = p < Hp * Hp;
-            const int j = ok ? p / Hp : 0, k2 = ok ? p - j * Hp : 0;
-            const int cj = __shfl(myc, j), ck = __shfl(myc, k2);
-            if (!ok || k2 < j || !((lastmask >> j) & 1ull) || !((lastmask >> k2) & 1ull)) continue;
-            const double v = s_B[p];
-            if (v == 0.0) continue;
-            const int r = cj < ck ? cj : ck, cc = cj < ck ? ck : cj;
-            pm_atomic_add(Wq + (int64_t)r * H + cc, PM_Q(v, 0));      // upper triangle (pm_spd_inverse_f64 layout)
-        }
-        wave_sync_lds_dsc();
+        DSC_FLUSH_WQ(64, lane, 0, s_B[p]);
+        pm_wave_lds_sync();
     }
 
-    sig = pm_wave_sum(sig);
-    fs = pm_wave_sum(fs);
-    kept = pm_wave_sum(kept);
-#pragma unroll
-    for (int k = 0; k < PM_DSC_MAX_K; ++k) cnt[k] = pm_wave_sum(cnt[k]);
-    if (lane == 0) {
-        atomicAdd(&s_scal[0], PM_Q(sig, 1));
-        atomicAdd(&s_scal[1], PM_Q(fs, 2));
-        atomicAdd(&s_scal[2], kept);
-#pragma unroll
-        for (int k = 0; k < PM_DSC_MAX_K; ++k)
-            if (cnt[k] != 0.0) atomicAdd(&s_cnt[k], PM_Q(cnt[k], 0));
-    }
-    __syncthreads();
-    double *g_qdiag = stats + (int64_t)H * D + (int64_t)H * H;
-    for (int h = tid; h < H + PM_DSC_MAX_K + 4; h += blockDim.x) {
-        const double v = s_qdiag[h];
-        if (v != 0.0) pm_atomic_add(g_qdiag + h, v);
-    }
+    DSC_STATS_EPILOGUE(PM_DSC_MAX_K, false);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -974,7 +970,7 @@ __global__ __launch_bounds__(256, (MAXHP <= 8 && VPL <= 8) ? PM_DSC_M16_WPE : 2)
     __syncthreads();
     const double *prior = stage ? s_prior : prior_g;
     const double inv_ecoef = 1.0 / P.ecoef;
-    const double qcut = -60.0;     // weights below e^-60 of the evidence add nothing in f64
+    constexpr double qcut = DSC_WEIGHT_CUT;
     double sig = 0.0, fs = 0.0, kept = 0.0;
     double cnt[PM_DSC_MAX_K];
 #pragma unroll
@@ -992,15 +988,7 @@ __global__ __launch_bounds__(256, (MAXHP <= 8 && VPL <= 8) ? PM_DSC_M16_WPE : 2)
         const int myc = j < Hp ? cand[nn * Hp + j] : -1;
         if (j < Hp) s_m[j] = 0.0;
         for (int p = j; p < Hp * Hp; p += 16) s_B[p] = 0.0;
-        // positions that are the last occurrence of their latent (all of them unless candidates repeat)
-        bool mine_last = j < Hp;
-        for (int k = 1; k < Hp; ++k) {                          // uniform trip count
-            const int other = __builtin_amdgcn_ds_bpermute((rowbase + k) << 2, myc);
-            if (k > j && other == myc) mine_last = false;
-        }
-        const unsigned lastmask = (P.flags & PM_DSC_LAST_POSITION)
-                                      ? (unsigned)((__ballot(mine_last) >> rowbase) & 0xFFFFull)
-                                      : ((1u << Hp) - 1u);
+        const unsigned lastmask = dsc_lastmask<16>(P.flags, Hp, j, rowbase, myc);
         if (j == 0 && use) {
             if (!tab) {
                 const double f0 = f[0];
@@ -1045,7 +1033,7 @@ __global__ __launch_bounds__(256, (MAXHP <= 8 && VPL <= 8) ? PM_DSC_M16_WPE : 2)
                 }
             }
         }
-        wave_sync_lds_dsc();
+        pm_wave_lds_sync();
         // multi-cause states, eight columns per lane at a time
         for (int s0 = 0; s0 < S; s0 += 128) {
             double fv[8];
@@ -1061,102 +1049,27 @@ __global__ __launch_bounds__(256, (MAXHP <= 8 && VPL <= 8) ? PM_DSC_M16_WPE : 2)
                 if (!(dl > qcut)) continue;
                 const double q = pm_exp_tab(dl, etab);
                 sig += q * ((fv[u] - P.pscale * prior[base + st]) * inv_ecoef);
-                const uint8_t *srow = s_tab + st * Hp;
-                int ki[MAXHP];
-                double vv[MAXHP];
-#pragma unroll
-                for (int a = 0; a < MAXHP; ++a) {
-                    ki[a] = (a < Hp) ? (int)srow[a] : P.K0;
-                    vv[a] = (a < Hp) ? s_val[ki[a]] : 0.0;
-                }
-#pragma unroll
-                for (int a = 0; a < MAXHP; ++a) {
-                    if (a < Hp && ki[a] != P.K0) {
-#pragma unroll
-                        for (int k = 0; k < PM_DSC_MAX_K; ++k)
-                            if (k == ki[a]) cnt[k] += q;
-                        atomicAdd(&s_m[a], q * vv[a]);
-#pragma unroll
-                        for (int k2 = a; k2 < MAXHP; ++k2)
-                            if (k2 < Hp && ki[k2] != P.K0) atomicAdd(&s_B[a * Hp + k2], q * vv[a] * vv[k2]);
-                    }
-                }
+                DSC_SCATTER_STATE(MAXHP, PM_DSC_MAX_K, s_tab + st * Hp, q, cnt);
             }
         }
-        wave_sync_lds_dsc();
+        pm_wave_lds_sync();
         if (j < Hp && ((lastmask >> j) & 1u)) s_row[myc] += s_m[j];   // distinct latents
-        wave_sync_lds_dsc();
+        pm_wave_lds_sync();
         if (live) {
             double *erow = expect + n * lde;
 #pragma unroll
             for (int i = 0; i < VPL; ++i)
                 if (j + 16 * i < H) erow[j + 16 * i] = s_row[j + 16 * i];
         }
-        if (nz_idx) {      // the row's non-zeros as a list too (pm_wp_sparse_f64; format of the BSC statistics pass)
-            uint16_t *nzi = nz_idx + nn * PM_BSC_NZ_MAX;
-            double *nzv = nz_val + nn * PM_BSC_NZ_MAX;
-            uint32_t nzn = 0;
-#pragma unroll
-            for (int i = 0; i < VPL; ++i) {
-                const int h = j + 16 * i;
-                const double v = h < H ? s_row[h] : 0.0;
-                const uint32_t mine = (uint32_t)((__ballot(v != 0.0) >> rowbase) & 0xFFFFull);
-                const uint32_t pos = nzn + __builtin_popcount(mine & ((1u << j) - 1u));
-                if (v != 0.0 && pos < PM_BSC_NZ_MAX && live) {
-                    nzi[pos] = (uint16_t)h;
-                    nzv[pos] = v;
-                }
-                nzn += __builtin_popcount(mine);
-            }
-            if (live) {
-                if ((uint32_t)j >= nzn) nzi[j] = 0xFFFFu;               // (16 lanes = PM_BSC_NZ_MAX slots)
-                if (j == 0 && nzn > PM_BSC_NZ_MAX) overflow += 1.0;
-            }
-        }
-        for (int p0 = 0; p0 < Hp * Hp; p0 += 16) {              // uniform trip count: every lane feeds the permutes
-            const int p = p0 + j;
-            const bool ok = p < Hp * Hp;
-            const int a = ok ? p / Hp : 0, k2 = ok ? p - a * Hp : 0;
-            const int cj = __builtin_amdgcn_ds_bpermute((rowbase + a) << 2, myc);
-            const int ck = __builtin_amdgcn_ds_bpermute((rowbase + k2) << 2, myc);
-            if (!ok || k2 < a || !((lastmask >> a) & 1u) || !((lastmask >> k2) & 1u)) continue;
-            const double v = s_B[p];
-            if (v == 0.0) continue;
-            const int r = cj < ck ? cj : ck, cc = cj < ck ? ck : cj;
-            pm_atomic_add(Wq + (int64_t)r * H + cc, PM_Q(v, 0));          // upper triangle (pm_spd_inverse_f64 layout)
-        }
-        wave_sync_lds_dsc();
+        DSC_ROW16_NZ_LIST(s_row[h]);
+        DSC_FLUSH_WQ(16, j, rowbase, s_B[p]);
+        pm_wave_lds_sync();
     }
 
-    sig = pm_wave_sum(sig);
-    fs = pm_wave_sum(fs);
-    kept = pm_wave_sum(kept);
-    overflow = pm_wave_sum(overflow);
-#pragma unroll
-    for (int k = 0; k < PM_DSC_MAX_K; ++k) cnt[k] = pm_wave_sum(cnt[k]);
-    if (lane == 0) {
-        atomicAdd(&s_scal[0], PM_Q(sig, 1));
-        atomicAdd(&s_scal[1], PM_Q(fs, 2));
-        atomicAdd(&s_scal[2], kept);
-        if (overflow != 0.0) atomicAdd(&s_scal[3], overflow);
-#pragma unroll
-        for (int k = 0; k < PM_DSC_MAX_K; ++k)
-            if (cnt[k] != 0.0) atomicAdd(&s_cnt[k], PM_Q(cnt[k], 0));
-    }
-    __syncthreads();
-    double *g_qdiag = stats + (int64_t)H * D + (int64_t)H * H;
-    for (int h = tid; h < H + PM_DSC_MAX_K + 4; h += blockDim.x) {
-        const double v = s_qdiag[h];
-        if (v != 0.0) pm_atomic_add(g_qdiag + h, v);
-    }
+    DSC_STATS_EPILOGUE(PM_DSC_MAX_K, true);
 }
 
 inline size_t align8(size_t x) { return (x + 7) & ~size_t(7); }
-
-inline int allow_lds_dsc(const void *kernel, size_t bytes) {
-    if (bytes <= 48 * 1024) return 0;
-    return (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
 
 inline bool bad_params(const pm_dsc_params *P) {
     return !P || P->K < 2 || P->K > PM_DSC_MAX_K || P->K0 < 0 || P->K0 >= P->K || P->values[P->K0] != 0.0;
@@ -1187,26 +1100,45 @@ extern "C" int pm_dsc_select_scores_f64(const double *scores, int64_t lds, const
     return (int)hipGetLastError();
 }
 
+// columns of a log-joint row: [ null state | (K - 1) H singletons | S table states ], the table states alone for TSC
+inline int64_t dsc_columns(int flags, int64_t K, int64_t H, int64_t S) {
+    return (flags & PM_DSC_TABLE_ONLY) ? S : 1 + (K - 1) * H + S;
+}
+
+// entries of the energy-term table (see dsc_estep_kernel), 0 where the kernels walk the states instead: the entry indices
+// are bytes, and without table states nothing reads it
+inline int64_t dsc_term_entries(int64_t Hprime, int64_t Kn, int64_t S) {
+    const int64_t NT = 1 + Hprime * Kn + Hprime * (Hprime - 1) / 2 * Kn * Kn;
+    return (NT > 256 || S == 0) ? 0 : NT;
+}
+
+// The layout of the sixteen-lane E-steps within 40 KB (four workgroups per CU): with the prior staged, else without.
+// False where neither fits or the kernels do not apply (H > 256: the scores row is held in registers); *stage is then
+// not meaningful (it may have been written).
+static bool dsc_fit_lay16(int64_t H, int64_t Hprime, int64_t S, int64_t Kt, int64_t NT, Lay16 *L, int *stage) {
+#ifdef PM_DSC_WAVE64
+    return false;
+#else
+    if (!(H <= 256 && S * Hprime < (1 << 20) && Kt < (1 << 20))) return false;
+    *stage = 1;
+    *L = dsc_lay16((int)H, (int)Hprime, (int)S, (int)Kt, (int)NT, 1);
+    if (L->bytes > 40 * 1024) {
+        *stage = 0;
+        *L = dsc_lay16((int)H, (int)Hprime, (int)S, (int)Kt, (int)NT, 0);
+    }
+    return L->bytes <= 40 * 1024;
+#endif
+}
+
 // E-step + M-step row statistics in one pass (dsc_estep16_ms_kernel): its LDS layout, or 0 where it does not apply
 static size_t dsc_estep_ms_lds(int64_t H, int64_t Hprime, int64_t S, int64_t Kt, int64_t Kn, int *stage16, int *nt16) {
-#ifdef PM_DSC_WAVE64
-    return 0;
-#else
-    if (!(H <= 256 && S * Hprime < (1 << 20) && Kt < (1 << 20))) return 0;
-    int64_t NT16 = 1 + Hprime * Kn + Hprime * (Hprime - 1) / 2 * Kn * Kn;
-    if (NT16 > 256 || S == 0) NT16 = 0;
-    *stage16 = 1;
-    Lay16 L = dsc_lay16((int)H, (int)Hprime, (int)S, (int)Kt, (int)NT16, 1);
-    if (L.bytes > 40 * 1024) {
-        *stage16 = 0;
-        L = dsc_lay16((int)H, (int)Hprime, (int)S, (int)Kt, (int)NT16, 0);
-    }
-    if (L.bytes > 40 * 1024) return 0;
+    const int64_t NT16 = dsc_term_entries(Hprime, Kn, S);
+    Lay16 L;
+    if (!dsc_fit_lay16(H, Hprime, S, Kt, NT16, &L, stage16)) return 0;
     *nt16 = (int)NT16;
     const size_t total = (size_t)((L.bytes + 7) & ~7) + sizeof(double) * (size_t)(H + PM_DSC_MAX_K + 4) +
                          sizeof(double) * 16 * (size_t)(Hprime + Hprime * Hprime);
     return total <= 64 * 1024 ? total : 0;
-#endif
 }
 
 // the launch geometry of dsc_mstep_rows16_kernel, or 0 bytes where it does not apply
@@ -1241,7 +1173,7 @@ static int dsc_plan(int which, int64_t H, int64_t Hprime, int64_t S, int64_t K, 
         return PM_EINVAL;
     if (Hprime > PM_MAX_HPRIME || Hprime > H || H > 65536) return PM_ERANGE;
     const int64_t Kn = K - 1;
-    const int64_t Kt = (flags & PM_DSC_TABLE_ONLY) ? S : 1 + Kn * H + S;
+    const int64_t Kt = dsc_columns(flags, K, H, S);
     *p = DscPlan{};
     p->maxhp = Hprime <= 8 ? 8 : PM_MAX_HPRIME;
     const int64_t blocks16 = (N + 15) / 16;
@@ -1275,41 +1207,29 @@ static int dsc_plan(int which, int64_t H, int64_t Hprime, int64_t S, int64_t K, 
         p->grid = row_grid(N, p->maxhp <= 8 ? 4 : 3);
         return PM_OK;
     }
-#ifndef PM_DSC_WAVE64
-    {
-        // sixteen lanes per datapoint where its LDS layout fits four workgroups per CU
-        int64_t NT16 = 1 + Hprime * Kn + Hprime * (Hprime - 1) / 2 * Kn * Kn;
-        if (NT16 > 256 || S == 0) NT16 = 0;
-        if (S * Hprime < (1 << 20) && Kt < (1 << 20)) {
-            int stage16 = 1;
-            Lay16 L = dsc_lay16((int)H, (int)Hprime, (int)S, (int)Kt, (int)NT16, stage16);
-            if (L.bytes > 40 * 1024) {
-                stage16 = 0;
-                L = dsc_lay16((int)H, (int)Hprime, (int)S, (int)Kt, (int)NT16, stage16);
-            }
-            if (L.bytes <= 40 * 1024 && H <= 256) {
-                p->family = PM_DSC_PLAN_LANES16;
-                p->vpl = H <= 128 ? 8 : 16;
-                p->stage = stage16;
-                p->nt = (int)NT16;
-                p->lds = (size_t)L.bytes;
-                p->grid = (unsigned)(blocks16 < 256 * 4 ? blocks16 : 256 * 4);
-                return PM_OK;
-            }
-        }
+    // sixteen lanes per datapoint where its LDS layout fits four workgroups per CU
+    int64_t NT = dsc_term_entries(Hprime, Kn, S);
+    Lay16 L;
+    if (dsc_fit_lay16(H, Hprime, S, Kt, NT, &L, &p->stage)) {      // (where it does not fit, p->stage is set again below)
+        p->family = PM_DSC_PLAN_LANES16;
+        p->vpl = H <= 128 ? 8 : 16;
+        p->nt = (int)NT;
+        p->lds = (size_t)L.bytes;
+        p->grid = (unsigned)(blocks16 < 256 * 4 ? blocks16 : 256 * 4);
+        return PM_OK;
     }
-#endif
     size_t shmem = sizeof(double) * (H + WAVES * (Hprime + Hprime * Hprime)) + align8((size_t)S * Hprime);
     if (shmem > 150 * 1024) return PM_ERANGE;
     const size_t staged = shmem + sizeof(double) * (size_t)(WAVES + 1) * (size_t)Kt;
     p->stage = staged <= 30 * 1024 ? 1 : 0;       // keep five workgroups per CU
     if (p->stage) shmem = staged;
-    // the energy-term tables (see the kernel): where they fit beside the rest
-    int64_t NT = 1 + Hprime * Kn + Hprime * (Hprime - 1) / 2 * Kn * Kn;
+    // the energy-term tables (see the kernel), where there are any (NT > 0) and they fit beside the rest
     const size_t fast_off = align8(shmem);
-    const size_t fast_bytes = (size_t)S * 8 + 2 * (size_t)((NT + 7) & ~7) + sizeof(double) * (size_t)NT * (2 + WAVES);
-    if (NT > 256 || S == 0 || fast_off + fast_bytes > 40 * 1024) NT = 0;
-    else shmem = fast_off + fast_bytes;
+    if (NT > 0) {
+        const size_t fast_bytes = (size_t)S * 8 + 2 * (size_t)((NT + 7) & ~7) + sizeof(double) * (size_t)NT * (2 + WAVES);
+        if (fast_off + fast_bytes <= 40 * 1024) shmem = fast_off + fast_bytes;
+        else NT = 0;
+    }
     p->family = PM_DSC_PLAN_WAVE;
     p->nt = (int)NT;
     p->fast_off = (int)fast_off;
@@ -1350,13 +1270,13 @@ extern "C" int pm_dsc_estep_f64(const double *scores, int64_t lds, const double 
     if (!scores || !gram || !ynorm2 || !cand || !prior || !logpj || !lse || N < 0 || H <= 0 || Hprime <= 0 || S < 0 ||
         lds < H || bad_params(params_host) || (S > 0 && !state_idx))
         return PM_EINVAL;
-    if (ldl < ((params_host->flags & PM_DSC_TABLE_ONLY) ? S : 1 + (params_host->K - 1) * H + S)) return PM_EINVAL;
+    if (ldl < dsc_columns(params_host->flags, params_host->K, H, S)) return PM_EINVAL;
     DscPlan pl;
     if (int e = dsc_plan(PM_DSC_PLAN_ESTEP, H, Hprime, S, params_host->K, params_host->flags, N, &pl)) return e;
     if (pl.family == PM_DSC_PLAN_LANES16) {
 #define PM_LAUNCH16(M, V)                                                                                              \
     do {                                                                                                               \
-        if (int e = allow_lds_dsc(reinterpret_cast<const void *>(dsc_estep16_kernel<M, V>), pl.lds)) return e;         \
+        if (int e = pm_allow_lds(reinterpret_cast<const void *>(dsc_estep16_kernel<M, V>), pl.lds)) return e;          \
         hipLaunchKernelGGL((dsc_estep16_kernel<M, V>), dim3(pl.grid), dim3(256), pl.lds,                               \
                            static_cast<hipStream_t>(stream), scores, lds, gram, ynorm2, cand, state_idx, (int)S, prior, \
                            *params_host, N, (int)H, (int)Hprime, logpj, ldl, lse, pl.stage, pl.nt);                    \
@@ -1367,7 +1287,7 @@ extern "C" int pm_dsc_estep_f64(const double *scores, int64_t lds, const double 
     }
 #define PM_LAUNCH(M)                                                                                                 \
     do {                                                                                                             \
-        if (int e = allow_lds_dsc(reinterpret_cast<const void *>(dsc_estep_kernel<M>), pl.lds)) return e;            \
+        if (int e = pm_allow_lds(reinterpret_cast<const void *>(dsc_estep_kernel<M>), pl.lds)) return e;             \
         hipLaunchKernelGGL(dsc_estep_kernel<M>, dim3(pl.grid), dim3(64 * WAVES), pl.lds,                             \
                            static_cast<hipStream_t>(stream), scores, lds, gram, ynorm2, cand, state_idx, (int)S, prior, \
                            *params_host, N, (int)H, (int)Hprime, logpj, ldl, lse, pl.stage, pl.fast_off, pl.nt);     \
@@ -1381,7 +1301,7 @@ extern "C" int pm_dsc_estep_f64(const double *scores, int64_t lds, const double 
 extern "C" int pm_dsc_estep_mstats_supported(int64_t H, int64_t Hprime, int64_t S, int64_t K, int flags) {
     if (H <= 0 || Hprime <= 0 || Hprime > PM_MAX_HPRIME || Hprime > H || S < 0 || K < 2 || K > PM_DSC_MAX_K) return 0;
     int st = 0, nt = 0;
-    return dsc_estep_ms_lds(H, Hprime, S, (flags & PM_DSC_TABLE_ONLY) ? S : 1 + (K - 1) * H + S, K - 1, &st, &nt) ? 1 : 0;
+    return dsc_estep_ms_lds(H, Hprime, S, dsc_columns(flags, K, H, S), K - 1, &st, &nt) ? 1 : 0;
 }
 
 extern "C" int pm_dsc_estep_mstats_f64(const double *scores, int64_t lds, const double *gram, const double *ynorm2,
@@ -1395,13 +1315,12 @@ extern "C" int pm_dsc_estep_mstats_f64(const double *scores, int64_t lds, const 
         Hprime <= 0 || S < 0 || lds < H || lde < H || bad_params(params_host) || (S > 0 && !state_idx) ||
         params_host->ecoef == 0.0)
         return PM_EINVAL;
-    const int64_t Kt = (params_host->flags & PM_DSC_TABLE_ONLY) ? S : 1 + (params_host->K - 1) * H + S;
-    if (ldl < Kt) return PM_EINVAL;
+    if (ldl < dsc_columns(params_host->flags, params_host->K, H, S)) return PM_EINVAL;
     DscPlan pl;
     if (int e = dsc_plan(PM_DSC_PLAN_ESTEP_MSTATS, H, Hprime, S, params_host->K, params_host->flags, N, &pl)) return e;
 #define PM_LAUNCH16K(M, V, KMV)                                                                                        \
     do {                                                                                                               \
-        if (int e = allow_lds_dsc(reinterpret_cast<const void *>(dsc_estep16_ms_kernel<M, V, KMV>), pl.lds)) return e; \
+        if (int e = pm_allow_lds(reinterpret_cast<const void *>(dsc_estep16_ms_kernel<M, V, KMV>), pl.lds)) return e;  \
         hipLaunchKernelGGL((dsc_estep16_ms_kernel<M, V, KMV>), dim3(pl.grid), dim3(256), pl.lds,                       \
                            static_cast<hipStream_t>(stream), scores, lds, gram, ynorm2, cand, state_idx, (int)S, prior, \
                            *params_host, N, (int)H, (int)D, (int)Hprime, logpj, ldl, lse, pl.stage, pl.nt, expect, lde, \
@@ -1424,7 +1343,7 @@ extern "C" int pm_dsc_estep_mstats_f64(const double *scores, int64_t lds, const 
 extern "C" int pm_dsc_rows16_supported(int64_t H, int64_t Hprime, int64_t S, int64_t K, int flags) {
     if (H <= 0 || Hprime <= 0 || Hprime > PM_MAX_HPRIME || S < 0 || K < 2 || K > PM_DSC_MAX_K) return 0;
     int st = 0;
-    return dsc_rows16_lds(H, Hprime, S, (flags & PM_DSC_TABLE_ONLY) ? S : 1 + (K - 1) * H + S, &st) ? 1 : 0;
+    return dsc_rows16_lds(H, Hprime, S, dsc_columns(flags, K, H, S), &st) ? 1 : 0;
 }
 
 extern "C" int pm_dsc_mstep_rows_f64(const double *logpj, int64_t ldl, const double *lse, double lse_cut,
@@ -1454,15 +1373,13 @@ extern "C" int pm_dsc_mstep_rows_cutp_f64(const double *logpj, int64_t ldl, cons
     if (!logpj || !lse || !cand || !prior || !expect || !stats || N < 0 || H <= 0 || D <= 0 || Hprime <= 0 || S < 0 ||
         lde < H || bad_params(params_host) || (S > 0 && !state_idx))
         return PM_EINVAL;
-    if (ldl < ((params_host->flags & PM_DSC_TABLE_ONLY) ? S : 1 + (params_host->K - 1) * H + S) ||
-        params_host->ecoef == 0.0)
-        return PM_EINVAL;
+    if (ldl < dsc_columns(params_host->flags, params_host->K, H, S) || params_host->ecoef == 0.0) return PM_EINVAL;
     DscPlan pl;
     if (int e = dsc_plan(PM_DSC_PLAN_MSTEP_ROWS, H, Hprime, S, params_host->K, params_host->flags, N, &pl)) return e;
     if (pl.family == PM_DSC_PLAN_LANES16) {
 #define PM_LAUNCH16(M, V)                                                                                              \
     do {                                                                                                               \
-        if (int e = allow_lds_dsc(reinterpret_cast<const void *>(dsc_mstep_rows16_kernel<M, V>), pl.lds)) return e;    \
+        if (int e = pm_allow_lds(reinterpret_cast<const void *>(dsc_mstep_rows16_kernel<M, V>), pl.lds)) return e;     \
         hipLaunchKernelGGL((dsc_mstep_rows16_kernel<M, V>), dim3(pl.grid), dim3(256), pl.lds,                          \
                            static_cast<hipStream_t>(stream), logpj, ldl, lse, lse_cut, cand, state_idx, (int)S, prior, \
                            *params_host, N, (int)H, (int)D, (int)Hprime, expect, lde, stats, pl.stage, nz_idx, nz_val, \
@@ -1475,7 +1392,7 @@ extern "C" int pm_dsc_mstep_rows_cutp_f64(const double *logpj, int64_t ldl, cons
     if (nz_idx) return PM_ERANGE;       // (lists come from the sixteen-lane kernel only: pm_dsc_rows16_supported)
 #define PM_LAUNCH(M)                                                                                                 \
     do {                                                                                                             \
-        if (int e = allow_lds_dsc(reinterpret_cast<const void *>(dsc_mstep_rows_kernel<M>), pl.lds)) return e;       \
+        if (int e = pm_allow_lds(reinterpret_cast<const void *>(dsc_mstep_rows_kernel<M>), pl.lds)) return e;        \
         hipLaunchKernelGGL(dsc_mstep_rows_kernel<M>, dim3(pl.grid), dim3(64 * WAVES), pl.lds,                        \
                            static_cast<hipStream_t>(stream), logpj, ldl, lse, lse_cut, cand, state_idx, (int)S, prior, \
                            *params_host, N, (int)H, (int)D, (int)Hprime, expect, lde, stats, pl.stage, cut_dev);     \
@@ -1498,3 +1415,7 @@ extern "C" int pm_tsc_select_scores_f64(const double *scores, int64_t lds, const
 }
 
 PM_DET_SETTER(dsc)
+#undef DSC_SCATTER_STATE
+#undef DSC_ROW16_NZ_LIST
+#undef DSC_FLUSH_WQ
+#undef DSC_STATS_EPILOGUE

@@ -742,11 +742,6 @@ __global__ __launch_bounds__(256) void gsc_colsum_kernel(const double *__restric
     }
 }
 
-static int allow_lds_gsc(const void *kernel, size_t bytes) {
-    if (bytes <= 48 * 1024) return 0;
-    return (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 }  // namespace
 
 #ifdef PM_GSC_STAMPS
@@ -1026,14 +1021,14 @@ static int gsc_estep_launch(const double *scores, int64_t lds, const double *gra
     const double inv_s2 = sigma_sq > 0.0 ? 1.0 / sigma_sq : 0.0;   // 0: tables[8 H] holds it (pm_gsc_mstep_finish_f64)
 #define PM_LAUNCH_LA(V, G, L, A)                                                                                        \
     do {                                                                                                               \
-        if (int e = allow_lds_gsc(reinterpret_cast<const void *>(gsc_estep_kernel<V, G, L, A>), shmem)) return e;       \
+        if (int e = pm_allow_lds(reinterpret_cast<const void *>(gsc_estep_kernel<V, G, L, A>), shmem)) return e;        \
         hipLaunchKernelGGL((gsc_estep_kernel<V, G, L, A>), grid, block, shmem, s, scores, lds, gram, psi_sq, ynorm2, T, \
                            state_masks, (int)S, beta, inv_s2, N, (int)H, (int)Hprime, do_select, cand, xpt_s, xpt_sz,  \
                            ldx, stats, logpj, ldl, nullptr, nullptr, nullptr, nullptr, blocks, ldb);                   \
     } while (0)
 #define PM_LAUNCH_LIST(V, G)                                                                                           \
     do {                                                                                                               \
-        if (int e = allow_lds_gsc(reinterpret_cast<const void *>(gsc_estep_kernel<V, G, false, true, true>), shmem))   \
+        if (int e = pm_allow_lds(reinterpret_cast<const void *>(gsc_estep_kernel<V, G, false, true, true>), shmem))    \
             return e;                                                                                                  \
         hipLaunchKernelGGL((gsc_estep_kernel<V, G, false, true, true>), grid, block, shmem, s, scores, lds, gram,      \
                            psi_sq, ynorm2, T, state_masks, (int)S, beta, inv_s2, N, (int)H, (int)Hprime, do_select,    \

@@ -16,32 +16,17 @@
 
 #include "prosper_hip.h"
 #include "pm_common.h"
+#include "mca_rows.h"
 
 namespace {
 
 constexpr int WAVES = 4;      // wavefronts per workgroup (BSC / prepare kernels)
 constexpr int WLD = 65;       // LDS row of a 64-dimension slab of a candidate's W row: 65 doubles, lanes on different rows hit different banks
 
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
 __device__ __forceinline__ int wave_sum_i32(int v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, PM_WAVE);
     return v;
-}
-
-inline int64_t grid_for_rows(int64_t N, int waves) {
-    int64_t blocks = (N + waves - 1) / waves;
-    const int64_t cap = 256 * 8;  // 8 workgroups per CU, grid-stride beyond
-    return blocks < cap ? (blocks < 1 ? 1 : blocks) : cap;
-}
-
-int allow_lds(const void *kernel, size_t bytes) {
-    if (bytes <= 48 * 1024) return 0;
-    return (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -170,7 +155,7 @@ __global__ __launch_bounds__(256) void bsc_masked_estep_kernel(const double *__r
                 s_c[Hp - 1 - r] = bi;
             }
         }
-        wave_lds_sync();
+        pm_wave_lds_sync();
 
         // ---- masked pair products of the candidates' rows of W^T
         double a0 = 0.0, a1 = 0.0;
@@ -182,7 +167,7 @@ __global__ __launch_bounds__(256) void bsc_masked_estep_kernel(const double *__r
                 if (on) w = Wt[(int64_t)s_c[j] * ldw + d];
                 s_w[j * WLD + lane] = w;
             }
-            wave_lds_sync();
+            pm_wave_lds_sync();
             if (own0) {
                 const double *wi = s_w + pi_[0] * WLD, *wj = s_w + pj_[0] * WLD;
 #pragma unroll 8
@@ -193,7 +178,7 @@ __global__ __launch_bounds__(256) void bsc_masked_estep_kernel(const double *__r
 #pragma unroll 8
                 for (int k = 0; k < 64; ++k) a1 = fma(wi[k], wj[k], a1);
             }
-            wave_lds_sync();
+            pm_wave_lds_sync();
         }
         if (own0) {
             s_gc[pi_[0] * Hp + pj_[0]] = a0;
@@ -208,7 +193,7 @@ __global__ __launch_bounds__(256) void bsc_masked_estep_kernel(const double *__r
             s_ac[lane] = brow[c];
             s_gc[lane * Hp + lane] = grow[c];
         }
-        wave_lds_sync();
+        pm_wave_lds_sync();
 
         // ---- log-joints
         const double yn = xnorm2[n];
@@ -239,7 +224,7 @@ __global__ __launch_bounds__(256) void bsc_masked_estep_kernel(const double *__r
             const double e = yn - 2.0 * lin + quad;
             out[1 + H + s] = ppil * (double)__builtin_popcount(mask_s) + P.ecoef * e;
         }
-        wave_lds_sync();  // s_c / s_ac / s_gc are rewritten for the next datapoint
+        pm_wave_lds_sync();  // s_c / s_ac / s_gc are rewritten for the next datapoint
     }
 }
 
@@ -357,7 +342,7 @@ __global__ __launch_bounds__(256) void mca_masked_estep_kernel(const double *__r
                 s_wr[j * DS + d] = (d < D) ? src[d] : 0.0;
             }
         }
-        wave_lds_sync();
+        pm_wave_lds_sync();
 
         auto states = [&](auto root_tag) {
             constexpr int ROOT = decltype(root_tag)::value;
@@ -391,65 +376,15 @@ __global__ __launch_bounds__(256) void mca_masked_estep_kernel(const double *__r
         if (r21) states(std::integral_constant<int, 21>{});
         else if (r6) states(std::integral_constant<int, 6>{});
         else states(std::integral_constant<int, 0>{});
-        wave_lds_sync();
+        pm_wave_lds_sync();
 
         const double yn = xnorm2[n];
         const double *arow = scores + n * lds;
         const double *wrow = wnorm2 + n * ldwn;
         double *out = logpj + n * ldl;
-        double m1 = -INFINITY;
-        if (lane == 0) {
-            const double f0 = P.pre1 * yn;
-            out[0] = f0;
-            m1 = f0;
-        }
-        for (int h = lane; h < H; h += 64) {
-            const double f = P.pil_bar + P.pre1 * (wrow[h] - 2.0 * arow[h] + yn);
-            out[1 + h] = f;
-            m1 = fmax(m1, f);
-        }
-        for (int s = lane; s < S; s += 64) {
-            const double f = P.pil_bar * (double)__builtin_popcount((unsigned)masks[s]) + P.pre1 * s_e[s];
-            out[1 + H + s] = f;
-            s_e[s] = f;
-            m1 = fmax(m1, f);
-        }
-        m1 = pm_wave_max(m1);
-        double s1 = 0.0, sb = 0.0;
-        if (lane == 0) {
-            const double dlt = out[0] - m1;  // own store, same lane
-            s1 += exp(dlt);
-            sb += exp(P.beta * dlt);
-        }
-        for (int h = lane; h < H; h += 64) {
-            const double dlt = (P.pil_bar + P.pre1 * (wrow[h] - 2.0 * arow[h] + yn)) - m1;
-            if (dlt > -745.0) {
-                s1 += exp(dlt);
-                sb += exp(P.beta * dlt);
-            }
-        }
-        for (int s = lane; s < S; s += 64) {
-            const double dlt = s_e[s] - m1;
-            if (dlt > -745.0) {
-                s1 += exp(dlt);
-                sb += exp(P.beta * dlt);
-            }
-        }
-        s1 = pm_wave_sum(s1);
-        sb = pm_wave_sum(sb);
-        if (lane == 0) {
-            lse1[n] = m1 + log(s1);
-            lseb[n] = P.beta * m1 + log(sb);
-        }
-        wave_lds_sync();
+        MCA_ROW_TAIL(wrow, yn, arow, out, lse1[n], lseb[n]);
+        pm_wave_lds_sync();
     }
-}
-
-// wavefronts per workgroup so that the per-wave LDS areas fit ~64 KB
-inline int pick_waves(size_t per_wave_bytes, size_t shared_bytes) {
-    int w = 4;
-    while (w > 1 && shared_bytes + w * per_wave_bytes > 64 * 1024) w >>= 1;
-    return w;
 }
 
 }  // namespace
@@ -461,7 +396,7 @@ extern "C" int pm_masked_prepare_f64(const double *Y, int64_t ldy, const uint8_t
         return PM_EINVAL;
     if (D > INT32_MAX) return PM_ERANGE;
     if (N == 0) return PM_OK;
-    hipLaunchKernelGGL(masked_prepare_kernel, dim3((unsigned)grid_for_rows(N, WAVES)), dim3(256), 0,
+    hipLaunchKernelGGL(masked_prepare_kernel, dim3((unsigned)pm_row_grid(N, WAVES)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), Y, ldy, mask, ldm, mu, N, (int)D, X0, ldx, Mf, ldf, xnorm2, dn);
     return (int)hipGetLastError();
 }
@@ -478,11 +413,11 @@ extern "C" int pm_bsc_masked_estep_f64(const double *b, int64_t ldb, const doubl
     if (N == 0) return PM_OK;
     const size_t shmem = sizeof(double) * WAVES * (16 + 256 + 16 * WLD + 8) + sizeof(uint16_t) * S;
     if (shmem > 160 * 1024) return PM_ERANGE;
-    dim3 grid((unsigned)grid_for_rows(N, WAVES)), block(256);
+    dim3 grid((unsigned)pm_row_grid(N, WAVES)), block(256);
     hipStream_t s = static_cast<hipStream_t>(stream);
 #define PM_LAUNCH(V)                                                                                                   \
     do {                                                                                                               \
-        if (int e = allow_lds(reinterpret_cast<const void *>(bsc_masked_estep_kernel<V>), shmem)) return e;            \
+        if (int e = pm_allow_lds(reinterpret_cast<const void *>(bsc_masked_estep_kernel<V>), shmem)) return e;            \
         hipLaunchKernelGGL(bsc_masked_estep_kernel<V>, grid, block, shmem, s, b, ldb, g, ldg, xnorm2, mask, ldm, Wt, ldw, \
                            state_masks, (int)S, *params_host, N, (int)H, (int)D, (int)Hprime, cand, logpj, ldl);       \
     } while (0)
@@ -524,13 +459,13 @@ extern "C" int pm_mca_masked_estep_f64(const double *scores, int64_t lds, const 
     if (per_wave > 150 * 1024) return PM_ERANGE;
     if (N == 0) return PM_OK;
     const size_t shared = sizeof(double) * PM_POWTAB_LEN;
-    const int waves = pick_waves(per_wave, shared);
+    const int waves = mca_pick_waves(per_wave, shared);
     const size_t shmem = shared + per_wave * waves;
-    dim3 grid((unsigned)grid_for_rows(N, waves)), block(64 * waves);
+    dim3 grid((unsigned)pm_row_grid(N, waves)), block(64 * waves);
     hipStream_t s = static_cast<hipStream_t>(stream);
 #define PM_LAUNCH(V)                                                                                                   \
     do {                                                                                                               \
-        if (int e = allow_lds(reinterpret_cast<const void *>(mca_masked_estep_kernel<V>), shmem)) return e;            \
+        if (int e = pm_allow_lds(reinterpret_cast<const void *>(mca_masked_estep_kernel<V>), shmem)) return e;           \
         hipLaunchKernelGGL(mca_masked_estep_kernel<V>, grid, block, shmem, s, scores, lds, wnorm2_obs, ldwn, xnorm2, X0, \
                            ldx, mask, ldm, Wrho, cand, state_masks, (int)S, *params_host, N, (int)H, (int)D, (int)Hprime, \
                            logpj, ldl, lse1, lseb);                                                                    \
@@ -545,3 +480,5 @@ extern "C" int pm_mca_masked_estep_f64(const double *scores, int64_t lds, const 
 #undef PM_LAUNCH
     return (int)hipGetLastError();
 }
+#undef MCA_ROW_TAIL
+#undef MCA_STATS_EPILOGUE

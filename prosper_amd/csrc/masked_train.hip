@@ -29,17 +29,6 @@ constexpr int64_t MT_MAX_CELLS = (int64_t)1 << 28;   // D H^2: A and its inverse
 constexpr int64_t CS_MAX_BLOCKS = 1024;
 constexpr int64_t CS_MIN_ROWS = 16;
 
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
-inline int64_t grid_for_rows(int64_t N, int waves) {
-    int64_t blocks = (N + waves - 1) / waves;
-    const int64_t cap = 256 * 8;  // 8 workgroups per CU, grid-stride beyond
-    return blocks < cap ? (blocks < 1 ? 1 : blocks) : cap;
-}
-
 // ---------------------------------------------------------------------------------------------
 // rows: one wavefront per row.  q(s) = exp(logpj_s - lse); the energy of a state is recovered from its log-joint,
 // e_s = (logpj_s - ppil |s|) / ecoef (logpj_s = ppil |s| + ecoef e_s is how pm_bsc_masked_estep_f64 formed it).
@@ -97,7 +86,7 @@ __global__ __launch_bounds__(64 * RW) void mtrain_rows_kernel(const double *__re
                 const double e = (x - ppil * (double)__builtin_popcount(mk)) / ecoef;
                 en = q == 0.0 ? en : fma(q, e, en);
             }
-            wave_lds_sync();
+            pm_wave_lds_sync();
             for (int k = 0; k < cnt; ++k) {
                 const unsigned mk = wk[k];
                 const double q = wq[k];
@@ -105,7 +94,7 @@ __global__ __launch_bounds__(64 * RW) void mtrain_rows_kernel(const double *__re
                 a1 += (mk & pm1) == pm1 ? q : 0.0;
                 am += (mk & cm) == cm ? q : 0.0;
             }
-            wave_lds_sync();
+            pm_wave_lds_sync();
         }
         if (lane < npair) q2[n * ldq + lane] = a0;
         if (lane + 64 < npair) q2[n * ldq + lane + 64] = a1;
@@ -113,7 +102,7 @@ __global__ __launch_bounds__(64 * RW) void mtrain_rows_kernel(const double *__re
             wm[lane] = am;
             wc[lane] = cand[n * Hp + lane];
         }
-        wave_lds_sync();
+        pm_wave_lds_sync();
         for (int h = lane; h < H; h += 64) {
             const double x = lp[1 + h], q = exp(x - l);
             const double e = (x - ppil) / ecoef;
@@ -124,7 +113,7 @@ __global__ __launch_bounds__(64 * RW) void mtrain_rows_kernel(const double *__re
         }
         en = pm_wave_sum(en);
         if (lane == 0) energy[n] = en;
-        wave_lds_sync();  // wm / wc are rewritten for the next row
+        pm_wave_lds_sync();  // wm / wc are rewritten for the next row
     }
 }
 
@@ -310,7 +299,7 @@ extern "C" int pm_bsc_mtrain_rows_f64(const double *logpj, int64_t ldl, const do
     if (npair > 0 && (!q2 || ldq < npair)) return PM_EINVAL;
     if (!(params_host->ecoef < 0.0)) return PM_EINVAL;      // (the energies are recovered by dividing by it)
     if (N == 0) return PM_OK;
-    hipLaunchKernelGGL(mtrain_rows_kernel, dim3((unsigned)grid_for_rows(N, RW)), dim3(64 * RW), 0,
+    hipLaunchKernelGGL(mtrain_rows_kernel, dim3((unsigned)pm_row_grid(N, RW)), dim3(64 * RW), 0,
                        static_cast<hipStream_t>(stream), logpj, ldl, lse, cand, state_masks, (int)S,
                        params_host->prior_scale * params_host->pil_bar, params_host->ecoef, N, (int)H, (int)Hprime, es, lde,
                        q2, ldq, energy);

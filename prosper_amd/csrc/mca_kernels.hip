@@ -22,6 +22,7 @@
 
 #include "prosper_hip.h"
 #include "pm_common.h"
+#include "mca_rows.h"
 
 // documented part of the statistics buffer; the per-XCD copies of [Wp | Wq] follow it (pm_common.h)
 __host__ __device__ static inline int64_t mca_stats_base(int64_t H, int64_t D) { return 3 * H * D + H + PM_MCA_NSCALARS; }
@@ -61,11 +62,6 @@ namespace {
 // the fused pass walks its states two per trip (see PAIRED in mca_estep_fused_body)
 __host__ __device__ constexpr bool mca_fused_paired(int dpl, int hp, bool sgn) {
     return (PM_MCA_PAIR == 1) || (PM_MCA_PAIR < 0 && sgn && dpl <= 4 && hp * dpl >= 24);
-}
-
-__device__ __forceinline__ void wave_sync_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -211,7 +207,7 @@ __global__ __launch_bounds__(256) void mca_estep_kernel(const double *__restrict
                 s_wr[j * DS + d] = (d < D) ? src[d] : 0.0;
             }
         }
-        wave_sync_lds();
+        pm_wave_lds_sync();
 
         // multi-cause states: e_s = sum_d (Wbar_sd - y_d)^2.  Padding dimensions hold W^rho = 0 and y = 0:
         // Wbar = 0 there and they add nothing, so the loop body is branch-free and the DPL powers of a
@@ -286,57 +282,14 @@ __global__ __launch_bounds__(256) void mca_estep_kernel(const double *__restrict
         if (r21) states(std::integral_constant<int, 21>{});
         else if (r6) states(std::integral_constant<int, 6>{});
         else states(std::integral_constant<int, 0>{});
-        wave_sync_lds();
+        pm_wave_lds_sync();
 
         // log-pseudo-joints and the two log-evidences (beta = 1 for Q, beta = 1/T for the weights)
         const double yn = ynorm2[n];
         const double *arow = scores + n * lds;
         double *out = logpj + n * ldl;
-        double m1 = -INFINITY;
-        if (lane == 0) {
-            const double f0 = P.pre1 * yn;
-            out[0] = f0;
-            m1 = f0;
-        }
-        for (int h = lane; h < H; h += 64) {
-            const double f = P.pil_bar + P.pre1 * (wnorm2[h] - 2.0 * arow[h] + yn);
-            out[1 + h] = f;
-            m1 = fmax(m1, f);
-        }
-        for (int s = lane; s < S; s += 64) {
-            const double f = P.pil_bar * (double)__builtin_popcount((unsigned)masks[s]) + P.pre1 * s_e[s];
-            out[1 + H + s] = f;
-            s_e[s] = f;
-            m1 = fmax(m1, f);
-        }
-        m1 = pm_wave_max(m1);
-        double s1 = 0.0, sb = 0.0;
-        if (lane == 0) {
-            const double dlt = out[0] - m1;  // own store, same lane
-            s1 += exp(dlt);
-            sb += exp(P.beta * dlt);
-        }
-        for (int h = lane; h < H; h += 64) {
-            const double dlt = (P.pil_bar + P.pre1 * (wnorm2[h] - 2.0 * arow[h] + yn)) - m1;
-            if (dlt > -745.0) {
-                s1 += exp(dlt);
-                sb += exp(P.beta * dlt);
-            }
-        }
-        for (int s = lane; s < S; s += 64) {
-            const double dlt = s_e[s] - m1;
-            if (dlt > -745.0) {
-                s1 += exp(dlt);
-                sb += exp(P.beta * dlt);
-            }
-        }
-        s1 = pm_wave_sum(s1);
-        sb = pm_wave_sum(sb);
-        if (lane == 0) {
-            lse1[n] = m1 + log(s1);
-            lseb[n] = P.beta * m1 + log(sb);
-        }
-        wave_sync_lds();
+        MCA_ROW_TAIL(wnorm2, yn, arow, out, lse1[n], lseb[n]);
+        pm_wave_lds_sync();
     }
 }
 
@@ -422,7 +375,7 @@ __device__ __forceinline__ void mca_estep_fused_body(const double *__restrict__ 
                 if (SIGNED) s_wm[j * DS + d] = (have && d < D) ? Wrm1[base + d] : 1.0;
             }
         }
-        wave_sync_lds();
+        pm_wave_lds_sync();
 
         double V[HP][DPL];
 #pragma unroll
@@ -725,7 +678,7 @@ __device__ __forceinline__ void mca_estep_fused_body(const double *__restrict__ 
         }
         if (PM_MCA_VDEFER) v_update();             // the last state
         }
-        wave_sync_lds();
+        pm_wave_lds_sync();
 
         // log-pseudo-joints and the two log-evidences (as mca_estep_kernel)
         const double yn = ynorm2[n];
@@ -865,31 +818,10 @@ __device__ __forceinline__ void mca_estep_fused_body(const double *__restrict__ 
                 }
             }
         }
-        wave_sync_lds();
+        pm_wave_lds_sync();
     }
 
-    st_pi = pm_wave_sum(st_pi);
-    st_sigma = pm_wave_sum(st_sigma);
-    st_ld = pm_wave_sum(st_ld);
-    st_cnt = pm_wave_sum(st_cnt);
-    if (lane == 0) {
-        s_red[wave * 4 + 0] = st_pi;
-        s_red[wave * 4 + 1] = st_sigma;
-        s_red[wave * 4 + 2] = st_ld;
-        s_red[wave * 4 + 3] = st_cnt;
-    }
-    __syncthreads();
-    double *g_q1sum = stats + 3 * (int64_t)H * D;
-    double *sc = g_q1sum + H;
-    if (tid < 4) {
-        double v = 0.0;
-        for (int w = 0; w < waves; ++w) v += s_red[w * 4 + tid];
-        if (v != 0.0) pm_atomic_add(sc + tid, PM_Q(v, tid == 1 ? 3 : tid == 2 ? 4 : 2));    // pi | sum q e | sum lse | count
-    }
-    for (int h = tid; h < H; h += blockDim.x) {
-        const double v = s_q1sum[h];
-        if (v != 0.0) pm_atomic_add(g_q1sum + h, v);
-    }
+    MCA_STATS_EPILOGUE();
 }
 
 #define PM_MCA_FUSED_BOUNDS __launch_bounds__(256, (HP <= 8 && DPL <= 4 && ROOT == 0 && !(SIGNED && HP * DPL >= 24) ? 2 : 1))     // (the table power at H' <= 8, D <= 256 would take 258 registers: keep two wavefronts per SIMD; the others fit uncapped, and schedule better so; signed W with >= 24 KB of rows per wavefront runs one per SIMD anyway)
@@ -1105,7 +1037,7 @@ __global__ __launch_bounds__(256) void mca_mstep_rows_kernel(const double *__res
                             if (SIGNED) s_wm[j * DS + d] = (d < Dl) ? Wrm1[(int64_t)cn[j] * D + d0 + d] : 1.0;
                         }
                     }
-                    wave_sync_lds();
+                    pm_wave_lds_sync();
                     staged = true;
                     pfx = 0xFFFFFFFFu;        // (the rows changed under the cached prefix)
                 }
@@ -1136,50 +1068,11 @@ __global__ __launch_bounds__(256) void mca_mstep_rows_kernel(const double *__res
                     }
                 }
             }
-            wave_sync_lds();
+            pm_wave_lds_sync();
         }
     }
 
-    st_pi = pm_wave_sum(st_pi);
-    st_sigma = pm_wave_sum(st_sigma);
-    st_ld = pm_wave_sum(st_ld);
-    st_cnt = pm_wave_sum(st_cnt);
-    if (lane == 0) {
-        s_red[wave * 4 + 0] = st_pi;
-        s_red[wave * 4 + 1] = st_sigma;
-        s_red[wave * 4 + 2] = st_ld;
-        s_red[wave * 4 + 3] = st_cnt;
-    }
-    __syncthreads();
-    double *g_q1sum = stats + 3 * (int64_t)H * D;
-    double *sc = g_q1sum + H;
-    if (tid < 4) {
-        double v = 0.0;
-        for (int w = 0; w < waves; ++w) v += s_red[w * 4 + tid];
-        if (v != 0.0) pm_atomic_add(sc + tid, PM_Q(v, tid == 1 ? 3 : tid == 2 ? 4 : 2));    // pi | sum q e | sum lse | count
-    }
-    for (int h = tid; h < H; h += blockDim.x) {
-        const double v = s_q1sum[h];
-        if (v != 0.0) pm_atomic_add(g_q1sum + h, v);
-    }
-}
-
-static int allow_lds_mca(const void *kernel, size_t bytes) {
-    if (bytes <= 48 * 1024) return 0;
-    return (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
-// wavefronts per workgroup so that the per-wave LDS areas fit ~64 KB
-inline int pick_waves(size_t per_wave_bytes, size_t shared_bytes) {
-    int w = 4;
-    while (w > 1 && shared_bytes + w * per_wave_bytes > 64 * 1024) w >>= 1;
-    return w;
-}
-
-inline int64_t grid_waves(int64_t N, int waves) {
-    int64_t blocks = (N + waves - 1) / waves;
-    const int64_t cap = 256 * 8;
-    return blocks < cap ? (blocks < 1 ? 1 : blocks) : cap;
+    MCA_STATS_EPILOGUE();
 }
 
 constexpr int DEFER_GROUPS = 64;      // datapoint groups of the scatter kernel (workspace: one [Wp | Wq] partial per group)
@@ -1211,9 +1104,9 @@ static int mca_plan(int which, int64_t H, int64_t D, int64_t Hprime, int64_t S, 
         const size_t per_wave = sizeof(double) * ((size_t)Hprime * 64 * p->dpl + S);
         if (per_wave > 150 * 1024) return PM_ERANGE;
         const size_t shared = sizeof(double) * PM_POWTAB_LEN;
-        p->waves = pick_waves(per_wave, shared);
+        p->waves = mca_pick_waves(per_wave, shared);
         p->lds = shared + per_wave * p->waves;
-        p->grid = (unsigned)grid_waves(N, p->waves);
+        p->grid = (unsigned)pm_row_grid(N, p->waves);
         return PM_OK;
     }
     if (which == PM_MCA_PLAN_MSTEP_ROWS) {
@@ -1230,10 +1123,10 @@ static int mca_plan(int which, int64_t H, int64_t D, int64_t Hprime, int64_t S, 
         p->root = (!sgn && MCA_RHO_IS(inv_rho, 21.0)) ? 21 : (sgn && MCA_RHO_IS(inv_rho, 6.0)) ? 6 : 0;
         const size_t per_wave = sizeof(double) * ((size_t)p->hp * 64 * p->dpl) * (sgn ? 2 : 1);
         const size_t shared = sizeof(double) * (PM_POWTAB_LEN + H + 16);
-        p->waves = pick_waves(per_wave, shared);
+        p->waves = mca_pick_waves(per_wave, shared);
         p->lds = shared + per_wave * p->waves;
         if (p->lds > 150 * 1024) return PM_ERANGE;
-        p->grid = (unsigned)grid_waves(N, p->waves);
+        p->grid = (unsigned)pm_row_grid(N, p->waves);
         return PM_OK;
     }
     if (which == PM_MCA_PLAN_FUSED) {
@@ -1255,10 +1148,10 @@ static int mca_plan(int which, int64_t H, int64_t D, int64_t Hprime, int64_t S, 
         p->paired = mca_fused_paired(p->dpl, p->hp, sgn) ? 1 : 0;
         const size_t per_wave = sizeof(double) * ((size_t)p->hp * 64 * p->dpl * (sgn ? 2 : 1) + S);
         const size_t shared = sizeof(double) * (PM_POWTAB_LEN + PM_FUSED_RT_LEN + H + 16);
-        p->waves = pick_waves(per_wave, shared);
+        p->waves = mca_pick_waves(per_wave, shared);
         p->lds = shared + per_wave * p->waves;
         if (p->lds > 150 * 1024) return PM_ERANGE;
-        p->grid = (unsigned)grid_waves(N, p->waves);
+        p->grid = (unsigned)pm_row_grid(N, p->waves);
         return PM_OK;
     }
     if (H > 512 || D > 512 || Hprime > 12) return PM_ERANGE;
@@ -1352,7 +1245,7 @@ extern "C" int pm_mca_estep_f64(const double *scores, int64_t lds, const double 
     hipStream_t s = static_cast<hipStream_t>(stream);
 #define PM_LAUNCH(V)                                                                                            \
     do {                                                                                                        \
-        if (int e = allow_lds_mca(reinterpret_cast<const void *>(mca_estep_kernel<V>), shmem)) return e;        \
+        if (int e = pm_allow_lds(reinterpret_cast<const void *>(mca_estep_kernel<V>), shmem)) return e;           \
         hipLaunchKernelGGL(mca_estep_kernel<V>, grid, block, shmem, s, scores, lds, wnorm2, ynorm2, Y, ldy, Wrho, \
                            cand, state_masks, (int)S, *params_host, N, (int)H, (int)D, (int)Hprime, logpj, ldl, \
                            lse1, lseb);                                                                         \
@@ -1377,7 +1270,7 @@ int launch_mstep_hp(int hp, int Hp, dim3 grid, dim3 block, size_t shmem, hipStre
     // hp: the register tile of the plan, Hp: the candidates
 #define PM_CASE(HPV)                                                                                              \
     case HPV: {                                                                                                   \
-        if (int e = allow_lds_mca(reinterpret_cast<const void *>(mca_mstep_rows_kernel<DPL, HPV, SIGNED>), shmem)) return e; \
+        if (int e = pm_allow_lds(reinterpret_cast<const void *>(mca_mstep_rows_kernel<DPL, HPV, SIGNED>), shmem)) return e;      \
         hipLaunchKernelGGL((mca_mstep_rows_kernel<DPL, HPV, SIGNED>), grid, block, shmem, s, logpj, ldl, lse1, lseb, lse_cut, Y, \
                            ldy, Wrho, Wrm1, cand, masks, S, P, N, H, D, d0, Dl, Hp, q1, ldq, stats);               \
         return (int)hipGetLastError();                                                                            \
@@ -1386,7 +1279,7 @@ int launch_mstep_hp(int hp, int Hp, dim3 grid, dim3 block, size_t shmem, hipStre
         PM_CASE(4) PM_CASE(8) PM_CASE(12)
         case 16:      // (V[16][DPL <= 2]: slabs of 128 observed dimensions)
             if (DPL <= 2) {
-                if (int e = allow_lds_mca(reinterpret_cast<const void *>(mca_mstep_rows_kernel<(DPL <= 2 ? DPL : 1), 16, SIGNED>), shmem)) return e;
+                if (int e = pm_allow_lds(reinterpret_cast<const void *>(mca_mstep_rows_kernel<(DPL <= 2 ? DPL : 1), 16, SIGNED>), shmem)) return e;
                 hipLaunchKernelGGL((mca_mstep_rows_kernel<(DPL <= 2 ? DPL : 1), 16, SIGNED>), grid, block, shmem, s, logpj, ldl, lse1,
                                    lseb, lse_cut, Y, ldy, Wrho, Wrm1, cand, masks, S, P, N, H, D, d0, Dl, Hp, q1, ldq, stats);
                 return (int)hipGetLastError();
@@ -1443,13 +1336,13 @@ int launch_fused_hp(int hp, int root, int Hp, dim3 grid, dim3 block, size_t shme
 #define PM_LAUNCH_F(HPV, SG, RT, DF)                                                                                  \
     do {                                                                                                              \
         if (DF) {                                                                                                     \
-            if (int e = allow_lds_mca(reinterpret_cast<const void *>(mca_estep_fused_defer_kernel<DPL, HPV, SG, RT>), shmem)) \
+            if (int e = pm_allow_lds(reinterpret_cast<const void *>(mca_estep_fused_defer_kernel<DPL, HPV, SG, RT>), shmem)) \
                 return e;                                                                                             \
             hipLaunchKernelGGL((mca_estep_fused_defer_kernel<DPL, HPV, SG, RT>), grid, block, shmem, s, scores, lds, wnorm2, \
                                ynorm2, Y, ldy, Wrho, Wrm1, cand, masks, S, P, N, H, D, Hp, logpj, ldl, lse1, lseb, q1, ldq, \
                                stats, defer_rec, defer_sc);                                                           \
         } else {                                                                                                      \
-            if (int e = allow_lds_mca(reinterpret_cast<const void *>(mca_estep_fused_kernel<DPL, HPV, SG, RT>), shmem)) \
+            if (int e = pm_allow_lds(reinterpret_cast<const void *>(mca_estep_fused_kernel<DPL, HPV, SG, RT>), shmem)) \
                 return e;                                                                                             \
             hipLaunchKernelGGL((mca_estep_fused_kernel<DPL, HPV, SG, RT>), grid, block, shmem, s, scores, lds, wnorm2, \
                                ynorm2, Y, ldy, Wrho, Wrm1, cand, masks, S, P, N, H, D, Hp, logpj, ldl, lse1, lseb, q1, ldq, \
@@ -1706,7 +1599,7 @@ extern "C" int pm_mca_defer_apply_f64(const double *lseb, const double *cut, con
     const size_t shmem = pl.lds;
 #define PM_SCATTER(DPLV)                                                                                                  \
     do {                                                                                                                  \
-        if (int e = allow_lds_mca(reinterpret_cast<const void *>(mca_defer_scatter_kernel<DPLV>), shmem)) return e;       \
+        if (int e = pm_allow_lds(reinterpret_cast<const void *>(mca_defer_scatter_kernel<DPLV>), shmem)) return e; \
         hipLaunchKernelGGL((mca_defer_scatter_kernel<DPLV>), dim3(pl.grid), dim3(1024), shmem, s, lseb, cut, \
                            Y, ldy, cand, records, work, N, (int)H, (int)D, (int)Hprime, hr, nranges);                     \
     } while (0)
@@ -1832,3 +1725,5 @@ extern "C" int pm_mca_w_update_f64(const double *stats, const double *wt, int64_
 
 PM_DET_SETTER(mca)
 #undef MCA_RHO_IS
+#undef MCA_ROW_TAIL
+#undef MCA_STATS_EPILOGUE

@@ -98,6 +98,30 @@ __device__ __forceinline__ void pm_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// The same hand-over between the lanes of one wavefront, in the form the row kernels were tuned with: ONE acquire-release
+// fence at WORKGROUP scope, then the barrier.  It is not pm_wave_sync (a release and an acquire fence at wavefront scope
+// around the barrier), and not gsc_kernels.hip's g_sync or bsc_rows16_body.h's wave_lds_sync16 (one acquire-release fence
+// at wavefront scope): the workgroup scope also waits for the wavefront's outstanding vector-memory operations, the
+// wavefront scope only keeps the compiler's order, so swapping one for another changes the waits of a kernel.
+__device__ __forceinline__ void pm_wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// Host: workgroups of a kernel that gives one wavefront to a row, `waves` wavefronts per workgroup: 8 workgroups per CU,
+// grid-stride beyond; at least one.
+inline int64_t pm_row_grid(int64_t N, int waves) {
+    int64_t blocks = (N + waves - 1) / waves;
+    const int64_t cap = 256 * 8;
+    return blocks < cap ? (blocks < 1 ? 1 : blocks) : cap;
+}
+
+// Host: a launch with more than 48 KB of dynamic LDS has to be allowed per kernel first.  Returns the HIP error, 0 if none.
+inline int pm_allow_lds(const void *kernel, size_t bytes) {
+    if (bytes <= 48 * 1024) return 0;
+    return (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
 // log sum_k exp(a x_k + o_k) of one row by a maximum pass and a sum pass (as rows_lse_kernel), the row LSE of every posterior
 // read-out (reconstruct(), its variance, sample_posterior()): NaN for a NaN entry, the maximum itself when it is infinite.
 // Wave-uniform.

@@ -32,11 +32,6 @@ constexpr int RV_CHUNK = 256;             // table states per LDS chunk of a wav
 constexpr int64_t RV_MAX_BLOCKS = 2048;   // 8 workgroups per CU, grid-stride beyond: the second trip starts at row 8192
 constexpr int RV_MAX_PAIRS = PM_MAX_HPRIME * (PM_MAX_HPRIME - 1) / 2;
 
-__device__ __forceinline__ void rv_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
 unsigned rv_grid(int64_t N) {
     int64_t nb = (N + RV_WAVES - 1) / RV_WAVES;
     if (nb > RV_MAX_BLOCKS) nb = RV_MAX_BLOCKS;
@@ -79,7 +74,7 @@ __global__ __launch_bounds__(RV_THREADS) void recon_moments2_kernel(
             const int cnt = min(RV_CHUNK, S - s0);
             for (int k = lane; k < cnt; k += 64)
                 wq[k] = exp(a * row[moff + s0 + k] + (off ? off[moff + s0 + k] : 0.0) - lse);
-            rv_lds_sync();
+            pm_wave_lds_sync();
             for (int k = 0; k < cnt; ++k) {
                 const double q = wq[k];
                 const double *ts = tab + (int64_t)(s0 + k) * Hp;
@@ -87,7 +82,7 @@ __global__ __launch_bounds__(RV_THREADS) void recon_moments2_kernel(
                 a1 = fma(q, ts[i1] * ts[j1], a1);
                 am = fma(q, ts[pos] * ts[pos], am);
             }
-            rv_lds_sync();
+            pm_wave_lds_sync();
         }
         if (p) {
             if (lane < npair) p[n * ldp + lane] = a0;
@@ -97,7 +92,7 @@ __global__ __launch_bounds__(RV_THREADS) void recon_moments2_kernel(
             wm[lane] = am;
             wc[lane] = S > 0 ? cand[n * Hp + lane] : -1;
         }
-        rv_lds_sync();
+        pm_wave_lds_sync();
         double *orow = m2 + n * ldm;
         for (int h = lane; h < H; h += 64) {
             double e = 0.0;
@@ -111,7 +106,7 @@ __global__ __launch_bounds__(RV_THREADS) void recon_moments2_kernel(
             orow[h] = e;
         }
         for (int h = H + lane; h < out_cols; h += 64) orow[h] = 0.0;
-        rv_lds_sync();      // wm / wc are rewritten for the next row
+        pm_wave_lds_sync();      // wm / wc are rewritten for the next row
     }
 }
 
@@ -141,7 +136,7 @@ __global__ __launch_bounds__(RV_THREADS) void recon_var_finish_kernel(double *__
                 c = c < 0 ? 0 : (c >= H ? H - 1 : c);
                 coff[j] = (int64_t)c * ldw;
             }
-            rv_lds_sync();
+            pm_wave_lds_sync();
         }
         double *vrow = V + n * ldv;
         const double *yrow = Yhat + n * ldy;
@@ -165,7 +160,7 @@ __global__ __launch_bounds__(RV_THREADS) void recon_var_finish_kernel(double *__
             const double v = fma(2.0, acc, vrow[d]) - c * c;
             vrow[d] = v < 0.0 ? 0.0 : v;
         }
-        if (npair > 0) rv_lds_sync();      // wp is rewritten for the next row
+        if (npair > 0) pm_wave_lds_sync();      // wp is rewritten for the next row
     }
 }
 

@@ -41,7 +41,7 @@ per wavefront for counts and scalars), each off by at most quantum / 2: the boun
 Mutants of dsc_kernels.hip (values and predicates only) and the check that fails on each, default library, MI355X:
   lse cut `>` -> `>=`                      32 tests: "cut rows are not zero" (the datapoint whose lse equals the cut)
   `2.0 * v[k] * s_G` -> `1.0 *`            5: logpj of km8_nt_over, km8_16_16, k8, too_many, too_many_wave (the generic walk)
-  `d > -37.0` -> `-3.0`                    32: lse of the cold runs
+  `DSC_TERM_CUT = -37.0` -> `-3.0`         32: lse of the cold runs
   pscale ignored in the states' columns    31: logpj of the cold runs (pscale = 1/2)
   lastmask always all-ones                 4: E[s] rows and Wq of tsc_l16, tsc_l16_16, tsc_wave
   `c2 = -2.0 * v` -> `+2.0 * v`            26: logpj of every case with energy-term tables
