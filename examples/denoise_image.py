@@ -2,7 +2,7 @@
 """Whole-image denoising by overlapping patches on an image the models are correctly specified for.
 
     python examples/denoise_image.py [bsc|mca] [--size 128] [--p 5] [--stride 1] [--steps 50] [--missing FRACTION]
-                                     [--train-missing] [--variance]
+                                     [--train-missing] [--variance] [--aggregate precision [--floor F ...]]
 
 No file is read.  The script draws a *bars image*: row indicators r_i and column indicators c_j ~ Bernoulli(pi),
 clean[i, j] = a (r_i + c_j) (MCA: a max(r_i, c_j)), plus Gaussian noise of standard deviation sigma.  Every p x p patch of
@@ -25,7 +25,12 @@ observed / missing MSE lines are printed.
 ``--variance``: ``reconstruct_image(..., variance=True)`` also returns ``var_map``, the overlap average of the
 patches' posterior variances of the noiseless value -- an upper bound on the variance of the averaged estimate.  Its mean is
 printed beside the actual MSE against the clean image (with ``--missing``: separately over the observed and over the missing
-pixels)."""
+pixels).
+
+``--aggregate precision``: beside the plain overlap average the image is also aggregated with every patch's
+estimate of a pixel weighted by 1 / (V + floor), V its posterior variance (``reconstruct_image(..., aggregate='precision')``);
+MSE and PSNR of both are printed side by side, with ``--missing`` over the observed, the missing and all pixels.  ``--floor F
+...``: the floor(s) to run instead of the default (``utils.patches.PRECISION_FLOOR`` times the model's noise variance)."""
 import argparse
 import os
 import sys
@@ -84,7 +89,13 @@ def main():
                     help="bsc with --missing: train on the incomplete image's own patches (my_data['mask'])")
     ap.add_argument("--variance", action="store_true",
                     help="also print the mean of var_map (the posterior variance the model reports) beside the MSE")
+    ap.add_argument("--aggregate", default="mean", choices=["mean", "precision"],
+                    help="precision: also aggregate with the estimates weighted by 1 / (V + floor) and print both")
+    ap.add_argument("--floor", type=float, nargs="+", default=None, metavar="F",
+                    help="with --aggregate precision: the floor(s) to use (default: PRECISION_FLOOR x the noise variance)")
     a = ap.parse_args()
+    if a.floor is not None and a.aggregate != "precision":
+        ap.error("--floor needs --aggregate precision")
     if a.train_missing and (a.model != "bsc" or not 0.0 < a.missing < 1.0):
         ap.error("--train-missing needs the bsc model and --missing FRACTION in (0, 1)")
     np.random.seed(a.seed)
@@ -122,6 +133,18 @@ def main():
     rmodel = build(a.model, a.p, min(H, 7), min(H, 5))
     peak = float(clean.max()) or 1.0
     kw = {'variance': True} if a.variance else {}
+    psnr = lambda m: 10 * np.log10(peak ** 2 / m)
+
+    def aggregates(params):
+        """[(label, keywords)]: the plain average, then the precision aggregate at every floor asked for."""
+        runs = [("", {})]
+        if a.aggregate == "precision":
+            from prosper_amd.utils.patches import PRECISION_FLOOR
+            for f in a.floor or [None]:
+                used = PRECISION_FLOOR * rmodel._noise_variance(params) if f is None else f
+                runs.append((", precision (floor %.4g)" % used, {'aggregate': 'precision', 'floor': f}))
+            runs[0] = (", mean", {})
+        return runs
     print("%s, %d x %d bars image (a = %g, sigma = %g, pi = %g), %d x %d patches at stride %d, %d patches trained on, %d EM steps"
           % (a.model.upper(), a.size, a.size, a.a, a.sigma, a.pi, a.p, a.p, a.stride, len(Y), a.steps))
     if a.missing > 0.0:
@@ -137,19 +160,35 @@ def main():
         print("  %-44s MSE observed %.4f   missing %.4f (filled with the observed mean)"
               % ("noisy image", mse(noisy, mask), mse(np.full_like(clean, noisy[mask].mean()), ~mask)))
         for tag, params in (("learned", learned), ("generating", gt)):
-            out = rmodel.reconstruct_image(params, holes, mask=mask, stride=a.stride, **kw)
-            out, var = out if a.variance else (out, None)
-            print("  %-44s MSE observed %.4f   missing %.4f" % ("reconstructed, %s parameters" % tag, mse(out, mask), mse(out, ~mask)))
-            if a.variance:
-                print("  %-44s     observed %.4f   missing %.4f" % ("  mean of var_map", var[mask].mean(), var[~mask].mean()))
+            base = None
+            for label, agg in aggregates(params):
+                out = rmodel.reconstruct_image(params, holes, mask=mask, stride=a.stride, **dict(kw, **agg))
+                out, var = out if a.variance else (out, None)
+                line = "  %-44s MSE observed %.4f   missing %.4f" % ("reconstructed, %s%s" % (tag, label or " parameters"),
+                                                                     mse(out, mask), mse(out, ~mask))
+                if a.aggregate == "precision":
+                    everything = mse(out, np.ones_like(mask))
+                    line += "   all %.4f   PSNR %.2f dB" % (everything, psnr(everything))
+                    line += "" if base is None else " (%+.3f dB)" % (psnr(everything) - base)
+                    base = psnr(everything) if base is None else base
+                print(line)
+                if a.variance:
+                    print("  %-44s     observed %.4f   missing %.4f" % ("  mean of var_map", var[mask].mean(), var[~mask].mean()))
         return
     report("noisy image", noisy, clean, peak)
     for tag, params in (("learned", learned), ("generating", gt)):
-        out = rmodel.reconstruct_image(params, noisy, stride=a.stride, **kw)
-        out, var = out if a.variance else (out, None)
-        report("denoised, %s parameters" % tag, out, clean, peak)
-        if a.variance:
-            print("  %-44s     %.4f (mean of var_map: the posterior variance the model reports)" % ("", var.mean()))
+        base = None
+        for label, agg in aggregates(params):
+            out = rmodel.reconstruct_image(params, noisy, stride=a.stride, **dict(kw, **agg))
+            out, var = out if a.variance else (out, None)
+            report("denoised, %s%s" % (tag, label or " parameters"), out, clean, peak)
+            if a.aggregate == "precision":
+                now = psnr(float(((np.asarray(out) - clean) ** 2).mean()))
+                if base is not None:
+                    print("  %-44s %+.3f dB against the mean aggregate" % ("", now - base))
+                base = now if base is None else base
+            if a.variance:
+                print("  %-44s     %.4f (mean of var_map: the posterior variance the model reports)" % ("", var.mean()))
     print("  learned pi %.4f (generating %.4f), sigma %.4f (generating %.4f)"
           % (float(np.asarray(learned['pi'])), a.pi, float(np.asarray(learned['sigma'])), a.sigma))
 

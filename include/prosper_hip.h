@@ -1221,6 +1221,32 @@ int pm_patches_accumulate_f64(const double *est, int64_t lde, const double *mean
  * pixel, computed from the grid rule.  out may be acc. */
 int pm_patches_finish_f64(const double *acc, int64_t lda, double *out, int64_t ldo, int64_t B, int64_t Hi, int64_t Wi,
                           int64_t ph, int64_t pw, int64_t stride, void *stream);
+/* The weighted overlap average.  Grid, patch numbering, ranges [n0, n0 + n) and the running-sum contract are
+ * those of pm_patches_accumulate_f64; num and den (B, Hi, Wi; row stride lda >= Wi) are two running sums the caller zeroes
+ * once.  The weight of element e of patch k is w = a b:
+ *   a = 1 (wgt == NULL), wgt[k - n0, e] (wmode 0) or 1.0 / (v + floor), v = wgt[k - n0, e] < 0 ? 0 : wgt[k - n0, e] (wmode 1:
+ *       wgt holds variances; a NaN stays NaN);
+ *   b = 1 (window == NULL) or window[e], window holding D doubles;
+ * with one factor present w is that factor and nothing is multiplied.  Every pixel receives, one patch at a time in
+ * ascending patch number, with t = est[k - n0, e] (means == NULL) or est[k - n0, e] + means[k - n0]:
+ *   num <- num + (w t)   (the product is rounded, then the sum: no fused multiply-add)
+ *   den <- den + w       (den == NULL: skipped)
+ * A pixel is owned by one lane; a workgroup stages the estimate rows and the weight rows that reach its tile together in
+ * LDS and reads them as rows.  No atomics, no branch on the build: both libraries give the same bits, and the sequence of
+ * additions of a pixel is the same for every split of [0, N) into ascending ranges.  est and wgt may be the same matrix.
+ * With wgt == window == NULL num receives the bits pm_patches_accumulate_f64 writes and den the cover count.
+ * PM_EINVAL, before anything touches a device: a null est or num; wmode other than 0 or 1; wmode 1 with wgt == NULL or a
+ * floor that is negative or not finite; ldw < D with wgt given; everything pm_patches_accumulate_f64 refuses, with its codes
+ * (PM_ERANGE for Hi or Wi > 2^30 or D > 4096).  n == 0 launches nothing. */
+int pm_patches_accumulate_w_f64(const double *est, int64_t lde, const double *wgt, int64_t ldw, int wmode, double floor,
+                                const double *window, const double *means, int64_t n0, int64_t n, double *num, double *den,
+                                int64_t lda, int64_t B, int64_t Hi, int64_t Wi, int64_t ph, int64_t pw, int64_t stride,
+                                void *stream);
+/* out[b, i, j] = num[b, i, j] / den[b, i, j], one IEEE division (0 / 0 is NaN: a pixel all of whose weights are 0 has no
+ * average).  out may be num.  PM_EINVAL for a null pointer, B, Hi or Wi < 1 or a leading dimension < Wi; PM_ERANGE for Hi or
+ * Wi > 2^30. */
+int pm_patches_finish_w_f64(const double *num, const double *den, int64_t lda, double *out, int64_t ldo, int64_t B,
+                            int64_t Hi, int64_t Wi, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Missing values: masked E-steps for inference (masked_kernels.hip)

@@ -116,13 +116,21 @@ class CAModel(Model):
         W_init = W_mean[:, None] + np.random.normal(scale=sigma_init / 4., size=[D, self.H])
         return {'W': W_init, 'pi': 1. / self.H, 'sigma': sigma_init}
 
+    def _noise_variance(self, model_params):
+        """sigma^2: what ``reconstruct_image(aggregate='precision')`` scales its default floor by (GSC overrides it)."""
+        return float(np.asarray(model_params['sigma'], dtype=np.float64)) ** 2
+
     def reconstruct_image(self, model_params, image, mask=None, **kw):
         """Whole-image denoising by overlapping patches: ``utils.patches.denoise_image(self, model_params,
         image, **kw)`` -- every patch through ``reconstruct()``, the estimates averaged where they overlap.  Keywords:
         ``patch``, ``stride``, ``center``, ``chunk``, ``device``, ``exact`` (every patch through
         ``reconstruct(exact=True)``), ``variance`` (returns ``(image, var_map)``, var_map the overlap average of
         the patches' posterior variances -- an upper bound on the variance of the averaged estimate).  ``mask`` (the image's
-        shape, non-zero = observed pixel): the patches go through the masked ``reconstruct()`` -- inpainting."""
+        shape, non-zero = observed pixel): the patches go through the masked ``reconstruct()`` -- inpainting.
+        ``aggregate='precision'`` (default ``'mean'``): the overlapping estimates of a pixel are weighted by 1 /
+        (V + floor), V each patch's posterior variance there; ``floor`` (default: ``utils.patches.PRECISION_FLOOR`` times
+        the model's noise variance) and ``window`` (a fixed positive weight per patch element, under either aggregate);
+        ``var_map`` is then the average of V under the same weights."""
         from ...utils.patches import denoise_image
         return denoise_image(self, model_params, image, mask=mask, **kw)
 

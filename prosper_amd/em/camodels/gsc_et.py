@@ -265,6 +265,12 @@ class GSC(DeviceCAModel):
             y[n] = Ws @ z_n + sd * np.random.randn(D)
         return {'y': y, 's': s, 'z': z}
 
+    def _noise_variance(self, model_params):
+        """The mean diagonal of ``sigma_sq`` (the scalar itself, the mean of the diagonal vector, the mean of the full
+        matrix's diagonal): what ``reconstruct_image(aggregate='precision')`` scales its default floor by."""
+        sig = np.asarray(model_params['sigma_sq'], dtype=np.float64)
+        return float(np.mean(np.diagonal(sig)) if sig.ndim == 2 else np.mean(sig))
+
     # ------------------------------------------------------------------ device tables
     def _require_scalar(self):
         if self.sigma_sq_type not in ('scalar', 'diagonal', 'full'):

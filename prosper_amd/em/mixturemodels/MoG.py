@@ -77,6 +77,12 @@ class MoG(DeviceMixture, MixtureModel):
         y = W[s] + np.sqrt(sig[s]) * np.random.randn(my_N, D).reshape(my_N, D)
         return {'y': y, 's': s}
 
+    def _noise_variance(self, model_params):
+        """The mean variance over components and dimensions (of a full covariance: its diagonal): what
+        ``reconstruct_image(aggregate='precision')`` scales its default floor by."""
+        sig = np.asarray(model_params['sigmas_sq'], dtype=np.float64)
+        return float(np.mean(np.diagonal(sig, axis1=1, axis2=2)) if sig.ndim == 3 else np.mean(sig))
+
     def check_params(self, model_params):
         assert np.isfinite(model_params['W']).all()
         assert np.isfinite(model_params['sigmas_sq']).all()
