@@ -3,14 +3,14 @@
 //
 // One wavefront per datapoint, lanes strided over the K = 1 + H + S log-joints of its row (a few KB: the passes below
 // re-read it from L1 / L2):
-//   pass 1   row maximum and log-sum-exp                                            (:297-301)
+//   pass 1   row maximum and log-sum-exp                                            (:308-312)
 //   top-K    round r takes the largest entry strictly below round r - 1's winner in the order (value, index) -- the
-//            reference sorts with argsort()[..., ::-1] (:302), so equal values come out larger index first; no entry is
+//            reference sorts with argsort()[..., ::-1] (:313), so equal values come out larger index first; no entry is
 //            marked or copied
 //   marginals  log p(s_h = 1 | y) = logpjc[1 + h] for a latent outside the candidates, else the log-sum-exp of its
-//            singleton and of the multi-cause states that contain its candidate position                   (:321-327)
+//            singleton and of the multi-cause states that contain its candidate position                   (:333-339)
 // The top-K state vectors (res['s']) are assembled by the caller from the returned column indices: that part is index
-// bookkeeping with the reference's quirks (entries of earlier adaptive rounds are never cleared, :313-319).
+// bookkeeping with the reference's quirks (entries of earlier adaptive rounds are never cleared, :324-330).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
