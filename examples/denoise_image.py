@@ -3,6 +3,7 @@
 
     python examples/denoise_image.py [bsc|mca] [--size 128] [--p 5] [--stride 1] [--steps 50] [--missing FRACTION]
                                      [--train-missing] [--variance] [--aggregate precision [--floor F ...]]
+                                     [--noise-ramp R]
 
 No file is read.  The script draws a *bars image*: row indicators r_i and column indicators c_j ~ Bernoulli(pi),
 clean[i, j] = a (r_i + c_j) (MCA: a max(r_i, c_j)), plus Gaussian noise of standard deviation sigma.  Every p x p patch of
@@ -30,7 +31,13 @@ pixels).
 ``--aggregate precision``: beside the plain overlap average the image is also aggregated with every patch's
 estimate of a pixel weighted by 1 / (V + floor), V its posterior variance (``reconstruct_image(..., aggregate='precision')``);
 MSE and PSNR of both are printed side by side, with ``--missing`` over the observed, the missing and all pixels.  ``--floor F
-...``: the floor(s) to run instead of the default (``utils.patches.PRECISION_FLOOR`` times the model's noise variance)."""
+...``: the floor(s) to run instead of the default (``utils.patches.PRECISION_FLOOR`` times the model's noise variance).
+
+``--noise-ramp R`` (per-pixel noise weights): the noise standard deviation rises linearly from the left edge to
+the right edge by the factor R, scaled so that the mean noise variance stays sigma^2.  The model trains as before (it learns one
+sigma), and the image is denoised twice: without weights, and with ``reconstruct_image(..., weight=)`` at weight = mean noise
+variance / pixel noise variance; MSE and PSNR of both are printed side by side.  Composes with ``--aggregate precision`` and
+``--variance``; not with ``--missing``."""
 import argparse
 import os
 import sys
@@ -93,7 +100,12 @@ def main():
                     help="precision: also aggregate with the estimates weighted by 1 / (V + floor) and print both")
     ap.add_argument("--floor", type=float, nargs="+", default=None, metavar="F",
                     help="with --aggregate precision: the floor(s) to use (default: PRECISION_FLOOR x the noise variance)")
+    ap.add_argument("--noise-ramp", type=float, default=None, metavar="R",
+                    help="noise standard deviation rising linearly left to right by the factor R; denoise without and with "
+                         "the weight image mean noise variance / pixel noise variance")
     a = ap.parse_args()
+    if a.noise_ramp is not None and (a.missing > 0.0 or a.train_missing or not a.noise_ramp > 0.0):
+        ap.error("--noise-ramp needs R > 0 and does not combine with --missing")
     if a.floor is not None and a.aggregate != "precision":
         ap.error("--floor needs --aggregate precision")
     if a.train_missing and (a.model != "bsc" or not 0.0 < a.missing < 1.0):
@@ -102,6 +114,13 @@ def main():
     rng = np.random.RandomState(a.seed)
     mca = a.model == "mca"
     clean, noisy = bars_image(rng, a.size, a.a, a.pi, a.sigma, mca)
+    weight = None
+    if a.noise_ramp is not None:
+        # sd(column j) = s0 (1 + (R - 1) j / (size - 1)), s0 so that the mean noise variance is sigma^2
+        ramp = 1.0 + (a.noise_ramp - 1.0) * np.arange(a.size) / max(a.size - 1, 1)
+        sd = np.tile((a.sigma * ramp / np.sqrt((ramp ** 2).mean()))[None, :], (a.size, 1))
+        noisy = clean + sd * rng.normal(size=clean.shape)
+        weight = (sd ** 2).mean() / sd ** 2
     H = 2 * a.p
     gt = {'W': bars_dict(a.p, a.a), 'pi': a.pi, 'sigma': a.sigma}
 
@@ -176,19 +195,24 @@ def main():
                     print("  %-44s     observed %.4f   missing %.4f" % ("  mean of var_map", var[mask].mean(), var[~mask].mean()))
         return
     report("noisy image", noisy, clean, peak)
+    if weight is not None:
+        print("  noise ramp %g: pixel noise standard deviation %.4f (left) to %.4f (right), weights %.4f to %.4f"
+              % (a.noise_ramp, sd[0, 0], sd[0, -1], weight.max(), weight.min()))
+    runs = [("", {})] if weight is None else [(", no weights", {}), (", weighted", {'weight': weight})]
     for tag, params in (("learned", learned), ("generating", gt)):
-        base = None
-        for label, agg in aggregates(params):
-            out = rmodel.reconstruct_image(params, noisy, stride=a.stride, **dict(kw, **agg))
-            out, var = out if a.variance else (out, None)
-            report("denoised, %s%s" % (tag, label or " parameters"), out, clean, peak)
-            if a.aggregate == "precision":
-                now = psnr(float(((np.asarray(out) - clean) ** 2).mean()))
-                if base is not None:
-                    print("  %-44s %+.3f dB against the mean aggregate" % ("", now - base))
-                base = now if base is None else base
-            if a.variance:
-                print("  %-44s     %.4f (mean of var_map: the posterior variance the model reports)" % ("", var.mean()))
+        for wlabel, wkw in runs:
+            base = None
+            for label, agg in aggregates(params):
+                out = rmodel.reconstruct_image(params, noisy, stride=a.stride, **dict(kw, **dict(agg, **wkw)))
+                out, var = out if a.variance else (out, None)
+                report("denoised, %s%s%s" % (tag, wlabel, label or ("" if wlabel else " parameters")), out, clean, peak)
+                if a.aggregate == "precision":
+                    now = psnr(float(((np.asarray(out) - clean) ** 2).mean()))
+                    if base is not None:
+                        print("  %-44s %+.3f dB against the mean aggregate" % ("", now - base))
+                    base = now if base is None else base
+                if a.variance:
+                    print("  %-44s     %.4f (mean of var_map: the posterior variance the model reports)" % ("", var.mean()))
     print("  learned pi %.4f (generating %.4f), sigma %.4f (generating %.4f)"
           % (float(np.asarray(learned['pi'])), a.pi, float(np.asarray(learned['sigma'])), a.sigma))
 

@@ -1288,6 +1288,49 @@ int pm_mca_masked_estep_f64(const double *scores, int64_t lds, const double *wno
                             double *lseb, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Per-entry noise weights: weighted E-steps for inference (weighted_kernels.hip)
+ * ---------------------------------------------------------------------------------------
+ * weight (N, ldo >= D) doubles omega >= 0, finite (the caller checks; the kernels do not): entry (n, d) was observed with noise
+ * variance sigma^2 / omega_nd, omega_nd = 0: not observed.  The masked entries above are the case omega in {0, 1}: on such
+ * weights every entry here performs exactly their operations and returns their bits.  A value at weight 0 is selected away
+ * where it is read (omega != 0 ? v : 0), never multiplied: NaN or inf there changes no bit of any output.  No atomics, every
+ * output element is written once by one lane and a row's sums over d run in an order fixed by D alone: both builds return the
+ * same bits and a row's bits depend on that row (of the data and of the weights) and on the parameters alone.  Every entry
+ * checks its arguments before it touches a device: PM_EINVAL for a null pointer, a negative size or a short leading
+ * dimension, PM_ERANGE past a limit; N == 0 launches nothing.
+ *
+ * pm_weighted_prepare_f64: with on = omega != 0 and x = on ? Y[n,d] - mu[d] : 0 (mu NULL: 0):  Xw[n,d] = on ? omega x : 0,
+ * Om[n,d] = on ? omega : 0, X0[n,d] = x (X0 may be NULL), xnorm2[n] = sum_d fma(Xw, x, .) = sum_d omega x^2, dn[n] = number
+ * of dimensions with omega != 0, logw[n] = sum_{on} log omega -- each per lane over d = lane, lane + 64, ... in ascending
+ * order, then the xor butterfly (the order of pm_masked_prepare_f64).  With these the terms that are dense over H are two
+ * products of pm_gemm_nt_rows_f64: b = Xw . W (N, H) and diag G_n = Om . (W o W) (N, H). */
+int pm_weighted_prepare_f64(const double *Y, int64_t ldy, const double *weight, int64_t ldo, const double *mu, int64_t N,
+                            int64_t D, double *Xw, int64_t ldxw, double *Om, int64_t ldom, double *X0, int64_t ldx0,
+                            double *xnorm2, int32_t *dn, double *logw, void *stream);
+/* BSC: pm_bsc_masked_estep_f64 with the pair products sum_d omega_d Wt[c_i, d] Wt[c_j, d]: the candidates' rows of Wt enter LDS
+ * in slabs of 64 dimensions as omega != 0 ? w : 0 beside one staged row of omega, pair p is owned by lane p mod 64, which walks
+ * d in ascending order with fma(wi * omega, wj, .).  Same selection (the Hprime largest b_h / sqrt(g_h), ascending, ties
+ * towards the larger index; a row of zero weights gets the Hprime largest indices), log-joint layout and limits:
+ * H <= PM_MAX_H, Hprime <= PM_MAX_HPRIME, S <= 65535. */
+int pm_bsc_weighted_estep_f64(const double *b, int64_t ldb, const double *g, int64_t ldg, const double *xnorm2,
+                              const double *weight, int64_t ldo, const double *Wt, int64_t ldw, const uint16_t *state_masks,
+                              int64_t S, const pm_bsc_estep_params *params_host, int64_t N, int64_t H, int64_t D,
+                              int64_t Hprime, int32_t *cand, double *logpj, int64_t ldl, void *stream);
+/* MCA selection scores R[n,h] = sum_d omega_d max(W[h,d] - Y[n,d], 0): per output one thread walks d in ascending order with
+ * acc = omega != 0 ? fma(omega, max(w - y, 0), acc) : acc. */
+int pm_mca_weighted_select_scores_f64(const double *Y, int64_t ldy, const double *weight, int64_t ldo, const double *W,
+                                      int64_t ldw, double *R, int64_t ldr, int64_t N, int64_t H, int64_t D, void *stream);
+/* MCA / MMCA E-step: pm_mca_masked_estep_f64 with e_s = sum_d omega_d (X0[n,d] - Wbar_d(s))^2, per dimension
+ * omega != 0 ? fma(omega df, df, e) : e; for the one-cause states wnorm2_obs (N, ldwn >= H) = Om . (W o W), scores = Xw . W and
+ * xnorm2, all from pm_weighted_prepare_f64 with mu = NULL.  Same power functions, limits (D <= 1024, Hprime <= PM_MAX_HPRIME)
+ * and outputs. */
+int pm_mca_weighted_estep_f64(const double *scores, int64_t lds, const double *wnorm2_obs, int64_t ldwn, const double *xnorm2,
+                              const double *X0, int64_t ldx, const double *weight, int64_t ldo, const double *Wrho,
+                              const int32_t *cand, const uint16_t *state_masks, int64_t S, const pm_mca_params *params_host,
+                              int64_t N, int64_t H, int64_t D, int64_t Hprime, double *logpj, int64_t ldl, double *lse1,
+                              double *lseb, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Missing values: the M-step of BSC on incomplete rows (masked_train.hip)
  * ---------------------------------------------------------------------------------------
  * With a mask every data dimension d has its own normal equations A_d w_d = r_d, A_d = sum_n m_nd E_q[s s^T]_n (H x H).  No

@@ -215,6 +215,13 @@ SIGNATURES = {
     "pm_mca_masked_select_scores_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, i64, c_dp, i64, i64, i64, i64, c_dp]),
     "pm_mca_masked_estep_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, c_dp, i64, c_dp, i64, c_dp, c_dp, c_dp, i64,
                                           C.POINTER(McaParams), i64, i64, i64, i64, c_dp, i64, c_dp, c_dp, c_dp]),
+    "pm_weighted_prepare_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, i64, i64, c_dp, i64, c_dp, i64, c_dp, i64, c_dp, c_dp, c_dp,
+                                          c_dp]),
+    "pm_bsc_weighted_estep_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, c_dp, i64, c_dp, i64, c_dp, i64,
+                                            C.POINTER(EStepParams), i64, i64, i64, i64, c_dp, c_dp, i64, c_dp]),
+    "pm_mca_weighted_select_scores_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, i64, c_dp, i64, i64, i64, i64, c_dp]),
+    "pm_mca_weighted_estep_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, c_dp, i64, c_dp, i64, c_dp, c_dp, c_dp, i64,
+                                            C.POINTER(McaParams), i64, i64, i64, i64, c_dp, i64, c_dp, c_dp, c_dp]),
     "pm_bsc_mtrain_rows_f64": (C.c_int, [c_dp, i64, c_dp, c_dp, c_dp, i64, C.POINTER(EStepParams), i64, i64, i64, c_dp, i64,
                                          c_dp, i64, c_dp, c_dp]),
     "pm_col_sum_ordered_work_len": (i64, [i64, i64]),
@@ -247,7 +254,7 @@ class HipError(RuntimeError):
     pass
 
 
-MIN_VERSION = 1029
+MIN_VERSION = 1030
 _lib = None
 _lib_det = None
 LIB_PATH_DET = os.path.join(os.path.dirname(LIB_PATH), "libprosper_hip_det.so")

@@ -30,9 +30,19 @@ class Model(object):
     def _refuse_training_mask(self, my_data):
         """Training on incomplete data is built for BSC_ET alone: a ``'mask'`` entry is never ignored
         silently -- every other model's ``step`` / ``E_step`` / ``M_step`` refuses it here, before any launch."""
+        self._refuse_training_weight(my_data)
         if isinstance(my_data, dict) and my_data.get('mask') is not None:
             raise NotImplementedError("%s: training on incomplete data (my_data['mask'] in step / E_step / M_step) is not "
                                       "built for this model; BSC_ET has the masked EM step" % type(self).__name__)
+
+    def _refuse_training_weight(self, my_data):
+        """Per-entry noise weights reach inference only -- ``log_likelihood``, ``reconstruct``,
+        ``sample_posterior`` of BSC_ET, MCA_ET and MMCA_ET: a ``'weight'`` entry is never ignored silently -- every model's
+        ``step`` / ``select_Hprimes`` / ``E_step`` / ``M_step`` refuses it here, before any launch."""
+        if isinstance(my_data, dict) and my_data.get('weight') is not None:
+            raise NotImplementedError("%s: training with per-entry noise weights (my_data['weight'] in step / select_Hprimes / "
+                                      "E_step / M_step) is not built for any model; log_likelihood, reconstruct and "
+                                      "sample_posterior of BSC_ET, MCA_ET and MMCA_ET take a weight" % type(self).__name__)
 
     @tracing.traced
     def noisify_params(self, model_params, anneal):

@@ -1046,8 +1046,12 @@ class DeviceCAModel(CAModel):
 
         ``my_data['mask']`` (N, D; non-zero = observed; BSC, MCA and MMCA): log sum_{s in K_n} p(s, y_obs,n), the
         unobserved dimensions left out of the likelihood and never read into the arithmetic.  Other models and
-        ``exact=True`` raise ``NotImplementedError``, a mask of another shape ``ValueError``."""
-        if my_data.get('mask') is not None:
+        ``exact=True`` raise ``NotImplementedError``, a mask of another shape ``ValueError``.
+
+        ``my_data['weight']`` (N, D; finite and >= 0; BSC, MCA and MMCA): entry (n, d) was observed with noise
+        variance sigma^2 / weight[n, d], 0 = not observed -- log sum_{s in K_n} p(s, y_n | weight_n), including the term 1/2
+        sum_{weight > 0} log weight.  The refusals are those ``reconstruct`` documents."""
+        if my_data.get('mask') is not None or my_data.get('weight') is not None:
             return self._log_likelihood_masked(model_params, my_data, per_datapoint, exact)
         if exact:
             return self._log_likelihood_exact(model_params, my_data, per_datapoint)
@@ -1220,6 +1224,14 @@ class DeviceCAModel(CAModel):
         ones are inpainted.  Whatever an unobserved entry holds changes no bit; a row's bits depend on that row of ``y``,
         that row of the mask and the parameters alone.  Other models raise ``NotImplementedError`` before any launch.
 
+        ``my_data['weight']`` (N, D; NumPy, torch or DeviceArray of any real numeric type -- a float64 device tensor with unit
+        column stride is used in place; BSC, MCA and MMCA): entry (n, d) was observed with noise variance sigma^2 /
+        weight[n, d], 0 = not observed; a mask is the weight restricted to {0, 1} and such a weight returns the masked call's
+        bits.  Whatever ``y`` holds at weight 0 changes no bit.  Raised before any launch: ``ValueError`` for a weight that is
+        negative, NaN or infinite anywhere (one reduction where the weight lives), of another shape, or given together with
+        ``'mask'`` (fold the mask into the weight as zeros); ``NotImplementedError`` for ``exact=True`` and for the other
+        models; ``HipError`` for H' > 16.
+
         ``exact=True``: yhat_n = sum_{all s} p(s | y_n, Theta) ybar(s) over the model's WHOLE state space by enumeration on
         the device (pm_recon_exact_*), the same generative model, parameters and ybar(s): no candidates, no
         state table, no E-step, and a result independent of Hprime, gamma and the annealing state.  A row's bits depend on
@@ -1238,9 +1250,9 @@ class DeviceCAModel(CAModel):
         pm_gemm_nt_rows_f64."""
         y = my_data['y']
         N = int(y.shape[0])
-        mask = my_data.get('mask')
-        if mask is not None:
-            self._masked_admit(y, mask, exact, what="reconstruct")
+        obs = self._observation(my_data)
+        if obs is not None:
+            self._masked_admit(y, obs[1], exact, what="reconstruct", key=obs[0])
         if variance and exact:
             raise NotImplementedError("%s.reconstruct: variance=True with exact=True is not built (the enumeration kernels "
                                       "keep no second moments)" % type(self).__name__)
@@ -1260,8 +1272,8 @@ class DeviceCAModel(CAModel):
             # is a function of that row of the data and of the parameters alone (attributes of the evaluation only)
             self._par, self._rows_gemm = {}, True
             kw = {"variance": True} if variance else {}
-            if mask is not None:
-                Yhat = self._reconstruct_masked(dict(model_params), y, mask, N, **kw)
+            if obs is not None:
+                Yhat = self._reconstruct_masked(dict(model_params), y, obs, N, **kw)
             elif exact:
                 Yhat = self._reconstruct_exact(dict(model_params), y, N)
             else:
@@ -1359,14 +1371,14 @@ class DeviceCAModel(CAModel):
         s[idx < 0] = float("nan")
         return s.permute(1, 0, 2)
 
-    def _sample(self, model_params, y, mask, N, M, U, latents, E=None):
+    def _sample(self, model_params, y, obs, N, M, U, latents, E=None):
         """The (M, N, D) device tensor of ``sample_posterior`` (and with ``latents`` the (M, N, H) one) for the models whose
-        E-step leaves (N, K) log-joints: the E-step of ``reconstruct``, then per row chunk pm_sample_states_f64, the active
-        list and the decode kernel, written in place."""
+        E-step leaves (N, K) log-joints: the E-step of ``reconstruct`` (``obs``: None or what ``_observation`` returned),
+        then per row chunk pm_sample_states_f64, the active list and the decode kernel, written in place."""
         H, D, Hp = self.H, self.D, self.Hprime
         par = None
-        if mask is not None:
-            out = self._masked_estep(model_params, y, mask)
+        if obs is not None:
+            out = self._obs_estep(model_params, y, obs)
             lay, lp, cand, par = out["lay"], out["logpj"], out["cand"], out.get("par")
         else:
             lay = self._recon_layout(model_params)
@@ -1434,6 +1446,8 @@ class DeviceCAModel(CAModel):
         ``my_data['mask']`` (BSC, MCA, MMCA): the draw comes from the posterior given the observed dimensions
         and covers all D -- an imputation; whatever an unobserved entry holds changes no bit.  Other models raise
         ``NotImplementedError`` before any launch.  A NaN in a data row makes that row's draws NaN and no other's.
+        ``my_data['weight']``: the draw comes from the posterior under the per-entry noise variances sigma^2 /
+        weight, with the refusals ``reconstruct`` documents.
 
         Raises ``ValueError`` for n_samples < 1, wrongly shaped ``uniforms`` / ``normals`` and host ``uniforms`` outside [0, 1),
         ``HipError`` for H' > 16 and for MCA / MMCA with D > 1024 -- all before any launch.  There is no ``exact=``.  Runs
@@ -1448,9 +1462,9 @@ class DeviceCAModel(CAModel):
         N = int(y.shape[0])
         nn = int(self._sample_n_normals)
         M = self._sample_check(N, n_samples, uniforms, normals, nn)
-        mask = my_data.get('mask')
-        if mask is not None:
-            self._masked_admit(y, mask, what="sample_posterior")
+        obs = self._observation(my_data)
+        if obs is not None:
+            self._masked_admit(y, obs[1], what="sample_posterior", key=obs[0])
         if self.Hprime > 16:
             raise _lib.HipError("%s.sample_posterior holds H' <= 16 candidates, got %d" % (type(self).__name__, self.Hprime))
         if self.D > self._recon_var_max_D:
@@ -1465,7 +1479,7 @@ class DeviceCAModel(CAModel):
         try:
             self._par, self._rows_gemm = {}, True
             U, E = self._sample_randoms(N, M, seed, uniforms, normals, nn)
-            Ys, Sl = self._sample(dict(model_params), y, mask, N, M, U, latents, E)
+            Ys, Sl = self._sample(dict(model_params), y, obs, N, M, U, latents, E)
             return (wrap(Ys), wrap(Sl)) if latents else wrap(Ys)
         finally:
             self._par = {}
@@ -1480,21 +1494,89 @@ class DeviceCAModel(CAModel):
         raise NotImplementedError("%s: missing values (my_data['mask']) are not built for this model; BSC_ET, MCA_ET and "
                                   "MMCA_ET have the masked E-step" % type(self).__name__)
 
-    def _masked_admit(self, y, mask, exact=False, what="log_likelihood"):
-        """Everything that refuses a masked call, before any launch: the model, ``exact=True``, the mask's shape, H'."""
-        if type(self)._masked_estep is DeviceCAModel._masked_estep:
+    def _weighted_estep(self, model_params, y, weight):
+        """Per model: ``_masked_estep`` for ``y`` observed with the per-entry noise variances sigma^2 / weight
+        (0 = not observed).  Returns the same dict -- log p(s, y | weight) = logpj + c0 + D_n c1 + logw -- plus ``logw`` (N,),
+        the per-row 1/2 sum_{weight > 0} log weight, left on the device."""
+        raise NotImplementedError("%s: per-entry noise weights (my_data['weight']) are not built for this model; BSC_ET, MCA_ET "
+                                  "and MMCA_ET have the weighted E-step" % type(self).__name__)
+
+    @staticmethod
+    def _observation(my_data):
+        """What ``my_data`` says about how its entries were observed: None, ``('mask', mask)`` or ``('weight', weight)``;
+        both at once is a ``ValueError``."""
+        mask, weight = my_data.get('mask'), my_data.get('weight')
+        if weight is None:
+            return ('mask', mask) if mask is not None else None
+        if mask is not None:
+            raise ValueError("my_data['weight'] together with my_data['mask']: fold the mask into the weight as zeros "
+                             "(weight = 0 where mask == 0)")
+        return ('weight', weight)
+
+    def _obs_estep(self, model_params, y, obs):
+        """``_masked_estep`` or ``_weighted_estep``, by the kind of observation record."""
+        return (self._weighted_estep if obs[0] == 'weight' else self._masked_estep)(model_params, y, obs[1])
+
+    def _masked_admit(self, y, mask, exact=False, what="log_likelihood", key='mask'):
+        """Everything that refuses a masked (``key='mask'``) or weighted (``key='weight'``, ``mask`` the weight) call, before
+        any launch: the model, ``exact=True``, the record's shape, a weight's values, H'."""
+        if key == 'weight':
+            if type(self)._weighted_estep is DeviceCAModel._weighted_estep:
+                self._weighted_estep(None, None, None)
+        elif type(self)._masked_estep is DeviceCAModel._masked_estep:
             self._masked_estep(None, None, None)
         if exact:
-            raise NotImplementedError("%s.%s: exact=True with a mask is not built (the enumeration kernels "
-                                      "read every dimension)" % (type(self).__name__, what))
+            raise NotImplementedError("%s.%s: exact=True with a %s is not built (the enumeration kernels "
+                                      "read every dimension)" % (type(self).__name__, what, key))
         shape = tuple(getattr(mask, "tensor", mask).shape) if hasattr(getattr(mask, "tensor", mask), "shape") \
             else np.asarray(mask).shape
         if len(shape) != 2:
-            raise ValueError("my_data['mask'] must be two-dimensional (N, D), got shape %r" % (shape,))
+            raise ValueError("my_data['%s'] must be two-dimensional (N, D), got shape %r" % (key, shape))
         if shape != tuple(y.shape):
-            raise ValueError("my_data['mask'] has shape %r, my_data['y'] %r" % (shape, tuple(y.shape)))
+            raise ValueError("my_data['%s'] has shape %r, my_data['y'] %r" % (key, shape, tuple(y.shape)))
+        if key == 'weight':
+            # (one reduction where the weight lives; NaN fails the first comparison)
+            t = getattr(mask, "tensor", mask)
+            if torch is not None and torch.is_tensor(t):
+                v = t.to(torch.uint8) if t.dtype == torch.bool else t
+                ok = bool(((v >= 0) & (v < float("inf"))).all())
+            else:
+                with np.errstate(invalid="ignore"):
+                    a = np.asarray(t)
+                    ok = bool(np.all((a >= 0) & (a < np.inf)))
+            if not ok:
+                raise ValueError("every entry of my_data['weight'] must be finite and >= 0 (0 = not observed): a weight is "
+                                 "never clamped")
         if self.Hprime > 16:
-            raise _lib.HipError("%s: the masked E-step holds H' <= 16 candidates, got %d" % (type(self).__name__, self.Hprime))
+            raise _lib.HipError("%s: the %s E-step holds H' <= 16 candidates, got %d"
+                                % (type(self).__name__, "weighted" if key == 'weight' else "masked", self.Hprime))
+
+    def _weight_resident(self, weight):
+        """``weight`` (NumPy, torch or DeviceArray of any real numeric type) as a float64 device tensor with unit column
+        stride, and its leading dimension.  A float64 device tensor of that layout is used in place; anything else is
+        converted once."""
+        t = getattr(weight, "tensor", weight)
+        if not torch.is_tensor(t):
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(t), dtype=np.float64))
+        t = t.to(device=self.device, dtype=torch.float64)
+        N, D = t.shape
+        if t.stride(1) != 1 or t.stride(0) < D:
+            t = t.contiguous()
+        return t, int(t.stride(0)) if N > 1 else max(int(t.stride(0)), D)
+
+    def _weighted_prepare(self, Y, Wg, ldo, mu=None, x0=False):
+        """pm_weighted_prepare_f64: (Xw = omega x, Om = omega, X0 = x or None, sum omega x^2, D_n, 1/2 sum log omega per row), x =
+        y - mu where omega != 0 and 0 elsewhere."""
+        N, D = Y.shape
+        Xw, Om = self._buf("wgt_xw", (N, D)), self._buf("wgt_om", (N, D))
+        X0 = self._buf("wgt_x0", (N, D)) if x0 else None
+        xn2 = self._buf("wgt_xn2", (N,))
+        dn = torch.empty(N, dtype=torch.int32, device=self.device)
+        logw = torch.empty(N, dtype=torch.float64, device=self.device)
+        mu_d = torch.from_numpy(np.ascontiguousarray(mu, dtype=np.float64).reshape(-1)).to(self.device) if mu is not None else None
+        self._call("weighted_prepare", "pm_weighted_prepare_f64", _ptr(Y), max(int(Y.stride(0)), D), _ptr(Wg), ldo, _ptr(mu_d),
+                   N, D, _ptr(Xw), D, _ptr(Om), D, _ptr(X0), D, _ptr(xn2), _ptr(dn), _ptr(logw), self._stream())
+        return Xw, Om, X0, xn2, dn, logw * 0.5
 
     def _mask_resident(self, mask):
         """``mask`` (NumPy, torch or DeviceArray; bool, uint8 or numeric, non-zero = observed) as a uint8 device tensor with
@@ -1530,10 +1612,11 @@ class DeviceCAModel(CAModel):
         g = self._gemm_nt(Mf, (Wt * Wt).contiguous(), self._buf("mask_g", (N, H)), "masked_gemm")
         return b, g
 
-    def _reconstruct_masked(self, model_params, y, mask, N, variance=False):
-        """``_reconstruct`` from the masked E-step's log-joints: the expectation and product kernels are the unmasked ones,
-        so the estimate (and with ``variance`` its variance given the observed dimensions) covers all D dimensions."""
-        out = self._masked_estep(model_params, y, mask)
+    def _reconstruct_masked(self, model_params, y, obs, N, variance=False):
+        """``_reconstruct`` from the masked or weighted E-step's log-joints (``obs``: what ``_observation`` returned): the
+        expectation and product kernels are the unmasked ones, so the estimate (and with ``variance`` its variance given the
+        observed dimensions) covers all D dimensions."""
+        out = self._obs_estep(model_params, y, obs)
         lay, lp, cand = out["lay"], out["logpj"], out["cand"]
         K = lp.shape[1]
         mu = lay.get("mu")
@@ -1553,17 +1636,19 @@ class DeviceCAModel(CAModel):
         return Yhat
 
     def _log_likelihood_masked(self, model_params, my_data, per_datapoint, exact):
-        """``log_likelihood`` with ``my_data['mask']``: log sum_{s in K_n} p(s, y_obs,n), the per-row constant c0 + D_n c1."""
-        y, mask = my_data['y'], my_data['mask']
-        self._masked_admit(y, mask, exact)
+        """``log_likelihood`` with ``my_data['mask']``: log sum_{s in K_n} p(s, y_obs,n), the per-row constant c0 + D_n c1; with
+        ``my_data['weight']`` the constant is c0 + D_n c1 + 1/2 sum_{weight > 0} log weight."""
+        y, obs = my_data['y'], self._observation(my_data)
+        self._masked_admit(y, obs[1], exact, key=obs[0])
         N = int(y.shape[0])
         if N == 0:
             return np.empty(0) if per_datapoint else self._sum_over_ranks(0.0)
         saved = self._eval_begin()
         try:
             self._par, self._rows_gemm = {}, True
-            out = self._masked_estep(dict(model_params), y, mask)
+            out = self._obs_estep(dict(model_params), y, obs)
             logpj, dn, c0, c1 = out["logpj"], out["dn"], out["c0"], out["c1"]
+            logw = out["logw"].cpu().numpy() if out.get("logw") is not None else None      # (weights: 1/2 sum log omega)
             K = logpj.shape[1]
             lib = _lib.load(self.deterministic)
             work = torch.empty(int(lib.pm_rows_lse_work_len(N)), dtype=torch.float64, device=self.device)
@@ -1573,9 +1658,12 @@ class DeviceCAModel(CAModel):
             self._call("loglik_rows", "pm_rows_lse_f64", _ptr(logpj), ld, N, K, ctypes.c_double(1.0), None, _ptr(rows),
                        _ptr(work), _ptr(total), self._stream())
             if per_datapoint:
-                return rows.cpu().numpy() + (c0 + dn.cpu().numpy().astype(np.float64) * c1)
+                rows = rows.cpu().numpy() + (c0 + dn.cpu().numpy().astype(np.float64) * c1)
+                return rows if logw is None else rows + logw
             # (the rows' sum in pm_rows_lse_f64's fixed order; sum_n D_n exactly, in integers)
             local = float(total.cpu()[0]) + N * c0 + int(dn.sum(dtype=torch.int64)) * c1
+            if logw is not None:
+                local += float(np.sum(logw))
         finally:
             self._par = {}
             self._eval_end(saved)

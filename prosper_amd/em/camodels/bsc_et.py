@@ -435,6 +435,7 @@ class BSC_ET(DeviceCAModel):
     def step(self, anneal, model_params, my_data):
         """CAModel.step (camodels/__init__.py:163-193); E_step knows that M_step follows with the same arguments.
         ``my_data['mask']`` (N, D; non-zero = observed): the EM step on incomplete data."""
+        self._refuse_training_weight(my_data)
         if my_data.get('mask') is not None:
             # (on records of its own: nothing the unmasked loop keeps between its steps is read or touched)
             self._mt_admit(my_data, anneal)
@@ -452,6 +453,7 @@ class BSC_ET(DeviceCAModel):
         """Annotate ``data`` with ``data['candidates']`` (N, Hprime): per datapoint the
         Hprime latents with the largest <W_h,y>/|W_h|/|y|, ascending (bsc_et.py:98-115).  With ``data['mask']``: the largest
         b_h / sqrt(G_n[h,h]) over the observed dimensions."""
+        self._refuse_training_weight(data)
         if data.get('mask') is not None:
             return self._mt_select(model_params, data)
         res = self._resident(data['y'])
@@ -573,6 +575,7 @@ class BSC_ET(DeviceCAModel):
     def E_step(self, anneal, model_params, my_data):
         """Log-pseudo-joints of the truncated state set -> ``{'logpj': (N, 1+H+S)}``
         (bsc_et.py:119-192).  Inserts ``model_params['mu']`` when absent, as upstream."""
+        self._refuse_training_weight(my_data)
         if my_data.get('mask') is not None:
             return self._mt_estep(anneal, model_params, my_data)
         res = self._resident(my_data['y'])
@@ -667,6 +670,32 @@ class BSC_ET(DeviceCAModel):
         return {"logpj": logpj, "cand": cand, "dn": dn, "c0": H * np.log(1. - pies),
                 "c1": -0.5 * np.log(2 * _PI * sigma ** 2), "lay": lay}
 
+    def _weighted_estep(self, model_params, y, weight):
+        """Per-entry noise weights: ``_masked_estep`` with b = W^T diag(omega) x and diag G_n = diag(W^T diag(omega)
+        W) from pm_weighted_prepare_f64's Xw = omega x and Om = omega, then pm_bsc_weighted_estep_f64 -- the same selection
+        rule, the candidates' weighted pair products, log-joints in the unmasked layout.  ``logw``: 1/2 sum log omega per row."""
+        lay = self._recon_layout(model_params)
+        res = self._resident(y)
+        Y = res["Y"]
+        N, D = Y.shape
+        H, Hp, S = self.H, self.Hprime, self.no_states
+        Wg, ldo = self._weight_resident(weight)
+        mu = model_params.get('mu')
+        if mu is not None and not np.any(np.asarray(mu)):
+            mu = None
+        Xw, Om, _, xn2, dn, logw = self._weighted_prepare(Y, Wg, ldo, mu)
+        Wt = torch.from_numpy(np.ascontiguousarray(np.asarray(model_params['W'], dtype=np.float64).T)).to(self.device)
+        b, g = self._masked_dense(Xw, Om, Wt)
+        pies, sigma = float(model_params['pi']), float(model_params['sigma'])
+        P = self._estep_params(LoglikPoint(), pies, sigma, np.zeros(1))
+        cand = torch.empty((N, Hp), dtype=torch.int32, device=self.device)
+        logpj, _ = self._estep_outputs(N)
+        self._call("weighted_estep", "pm_bsc_weighted_estep_f64", _ptr(b), H, _ptr(g), H, _ptr(xn2), _ptr(Wg), ldo, _ptr(Wt), D,
+                   _ptr(self._state_tables()["masks"]), S, ctypes.byref(P), N, H, D, Hp, _ptr(cand), _ptr(logpj),
+                   logpj.stride(0), self._stream())
+        return {"logpj": logpj, "cand": cand, "dn": dn, "c0": H * np.log(1. - pies),
+                "c1": -0.5 * np.log(2 * _PI * sigma ** 2), "lay": lay, "logw": logw}
+
     def _loglik_exact(self, model_params):
         """exact log_likelihood: states {0,1}^H, log prior |s| log pi + (H - |s|) log(1 - pi), y ~ N(mu + W s,
         sigma^2 I) (mu when given)."""
@@ -681,6 +710,7 @@ class BSC_ET(DeviceCAModel):
         """New W, pi, sigma (, mu) from the posterior over the truncated states
         (bsc_et.py:195-438).  Logs ``N``, ``L`` (free energy) and ``N_use`` to dlog.  With ``my_data['mask']``: one solve per
         data dimension; ``W_kept`` = the dimensions that kept their row of W."""
+        self._refuse_training_weight(my_data)
         if my_data.get('mask') is not None:
             return self._mt_mstep(anneal, model_params, my_suff_stat, my_data)
         comm = self.comm

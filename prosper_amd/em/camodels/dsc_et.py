@@ -285,6 +285,7 @@ class DSC_ET(TableCAModel):
     def select_Hprimes(self, model_params, data):
         """``data['candidates']`` (N, Hprime): latents ranked by their best singleton log-joint, best
         first (dsc_et.py:347-410)."""
+        self._refuse_training_weight(data)
         res = self._resident(data['y'])
         N = res["Y"].shape[0]
         H, Hp = self.H, self.Hprime

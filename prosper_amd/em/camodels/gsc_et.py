@@ -485,6 +485,7 @@ class GSC(DeviceCAModel):
         (gsc_et.py:721-728).  The selection itself is fused into the E-step kernel; ``data_clusters`` -- the reference's
         bucketing of the datapoints by candidate set (gsc_et.py:731-747) -- is a ``LazyClusters`` that is filled when
         somebody looks at it.  Statistics stay in datapoint order unless ``self.reference_order`` is set."""
+        self._refuse_training_weight(my_data)
         self._require_scalar()
         res = self._resident(my_data['y'])
         my_data['data_clusters'] = LazyClusters(self, dict(model_params), my_data)     # (shallow: nothing is copied)

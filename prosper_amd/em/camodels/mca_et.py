@@ -147,6 +147,7 @@ class MCA_ET(DeviceCAModel):
     def select_Hprimes(self, model_params, data):
         """``data['candidates']`` (N, Hprime): the latents with the smallest
         sum_d |max(W_hd, y_d) - y_d|, ascending (mca_et.py:88-111)."""
+        self._refuse_training_weight(data)
         res = self._resident(data['y'])
         Y = res["Y"]
         N, D = Y.shape
@@ -318,6 +319,45 @@ class MCA_ET(DeviceCAModel):
                    _ptr(lseb), self._stream())
         return {"logpj": logpj, "cand": cand, "dn": dn, "c0": H * np.log(1. - pies),
                 "c1": -0.5 * np.log(2 * _PI * sigma ** 2), "lay": lay, "par": par}
+
+    def _weighted_select(self, res, Wg, ldo, par, A, wn, xn2):
+        """Weighted selection: the H' smallest R[n,h] = sum_d omega_d max(W_hd - y_d, 0), ranked as
+        ``_select_on_device`` does."""
+        Y = res["Y"]
+        N, D = Y.shape
+        H = self.H
+        R = self._buf("mca_sim", (N, H))
+        self._call("select_scores", "pm_mca_weighted_select_scores_f64", _ptr(Y), D, _ptr(Wg), ldo, _ptr(par["Wt"]), D, _ptr(R),
+                   H, N, H, D, self._stream())
+        return self._rank_smallest(R, res)
+
+    def _weighted_estep(self, model_params, y, weight):
+        """Per-entry noise weights: ``_masked_estep`` with the one-cause energies from sum omega W_hd^2 - 2 sum
+        omega W_hd y_d + sum omega y_d^2 (two one-kernel GEMMs on pm_weighted_prepare_f64's outputs) and the multi-cause
+        energies sum_d omega_d (y_d - Wbar_d(s))^2 in pm_mca_weighted_estep_f64.  ``logw``: 1/2 sum log omega per row."""
+        lay = self._recon_layout(model_params)
+        mp = lay["params"]
+        res = self._resident(y)
+        Y = res["Y"]
+        N, D = Y.shape
+        H, Hp, S = self.H, self.Hprime, self.no_states
+        Wg, ldo = self._weight_resident(weight)
+        masks = self._masks()
+        Xw, Om, X0, xn2, dn, logw = self._weighted_prepare(Y, Wg, ldo, x0=True)
+        par = self._tables_for(mp['W'], 1.0, res)
+        A, wn = self._masked_dense(Xw, Om, par["Wt"])
+        cand = self._weighted_select(res, Wg, ldo, par, A, wn, xn2)
+        pies, sigma = float(mp['pi']), float(mp['sigma'])
+        P = self._params(LoglikPoint(), pies, sigma, par["rho"])
+        K = 1 + H + S
+        logpj = torch.empty((N, K), dtype=torch.float64, device=self.device)
+        lse1 = torch.empty((N,), dtype=torch.float64, device=self.device)
+        lseb = torch.empty((N,), dtype=torch.float64, device=self.device)
+        self._call("weighted_estep", "pm_mca_weighted_estep_f64", _ptr(A), H, _ptr(wn), H, _ptr(xn2), _ptr(X0), D, _ptr(Wg), ldo,
+                   _ptr(par["Wrho"]), _ptr(cand), _ptr(masks), S, ctypes.byref(P), N, H, D, Hp, _ptr(logpj), K, _ptr(lse1),
+                   _ptr(lseb), self._stream())
+        return {"logpj": logpj, "cand": cand, "dn": dn, "c0": H * np.log(1. - pies),
+                "c1": -0.5 * np.log(2 * _PI * sigma ** 2), "lay": lay, "par": par, "logw": logw}
 
     def _loglik_exact(self, model_params):
         """exact log_likelihood: states {0,1}^H, y ~ N(Wbar(s), sigma^2 I) with the rho-combination of

@@ -95,6 +95,7 @@ class MMCA_ET(MCA_ET):
     def select_Hprimes(self, model_params, data):
         """``data['candidates']`` (N, Hprime): the latents with the smallest |W_h - y|^2, ascending
         (mmca_et.py:96-124)."""
+        self._refuse_training_weight(data)
         res = self._resident(data['y'])
         Y = res["Y"]
         N = Y.shape[0]
@@ -116,6 +117,11 @@ class MMCA_ET(MCA_ET):
         smallest sum_d m_d (W_hd - y_d)^2 = |W_h|^2_obs - 2 <W_h, y>_obs + |y|^2_obs, from the E-step's three terms."""
         R = (wn - 2.0 * A + xn2[:, None]).contiguous()
         return self._rank_smallest(R, res)
+
+    def _weighted_select(self, res, Wg, ldo, par, A, wn, xn2):
+        """Weighted selection: the H' smallest sum_d omega_d (W_hd - y_d)^2, from the E-step's three weighted
+        terms -- ``_masked_select``'s expression on them."""
+        return self._masked_select(res, Wg, ldo, par, A, wn, xn2)
 
     def _finalize(self, stats, model_params, par, A_pi_gamma, B_pi_gamma):
         """W update with inertia and the scalars (mmca_et.py:365-427), one device->host copy."""

@@ -189,6 +189,7 @@ class TSC_ET(TableCAModel):
     def select_Hprimes(self, model_params, data):
         """``data['candidates']`` (N, Hprime): latents of the Hprime best one-cause states, best last; a latent
         may repeat (tsc_et.py:142-213)."""
+        self._refuse_training_weight(data)
         res = self._resident(data['y'])
         N = res["Y"].shape[0]
         H, Hp = self.H, self.Hprime

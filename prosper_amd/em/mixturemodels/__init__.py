@@ -58,19 +58,21 @@ class MixtureModel(Model):
         noise parameter (MoP) has none."""
         raise ValueError("%s has no noise parameter to derive the precision floor from: give floor=" % type(self).__name__)
 
-    def reconstruct_image(self, model_params, image, mask=None, **kw):
+    def reconstruct_image(self, model_params, image, mask=None, weight=None, **kw):
         """Whole-image denoising by overlapping patches: ``utils.patches.denoise_image(self, model_params,
         image, **kw)`` -- every patch through ``reconstruct()``, the estimates averaged where they overlap.  Keywords:
         ``patch``, ``stride``, ``center``, ``chunk``, ``device``, ``exact`` (every patch through
         ``reconstruct(exact=True)``), ``variance`` (returns ``(image, var_map)``, var_map the overlap average of
         the patches' posterior variances -- an upper bound on the variance of the averaged estimate).  ``mask`` (the image's
         shape, non-zero = observed pixel): the patches go through the masked ``reconstruct()`` -- inpainting.
+        ``weight`` (the image's shape, finite and >= 0): pixel (i, j) was observed with noise variance sigma^2 /
+        weight[i, j], 0 = not observed; the patches go through the weighted ``reconstruct()`` (BSC, MCA, MMCA).
         ``aggregate='precision'`` (default ``'mean'``): the overlapping estimates of a pixel are weighted by 1 /
         (V + floor), V each patch's posterior variance there; ``floor`` (default: ``utils.patches.PRECISION_FLOOR`` times the
         mean component variance of MoG; MoP has no noise parameter and needs ``floor=``) and ``window`` (a fixed positive
         weight per patch element, under either aggregate); ``var_map`` is then the average of V under the same weights."""
         from ...utils.patches import denoise_image
-        return denoise_image(self, model_params, image, mask=mask, **kw)
+        return denoise_image(self, model_params, image, mask=mask, weight=weight, **kw)
 
     def sample_posterior(self, model_params, my_data, n_samples=1, seed=None, latents=False, device=False, uniforms=None,
                          normals=None):

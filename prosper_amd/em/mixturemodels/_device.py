@@ -88,6 +88,9 @@ class DeviceMixture(object):
         if my_data.get('mask') is not None:
             raise NotImplementedError("%s: missing values (my_data['mask']) are not built for the mixture models; BSC_ET, "
                                       "MCA_ET and MMCA_ET have the masked E-step" % type(self).__name__)
+        if my_data.get('weight') is not None:
+            raise NotImplementedError("%s: per-entry noise weights (my_data['weight']) are not built for the mixture models; "
+                                      "BSC_ET, MCA_ET and MMCA_ET have the weighted E-step" % type(self).__name__)
 
     # ---- held-out log-likelihood --------------------------------------------------------------------------
     def log_likelihood(self, model_params, my_data, per_datapoint=False, exact=False):

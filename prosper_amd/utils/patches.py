@@ -253,8 +253,32 @@ def _mask_image(mask, shape, dev):
     return _image_tensor((t.to(dev) != 0).to(torch.float64), dev)
 
 
+def _weight_check(weight):
+    """``ValueError`` naming the weight unless every entry is finite and >= 0: one reduction where the weight lives (NaN fails
+    the first comparison)."""
+    t = getattr(weight, "tensor", weight)
+    if torch is not None and torch.is_tensor(t):
+        v = t.to(torch.uint8) if t.dtype == torch.bool else t
+        ok = bool(((v >= 0) & (v < float("inf"))).all())
+    else:
+        with np.errstate(invalid="ignore"):
+            t = np.asarray(t)
+            ok = bool(np.all((t >= 0) & (t < np.inf)))
+    if not ok:
+        raise ValueError("every entry of 'weight' must be finite and >= 0 (0 = not observed): a weight is never clamped")
+
+
+def _weight_image(weight, dev):
+    """The float64 device image of ``weight`` (any type ``_image_tensor`` reads), cut into patches by the extraction kernel
+    like the image itself."""
+    t = getattr(weight, "tensor", weight)
+    if not torch.is_tensor(t):
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(t), dtype=np.float64))
+    return _image_tensor(t.to(device=dev, dtype=torch.float64), dev)
+
+
 def denoise_image(model, model_params, image, patch=None, stride=1, center=False, chunk=None, device=False, mask=None,
-                  exact=False, variance=False, aggregate='mean', floor=None, window=None):
+                  exact=False, variance=False, aggregate='mean', floor=None, window=None, weight=None):
     """Denoise ``image`` ((H_i, W_i) or a stack (B, H_i, W_i); NumPy array, torch tensor -- a device tensor is used in place,
     without a host round trip -- or ``DeviceArray``) with ``model`` at ``model_params``: every overlapping patch on the grid of
     the module docstring is replaced by its posterior mean ``model.reconstruct()`` and every pixel by the average of the
@@ -278,6 +302,14 @@ def denoise_image(model, model_params, image, patch=None, stride=1, center=False
     there -- NaN included.  The overlap average is unchanged and covers every pixel.  ``center=True`` with a mask raises
     ``ValueError`` (a mean over the observed pixels only is not built); a model without the masked E-step raises
     ``NotImplementedError``.
+
+    ``weight`` (per-pixel noise weights): an array of the image's shape, finite and >= 0: pixel (i, j) was observed
+    with noise variance sigma^2 / weight[i, j], 0 = not observed.  Its patches are cut on the same grid by the same kernel, kept
+    as float64, and every chunk goes through ``model.reconstruct(model_params, {'y': chunk, 'weight': chunk's weights})``;
+    ``aggregate``, ``variance``, ``window``, stacks and ``chunk`` work as without it and the bits do not depend on ``chunk``.
+    What the image holds at weight 0 changes no bit.  A weight that is negative, NaN or infinite anywhere, one of another
+    shape, ``weight`` together with ``mask`` (fold the mask into the weight as zeros) and ``center=True`` raise
+    ``ValueError``, ``exact=True`` and a model without the weighted E-step ``NotImplementedError`` -- all before any launch.
 
     ``exact=True``: every patch through ``model.reconstruct(..., exact=True)``, the posterior mean over the
     model's whole state space; its limits apply, and with a mask it raises ``NotImplementedError``.  The keyword reaches
@@ -313,6 +345,10 @@ def denoise_image(model, model_params, image, patch=None, stride=1, center=False
     from ..em.camodels._device import DeviceArray
     if mask is not None and center:
         raise ValueError("center=True with a mask is not built: the patch mean would have to run over the observed pixels only")
+    if weight is not None and mask is not None:
+        raise ValueError("'weight' together with 'mask': fold the mask into the weight as zeros (weight = 0 where mask == 0)")
+    if weight is not None and center:
+        raise ValueError("center=True with a weight is not built: the patch mean would have to be the weighted one")
     D = int(model.D)
     if patch is None:
         p = int(round(D ** 0.5))
@@ -338,6 +374,12 @@ def denoise_image(model, model_params, image, patch=None, stride=1, center=False
             raise ValueError("mask has shape %r, the image %r" % (_shape_of(mask), tuple(shape)))
         # (an empty masked call: a model without the masked E-step refuses here, before anything reaches the device)
         model.reconstruct(model_params, {'y': np.empty((0, D)), 'mask': np.empty((0, D), dtype=bool)}, **extra)
+    if weight is not None:
+        if _shape_of(weight) != tuple(shape):
+            raise ValueError("weight has shape %r, the image %r" % (_shape_of(weight), tuple(shape)))
+        _weight_check(weight)
+        # (an empty weighted call: a model without the weighted E-step refuses here, before anything reaches the device)
+        model.reconstruct(model_params, {'y': np.empty((0, D)), 'weight': np.empty((0, D))}, **extra)
     if variance and exact:
         raise NotImplementedError("denoise_image: variance=True with exact=True is not built (the enumeration kernels keep no "
                                   "second moments)")
@@ -366,6 +408,7 @@ def denoise_image(model, model_params, image, patch=None, stride=1, center=False
     det = bool(getattr(model, "deterministic", False))
     img, ldi = _image_tensor(image, dev)
     mimg, ldmi = _mask_image(mask, shape, dev) if mask is not None else (None, 0)
+    wimg, ldwi = _weight_image(weight, dev) if weight is not None else (None, 0)
     acc = torch.zeros((B, Hi, Wi), dtype=torch.float64, device=dev)
     vacc = torch.zeros((B, Hi, Wi), dtype=torch.float64, device=dev) if variance else None
     den = torch.zeros((B, Hi, Wi), dtype=torch.float64, device=dev) if weighted else None
@@ -376,6 +419,8 @@ def denoise_image(model, model_params, image, patch=None, stride=1, center=False
         data = {'y': DeviceArray(Y)}
         if mimg is not None:
             data['mask'] = DeviceArray((_extract(mimg, ldmi, geo, n0, n, False, det)[0] != 0).view(torch.uint8))
+        if wimg is not None:
+            data['weight'] = DeviceArray(_extract(wimg, ldwi, geo, n0, n, False, det)[0])
         est = model.reconstruct(model_params, data, device=True, **extra)
         del Y, data
         var, ldv = None, 0
