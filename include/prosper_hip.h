@@ -1028,13 +1028,35 @@ int pm_rows_lse_f64(const double *logpj, int64_t ld, int64_t N, int64_t S, doubl
  * ---------------------------------------------------------------------------------------
  * v_n = log sum_{all s} p(s, y_n | Theta) over the model's WHOLE state space, by enumeration on the device: states are
  * decoded from their index inside the kernels, nothing is stored per state.  rows_out (N; NULL = not written) receives v,
- * total[0] = sum_n v_n in a fixed order; the grid splits the state space into ranges whose number depends on N alone, the
+ * total[0] = sum_n v_n in a fixed order; the grid splits the state space into R ranges, R a function of N (through the tile
+ * width and the number of tiles) and of the state count (never more ranges than chunks of the linear kernels, than states /
+ * 1024 for MCA / MMCA, than supports / 32 for GSC, rounded up) and of nothing else: pm_loglik_exact_plan reports it; the
  * (max, sum exp) partials of every (range, datapoint) are combined in range order, no atomics: the same bits on every run
  * and in both builds.  N == 0 writes total[0] = 0.  A state of zero prior contributes nothing, a NaN in y_n gives v_n = NaN
  * (that row only).  `work`: pm_loglik_exact_work_len(N, H) doubles (a function of N and H only, linear in H).  Every entry
  * checks its arguments before it touches a device: PM_EINVAL for a null pointer, N < 0, D < 1, H < 1, ldy < D or a bad K,
  * PM_ERANGE past the bounds: K^H <= 2^32 and H <= 32 (linear models), H <= 32 (MCA / MMCA), H <= 16 (GSC). */
 int64_t pm_loglik_exact_work_len(int64_t N, int64_t H);
+/* What pm_loglik_exact_{lin,mca,gsc}_f64 launch for (N, D, K, H), from the host function the entries themselves take it from;
+ * nothing is launched and no device is needed.  `kind`: PM_EXACT_LIN (K is read), PM_EXACT_MCA, PM_EXACT_GSC (K is ignored).
+ * out[PM_EXACT_PLAN_LEN]:
+ *   0 TN        datapoints per workgroup: lin 1 below N = 64 and 8 from there, MCA 1 below N = 16 and 4 from there, GSC 64
+ *   1 L, 2 CH   lin: the L low digits of the state index are fixed per thread, CH = K^L <= 1024 lo states, at most four per
+ *               thread; L is the largest such number of digits, and H where K^H <= 1024 (else 0, 1)
+ *   3 space     what the ranges cut: lin the K^(H-L) chunks (values of the high digits), MCA / GSC the 2^H states; range r of R
+ *               is [space r / R, space (r + 1) / R) in integer arithmetic
+ *   4 units     the cap on R: lin the chunks, MCA ceil(2^H / 1024), GSC ceil(2^H / 32)
+ *   5 R         min(units, min(4096, ceil(4096 / tiles))), tiles = ceil(N / TN); 1 for N = 0.  1 <= R <= units: no range is empty
+ *   6 grid      tiles R workgroups of 256 threads
+ *   7, 8        offset and length (doubles) of the (range, datapoint) partials inside `work`: N (H + 2) and 2 N R
+ *   9           0
+ * Returns PM_OK, PM_EINVAL (null `out`, unknown kind, N < 0, D < 1, H < 1, lin: K outside 2..8) or PM_ERANGE exactly where
+ * the entry of the kind returns it. */
+#define PM_EXACT_LIN 0
+#define PM_EXACT_MCA 1
+#define PM_EXACT_GSC 2
+#define PM_EXACT_PLAN_LEN 10
+int pm_loglik_exact_plan(int kind, int64_t N, int64_t D, int64_t K, int64_t H, int64_t *out);
 /* BSC, TSC, DSC: log p(s, y) = sum_h logp[h*K + k_h] - 1/2 s^T G s + x^T P s + cst + qcoef |x|^2, x = y - ymu (ymu: D values
  * or NULL for 0, BSC's mu), s_h = values[k_h] (K in 2..8 values, any reals), i.e. P = W / sigma^2 (D x H row-major),
  * G = W^T W / sigma^2 (H x H), logp the per-latent log-prior table (-inf for a value of zero prior), cst = -D/2 log(2 pi
@@ -1077,6 +1099,19 @@ int pm_loglik_exact_gsc_f64(const double *Y, int64_t ldy, const double *P, const
  * an output leading dimension below the row width or a bad K; PM_ERANGE past the bounds of pm_loglik_exact_* (K^H <= 2^32
  * and H <= 32; GSC H <= 16) and, for MCA / MMCA, D > 1024.  N == 0 launches nothing and returns PM_OK. */
 int64_t pm_recon_exact_work_len(int64_t N, int64_t H, int64_t D);
+/* What pm_recon_exact_{lin,mca,gsc}_f64 do for (N, D, K, H), from the host function the entries themselves take it from;
+ * nothing is launched and no device is needed.  `kind` as for pm_loglik_exact_plan.  out[PM_EXACT_PLAN_LEN]:
+ *   0 rows      rows per block of the host walk: 256, MCA 64            1 blocks   ceil(N / rows)
+ *   2 L, 3 CH   as in pm_loglik_exact_plan (MCA, GSC: 0, 1)
+ *   4 space     what the ranges cut: lin the chunks, MCA / GSC the states; range r is [space r / R, space (r + 1) / R)
+ *   5 R         lin min(256, max(1, chunks / 2)), MCA min(64, max(1, states / 64)), GSC min(256, max(1, states / 32)): a
+ *               function of the state count alone, 1 <= R <= space
+ *   6 slabs     MCA: ceil(D / 64) 64-wide slabs of the dimensions a lane walks; else 0
+ *   7           offset (doubles) of the partials inside `work` for the largest block, nb = min(N, rows) rows: nb (H + 1), MCA nb
+ *   8, 9        length of the partials of sweep 1 (2 nb R) and of sweep 2 (nb R H, MCA nb R D)
+ * Returns PM_OK, PM_EINVAL or PM_ERANGE as pm_loglik_exact_plan does, and PM_ERANGE where the entry of the kind returns it
+ * (MCA: D > 1024). */
+int pm_recon_exact_plan(int kind, int64_t N, int64_t D, int64_t K, int64_t H, int64_t *out);
 /* BSC, TSC, DSC: E (N x H, row stride lde >= H) receives E_n[s]_h = sum_s q_n(s) values[k_h]; Y, ymu, P, G, logp, values and
  * K as for pm_loglik_exact_lin_f64.  Columns of E past H are not written. */
 int pm_recon_exact_lin_f64(const double *Y, int64_t ldy, const double *ymu, const double *P, const double *G,

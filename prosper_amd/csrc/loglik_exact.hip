@@ -8,7 +8,7 @@
 //               merges the 256 threads' pairs into ONE partial per (range, datapoint);
 //   ex_combine  per datapoint, the R partials merged in a fixed order, plus the row constant cst + qcoef q_n; then one
 //               workgroup adds the rows in a fixed order.
-// R (ranges per tile) depends on N and the state count alone, the ranges are fixed slices of the state index space, and
+// R (ranges per tile) depends on N and the state count alone (ex_plan; pm_loglik_exact_plan exports it), the ranges are fixed slices of the state index space, and
 // nothing is added by atomics: the result is a function of the input bits (every run, both library builds).  States are decoded from their
 // index; every per-state quantity is recomputed directly from its digits (no incremental updates), so the accuracy does
 // not depend on how far a range reaches.  What recon_exact.hip must form the same way -- the log-sum-exp, the bounds, the state
@@ -60,17 +60,58 @@ int64_t ex_part_len(int64_t N) {
     return 2 * N * m;
 }
 
-// work layout (doubles): B (N x H) | q (N) | rows (N) | partials (2 N R)
+// What a launch is made of, for the three kinds (PM_EXACT_LIN / _MCA / _GSC): the ONE place the entries below and
+// pm_loglik_exact_plan take it from.  `space` is what the ranges cut (lin: chunks of CH lo states; MCA, GSC: states), `units`
+// what caps their number (lin: chunks; MCA, GSC: states over the minimum per range, rounded up).
+struct ExPlan {
+    int tn, L, CH;
+    uint64_t space, units;
+    int64_t R, grid, part_off, part_len;
+};
+
+// PM_EINVAL / PM_ERANGE exactly as the entries document them for (N, D, K, H); K is read by the linear kind alone
+int ex_plan(int kind, int64_t N, int64_t D, int64_t K, int64_t H, ExPlan &p) {
+    if (N < 0 || D < 1 || H < 1) return PM_EINVAL;
+    p.L = 0;
+    p.CH = 1;
+    if (kind == PM_EXACT_LIN) {
+        if (K < 2 || K > PMX_LIN_MAX_K) return PM_EINVAL;
+        const uint64_t S = pmx_state_count(K, H);
+        if (H > PMX_MAX_H || S == 0) return PM_ERANGE;
+        p.tn = ex_lin_tn(N);
+        pmx_lin_split(K, H, p.L, p.CH);
+        p.space = p.units = S / (uint64_t)p.CH;
+    } else if (kind == PM_EXACT_MCA) {
+        if (H > PMX_MAX_H) return PM_ERANGE;
+        p.tn = ex_mca_tn(N);
+        p.space = 1ull << H;
+        p.units = (p.space + EX_MCA_MIN_STATES - 1) / EX_MCA_MIN_STATES;
+    } else if (kind == PM_EXACT_GSC) {
+        if (H > PMX_GSC_MAX_H) return PM_ERANGE;
+        p.tn = PMX_GSC_TN;
+        p.space = 1ull << H;
+        p.units = (p.space + EX_GSC_MIN_STATES - 1) / EX_GSC_MIN_STATES;
+    } else {
+        return PM_EINVAL;
+    }
+    p.R = ex_ranges_for(N, p.tn, p.units);
+    p.grid = ex_tiles(N, p.tn) * p.R;
+    p.part_off = N * (H + 2);
+    p.part_len = 2 * N * p.R;
+    return PM_OK;
+}
+
+// work layout (doubles): B (N x H) | q (N) | rows (N) | partials (2 N R, from the plan's part_off)
 struct ExWork {
     double *B, *q, *rows, *part;
 };
 
-ExWork ex_work(double *work, int64_t N, int64_t H) {
+ExWork ex_work(double *work, int64_t N, int64_t H, const ExPlan &p) {
     ExWork w;
     w.B = work;
     w.q = work + N * H;
     w.rows = w.q + N;
-    w.part = w.rows + N;
+    w.part = work + p.part_off;
     return w;
 }
 
@@ -457,6 +498,24 @@ extern "C" int64_t pm_loglik_exact_work_len(int64_t N, int64_t H) {
     return len > 0 ? len : 1;
 }
 
+extern "C" int pm_loglik_exact_plan(int kind, int64_t N, int64_t D, int64_t K, int64_t H, int64_t *out) {
+    if (!out) return PM_EINVAL;
+    ExPlan p;
+    const int rc = ex_plan(kind, N, D, K, H, p);
+    if (rc) return rc;
+    out[0] = p.tn;
+    out[1] = p.L;
+    out[2] = p.CH;
+    out[3] = (int64_t)p.space;
+    out[4] = (int64_t)p.units;
+    out[5] = p.R;
+    out[6] = p.grid;
+    out[7] = p.part_off;
+    out[8] = p.part_len;
+    out[9] = 0;
+    return PM_OK;
+}
+
 extern "C" int pm_loglik_exact_lin_f64(const double *Y, int64_t ldy, const double *ymu, const double *P, const double *G,
                                        const double *logp, const double *values, int64_t K, double cst, double qcoef,
                                        int64_t N, int64_t D, int64_t H, double *rows_out, double *work, double *total,
@@ -464,15 +523,13 @@ extern "C" int pm_loglik_exact_lin_f64(const double *Y, int64_t ldy, const doubl
     if (N < 0 || D < 1 || H < 1 || K < 2 || K > PMX_LIN_MAX_K || ldy < D || !P || !G || !logp || !values || !work || !total ||
         (N > 0 && !Y))
         return PM_EINVAL;
-    const uint64_t S = pmx_state_count(K, H);
-    if (H > PMX_MAX_H || S == 0) return PM_ERANGE;
+    ExPlan pl;
+    const int rc = ex_plan(PM_EXACT_LIN, N, D, K, H, pl);
+    if (rc) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const ExWork w = ex_work(work, N, H);
-    const int tn = ex_lin_tn(N);
-    int L, CH;
-    pmx_lin_split(K, H, L, CH);
-    const uint64_t nchunks = S / (uint64_t)CH;
-    const int64_t R = ex_ranges_for(N, tn, nchunks);
+    const ExWork w = ex_work(work, N, H, pl);
+    const int tn = pl.tn;
+    const int64_t R = pl.R;
     if (N > 0) {
         int err = ex_prep(Y, ldy, ymu, N, D, P, H, nullptr, nullptr, w, st);
         if (err) return err;
@@ -486,12 +543,12 @@ extern "C" int pm_loglik_exact_lin_f64(const double *Y, int64_t ldy, const doubl
         a.R = R;
         a.H = (int)H;
         a.K = (int)K;
-        a.L = L;
-        a.CH = CH;
-        a.nchunks = nchunks;
+        a.L = pl.L;
+        a.CH = pl.CH;
+        a.nchunks = pl.space;
         const size_t lds = sizeof(double) * ((size_t)H * H + H * K + PMX_LIN_MAX_K + (size_t)tn * H + PMX_MAX_H * PMX_LIN_MAX_K +
                                              PMX_MAX_H + tn + PMX_MAX_H + 2 * (size_t)tn * EX_THREADS);
-        const dim3 grid((unsigned)(ex_tiles(N, tn) * R));
+        const dim3 grid((unsigned)pl.grid);
         if (tn == 8)
             hipLaunchKernelGGL(ex_lin_kernel<8>, grid, dim3(EX_THREADS), lds, st, a);
         else
@@ -506,11 +563,13 @@ extern "C" int pm_loglik_exact_mca_f64(const double *Y, int64_t ldy, const doubl
                                        double lp1, double lp0, double inv_s2, double cst, int64_t N, int64_t D, int64_t H,
                                        double *rows_out, double *work, double *total, void *stream) {
     if (N < 0 || D < 1 || H < 1 || ldy < D || !Wrho || !work || !total || (N > 0 && !Y)) return PM_EINVAL;
-    if (H > PMX_MAX_H) return PM_ERANGE;
+    ExPlan pl;
+    const int rc = ex_plan(PM_EXACT_MCA, N, D, 0, H, pl);
+    if (rc) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const ExWork w = ex_work(work, N, H);
-    const int tn = ex_mca_tn(N);
-    const int64_t R = ex_ranges_for(N, tn, ((1ull << H) + EX_MCA_MIN_STATES - 1) / EX_MCA_MIN_STATES);
+    const ExWork w = ex_work(work, N, H, pl);
+    const int tn = pl.tn;
+    const int64_t R = pl.R;
     if (N > 0) {
         int err = ex_prep(Y, ldy, nullptr, N, D, nullptr, H, nullptr, nullptr, w, st);
         if (err) return err;
@@ -522,14 +581,14 @@ extern "C" int pm_loglik_exact_mca_f64(const double *Y, int64_t ldy, const doubl
         a.N = N;
         a.R = R;
         a.D = D;
-        a.nstates = 1ull << H;
+        a.nstates = pl.space;
         a.inv_rho = inv_rho;
         a.lp1 = lp1;
         a.lp0 = lp0;
         a.inv_s2 = inv_s2;
         a.H = (int)H;
         a.signed_w = signed_w ? 1 : 0;
-        const dim3 grid((unsigned)(ex_tiles(N, tn) * R));
+        const dim3 grid((unsigned)pl.grid);
         if (tn == EX_MCA_TN)
             hipLaunchKernelGGL(ex_mca_kernel<EX_MCA_TN>, grid, dim3(EX_THREADS), 0, st, a);
         else
@@ -547,10 +606,12 @@ extern "C" int pm_loglik_exact_gsc_f64(const double *Y, int64_t ldy, const doubl
     if (N < 0 || D < 1 || H < 1 || ldy < D || !P || !M || !Psi || !mu || !logp || !work || !total || (N > 0 && !Y) ||
         (wdiag && Lw))
         return PM_EINVAL;
-    if (H > PMX_GSC_MAX_H) return PM_ERANGE;
+    ExPlan pl;
+    const int rc = ex_plan(PM_EXACT_GSC, N, D, 0, H, pl);
+    if (rc) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const ExWork w = ex_work(work, N, H);
-    const int64_t R = ex_ranges_for(N, PMX_GSC_TN, ((1ull << H) + EX_GSC_MIN_STATES - 1) / EX_GSC_MIN_STATES);
+    const ExWork w = ex_work(work, N, H, pl);
+    const int64_t R = pl.R;
     if (N > 0) {
         int err = ex_prep(Y, ldy, nullptr, N, D, P, H, wdiag, Lw, w, st);
         if (err) return err;
@@ -563,9 +624,9 @@ extern "C" int pm_loglik_exact_gsc_f64(const double *Y, int64_t ldy, const doubl
         a.part = w.part;
         a.N = N;
         a.R = R;
-        a.nstates = 1ull << H;
+        a.nstates = pl.space;
         a.H = (int)H;
-        hipLaunchKernelGGL(ex_gsc_kernel, dim3((unsigned)(ex_tiles(N, PMX_GSC_TN) * R)), dim3(EX_THREADS), 0, st, a);
+        hipLaunchKernelGGL(ex_gsc_kernel, dim3((unsigned)pl.grid), dim3(EX_THREADS), 0, st, a);
         err = (int)hipGetLastError();
         if (err) return err;
     }

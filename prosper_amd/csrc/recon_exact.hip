@@ -491,6 +491,67 @@ int rx_combine_sum(const double *part, int64_t nb, int64_t R, int64_t width, dou
 int64_t rx_min(int64_t a, int64_t b) { return a < b ? a : b; }
 int64_t rx_max(int64_t a, int64_t b) { return a > b ? a : b; }
 
+// What a call is made of, for the three kinds (PM_EXACT_LIN / _MCA / _GSC): the ONE place the entries below and
+// pm_recon_exact_plan take it from.  `space` is what the ranges cut (lin: chunks of CH lo states; MCA, GSC: states); a block
+// of nb rows keeps [B (nb x H; not MCA) | v (nb) | partials] in `work`, the partials 2 nb R doubles in sweep 1 and
+// width nb R in sweep 2 (width: H; MCA: D).
+struct RxPlan {
+    int64_t rows, blocks, R, width;
+    uint64_t space;
+    int L, CH, slabs, has_b;
+};
+
+// PM_EINVAL / PM_ERANGE exactly as the entries document them for (N, D, K, H); K is read by the linear kind alone
+int rx_plan(int kind, int64_t N, int64_t D, int64_t K, int64_t H, RxPlan &p) {
+    if (N < 0 || D < 1 || H < 1) return PM_EINVAL;
+    p.L = 0;
+    p.CH = 1;
+    p.slabs = 0;
+    p.has_b = 1;
+    p.rows = RX_ROWS;
+    p.width = H;
+    if (kind == PM_EXACT_LIN) {
+        if (K < 2 || K > PMX_LIN_MAX_K) return PM_EINVAL;
+        const uint64_t S = pmx_state_count(K, H);
+        if (H > PMX_MAX_H || S == 0) return PM_ERANGE;
+        pmx_lin_split(K, H, p.L, p.CH);
+        if (H - p.L > LIN_MAX_NH) return PM_ERANGE;
+        p.space = S / (uint64_t)p.CH;
+        p.R = rx_ranges(p.space, RX_LIN_MIN_CHUNKS, RX_MAX_RANGES);
+    } else if (kind == PM_EXACT_MCA) {
+        if (H > PMX_MAX_H || D > RX_MCA_MAX_D) return PM_ERANGE;
+        p.rows = RX_MCA_ROWS;
+        p.width = D;
+        p.has_b = 0;
+        p.slabs = (int)((D + 63) / 64);
+        p.space = 1ull << H;
+        p.R = rx_ranges(p.space, RX_MCA_MIN_STATES, RX_MCA_MAX_RANGES);
+    } else if (kind == PM_EXACT_GSC) {
+        if (H > PMX_GSC_MAX_H) return PM_ERANGE;
+        p.space = 1ull << H;
+        p.R = rx_ranges(p.space, RX_GSC_MIN_STATES, RX_MAX_RANGES);
+    } else {
+        return PM_EINVAL;
+    }
+    p.blocks = (N + p.rows - 1) / p.rows;
+    return PM_OK;
+}
+
+// the three parts of `work` for a block of nb rows
+struct RxWork {
+    double *B, *v, *part;
+};
+
+int64_t rx_part_off(int64_t nb, int64_t H, const RxPlan &p) { return (p.has_b ? nb * H : 0) + nb; }
+
+RxWork rx_work(double *work, int64_t nb, int64_t H, const RxPlan &p) {
+    RxWork w;
+    w.B = work;
+    w.part = work + rx_part_off(nb, H, p);
+    w.v = w.part - nb;
+    return w;
+}
+
 }  // namespace
 
 extern "C" int64_t pm_recon_exact_work_len(int64_t N, int64_t H, int64_t D) {
@@ -500,17 +561,34 @@ extern "C" int64_t pm_recon_exact_work_len(int64_t N, int64_t H, int64_t D) {
     return rx_max(rx_max(a, b), 1);
 }
 
+extern "C" int pm_recon_exact_plan(int kind, int64_t N, int64_t D, int64_t K, int64_t H, int64_t *out) {
+    if (!out) return PM_EINVAL;
+    RxPlan p;
+    const int rc = rx_plan(kind, N, D, K, H, p);
+    if (rc) return rc;
+    const int64_t nb = rx_min(N, p.rows);
+    out[0] = p.rows;
+    out[1] = p.blocks;
+    out[2] = p.L;
+    out[3] = p.CH;
+    out[4] = (int64_t)p.space;
+    out[5] = p.R;
+    out[6] = p.slabs;
+    out[7] = rx_part_off(nb, H, p);
+    out[8] = 2 * nb * p.R;
+    out[9] = p.width * nb * p.R;
+    return PM_OK;
+}
+
 extern "C" int pm_recon_exact_lin_f64(const double *Y, int64_t ldy, const double *ymu, const double *P, const double *G,
                                       const double *logp, const double *values, int64_t K, int64_t N, int64_t D, int64_t H,
                                       double *E, int64_t lde, double *work, void *stream) {
     if (N < 0 || D < 1 || H < 1 || K < 2 || K > PMX_LIN_MAX_K || ldy < D || lde < H || !P || !G || !logp || !values || !work ||
         (N > 0 && (!Y || !E)))
         return PM_EINVAL;
-    const uint64_t S = pmx_state_count(K, H);
-    if (H > PMX_MAX_H || S == 0) return PM_ERANGE;
-    int L, CH;
-    pmx_lin_split(K, H, L, CH);
-    if (H - L > LIN_MAX_NH) return PM_ERANGE;
+    RxPlan pl;
+    const int rc = rx_plan(PM_EXACT_LIN, N, D, K, H, pl);
+    if (rc) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     LinArgs a;
     a.G = G;
@@ -518,13 +596,14 @@ extern "C" int pm_recon_exact_lin_f64(const double *Y, int64_t ldy, const double
     a.values = values;
     a.H = (int)H;
     a.K = (int)K;
-    a.L = L;
-    a.CH = CH;
-    a.nchunks = S / (uint64_t)CH;
-    a.R = rx_ranges(a.nchunks, RX_LIN_MIN_CHUNKS, RX_MAX_RANGES);
-    for (int64_t n0 = 0; n0 < N; n0 += RX_ROWS) {
-        const int64_t nb = rx_min(RX_ROWS, N - n0);
-        double *B = work, *v = B + nb * H, *part = v + nb;
+    a.L = pl.L;
+    a.CH = pl.CH;
+    a.nchunks = pl.space;
+    a.R = pl.R;
+    for (int64_t n0 = 0; n0 < N; n0 += pl.rows) {
+        const int64_t nb = rx_min(pl.rows, N - n0);
+        const RxWork w = rx_work(work, nb, H, pl);
+        double *B = w.B, *v = w.v, *part = w.part;
         hipLaunchKernelGGL(rx_prep_kernel, dim3(rx_blocks(nb * H)), dim3(RX_THREADS), 0, st, Y + n0 * ldy, ldy, ymu, nb, D, P,
                            H, B);
         int err = (int)hipGetLastError();
@@ -548,23 +627,26 @@ extern "C" int pm_recon_exact_mca_f64(const double *Y, int64_t ldy, const double
                                       double lp1, double lp0, double inv_s2, int64_t N, int64_t D, int64_t H, double *Yhat,
                                       int64_t ldo, double *work, void *stream) {
     if (N < 0 || D < 1 || H < 1 || ldy < D || ldo < D || !Wrho || !work || (N > 0 && (!Y || !Yhat))) return PM_EINVAL;
-    if (H > PMX_MAX_H || D > RX_MCA_MAX_D) return PM_ERANGE;
+    RxPlan pl;
+    const int rc = rx_plan(PM_EXACT_MCA, N, D, 0, H, pl);
+    if (rc) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     McaArgs a;
     a.ldy = ldy;
     a.Wrho = Wrho;
     a.D = D;
-    a.nstates = 1ull << H;
+    a.nstates = pl.space;
     a.inv_rho = inv_rho;
     a.lp1 = lp1;
     a.lp0 = lp0;
     a.inv_s2 = inv_s2;
     a.H = (int)H;
     a.signed_w = signed_w ? 1 : 0;
-    a.R = rx_ranges(a.nstates, RX_MCA_MIN_STATES, RX_MCA_MAX_RANGES);
-    for (int64_t n0 = 0; n0 < N; n0 += RX_MCA_ROWS) {
-        const int64_t nb = rx_min(RX_MCA_ROWS, N - n0);
-        double *v = work, *part = v + nb;
+    a.R = pl.R;
+    for (int64_t n0 = 0; n0 < N; n0 += pl.rows) {
+        const int64_t nb = rx_min(pl.rows, N - n0);
+        const RxWork w = rx_work(work, nb, H, pl);
+        double *v = w.v, *part = w.part;
         a.Y = Y + n0 * ldy;
         a.v = v;
         a.part = part;
@@ -586,19 +668,22 @@ extern "C" int pm_recon_exact_gsc_f64(const double *Y, int64_t ldy, const double
                                       int64_t lde, double *work, void *stream) {
     if (N < 0 || D < 1 || H < 1 || ldy < D || lde < H || !P || !M || !Psi || !mu || !logp || !work || (N > 0 && (!Y || !E)))
         return PM_EINVAL;
-    if (H > PMX_GSC_MAX_H) return PM_ERANGE;
+    RxPlan pl;
+    const int rc = rx_plan(PM_EXACT_GSC, N, D, 0, H, pl);
+    if (rc) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     GscArgs a;
     a.M = M;
     a.Psi = Psi;
     a.mu = mu;
     a.logp = logp;
-    a.nstates = 1ull << H;
+    a.nstates = pl.space;
     a.H = (int)H;
-    a.R = rx_ranges(a.nstates, RX_GSC_MIN_STATES, RX_MAX_RANGES);
-    for (int64_t n0 = 0; n0 < N; n0 += RX_ROWS) {
-        const int64_t nb = rx_min(RX_ROWS, N - n0);
-        double *B = work, *v = B + nb * H, *part = v + nb;
+    a.R = pl.R;
+    for (int64_t n0 = 0; n0 < N; n0 += pl.rows) {
+        const int64_t nb = rx_min(pl.rows, N - n0);
+        const RxWork w = rx_work(work, nb, H, pl);
+        double *B = w.B, *v = w.v, *part = w.part;
         hipLaunchKernelGGL(rx_prep_kernel, dim3(rx_blocks(nb * H)), dim3(RX_THREADS), 0, st, Y + n0 * ldy, ldy,
                            (const double *)nullptr, nb, D, P, H, B);
         int err = (int)hipGetLastError();
