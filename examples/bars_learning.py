@@ -107,6 +107,10 @@ def main():
                     help="with --heldout --reconstruct: M posterior draws of the noiseless data per datapoint (sample_posterior, "
                     "DESIGN 4.20): the mean squared error of their mean beside the reconstruction's, and the share of clean "
                     "pixels inside the draws' [5 %%, 95 %%] range")
+    ap.add_argument("--encode", action="store_true",
+                    help="with --heldout: the codes of the held-out datapoints under the learned parameters (encode, DESIGN "
+                    "4.23): the mean number of active latents per datapoint, sum_h P(s_h != 0 | y_n), beside the generating "
+                    "pi H; with --exact (BSC, MCA, MMCA, the mixtures) also the largest |prob_truncated - prob_exact|")
     a = ap.parse_args()
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         import torch
@@ -168,6 +172,26 @@ def main():
             if comm.rank == 0:
                 print("held-out log-likelihood per datapoint of the learned parameters: truncated bound %.6f, exact %.6f, "
                       "difference %.3e" % (learned, exact, exact - learned))
+        if a.encode:
+            # which causes each held-out datapoint contains: the posterior activation probabilities over the wider truncated
+            # state set --reconstruct uses (H' = 7, gamma = 5), summed over the latents -- the generator activates pi H of them
+            emodel = model if a.model in ("mog", "mop") else build(a.model, a.size, min(H, 7), min(H, 5), comm)[0]
+            _, prob = emodel.encode(dict(em.lparams), heldout)
+            if a.model in ("mog", "mop"):
+                active = 1.0
+            elif a.model == "dsc":
+                active = float(H * (1.0 - np.asarray(gt['pi'])[1]))
+            else:
+                active = float(np.broadcast_to(np.asarray(gt['pi'], dtype=np.float64), (H,)).sum())
+            tot = comm.allreduce(np.array([float(prob.sum()), float(prob.shape[0])]))
+            if comm.rank == 0:
+                print("held-out codes (%d datapoints): mean number of active latents sum_h P(s_h != 0 | y) %.4f, generating "
+                      "pi H %.4f" % (a.heldout, tot[0] / tot[1], active))
+            if a.exact and a.model in ("bsc", "mca", "mmca", "mog", "mop"):
+                _, exact_prob = emodel.encode(dict(em.lparams), heldout, exact=True)
+                worst = max(comm.allgather(float(np.abs(prob - exact_prob).max()) if prob.size else 0.0))
+                if comm.rank == 0:
+                    print("held-out codes: largest |prob_truncated - prob_exact| %.3e" % worst)
         if a.reconstruct:
             y = np.asarray(heldout['y'], dtype=np.float64)
             sq = lambda x: float(((np.asarray(x) - clean) ** 2).sum())

@@ -1213,6 +1213,37 @@ int pm_recon_mca_var_f64(const double *logpj, int64_t ld, const double *lse, con
                          int64_t S, double *V, int64_t ldv, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Latent codes (encode_kernels.hip)
+ * ---------------------------------------------------------------------------------------
+ * mean[n, h] = sum_s q_n(s) s_h and prob[n, h] = sum_s q_n(s) [s_h != 0] under the weights of the reconstruction entries
+ * above, over exactly the states of logpj (pm_encode_f64) or over the whole state space (pm_encode_exact_mca_f64).  No atomics
+ * and no branch on the build: every output element is written once by one lane and every sum runs in an order fixed by the
+ * shape alone, so both builds return the same bits and a row's bits depend on that row alone.  Every entry checks its
+ * arguments before it touches a device (PM_EINVAL: null pointer, negative size, short leading dimension, inconsistent
+ * layout; PM_ERANGE: past a limit); N == 0 launches nothing.
+ *
+ * pm_encode_f64: logpj, ld, lse, a, col_offset, cand, state_vals, block_values_host, N, H, Hprime, K, single_off, nblocks,
+ * multi_off, S exactly as pm_recon_expect_f64; the row is read and every column's weight evaluated once for both outputs.
+ * mean (N, ldm >= H): the bits pm_recon_expect_f64 writes into out[:, :H] for the same arguments (same order, same fma's; a
+ * latent held by two candidate positions (TSC) receives both) -- except in a row whose log-sum-exp is NaN, which is NaN at
+ * EVERY latent of both outputs, also where no column gives the latent a value and that entry writes 0.  prob (N, ldp >= H): sum_c q(block c, h) over the blocks of
+ * non-zero value + the weights of the table states in which ANY position that holds h is non-zero -- a state counts once per
+ * latent, so prob <= 1 --, returned as min(p, 1); a NaN stays NaN.  With one block of value 1 and a 0/1 table prob carries the
+ * bits of mean (below the clamp).  With single_off = 0, nblocks = 1, the value 1 and S = 0 both are the row softmax of a X + o.
+ * Hprime <= PM_MAX_HPRIME, nblocks <= 8. */
+int pm_encode_f64(const double *logpj, int64_t ld, const double *lse, double a, const double *col_offset, const int32_t *cand,
+                  const double *state_vals, const double *block_values_host, int64_t N, int64_t H, int64_t Hprime, int64_t K,
+                  int64_t single_off, int64_t nblocks, int64_t multi_off, int64_t S, double *mean, int64_t ldm, double *prob,
+                  int64_t ldp, void *stream);
+/* MCA (signed_w = 0) and MMCA (signed_w = 1): E (N x H, row stride lde >= H) receives E_n[s]_h = sum_{all s} q_n(s) s_h, the
+ * posterior activation probabilities over all 2^H states; model, arguments, sweeps, row blocks and ranges of
+ * pm_recon_exact_mca_f64 (R from pm_recon_exact_plan: a function of the state count alone; partials merged in range order).
+ * `work`: pm_recon_exact_work_len(N, H, D) doubles.  PM_ERANGE for H > 32 or D > 1024.  Columns of E past H are not written. */
+int pm_encode_exact_mca_f64(const double *Y, int64_t ldy, const double *Wrho, double inv_rho, int signed_w, double lp1,
+                            double lp0, double inv_s2, int64_t N, int64_t D, int64_t H, double *E, int64_t lde, double *work,
+                            void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Whole-image denoising by overlapping patches (patch_kernels.hip)
  * ---------------------------------------------------------------------------------------
  * The patch grid.  Along an axis of length L, patches of length p at stride s >= 1 start at 0, s, 2s, ... while start + p <=

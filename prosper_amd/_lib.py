@@ -211,6 +211,10 @@ SIGNATURES = {
     "pm_recon_var_finish_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, c_dp, i64, c_dp, c_dp, i64, i64, i64, i64, i64, c_dp]),
     "pm_recon_mca_var_f64": (C.c_int, [c_dp, i64, c_dp, c_dp, c_dp, c_dp, C.c_double, C.c_int, i64, i64, i64, i64, i64, c_dp,
                                        i64, c_dp]),
+    "pm_encode_f64": (C.c_int, [c_dp, i64, c_dp, C.c_double, c_dp, c_dp, c_dp, c_dp, i64, i64, i64, i64, i64, i64, i64, i64,
+                                c_dp, i64, c_dp, i64, c_dp]),
+    "pm_encode_exact_mca_f64": (C.c_int, [c_dp, i64, c_dp, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, i64, i64,
+                                          i64, c_dp, i64, c_dp, c_dp]),
     "pm_masked_prepare_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, i64, i64, c_dp, i64, c_dp, i64, c_dp, c_dp, c_dp]),
     "pm_bsc_masked_estep_f64": (C.c_int, [c_dp, i64, c_dp, i64, c_dp, c_dp, i64, c_dp, i64, c_dp, i64,
                                           C.POINTER(EStepParams), i64, i64, i64, i64, c_dp, c_dp, i64, c_dp]),
@@ -256,7 +260,7 @@ class HipError(RuntimeError):
     pass
 
 
-MIN_VERSION = 1031
+MIN_VERSION = 1032
 _lib = None
 _lib_det = None
 LIB_PATH_DET = os.path.join(os.path.dirname(LIB_PATH), "libprosper_hip_det.so")

@@ -1285,6 +1285,131 @@ class DeviceCAModel(CAModel):
             self._par = {}
             self._eval_end(saved)
 
+    # ---- latent codes -------------------------------------------------------------------------------------
+    _binary_latents = False           # BSC, MCA, MMCA: s_h in {0, 1} -- prob is min(mean, 1), and ``encode(exact=True)`` is built
+
+    def _encode_from(self, lp, N, cand, lay):
+        """(mean, prob), two (N, H) device tensors, by pm_encode_f64 from the log-joints ``lp``, the candidates and the layout
+        (``_recon_layout``) that ``reconstruct`` reads; ``lay['encode_table']`` is the table of a model whose reconstruction
+        needs none (MCA / MMCA)."""
+        H = self.H
+        K = lp.shape[1]
+        table = lay.get("encode_table", lay.get("table"))
+        blocks = lay["blocks"]
+        S = 0 if table is None else int(table.shape[0])
+        tab_d = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float64)).to(self.device) if S else None
+        bv = (ctypes.c_double * 8)(*([float(v) for v in blocks] + [0.0] * (8 - len(blocks))))
+        ld = lp.stride(0) if N > 1 else max(int(lp.stride(0)), K)
+        mean = torch.empty((N, H), dtype=torch.float64, device=self.device)
+        prob = torch.empty((N, H), dtype=torch.float64, device=self.device)
+        self._call("encode", "pm_encode_f64", _ptr(lp), ld, None, ctypes.c_double(1.0), None, _ptr(cand) if S else None,
+                   _ptr(tab_d), bv, N, H, self.Hprime if S else 0, K, lay["soff"], len(blocks), lay["moff"], S, _ptr(mean), H,
+                   _ptr(prob), H, self._stream())
+        return mean, prob
+
+    def _encode(self, model_params, my_data, N):
+        """``encode`` for the models whose E-step leaves (N, K) log-joints: the selection and T = 1 E-step of
+        ``_reconstruct``, then ``_encode_from``."""
+        lay = self._recon_layout(model_params)
+        mp = lay["params"]
+        data = self.select_Hprimes(mp, my_data)
+        lp = self.E_step(LoglikPoint(), mp, data)['logpj'].tensor
+        cand = self._device_candidates(data['candidates'], N)
+        return self._encode_from(lp, N, cand, lay)
+
+    def _encode_masked(self, model_params, y, obs, N):
+        """``_encode`` from the masked or weighted E-step's log-joints, which keep the unmasked layout."""
+        out = self._obs_estep(model_params, y, obs)
+        return self._encode_from(out["logpj"], N, out["cand"], out["lay"])
+
+    def _encode_exact(self, model_params, y, N):
+        """``encode(exact=True)`` of the binary models from the ``_loglik_exact`` hook: E[s] over all 2^H states by
+        pm_recon_exact_lin_f64 (BSC) or pm_encode_exact_mca_f64 (MCA / MMCA); prob = min(E[s], 1)."""
+        D, H = self.D, self.H
+        kind, arrays, sc = self._loglik_exact(model_params)
+        dev = {k: (torch.from_numpy(np.array(v, dtype=np.float64, order="C")).to(self.device) if v is not None else None)
+               for k, v in arrays.items()}
+        dbl = ctypes.c_double
+
+        def entry(call, Yp, ld, n, out, work):
+            if kind == "lin":
+                call("pm_recon_exact_lin_f64", Yp, ld, _ptr(dev.get("mu")), _ptr(dev["P"]), _ptr(dev["G"]), _ptr(dev["logp"]),
+                     _ptr(dev["values"]), int(arrays["values"].shape[0]), n, D, H, out, H, work, self._stream())
+            else:
+                call("pm_encode_exact_mca_f64", Yp, ld, _ptr(dev["Wrho"]), dbl(sc["inv_rho"]), int(sc["signed"]),
+                     dbl(sc["lp1"]), dbl(sc["lp0"]), dbl(sc["inv_s2"]), n, D, H, out, H, work, self._stream())
+
+        # (the limits first, as ``_reconstruct_exact``: with no rows the entry checks its arguments and returns)
+        probe = torch.empty(1, dtype=torch.float64, device=self.device)
+        entry(lambda name, *a: _lib.call(name, *a, det=self.deterministic), None, D, 0, None, _ptr(probe))
+        Y = self._resident(y)["Y"]
+        lib = _lib.load(self.deterministic)
+        work = torch.empty(max(int(lib.pm_recon_exact_work_len(N, H, D)), 1), dtype=torch.float64, device=self.device)
+        mean = torch.empty((N, H), dtype=torch.float64, device=self.device)
+        entry(lambda name, *a: self._call("encode_exact", name, *a), _ptr(Y), max(int(Y.stride(0)), D), N, _ptr(mean),
+              _ptr(work))
+        return mean, torch.clamp(mean, max=1.0)
+
+    def _encode_admit(self, exact):
+        """The refusals of ``encode`` that depend on the model alone, before any device call."""
+        if exact and not self._binary_latents:
+            raise NotImplementedError("%s.encode: exact=True is not built for this model (the enumeration kernels of DSC, TSC "
+                                      "and GSC carry no indicator sums); BSC_ET, MCA_ET and MMCA_ET have it"
+                                      % type(self).__name__)
+        if not exact and self.Hprime > 16:
+            raise _lib.HipError("%s.encode holds H' <= 16 candidates (pm_encode_f64), got %d"
+                                % (type(self).__name__, self.Hprime))
+
+    def encode(self, model_params, my_data, device=False, exact=False):
+        """The code of every datapoint of ``my_data['y']`` (host array, torch tensor or DeviceArray): ``(mean, prob)``, both
+        (my_N, H) float64 -- mean[n, h] = sum_{s in K_n} q_n(s) s_h = E[s_h | y_n] and prob[n, h] = sum_{s in K_n} q_n(s) [s_h
+        != 0] = P(s_h != 0 | y_n).  K_n and q_n are exactly those of ``reconstruct`` and ``log_likelihood``: the states the
+        E-step scores for y_n, weighted by the full generative joint at T = 1; no weight is dropped or thresholded.  At H' =
+        gamma = H these are the exact posterior marginals.  BSC, MCA, MMCA: the latents are binary and prob = min(mean, 1).
+        DSC, TSC: mean carries the latent values, prob the non-zero indicator.  A TSC row whose candidates repeat a latent
+        (tsc_et.py:142-213) holds pseudo-states: mean counts the latent at both positions, as ``reconstruct`` does; prob counts
+        a state once for a latent if any position holding it is non-zero, so prob <= 1 always.  GSC: mean = E[s_h z_h | y_n]
+        and prob = E[s_h | y_n], the moments of the doubled-logit pass ``reconstruct`` runs (weights floored at DBL_MIN as
+        there).
+
+        Returns NumPy arrays, or with ``device=True`` two ``DeviceArray`` left on the device; there is no collective.  A NaN
+        in a data row makes that row of both outputs NaN and no other.  A row's bits depend on that row (and its row of the
+        mask or weight) and the parameters alone: the same from both libraries, under a row permutation, in a shard and on
+        a second call.  ``model_params``, the training shard's residency, the records the last M-step left and Hprime / gamma
+        stay as they were: a call between two EM steps does not change the training trajectory.  Runs the E-step kernels and
+        pm_encode_f64 on the device.
+
+        ``my_data['mask']`` / ``my_data['weight']`` (BSC, MCA and MMCA): the codes are conditioned on the
+        observed entries; whatever an unobserved or zero-weight entry holds changes no bit.  The refusals are those
+        ``reconstruct`` documents, raised before any launch.
+
+        ``exact=True`` (BSC, MCA, MMCA): the marginals over the model's WHOLE state space by enumeration on the device
+        (pm_recon_exact_lin_f64, pm_encode_exact_mca_f64), within the limits of ``reconstruct(exact=True)``
+        (``HipError`` past them).  DSC, TSC and GSC raise ``NotImplementedError``, and so does a mask or weight with it."""
+        y = my_data['y']
+        N = int(y.shape[0])
+        obs = self._observation(my_data)
+        if obs is not None:
+            self._masked_admit(y, obs[1], exact, what="encode", key=obs[0])
+        self._encode_admit(exact)
+        if N == 0:
+            empty = lambda: DeviceArray(torch.empty((0, self.H), dtype=torch.float64, device=self.device)) if device \
+                else np.empty((0, self.H))
+            return empty(), empty()
+        saved = self._eval_begin()
+        try:
+            self._par, self._rows_gemm = {}, True
+            if obs is not None:
+                pair = self._encode_masked(dict(model_params), y, obs, N)
+            elif exact:
+                pair = self._encode_exact(dict(model_params), y, N)
+            else:
+                pair = self._encode(dict(model_params), {'y': y}, N)
+            return tuple(DeviceArray(t) if device else t.cpu().numpy() for t in pair)
+        finally:
+            self._par = {}
+            self._eval_end(saved)
+
     # ---- posterior draws (DESIGN 4.20) ----------------------------------------------------------------------------------
     sample_chunk_bytes = 1 << 26      # bound of the workspace beside the result (indices and active lists of one row chunk)
     sample_chunk_rows = None          # rows per chunk when set (tests): the draws do not depend on it

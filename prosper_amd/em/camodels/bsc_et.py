@@ -633,6 +633,8 @@ class BSC_ET(DeviceCAModel):
         c = self.H * np.log(1. - pies) - 0.5 * self.D * np.log(2 * _PI * sigma ** 2)
         return self._loglik_estep(model_params, my_data), 1.0, c
 
+    _binary_latents = True            # (encode)
+
     def _recon_layout(self, model_params):
         """reconstruct: columns [null ; H one-cause states ; S multi-cause states over the candidates], binary
         latents, ybar(s) = mu + W s (mu when the parameters carry it).  The log-joints come from the general E-step kernels

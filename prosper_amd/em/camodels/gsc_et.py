@@ -570,6 +570,21 @@ class GSC(DeviceCAModel):
             return out, self._recon_variance_gsc(model_params, res, cand, out, N)
         return out
 
+    def _encode(self, model_params, my_data, N):
+        """encode: mean = E[s_h z_h | y_n] (xpt_sz) and prob = E[s_h | y_n] (xpt_s) of the pass ``_reconstruct``
+        runs -- beta = 1/2, every logit doubled, every state's weight floored at DBL_MIN as there --, returned as copies: the
+        pass's two output buffers alternate.  prob is clamped at 1 (rounding).  A noise covariance that is not positive
+        definite: every row NaN."""
+        sig = np.asarray(model_params['sigma_sq'], dtype=np.float64)
+        if (np.linalg.eigvalsh(0.5 * (sig + sig.T)).min() <= 0) if sig.ndim == 2 else not np.all(sig > 0):
+            nan = lambda: torch.full((N, self.H), float("nan"), dtype=torch.float64, device=self.device)
+            return nan(), nan()
+        self._lpi_scale = 2.0          # (an attribute of the evaluation only: _eval_end restores the model's)
+        self._require_scalar()
+        res = self._resident(my_data['y'])
+        _, xs, xsz, _ = self._run(2.0, model_params, res, None)
+        return xsz.clone(memory_format=torch.contiguous_format), torch.clamp(xs, max=1.0).contiguous()
+
     def _recon_variance_gsc(self, model_params, res, cand, Yhat, N):
         """V of ``reconstruct(variance=True)``: V_nd = sum_s q_n(s) (W_s (kappa_s kappa_s^T + Lambda_s^-1) W_s^T)_dd -
         yhat_nd^2, the variance over s and z | s, y_n.  A second E-step pass on the candidates of the first (handed in, so the

@@ -263,6 +263,7 @@ class MCA_ET(DeviceCAModel):
         return self._loglik_estep(model_params, my_data), 1.0, c
 
     _recon_var_max_D = 1024
+    _binary_latents = True            # (encode)
 
     def _recon_layout(self, model_params):
         """reconstruct: the mean of ``_loglik_terms``' model -- W_h for a one-cause state (the E-step's energy
@@ -271,7 +272,9 @@ class MCA_ET(DeviceCAModel):
         model_params['W'] = np.array(model_params['W'], dtype=np.float64, copy=True)
         model_params = self.check_params(model_params)
         return {"params": model_params, "blocks": (1.0,), "soff": 1, "moff": 1 + self.H, "table": None,
-                "W": model_params['W'], "mu": None, "mca": True}
+                "W": model_params['W'], "mu": None, "mca": True,
+                # (encode, DESIGN 4.23: which candidate positions a multi-cause state holds -- the mean above has no use for it)
+                "encode_table": self.state_matrix if self.no_states else None}
 
     def _masked_select(self, res, M, ldm, par, A, wn, xn2):
         """Masked selection: the H' smallest R[n,h] = sum_d m_d max(W_hd - y_d, 0), ranked as ``_select_on_device`` does."""

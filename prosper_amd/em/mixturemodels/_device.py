@@ -260,6 +260,40 @@ class DeviceMixture(object):
             self.__dict__.update(saved)
             self._eval_slot = slot
 
+    # ---- latent codes -----------------------------------------------------------------------------------
+    def encode(self, model_params, my_data, device=False, exact=False):
+        """The code of every datapoint: ``(mean, prob)``, both (my_N, H) float64 and both the responsibilities r_nh = pies_h
+        p(y_n | h) / sum_h' pies_h' p(y_n | h') that ``reconstruct`` averages with (the proper densities of
+        ``log_likelihood``, from the same scores): the latent of a mixture is one-hot, so E[s_h | y_n] = P(s_h != 0 | y_n).
+        NumPy arrays, or with ``device=True`` two ``DeviceArray`` left on the device; no collective.  A NaN in a data row
+        makes that row NaN and no other; ``model_params`` and the training shard are left as they were.  ``exact`` is
+        accepted for the component-analysis models' signature and returns the same bits; ``my_data['mask']`` and
+        ``my_data['weight']`` are refused.  One launch of pm_encode_f64 (a row softmax in a maximum and a sum pass)."""
+        self._refuse_mask(my_data)
+        y = my_data['y']
+        N, H = int(y.shape[0]), self.H
+        if N == 0:
+            empty = lambda: DeviceArray(torch.empty((0, H), dtype=torch.float64, device=self.device)) if device \
+                else np.empty((0, H))
+            return empty(), empty()
+        saved = dict(self.__dict__)
+        slot = saved.get("_eval_slot") or {"_data": {}, "_ws": {}}
+        self._data, self._ws = slot["_data"], slot["_ws"]
+        try:
+            res = self._resident(y)
+            X, a, off_d = self._recon_scores(dict(model_params), res)
+            mean = torch.empty((N, H), dtype=torch.float64, device=self.device)
+            prob = torch.empty((N, H), dtype=torch.float64, device=self.device)
+            one = (ctypes.c_double * 8)(1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+            _lib.call("pm_encode_f64", _ptr(X), H, None, ctypes.c_double(a), _ptr(off_d), None, None, one, N, H, 0, H, 0, 1,
+                      0, 0, _ptr(mean), H, _ptr(prob), H, self._stream())
+            return (DeviceArray(mean), DeviceArray(prob)) if device else (mean.cpu().numpy(), prob.cpu().numpy())
+        finally:
+            slot = {"_data": self._data, "_ws": self._ws}
+            self.__dict__.clear()
+            self.__dict__.update(saved)
+            self._eval_slot = slot
+
     # ---- posterior draws (DESIGN 4.20) --------------------------------------------------------------------------------
     sample_chunk_bytes = 1 << 26      # bound of the workspace beside the result (indices and lists of one row chunk)
     sample_chunk_rows = None          # rows per chunk when set (tests): the draws do not depend on it
