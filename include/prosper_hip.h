@@ -1315,6 +1315,39 @@ int pm_patches_finish_w_f64(const double *num, const double *den, int64_t lda, d
                             int64_t Hi, int64_t Wi, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Pooled feature maps of an image's patch codes (pool_kernels.hip)
+ * ---------------------------------------------------------------------------------------
+ * The codes of the N = B nr nc patches of an image stack (numbered as above: row-major over image, start row, start column)
+ * are an (N, H) matrix, row stride ldc >= H: H channels on the patch grid (B, nr, nc).  Pooling reduces the grid to (B, gh,
+ * gw) regions.  The region rule: region i of an axis of n patch positions cut into g regions is [floor(i n / g), floor((i +
+ * 1) n / g)), 1 <= g <= n -- ascending, never empty, lengths differing by at most 1.  Output (b, i, j, h) covers the patches
+ * of image b whose start-row index lies in region i of (nr, gh) and whose start-column index lies in region j of (nc, gw).
+ *
+ * pm_codes_pool_f64 works on the rows [n0, n0 + n) of the matrix, handed over as the pointer to row n0; n0 and n are
+ * multiples of nc (whole patch rows R = b nr + r).  acc (B, gh, gw, H), contiguous, is a running result the caller fills once:
+ * with +0 for mode 0 (sum), with -inf for mode 1 (max).
+ *   mode 0: acc[b, i, j, h] <- acc + t_R for the patch rows R of image b in region row i that lie in the range, in ascending R,
+ *           one addition at a time, with t_R = (((+0 + x[R, c0, h]) + x[R, c0 + 1, h]) + ...) over the columns [c0, c1) of
+ *           region column j in ascending order: a sum over rows of sums over columns, both ascending.
+ *   mode 1: the same walk with the larger of the two in place of the sum and -inf in place of +0, by explicit compares: a NaN
+ *           input makes that output NaN, and of -0 and +0 the larger is +0, so the order changes no bit.
+ * t_R depends on patch row R alone, so called with ascending, disjoint ranges that together cover [0, N) the sequence of
+ * operations of an output -- and its bits -- is the same for every split into ranges.  Two launches: the partials t of the
+ * range into `work` (pm_codes_pool_work_len(n, nc, gw, H) = (n / nc) gw H doubles; -1 for arguments the entry refuses), then
+ * every output, owned by one lane, walks its partials.  h runs on the lanes; with H < 64 a wavefront holds several (patch
+ * row, region column) pairs.  No atomics and no branch on the build: both libraries return the same bits.
+ * pm_codes_pool_finish_f64: out[b, i, j, h] = acc[b, i, j, h] / (rows of region i x columns of region j), one IEEE division
+ * (the mean; the count is exact in a double up to 2^53); out may be acc.
+ * Every entry checks its arguments before it touches a device: PM_EINVAL for a null pointer, B, nr, nc, gh, gw or H < 1, gh >
+ * nr, gw > nc, ldc < H, a mode other than 0 or 1, n0 < 0, n < 0, n0 + n > B nr nc, n0 or n not a multiple of nc; PM_ERANGE for
+ * nr or nc > 2^30 or H > 2^20.  n == 0 launches nothing. */
+int64_t pm_codes_pool_work_len(int64_t n, int64_t nc, int64_t gw, int64_t H);
+int pm_codes_pool_f64(const double *codes, int64_t ldc, int64_t n0, int64_t n, int64_t B, int64_t nr, int64_t nc, int64_t gh,
+                      int64_t gw, int64_t H, int mode, double *acc, double *work, void *stream);
+int pm_codes_pool_finish_f64(const double *acc, double *out, int64_t B, int64_t nr, int64_t nc, int64_t gh, int64_t gw,
+                             int64_t H, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Missing values: masked E-steps for inference (masked_kernels.hip)
  * ---------------------------------------------------------------------------------------
  * mask (N, ldm >= D) bytes, non-zero = observed.  An unobserved value is selected away where it is read (m ? v : 0), never

@@ -243,6 +243,9 @@ SIGNATURES = {
     "pm_patches_accumulate_w_f64": (C.c_int, [c_dp, i64, c_dp, i64, C.c_int, C.c_double, c_dp, c_dp, i64, i64, c_dp, c_dp, i64,
                                               i64, i64, i64, i64, i64, i64, c_dp]),
     "pm_patches_finish_w_f64": (C.c_int, [c_dp, c_dp, i64, c_dp, i64, i64, i64, i64, c_dp]),
+    "pm_codes_pool_work_len": (i64, [i64, i64, i64, i64]),
+    "pm_codes_pool_f64": (C.c_int, [c_dp, i64, i64, i64, i64, i64, i64, i64, i64, i64, C.c_int, c_dp, c_dp, c_dp]),
+    "pm_codes_pool_finish_f64": (C.c_int, [c_dp, c_dp, i64, i64, i64, i64, i64, i64, c_dp]),
     "pm_sample_states_max_cols": (i64, []),
     "pm_sample_states_f64": (C.c_int, [c_dp, i64, c_dp, C.c_double, c_dp, C.c_double, i64, c_dp, i64, i64, i64, i64, c_dp,
                                        c_dp]),
@@ -260,7 +263,7 @@ class HipError(RuntimeError):
     pass
 
 
-MIN_VERSION = 1032
+MIN_VERSION = 1033
 _lib = None
 _lib_det = None
 LIB_PATH_DET = os.path.join(os.path.dirname(LIB_PATH), "libprosper_hip_det.so")

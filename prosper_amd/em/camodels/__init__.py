@@ -136,6 +136,18 @@ class CAModel(Model):
         from ...utils.patches import denoise_image
         return denoise_image(self, model_params, image, mask=mask, weight=weight, **kw)
 
+    def encode_image(self, model_params, image, mask=None, weight=None, **kw):
+        """Feature maps of a whole image: ``utils.patches.encode_image(self, model_params, image, **kw)`` --
+        every patch through ``encode()``; returns ``(mean, prob)`` as H channels on the patch grid, (B, nr, nc, H) or (nr, nc,
+        H) for a 2-D image.  Keywords: ``patch``, ``stride``, ``center``, ``chunk``, ``device``, ``exact`` (every patch through
+        ``encode(exact=True)``), ``pool`` ((gh, gw) or an int: both results pooled over a gh x gw grid of regions of the patch
+        grid into (B, gh, gw, H), a fixed-length feature vector per image) and ``reduce`` (``'mean'``, ``'sum'`` or
+        ``'max'``).  ``mask`` (the image's shape, non-zero = observed pixel) and ``weight`` (the image's shape,
+        finite and >= 0): the patches go through the masked / weighted ``encode()`` (BSC, MCA, MMCA).  The bits
+        do not depend on ``chunk``."""
+        from ...utils.patches import encode_image
+        return encode_image(self, model_params, image, mask=mask, weight=weight, **kw)
+
     def compute_lpj(self, anneal, model_params, my_data):
         """Candidates + log-pseudo-joints for ``my_data['y']`` (upstream :238-253)."""
         assert 'y' in my_data, "Key 'y' in my_data dict not defined."

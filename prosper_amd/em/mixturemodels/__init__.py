@@ -74,6 +74,18 @@ class MixtureModel(Model):
         from ...utils.patches import denoise_image
         return denoise_image(self, model_params, image, mask=mask, weight=weight, **kw)
 
+    def encode_image(self, model_params, image, mask=None, weight=None, **kw):
+        """Feature maps of a whole image: ``utils.patches.encode_image(self, model_params, image, **kw)`` --
+        every patch through ``encode()``; returns ``(mean, prob)``, both the responsibilities, as H channels on the patch
+        grid, (B, nr, nc, H) or (nr, nc, H) for a 2-D image.  Keywords: ``patch``, ``stride``, ``center``, ``chunk``,
+        ``device``, ``exact`` (passed on; the responsibilities are exact already), ``pool`` ((gh, gw) or an int: both results
+        pooled over a gh x gw grid of regions of the patch grid into (B, gh, gw, H), a fixed-length feature vector per image)
+        and ``reduce`` (``'mean'``, ``'sum'`` or ``'max'``).  ``mask`` and ``weight`` (the image's shape)
+        reach ``encode()``, which refuses them for the mixture models by name before any launch.  The bits do not depend on
+        ``chunk``."""
+        from ...utils.patches import encode_image
+        return encode_image(self, model_params, image, mask=mask, weight=weight, **kw)
+
     def sample_posterior(self, model_params, my_data, n_samples=1, seed=None, latents=False, device=False, uniforms=None,
                          normals=None):
         """Posterior draws of the noiseless data: ``Ys`` (n_samples, my_N, D) float64, Ys[m, n] = W_h with h ~

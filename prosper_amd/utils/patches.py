@@ -7,7 +7,10 @@ The patch grid (one rule, used everywhere): along an axis of length L, patches o
 2s, ... while start + p <= L, plus at L - p if the last of these is not L - p: every pixel is covered for every stride
 s <= p (a larger stride would leave gaps between the regular starts and is refused where an image is cut).  Patches are
 numbered row-major over (image, start row, start column); inside a patch the D = p_h p_w values are row-major, (a, b) ->
-a p_w + b."""
+a p_w + b.
+
+Feature maps: ``encode_image`` runs every patch through a model's ``encode()`` instead and returns the codes as
+H channels on the patch grid, or pooled over a coarse grid of regions (``pool_regions``, ``pool_codes``; pm_codes_pool_*)."""
 import ctypes
 
 import numpy as np
@@ -452,3 +455,207 @@ def denoise_image(model, model_params, image, patch=None, stride=1, center=False
     if variance:
         return out, _hand_back(_finish(vacc, geo, det), len(shape) == 2, device)
     return out
+
+
+# ---- pooled feature maps of an image's patch codes ------------------------------------------------------------
+REDUCES = ("mean", "sum", "max")
+
+
+def pool_regions(n, g):
+    """The ``g`` regions of an axis of ``n`` patch positions, as a list of ``(start, stop)``: region i is [floor(i n / g),
+    floor((i + 1) n / g)) -- ascending, never empty, lengths differing by at most 1.  ``ValueError`` unless 1 <= g <= n.  The
+    one region rule: pm_codes_pool_f64 (include/prosper_hip.h) and the tests' reference cut the same way."""
+    if int(n) != n or int(g) != g or not 1 <= int(g) <= int(n):
+        raise ValueError("an axis of %r patch positions is cut into 1 <= g <= n regions, got g = %r" % (n, g))
+    n, g = int(n), int(g)
+    return [(i * n // g, (i + 1) * n // g) for i in range(g)]
+
+
+def _pool_pair(pool, nr, nc):
+    """(gh, gw) of ``pool`` (an int g meaning (g, g), or a pair) on an (nr, nc) patch grid, or ValueError."""
+    if isinstance(pool, (tuple, list, np.ndarray)):
+        if len(pool) != 2:
+            raise ValueError("pool is an int or a pair (gh, gw), got %r" % (pool,))
+        gh, gw = pool
+    else:
+        gh = gw = pool
+    try:
+        ok = int(gh) == gh and int(gw) == gw
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or int(gh) < 1 or int(gw) < 1:
+        raise ValueError("pool is an int or a pair (gh, gw) of integers >= 1, got %r" % (pool,))
+    if int(gh) > nr or int(gw) > nc:
+        raise ValueError("pool=(%d, %d) has more regions than the (%d, %d) patch grid has positions" % (gh, gw, nr, nc))
+    return int(gh), int(gw)
+
+
+def _reduce_check(reduce):
+    if not isinstance(reduce, str) or reduce not in REDUCES:
+        raise ValueError("reduce is 'mean', 'sum' or 'max', got %r" % (reduce,))
+
+
+def _pool_begin(grid, pool, H, reduce, dev):
+    """The running result (B, gh, gw, H) of pm_codes_pool_f64: +0 for a sum, -inf for a maximum."""
+    return torch.full((grid[0], pool[0], pool[1], H), float("-inf") if reduce == 'max' else 0.0, dtype=torch.float64,
+                      device=dev)
+
+
+def _pool_work(rows, nc, gw, H, dev):
+    """The scratch of pm_codes_pool_f64 for ranges of at most ``rows`` patch rows."""
+    return torch.empty(max(int(_lib.load().pm_codes_pool_work_len(rows * nc, nc, gw, H)), 1), dtype=torch.float64, device=dev)
+
+
+def _pool(acc, codes, ldc, grid, pool, n0, n, reduce, work, det):
+    (B, nr, nc), (gh, gw) = grid, pool
+    _lib.call("pm_codes_pool_f64", _ptr(codes), ldc, n0, n, B, nr, nc, gh, gw, acc.shape[3], int(reduce == 'max'), _ptr(acc),
+              _ptr(work), _stream(acc.device), det=det)
+
+
+def _pool_finish(acc, grid, pool, reduce, det):
+    """The mean's one division per output, in place; a sum or a maximum is the running result itself."""
+    if reduce == 'mean':
+        (B, nr, nc), (gh, gw) = grid, pool
+        _lib.call("pm_codes_pool_finish_f64", _ptr(acc), _ptr(acc), B, nr, nc, gh, gw, acc.shape[3], _stream(acc.device),
+                  det=det)
+    return acc
+
+
+def pool_codes(codes, grid, pool, reduce='mean', device=False):
+    """Pool the (N, H) ``codes`` (NumPy, torch or ``DeviceArray``) of the patches of a grid ``(B, nr, nc)``, N = B nr nc,
+    numbered as the module docstring says, over ``pool = (gh, gw)`` regions (an int g: (g, g)): the (B, gh, gw, H) float64
+    array whose entry (b, i, j, h) reduces channel h over the patches of image b with start-row index in
+    ``pool_regions(nr, gh)[i]`` and start-column index in ``pool_regions(nc, gw)[j]``.  The aggregation of ``encode_image`` on
+    its own, as ``average_patches`` is that of ``denoise_image``.
+
+    ``reduce``: ``'sum'`` -- per patch row the region's columns are added one at a time in ascending order starting from +0,
+    and the patch rows' sums are added one at a time in ascending order (pm_codes_pool_f64: no atomics, the same bits on
+    every run and for every split into chunks); ``'mean'`` -- that sum divided once by the number of patches of the region;
+    ``'max'`` -- the largest value, a NaN input making that output NaN (and max(-0, +0) = +0).  Anything else, a grid or
+    ``pool`` that does not fit and codes of another shape raise ``ValueError`` before any device call.  Returns a NumPy array,
+    or with ``device=True`` a ``DeviceArray``."""
+    _reduce_check(reduce)
+    try:
+        B, nr, nc = (int(v) for v in grid)
+    except (TypeError, ValueError):
+        raise ValueError("grid is (B, nr, nc), got %r" % (grid,))
+    if min(B, nr, nc) < 1:
+        raise ValueError("grid is (B, nr, nc) with no empty axis, got %r" % (grid,))
+    pool = _pool_pair(pool, nr, nc)
+    shape = _shape_of(codes)
+    if len(shape) != 2 or shape[0] != B * nr * nc or shape[1] < 1:
+        raise ValueError("codes must be (%d, H >= 1) for the grid %r, got %r" % (B * nr * nc, (B, nr, nc), shape))
+    H = int(shape[1])
+    dev = _device()
+    t, ldc = _rows_tensor(codes, H, dev, "codes")
+    acc = _pool_begin((B, nr, nc), pool, H, reduce, dev)
+    _pool(acc, t, ldc, (B, nr, nc), pool, 0, B * nr * nc, reduce, _pool_work(B * nr, nc, pool[1], H, dev), False)
+    return _hand_back(_pool_finish(acc, (B, nr, nc), pool, reduce, False), False, device)
+
+
+def encode_image(model, model_params, image, patch=None, stride=1, center=False, chunk=None, device=False, mask=None,
+                 weight=None, exact=False, pool=None, reduce='mean'):
+    """The feature maps of ``image`` ((H_i, W_i) or a stack (B, H_i, W_i); NumPy array, torch tensor -- a device tensor is
+    used in place -- or ``DeviceArray``) under ``model`` at ``model_params``: every patch on the grid of the module docstring
+    through ``model.encode()``.  Returns ``(mean, prob)``, the two codes ``encode()`` documents, as H channels on the patch
+    grid, channel-last: (B, nr, nc, H) float64 for a stack, (nr, nc, H) for a 2-D image -- ``encode()`` of the whole patch
+    matrix, reshaped, bit for bit.  Codes are not overlap-averaged: a patch keeps its own.
+
+    ``image``, ``patch``, ``stride``, ``center``, ``mask``, ``weight`` and ``device`` mean what they mean in
+    ``denoise_image``: the same grid (stride <= patch), ``center`` removes each patch's mean before the model sees it, a
+    ``mask`` / ``weight`` of the image's shape is cut into patches by the same kernel and every chunk goes through
+    ``model.encode(model_params, {'y': chunk, 'mask' | 'weight': ...})`` (BSC, MCA, MMCA; what the image holds under a hole or
+    at weight 0 changes no bit).  ``center=True`` with a mask or a weight, ``weight`` together with ``mask`` and a weight that
+    is negative, NaN or infinite raise ``ValueError``, a model without the masked / weighted E-step ``NotImplementedError`` --
+    all before any launch.  ``exact=True`` reaches ``encode()`` only when it is set; ``encode()``'s own refusals and
+    ``HipError`` limits apply unchanged.
+
+    The patches are walked in chunks of whole patch rows: extract -> ``model.encode(..., device=True)`` -> write into the
+    preallocated maps, or pool.  ``chunk``: patches per chunk, rounded down to whole patch rows (at least one); None: as many
+    patch rows as keep a chunk's input rows plus its two code rows, 8 (D + 2 H) bytes per patch, within ``CHUNK_BYTES``.
+    The result's bits do not depend on ``chunk``.
+
+    ``pool=(gh, gw)`` (an int g: (g, g); ``ValueError`` if gh > nr or gw > nc): both results are pooled over a gh x gw grid of
+    regions into (B, gh, gw, H) -- (gh, gw, H) for a 2-D image --, a fixed-length feature vector per image whatever its
+    size: region (i, j) holds the patches whose start-row index is in ``pool_regions(nr, gh)[i]`` and whose start-column
+    index is in ``pool_regions(nc, gw)[j]``.  ``reduce`` is ``'mean'``, ``'sum'`` or ``'max'`` (``pool_codes``; validated
+    always, read only with ``pool``).  The maps themselves are then never held: every chunk's codes are pooled on the device
+    (pm_codes_pool_f64) in an order that is the same for every chunking.
+
+    It inherits from ``encode()``: this rank's images only, no collective; the training state, ``model_params`` and Hprime /
+    gamma are left as they were.  A NaN pixel makes NaN exactly the map cells of the patches that contain it, and exactly the
+    regions that contain those.  NumPy arrays, or with ``device=True`` ``DeviceArray``s."""
+    from ..em.camodels._device import DeviceArray
+    if mask is not None and center:
+        raise ValueError("center=True with a mask is not built: the patch mean would have to run over the observed pixels only")
+    if weight is not None and mask is not None:
+        raise ValueError("'weight' together with 'mask': fold the mask into the weight as zeros (weight = 0 where mask == 0)")
+    if weight is not None and center:
+        raise ValueError("center=True with a weight is not built: the patch mean would have to be the weighted one")
+    _reduce_check(reduce)
+    D, H = int(model.D), int(model.H)
+    if patch is None:
+        p = int(round(D ** 0.5))
+        if p * p != D:
+            raise ValueError("model.D = %d is not a square: give patch=(p_h, p_w)" % D)
+        patch = (p, p)
+    ph, pw = _patch_pair(patch)
+    if ph * pw != D:
+        raise ValueError("a %d x %d patch has %d values, model.D is %d" % (ph, pw, ph * pw, D))
+    shape = _shape_of(image)
+    geo = _geometry(shape, (ph, pw), stride)
+    (B, Hi, Wi), _, _, nr, nc = geo
+    if chunk is None:
+        chunk = CHUNK_BYTES // (8 * (D + 2 * H))
+    elif int(chunk) != chunk or int(chunk) < 1:
+        raise ValueError("chunk must be a positive number of patches, got %r" % (chunk,))
+    rows = min(max(1, int(chunk) // nc), B * nr)
+    if pool is not None:
+        pool = _pool_pair(pool, nr, nc)
+    extra = {'exact': True} if exact else {}
+    if mask is not None:
+        if _shape_of(mask) != tuple(shape):
+            raise ValueError("mask has shape %r, the image %r" % (_shape_of(mask), tuple(shape)))
+        # (an empty masked call: a model without the masked E-step refuses here, before anything reaches the device)
+        model.encode(model_params, {'y': np.empty((0, D)), 'mask': np.empty((0, D), dtype=bool)}, **extra)
+    if weight is not None:
+        if _shape_of(weight) != tuple(shape):
+            raise ValueError("weight has shape %r, the image %r" % (_shape_of(weight), tuple(shape)))
+        _weight_check(weight)
+        # (an empty weighted call: a model without the weighted E-step refuses here, before anything reaches the device)
+        model.encode(model_params, {'y': np.empty((0, D)), 'weight': np.empty((0, D))}, **extra)
+    dev = _device(model)
+    det = bool(getattr(model, "deterministic", False))
+    img, ldi = _image_tensor(image, dev)
+    mimg, ldmi = _mask_image(mask, shape, dev) if mask is not None else (None, 0)
+    wimg, ldwi = _weight_image(weight, dev) if weight is not None else (None, 0)
+    grid, N = (B, nr, nc), B * nr * nc
+    if pool is None:
+        outs = [torch.empty((N, H), dtype=torch.float64, device=dev) for _ in range(2)]
+    else:
+        outs = [_pool_begin(grid, pool, H, reduce, dev) for _ in range(2)]
+        work = _pool_work(rows, nc, pool[1], H, dev)
+    for R0 in range(0, B * nr, rows):
+        n0, n = R0 * nc, min(rows, B * nr - R0) * nc
+        Y, _ = _extract(img, ldi, geo, n0, n, center, det)
+        data = {'y': DeviceArray(Y)}
+        if mimg is not None:
+            data['mask'] = DeviceArray((_extract(mimg, ldmi, geo, n0, n, False, det)[0] != 0).view(torch.uint8))
+        if wimg is not None:
+            data['weight'] = DeviceArray(_extract(wimg, ldwi, geo, n0, n, False, det)[0])
+        pair = model.encode(model_params, data, device=True, **extra)
+        del Y, data
+        for out, code, what in zip(outs, pair, ("mean", "prob")):
+            if _shape_of(code) != (n, H):
+                raise ValueError("encode() returned a %s of %r for a chunk of (%d, %d)" % (what, _shape_of(code), n, H))
+            code, ldc = _rows_tensor(code, H, dev, "encode()'s %s" % what)
+            if pool is None:
+                out[n0:n0 + n].copy_(code)
+            else:
+                _pool(out, code, ldc, grid, pool, n0, n, reduce, work, det)
+        del pair, code
+    if pool is None:
+        outs = [t.view(B, nr, nc, H) for t in outs]
+    else:
+        outs = [_pool_finish(t, grid, pool, reduce, det) for t in outs]
+    return tuple(_hand_back(t, len(shape) == 2, device) for t in outs)
