@@ -111,7 +111,13 @@ def main():
                     help="with --heldout: the codes of the held-out datapoints under the learned parameters (encode, DESIGN "
                     "4.23): the mean number of active latents per datapoint, sum_h P(s_h != 0 | y_n), beside the generating "
                     "pi H; with --exact (BSC, MCA, MMCA, the mixtures) also the largest |prob_truncated - prob_exact|")
+    ap.add_argument("--exact-em", action="store_true",
+                    help="bsc: train the same start parameters twice on the same data and schedule -- truncated (H' = 5, gamma = "
+                    "3) and with the posterior over all 2^H states (model.exact = True, DESIGN 4.25) -- and print the bars "
+                    "error and log_likelihood(exact=True) per datapoint of both end points side by side")
     a = ap.parse_args()
+    if a.exact_em and a.model != "bsc":
+        ap.error("--exact-em is built for bsc")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         import torch
         import torch.distributed as dist
@@ -133,10 +139,32 @@ def main():
         heldout = {'y': drawn['y']}
         clean = noiseless_mean(a.model, gt, drawn)
 
-    anneal = LinearAnnealing(a.steps)
-    anneal['T'] = [(0, 2.), (.7, 1.)]
-    anneal['Ncut_factor'] = [(0, 0.), (2. / 3, 1.)]
-    anneal['anneal_prior'] = False
+    def schedule():
+        anneal = LinearAnnealing(a.steps)
+        anneal['T'] = [(0, 2.), (.7, 1.)]
+        anneal['Ncut_factor'] = [(0, 0.), (2. / 3, 1.)]
+        anneal['anneal_prior'] = False
+        return anneal
+
+    if a.exact_em:
+        ends = {}
+        for exact in (False, True):
+            model.exact = exact
+            start = {k: np.array(v, copy=True) if np.ndim(v) else v for k, v in init.items()}
+            em = EM(model=model, anneal=schedule(), data={'y': my_data['y']}, lparams=start)
+            em.run()
+            model.exact = False
+            _, mae = find_permutation(np.asarray(em.lparams['W']), np.asarray(gt['W']))
+            ll = model.log_likelihood(dict(em.lparams), {'y': my_data['y']}, exact=True) / a.N
+            ends[exact] = (mae, ll, float(em.lparams['pi']), float(em.lparams['sigma']))
+        if comm.rank == 0:
+            print("BSC on %d bars datapoints (%d ranks), %d EM steps from the same start, H = %d:" % (a.N, comm.size, a.steps, H))
+            print("  %-28s %14s %14s" % ("", "truncated 5/3", "exact 2^H"))
+            for i, what in enumerate(("bars mean abs error", "exact log-likelihood / N", "pi", "sigma")):
+                print("  %-28s %14.6f %14.6f" % (what, ends[False][i], ends[True][i]))
+        return
+
+    anneal = schedule()
     log = dlog.set_handler(('L', 'Q'), StoreInMemory)
     store = None
     if a.h5:

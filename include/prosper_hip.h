@@ -1117,6 +1117,40 @@ int pm_recon_exact_plan(int kind, int64_t N, int64_t D, int64_t K, int64_t H, in
 int pm_recon_exact_lin_f64(const double *Y, int64_t ldy, const double *ymu, const double *P, const double *G,
                            const double *logp, const double *values, int64_t K, int64_t N, int64_t D, int64_t H, double *E,
                            int64_t lde, double *work, void *stream);
+/* First and second posterior moments of the latents and the log-evidence term, per row, for exact EM; the
+ * arguments of pm_recon_exact_lin_f64 and its contract (no atomics, nothing depends on PM_DETERMINISTIC, the state split and
+ * every merge order are functions of the state count, H and K alone, a row's outputs are a function of that row and of the
+ * parameters: the same bits on every run, in both builds, under a row permutation, in any shard and in any row block; a NaN
+ * in y_n makes that row NaN and no other; a state of zero prior carries weight 0):
+ *   E (N x H, row stride lde >= H)             E_n[s_h] -- the bits pm_recon_exact_lin_f64 writes for the same arguments
+ *   C (N x H (H + 1) / 2, row stride ldc)      E_n[s_h s_h'] for h <= h', s_h = values[k_h], in the order (0,0), (0,1), ...,
+ *                                              (0,H-1), (1,1), ...: the pair (h, h') sits at h H - h (h - 1) / 2 + h' - h
+ *   v (N)                                      v_n = log sum_{all s} exp l_n(s), l the log-joint of pm_loglik_exact_lin_f64
+ *                                              without its row constants
+ * Per row block of 256 rows: sweeps 1 (v) and 2 (E) as pm_recon_exact_lin_f64 runs them; then the pair sweeps, over R3 =
+ * min(256, max(1, chunks / 16)) ranges of their own (their epilogue is longer): one full weighted sweep that leaves the pairs
+ * of the L low digits (from the per-thread masses of the lo states, after the loop), and one sweep per high digit i with every
+ * weight multiplied by that digit's value, over the chunks where the value is not 0 (K = 2: half of them) -- row L + i of
+ * E[s s^T], which gives the lo-hi and hi-hi pairs.  3 + (H - L) (K - 1) / K sweeps in all, against pm_recon_exact_lin_f64's 2.
+ * Columns of E and C past their row widths are not written.
+ * `work`: pm_moments_exact_work_len(N, H) doubles = min(N, 256) (H + 1 + 256 max(H, 55)) (-1 for N < 0 or H < 1): bounded in N.
+ * PM_EINVAL / PM_ERANGE exactly where pm_recon_exact_lin_f64 returns them (K^H <= 2^32, H <= 32), PM_EINVAL also for
+ * ldc < H (H + 1) / 2 or a null C or v with N > 0; checked before a device is touched; N == 0 launches nothing. */
+int64_t pm_moments_exact_work_len(int64_t N, int64_t H);
+/* What pm_moments_exact_lin_f64 does for (N, D, K, H); nothing is launched and no device is needed.
+ * out[PM_MOMENTS_PLAN_LEN]:
+ *   0 rows, 1 blocks, 2 L, 3 CH, 4 chunks, 5 R   as pm_recon_exact_plan(PM_EXACT_LIN, ...) reports them
+ *   6 pinned sweeps   H - L, one per high digit          7 lo-lo pairs   L (L + 1) / 2, formed after the full sweep's loop
+ *   8 R3              ranges of the pair sweeps: min(256, max(1, chunks / 16)), a function of the state count alone
+ *   9                 offset (doubles) of the partials inside `work` for the largest block, nb = min(N, rows): nb (H + 1)
+ *   10, 11            length of the largest partials of sweeps 1 and 2 (nb R max(2, H)) and of the pair sweeps
+ *                     (nb R3 max(H, lo-lo pairs))
+ * Returns PM_OK, PM_EINVAL or PM_ERANGE as pm_recon_exact_plan does. */
+#define PM_MOMENTS_PLAN_LEN 12
+int pm_moments_exact_plan(int64_t N, int64_t D, int64_t K, int64_t H, int64_t *out);
+int pm_moments_exact_lin_f64(const double *Y, int64_t ldy, const double *ymu, const double *P, const double *G,
+                             const double *logp, const double *values, int64_t K, int64_t N, int64_t D, int64_t H, double *E,
+                             int64_t lde, double *C, int64_t ldc, double *v, double *work, void *stream);
 /* MCA (signed_w = 0) and MMCA (signed_w = 1): Yhat (N x D, row stride ldo >= D) receives sum_s q_n(s) Wbar_d(s); Wrho,
  * inv_rho, lp1, lp0 and inv_s2 as for pm_loglik_exact_mca_f64.  One wavefront per state, lanes over the dimensions. */
 int pm_recon_exact_mca_f64(const double *Y, int64_t ldy, const double *Wrho, double inv_rho, int signed_w, double lp1,

@@ -15,6 +15,8 @@
 // function of that row of Y and of the parameters.  Nothing is added by atomics and nothing depends on PM_DETERMINISTIC.
 // States are decoded from their index; every per-state quantity is recomputed from its digits.  The pieces of l_n(s) shared
 // with loglik_exact.hip are the single definitions of pm_exact.h.
+// pm_moments_exact_lin_f64 adds the second moments E[s s^T] of the linear models for exact EM: sweeps 1 and 2
+// as above, then rx_lin_kernel<3>'s pair sweeps over coarser ranges of their own.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -34,6 +36,7 @@ constexpr int64_t RX_MAX_RANGES = 256;
 constexpr int64_t RX_MCA_ROWS = 64;           // ... MCA / MMCA (a partial is D wide)
 constexpr int64_t RX_MCA_MAX_RANGES = 64;
 constexpr uint64_t RX_LIN_MIN_CHUNKS = 2;     // chunks per range at least (where there are two)
+constexpr uint64_t RX_PAIR_MIN_CHUNKS = 16;   // ... of the moments entry's pair sweeps, whose epilogue is longer
 constexpr uint64_t RX_MCA_MIN_STATES = 64;    // states per range at least: 16 per wavefront
 constexpr uint64_t RX_GSC_MIN_STATES = 32;    // supports per range at least: 8 per wavefront
 
@@ -110,6 +113,9 @@ __global__ void __launch_bounds__(RX_THREADS) rx_combine_sum_kernel(const double
 // the chunk's own digit values (NH fmas per chunk, i.e. per up to four states), and turns the lo masses into the low
 // latents' sums once, after the loop.  E[s]_h = sum over threads of these sums, by block_sum's fixed tree.
 constexpr int LIN_MAX_NH = 24;            // high digits at most (K = 2, H = 32: 22)
+constexpr int LIN_MAX_LL = 55;            // pairs of low digits at most: L <= 10 (K = 2, CH = 1024)
+constexpr int LIN_OUT3 = LIN_MAX_LL;      // outputs of sweep 3 at most (a pinned sweep: H <= 32)
+static_assert(PMX_MAX_H <= LIN_OUT3, "a pinned sweep's outputs fit");
 
 struct LinArgs {
     const double *G;        // H x H
@@ -121,6 +127,11 @@ struct LinArgs {
     int64_t nb, R;
     uint64_t nchunks;
     int H, K, L, CH;
+    // sweep 3 (the moments entry): sweep 2 with every weight multiplied by the value of hi digit `pin`, over the
+    // chunks where that value is not 0 -- or, pin = -1, sweep 2's loop with the lo-lo pair sums as its only outputs
+    int pin = -1;
+    uint64_t pdiv = 1;          // K^pin: digit `pin` of chunk c is (c / pdiv) % K
+    int64_t width = 0;      // doubles per partial of sweep 3: H, or L (L + 1) / 2 for pin = -1
 };
 
 template <int SWEEP>
@@ -132,6 +143,7 @@ __global__ void __launch_bounds__(RX_THREADS) rx_lin_kernel(LinArgs a) {
     __shared__ double sBh[1];
     __shared__ int sDig[PMX_MAX_H];
     __shared__ double red[2 * RX_WAVES];
+    __shared__ double sOut[SWEEP == 3 ? RX_WAVES * LIN_OUT3 : 1];   // sweep 3: the wavefronts' sums of every output
     const int H = a.H, K = a.K, L = a.L, CH = a.CH, NH = H - L;
     const int64_t R = a.R, n = blockIdx.x / R, r = blockIdx.x % R;
     for (int i = threadIdx.x; i < H * H; i += RX_THREADS) sG[i] = a.G[i];
@@ -139,6 +151,20 @@ __global__ void __launch_bounds__(RX_THREADS) rx_lin_kernel(LinArgs a) {
     if ((int)threadIdx.x < K) sVal[threadIdx.x] = a.values[threadIdx.x];
     if ((int)threadIdx.x < H) sB[threadIdx.x] = a.B[n * H + threadIdx.x];
     const uint64_t c0 = a.nchunks * (uint64_t)r / (uint64_t)R, c1 = a.nchunks * (uint64_t)(r + 1) / (uint64_t)R;
+    if (SWEEP == 3 && a.pin >= 0) {
+        // a range none of whose chunks carries weight (the pinned digit moves every pdiv chunks and shows every value within
+        // K of its moves): zeros, before any setup
+        bool any = false;
+        uint64_t c = c0;
+        for (int i = 0; i <= K && c < c1 && !any; ++i) {
+            any = a.values[(c / a.pdiv) % (uint64_t)K] != 0.0;
+            c = (c / a.pdiv + 1) * a.pdiv;
+        }
+        if (!any) {
+            if ((int)threadIdx.x < H) a.part[(r * a.nb + n) * a.width + threadIdx.x] = 0.0;
+            return;
+        }
+    }
     if (threadIdx.x == 0) {                    // the hi digits of chunk c0
         uint64_t c = c0;
         for (int i = 0; i < NH; ++i) {
@@ -178,7 +204,7 @@ __global__ void __launch_bounds__(RX_THREADS) rx_lin_kernel(LinArgs a) {
         blo[j] = bl;
     }
 
-    const double vn = SWEEP == 2 ? a.v[n] : 0.0;
+    const double vn = SWEEP >= 2 ? a.v[n] : 0.0;
     double m = -INFINITY, s = 0.0;             // sweep 1
     double mlo[PMX_LIN_MAX_J], ehi[LIN_MAX_NH];    // sweep 2
 #pragma unroll
@@ -186,6 +212,20 @@ __global__ void __launch_bounds__(RX_THREADS) rx_lin_kernel(LinArgs a) {
 #pragma unroll
     for (int i = 0; i < LIN_MAX_NH; ++i) ehi[i] = 0.0;
     for (uint64_t c = c0; c < c1; ++c) {
+        double wpin = 1.0;                                  // sweep 3: the pinned digit's value in this chunk (uniform)
+        if (SWEEP == 3 && a.pin >= 0) {
+            wpin = sVal[(int)((c / a.pdiv) % (uint64_t)K)];
+            if (wpin == 0.0) {                              // no state of the chunk carries weight: on to the next one
+                if (threadIdx.x == 0) {
+                    for (int i = 0; i < NH; ++i) {
+                        if (++sDig[i] < K) break;
+                        sDig[i] = 0;
+                    }
+                }
+                __syncthreads();
+                continue;
+            }
+        }
         // shared per-chunk terms from the hi digits
         const int t = threadIdx.x;
         if (t < L) {                                        // g_t = (G_lh s_hi)_t, times every value
@@ -219,12 +259,13 @@ __global__ void __launch_bounds__(RX_THREADS) rx_lin_kernel(LinArgs a) {
             if (SWEEP == 1) {
                 pmx_lse_add(m, s, l);
             } else {
-                const double q = exp(l - vn);              // (-inf - v: 0, a state of zero prior)
+                double q = exp(l - vn);                    // (-inf - v: 0, a state of zero prior)
+                if (SWEEP == 3 && a.pin >= 0) q *= wpin;
                 mlo[j] += q;
                 cm += q;
             }
         }
-        if (SWEEP == 2) {
+        if (SWEEP >= 2) {
 #pragma unroll
             for (int i = 0; i < LIN_MAX_NH; ++i)
                 if (i < NH) ehi[i] = fma(sSv[i], cm, ehi[i]);
@@ -245,7 +286,50 @@ __global__ void __launch_bounds__(RX_THREADS) rx_lin_kernel(LinArgs a) {
         }
         return;
     }
-    double *out = a.part + (r * a.nb + n) * H;
+    if (SWEEP == 3) {
+        // Sweep 2's outputs (a pinned sweep) or, pin = -1, sum_s q(s) s_h s_h' of the low latents (h <= h') from the lo masses,
+        // with ONE barrier for all of them: per output block_sum's lane tree, the wavefront's sum into sOut, then (0 + 1) +
+        // (2 + 3).
+        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+        double *mine = sOut + wv * LIN_OUT3;
+        for (int h = 0; h < L && a.pin >= 0; ++h) {
+            double e = 0.0;
+#pragma unroll
+            for (int j = 0; j < PMX_LIN_MAX_J; ++j)
+                if (threadIdx.x + j * RX_THREADS < (unsigned)CH) e = fma(sVal[(code[j] >> (3 * h)) & 7], mlo[j], e);
+            for (int o = 32; o > 0; o >>= 1) e += __shfl_down(e, o);
+            if (lane == 0) mine[h] = e;
+        }
+#pragma unroll
+        for (int i = 0; i < LIN_MAX_NH; ++i) {
+            if (i < NH && a.pin >= 0) {
+                double e = ehi[i];
+                for (int o = 32; o > 0; o >>= 1) e += __shfl_down(e, o);
+                if (lane == 0) mine[L + i] = e;
+            }
+        }
+        if (a.pin < 0) {
+            int t = 0;
+            for (int h = 0; h < L; ++h) {
+                for (int h2 = h; h2 < L; ++h2) {
+                    double e = 0.0;
+#pragma unroll
+                    for (int j = 0; j < PMX_LIN_MAX_J; ++j)
+                        if (threadIdx.x + j * RX_THREADS < (unsigned)CH)
+                            e = fma(sVal[(code[j] >> (3 * h)) & 7] * sVal[(code[j] >> (3 * h2)) & 7], mlo[j], e);
+                    for (int o = 32; o > 0; o >>= 1) e += __shfl_down(e, o);
+                    if (lane == 0) mine[t] = e;
+                    ++t;
+                }
+            }
+        }
+        __syncthreads();
+        double *out3 = a.part + (r * a.nb + n) * a.width;
+        for (int t = threadIdx.x; t < (int)a.width; t += RX_THREADS)
+            out3[t] = (sOut[t] + sOut[LIN_OUT3 + t]) + (sOut[2 * LIN_OUT3 + t] + sOut[3 * LIN_OUT3 + t]);
+        return;
+    }
+    double *out = a.part + (r * a.nb + n) * (int64_t)H;
     for (int h = 0; h < L; ++h) {                           // the low latents from the lo masses
         double e = 0.0;
 #pragma unroll
@@ -261,6 +345,41 @@ __global__ void __launch_bounds__(RX_THREADS) rx_lin_kernel(LinArgs a) {
             if (threadIdx.x == 0) out[L + i] = e;
         }
     }
+}
+
+// The partials of one launch of sweep 3 added in range order into the moments' outputs, one thread per (row, column).  The
+// place of the pair (h, h'), h <= h', in a row of C is h H - h (h - 1) / 2 + h' - h.  pin = -1: the columns are the lo-lo pairs
+// in that order; pin >= 0 (latent p = L + pin): column j is the pair (j, p) for j < L and (p, j) for j >= p -- every pair of
+// C is written by exactly one launch.
+__global__ void __launch_bounds__(RX_THREADS) rx_combine_moments_kernel(const double *__restrict__ part, int64_t nb, int64_t R,
+                                                                        int64_t width, int H, int L, int pin,
+                                                                        double *__restrict__ C, int64_t ldc) {
+    const int64_t i = (int64_t)blockIdx.x * RX_THREADS + threadIdx.x;
+    if (i >= nb * width) return;
+    const int64_t n = i / width;
+    const int j = (int)(i % width);
+    double *dst;
+    {
+        int h, h2;
+        if (pin < 0) {
+            int t = j;
+            h = 0;
+            while (t >= L - h) {
+                t -= L - h;
+                ++h;
+            }
+            h2 = h + t;
+        } else {
+            const int p = L + pin;
+            if (j >= L && j < p) return;
+            h = j < L ? j : p;
+            h2 = j < L ? p : j;
+        }
+        dst = C + n * ldc + ((int64_t)h * H - (int64_t)h * (h - 1) / 2 + (h2 - h));
+    }
+    double acc = 0.0;
+    for (int64_t r = 0; r < R; ++r) acc += part[(r * nb + n) * width + j];
+    *dst = acc;
 }
 
 // ---- MCA / MMCA ----------------------------------------------------------------------------------------------------------
@@ -619,6 +738,100 @@ extern "C" int pm_recon_exact_lin_f64(const double *Y, int64_t ldy, const double
         hipLaunchKernelGGL(rx_lin_kernel<2>, grid, dim3(RX_THREADS), 0, st, a);
         if ((err = (int)hipGetLastError())) return err;
         if ((err = rx_combine_sum(part, nb, a.R, H, E + n0 * lde, lde, st))) return err;
+    }
+    return PM_OK;
+}
+
+// ---- the moments entry -------------------------------------------------------------------------------------
+// E[s], E[s s^T] (packed upper triangle) and v per row: sweeps 1 and 2 as pm_recon_exact_lin_f64 runs them (E carries its
+// bits), then the pair sweeps over R3 ranges of their own -- at least RX_PAIR_MIN_CHUNKS chunks each, so that their longer
+// epilogue is paid per 64 states of a thread and not per 8: sweep 3 with pin = -1 for the lo-lo pairs, then one pinned sweep per
+// hi digit over the chunks where that digit's value is not 0: sum_s q(s) s_p s_h for every h, which gives the lo-hi and hi-hi
+// pairs.  3 + (H - L) (K - 1) / K sweeps.
+int64_t rx_pair_ranges(const RxPlan &p) { return rx_ranges(p.space, RX_PAIR_MIN_CHUNKS, RX_MAX_RANGES); }
+
+
+extern "C" int64_t pm_moments_exact_work_len(int64_t N, int64_t H) {
+    if (N < 0 || H < 1) return -1;
+    return rx_max(rx_min(N, RX_ROWS) * (H + 1 + RX_MAX_RANGES * rx_max(H, LIN_MAX_LL)), 1);
+}
+
+extern "C" int pm_moments_exact_plan(int64_t N, int64_t D, int64_t K, int64_t H, int64_t *out) {
+    if (!out) return PM_EINVAL;
+    RxPlan p;
+    const int rc = rx_plan(PM_EXACT_LIN, N, D, K, H, p);
+    if (rc) return rc;
+    const int64_t nb = rx_min(N, p.rows), ll = (int64_t)p.L * (p.L + 1) / 2;
+    out[0] = p.rows;
+    out[1] = p.blocks;
+    out[2] = p.L;
+    out[3] = p.CH;
+    out[4] = (int64_t)p.space;
+    out[5] = p.R;
+    out[6] = H - p.L;
+    out[7] = ll;
+    out[8] = rx_pair_ranges(p);
+    out[9] = rx_part_off(nb, H, p);
+    out[10] = rx_max(2, H) * nb * p.R;
+    out[11] = rx_max(H, ll) * nb * out[8];
+    return PM_OK;
+}
+
+extern "C" int pm_moments_exact_lin_f64(const double *Y, int64_t ldy, const double *ymu, const double *P, const double *G,
+                                        const double *logp, const double *values, int64_t K, int64_t N, int64_t D, int64_t H,
+                                        double *E, int64_t lde, double *C, int64_t ldc, double *v, double *work, void *stream) {
+    if (N < 0 || D < 1 || H < 1 || K < 2 || K > PMX_LIN_MAX_K || ldy < D || lde < H || ldc < H * (H + 1) / 2 || !P || !G ||
+        !logp || !values || !work || (N > 0 && (!Y || !E || !C || !v)))
+        return PM_EINVAL;
+    RxPlan pl;
+    const int rc = rx_plan(PM_EXACT_LIN, N, D, K, H, pl);
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    LinArgs a;
+    a.G = G;
+    a.logp = logp;
+    a.values = values;
+    a.H = (int)H;
+    a.K = (int)K;
+    a.L = pl.L;
+    a.CH = pl.CH;
+    a.nchunks = pl.space;
+    a.R = pl.R;
+    const int NH = (int)H - pl.L;
+    const int64_t ll = (int64_t)pl.L * (pl.L + 1) / 2, R3 = rx_pair_ranges(pl);
+    for (int64_t n0 = 0; n0 < N; n0 += pl.rows) {
+        const int64_t nb = rx_min(pl.rows, N - n0);
+        const RxWork w = rx_work(work, nb, H, pl);
+        hipLaunchKernelGGL(rx_prep_kernel, dim3(rx_blocks(nb * H)), dim3(RX_THREADS), 0, st, Y + n0 * ldy, ldy, ymu, nb, D, P,
+                           H, w.B);
+        int err = (int)hipGetLastError();
+        if (err) return err;
+        a.B = w.B;
+        a.v = v + n0;
+        a.part = w.part;
+        a.nb = nb;
+        a.pin = -1;
+        a.pdiv = 1;
+        a.R = pl.R;
+        const dim3 grid((unsigned)(nb * a.R));
+        hipLaunchKernelGGL(rx_lin_kernel<1>, grid, dim3(RX_THREADS), 0, st, a);
+        if ((err = (int)hipGetLastError())) return err;
+        if ((err = rx_combine_lse(w.part, nb, a.R, v + n0, st))) return err;
+        hipLaunchKernelGGL(rx_lin_kernel<2>, grid, dim3(RX_THREADS), 0, st, a);
+        if ((err = (int)hipGetLastError())) return err;
+        if ((err = rx_combine_sum(w.part, nb, a.R, H, E + n0 * lde, lde, st))) return err;
+        a.R = R3;
+        const dim3 grid3((unsigned)(nb * R3));
+        for (int pin = -1; pin < NH; ++pin) {
+            a.pin = pin;
+            a.width = pin < 0 ? ll : H;
+            if (pin > 0) a.pdiv *= (uint64_t)K;
+            hipLaunchKernelGGL(rx_lin_kernel<3>, grid3, dim3(RX_THREADS), 0, st, a);
+            if ((err = (int)hipGetLastError())) return err;
+            hipLaunchKernelGGL(rx_combine_moments_kernel, dim3(rx_blocks(nb * a.width)), dim3(RX_THREADS), 0, st, w.part, nb, R3,
+                               a.width, (int)H, pl.L, pin, C + n0 * ldc, ldc);
+            if ((err = (int)hipGetLastError())) return err;
+        }
     }
     return PM_OK;
 }

@@ -27,6 +27,15 @@ class Model(object):
     def standard_init(self, data):
         raise NotImplementedError
 
+    # True: ``step`` is one EM step with the posterior over the WHOLE state space, built for BSC_ET; a plain
+    # attribute like ``deterministic``.  A model that has no exact step refuses in ``step`` instead of running truncated.
+    exact = False
+
+    def exact_step(self, anneal, model_params, my_data):
+        """One EM step with the posterior over every latent state: BSC_ET has it."""
+        raise NotImplementedError("%s has no exact EM step (exact_step / model.exact = True): BSC_ET has it"
+                                  % type(self).__name__)
+
     def _refuse_training_mask(self, my_data):
         """Training on incomplete data is built for BSC_ET alone: a ``'mask'`` entry is never ignored
         silently -- every other model's ``step`` / ``E_step`` / ``M_step`` refuses it here, before any launch."""

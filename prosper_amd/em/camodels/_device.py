@@ -341,6 +341,8 @@ class DeviceCAModel(CAModel):
 
     def step(self, anneal, model_params, my_data):
         """CAModel.step (camodels/__init__.py:163-193); the E-step knows that the M-step follows with the same arguments."""
+        if self.exact:
+            return self.exact_step(anneal, model_params, my_data)
         self._refuse_training_mask(my_data)
         was, self._in_step = getattr(self, "_in_step", False), True
         self._step_id = getattr(self, "_step_id", 0) + 1

@@ -434,7 +434,10 @@ class BSC_ET(DeviceCAModel):
     # ------------------------------------------------------------------ hot path
     def step(self, anneal, model_params, my_data):
         """CAModel.step (camodels/__init__.py:163-193); E_step knows that M_step follows with the same arguments.
-        ``my_data['mask']`` (N, D; non-zero = observed): the EM step on incomplete data."""
+        ``my_data['mask']`` (N, D; non-zero = observed): the EM step on incomplete data.  With ``self.exact``:
+        ``exact_step``."""
+        if self.exact:
+            return self.exact_step(anneal, model_params, my_data)
         self._refuse_training_weight(my_data)
         if my_data.get('mask') is not None:
             # (on records of its own: nothing the unmasked loop keeps between its steps is read or touched)
@@ -1108,6 +1111,158 @@ class BSC_ET(DeviceCAModel):
         dlog.append('N_use', N)
         return {'W': W_new, 'pi': pi_new, 'sigma': sigma_new, 'mu': mu}
 
+    # ------------------------------------------------------------------ exact EM
+    # what the truncated loop keeps between its steps and ``_finalize`` writes: saved and put back around an exact step
+    _XE_KEEP = ("_par", "_a0", "_winv_prev", "_winv_was_warm", "_refine_next", "_warm_long", "_warm_force_long", "_last_solve",
+                "_redo_dev", "_spec_ok", "_spec_estep")
+
+    def _xe_admit(self, anneal, my_data):
+        """Everything that refuses an exact step, before any launch; returns the 'lin' call with no rows, which checks the
+        limits of the enumeration (PM_ERANGE past H = 32 -> HipError) before the data is uploaded."""
+        if isinstance(my_data, dict) and (my_data.get('mask') is not None or my_data.get('weight') is not None):
+            raise NotImplementedError("BSC_ET: the exact EM step (exact_step / model.exact = True) takes neither my_data['mask'] "
+                                      "nor my_data['weight']")
+        if anneal['data_noise'] > 0:
+            raise NotImplementedError("anneal['data_noise'] > 0 is not supported by the HIP M-step (exact_step) "
+                                      "(reference bsc_et.py:228-230 reads an undefined my_data['data_noise'])")
+        H, D = self.H, self.D
+        host = (ctypes.c_double * 4)()            # (with no rows the entry reads none of its arrays)
+        hp = ctypes.cast(host, ctypes.c_void_p)
+        _lib.call("pm_moments_exact_lin_f64", None, D, None, hp, hp, hp, hp, 2, 0, D, H, None, H, None, H * (H + 1) // 2, None,
+                  hp, None, det=self.deterministic)
+
+    def _xe_record(self, y, mu):
+        """The exact step's own record of the shard -- Y, X = Y - mu, X^T and |x_n|^2 --, apart from the truncated loop's
+        residency (``_resident``) and from the masked branch's."""
+        rec = getattr(self, "_xe", None)
+        ver = self._mt_version(y)
+        if not (rec is not None and rec["y"] is y and rec["ver"] == ver):
+            t = getattr(y, "tensor", y)
+            if torch.is_tensor(t):
+                Y = t.to(device=self.device, dtype=torch.float64).contiguous()
+            else:
+                Y = torch.from_numpy(np.ascontiguousarray(np.asarray(t), dtype=np.float64)).to(self.device)
+            assert Y.dim() == 2 and Y.shape[1] == self.D
+            rec = self._xe = {"y": y, "ver": ver, "Y": Y, "mu": False, "N_global": None}
+        mu = None if mu is None or not np.any(mu) else np.array(mu, dtype=np.float64)
+        old = rec["mu"]
+        if old is False or (mu is None) != (old is None) or (mu is not None and not np.array_equal(mu, old)):
+            Y = rec["Y"]
+            N = Y.shape[0]
+            mu_d = torch.from_numpy(mu).to(self.device) if mu is not None else None
+            X = Y - mu_d if mu is not None else Y
+            xn2 = torch.empty(N, dtype=torch.float64, device=self.device)
+            if N:
+                self._call("row_sqnorm", "pm_row_sqnorm_f64", _ptr(X), self.D, N, self.D, _ptr(xn2), self._stream())
+            rec.update(mu=mu, mu_d=mu_d, Xt=X.t().contiguous(), xn2=xn2)
+        return rec
+
+    XE_ROWS = 1 << 16         # rows per call of the moments entry: the (rows, H (H + 1) / 2) pair block is bounded
+
+    @tracing.traced
+    def exact_step(self, anneal, model_params, my_data):
+        """One EM step with the posterior over all 2^H states: the reference's M-step (bsc_et.py:195-438) at
+        H' = gamma = H, where A_pi_gamma = E_pi_gamma = 1 and ``Ncut_factor`` cuts nothing.  Per row E[s], E[s s^T] and
+        v_n = log sum_s exp l_n(s) by pm_moments_exact_lin_f64 at the annealing point (beta on the energy, and on the
+        log-odds with ``anneal_prior``), their ordered totals, Wp = sum_n E[s]_n x_n^T by the one-kernel GEMM, the expected
+        energy from the moments, all packed into the layout ``_finalize`` consumes.  Independent of ``Hprime``, ``gamma`` and
+        the candidates; nothing the truncated loop keeps between its steps is read or left changed.  Goes through
+        ``noisify_params`` / ``check_params`` / ``select_partial_data`` and logs what ``step`` logs."""
+        self._xe_admit(anneal, my_data)
+        model_params = self.noisify_params(model_params, anneal)
+        model_params = self.check_params(model_params)
+        my_pdata = self.select_partial_data(anneal, my_data)
+        if 'mu' not in model_params:
+            model_params['mu'] = np.zeros(self.D)
+        keep = {k: getattr(self, k) for k in self._XE_KEEP if hasattr(self, k)}
+        try:
+            self._winv_prev = None                # (the exact step's solve is the cold, refined one: no call history in its bits)
+            new_model_params = self._xe_mstep(anneal, model_params, my_pdata)
+        finally:
+            for k in self._XE_KEEP:
+                if k in keep:
+                    setattr(self, k, keep[k])
+                elif hasattr(self, k):
+                    delattr(self, k)
+        dlog.append_all(new_model_params)
+        dlog.append_all(anneal.as_dict())
+        return new_model_params
+
+    def _xe_mstep(self, anneal, model_params, my_data):
+        H, D = self.H, self.D
+        W = np.asarray(model_params['W'], dtype=np.float64)
+        pies, sigma = model_params['pi'], model_params['sigma']
+        mu = np.asarray(model_params['mu'], dtype=np.float64)
+        rec = self._xe_record(my_data['y'], mu)
+        Y = rec["Y"]
+        my_N, dev, st = Y.shape[0], self.device, self._stream()
+        learn_mu = 'mu' in self.to_learn
+        lib = _lib.load(self.deterministic)
+        n_stats = lib.pm_bsc_stats_len(H, D)
+        o_wq, o_qd = lib.pm_bsc_stats_offset_wq(H, D), lib.pm_bsc_stats_offset_qdiag(H, D)
+        o_sc = lib.pm_bsc_stats_offset_scalars(H, D)
+        o_mus = lib.pm_bsc_stats_offset_mus(H, D)
+        packed = self._buf("xe_packed", (n_stats + (D if learn_mu else 0),))
+        packed.zero_()
+        tracing.tracepoint("M_step:iterating")
+        if my_N:
+            # the annealing point: energies scaled by beta = 1 / T (sigma^2 / beta in P and G), log-odds by beta with anneal_prior
+            beta = 1. / anneal['T']
+            ecoef = -0.5 * beta / sigma / sigma
+            odds = float((beta if anneal['anneal_prior'] else 1.0) * np.log(pies / (1. - pies)))
+            _, arrays, _ = self._exact_linear(W, sigma / np.sqrt(beta), [0., 1.], np.tile([0., odds], (H, 1)))
+            up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)
+            P, G, logp, values = up(arrays["P"]), up(arrays["G"]), up(arrays["logp"]), up(arrays["values"])
+            npair = H * (H + 1) // 2
+            rows = min(my_N, self.XE_ROWS)
+            E = self._buf("xe_E", (my_N, H))
+            C = self._buf("xe_C", (rows, npair))
+            v = self._buf("xe_v", (my_N,))
+            work = self._buf("xe_work", (int(lib.pm_moments_exact_work_len(rows, H)),))
+            cwork = self._buf("xe_cs_work", (int(lib.pm_col_sum_ordered_work_len(my_N, max(npair, D))),))
+            tot = self._buf("xe_tot", (H + npair + 2,))         # [sum E[s] | sum E[s s^T], packed | sum v | sum |x|^2]
+            sumC, part = tot[H:H + npair], self._buf("xe_part", (npair,))
+            sumC.zero_()
+            ldy = max(int(Y.stride(0)), D)
+            for n0 in range(0, my_N, rows):                    # (blocks of a fixed size, their totals added in block order)
+                nb = min(rows, my_N - n0)
+                self._call("moments_exact", "pm_moments_exact_lin_f64", _ptr(Y[n0:]), ldy, _ptr(rec["mu_d"]), _ptr(P), _ptr(G),
+                           _ptr(logp), _ptr(values), 2, nb, D, H, _ptr(E[n0:]), H, _ptr(C), npair, _ptr(v[n0:]), _ptr(work), st)
+                self._call("xe_colsum", "pm_col_sum_ordered_f64", _ptr(C), npair, nb, npair, _ptr(cwork), _ptr(part), st)
+                sumC += part
+            self._call("xe_colsum", "pm_col_sum_ordered_f64", _ptr(E), H, my_N, H, _ptr(cwork), _ptr(tot[:H]), st)
+            self._call("xe_colsum", "pm_col_sum_ordered_f64", _ptr(v), 1, my_N, 1, _ptr(cwork), _ptr(tot[H + npair:]), st)
+            self._call("xe_colsum", "pm_col_sum_ordered_f64", _ptr(rec["xn2"]), 1, my_N, 1, _ptr(cwork),
+                       _ptr(tot[H + npair + 1:]), st)
+            # Wp = sum_n E[s]_n x_n^T through the one-kernel GEMM on the transposed operands: the whole row range per output
+            # tile, no K-slices meeting in atomics (DESIGN 4.17)
+            Wpx = self._buf("xe_wpx", (H, D))
+            self._call("xe_gemm", "pm_gemm_nt_rows_f64", _ptr(E.t().contiguous()), my_N, _ptr(rec["Xt"]), my_N, _ptr(Wpx), D,
+                       H, D, my_N, st)
+            iu = getattr(self, "_xe_iu", None)
+            if iu is None or iu[0].numel() != npair or iu[0].device != dev:
+                iu = self._xe_iu = tuple(torch.from_numpy(i).to(dev) for i in np.triu_indices(H))
+            Wq = packed[o_wq:o_qd].view(H, H)
+            Wq[iu[0], iu[1]] = sumC
+            Wq[iu[1], iu[0]] = sumC
+            sumE, sum_v, sum_x2 = tot[:H], tot[H + npair], tot[H + npair + 1]
+            packed[o_mus:o_sc] = sumE
+            # the expected energy from the moments: sum_n (|x_n|^2 - 2 x_n^T W E[s]_n + tr(W^T W E[s s^T]_n))
+            Wt = up(W.T)
+            WtW = up(W.T @ W)
+            energy = sum_x2 - 2.0 * (Wt * Wpx).sum() + (WtW * Wq).sum()
+            packed[:o_wq].view(H, D).copy_(Wpx)
+            if rec["mu_d"] is not None:            # (_finalize takes Wp against y and subtracts sum E[s] mu^T itself)
+                packed[:o_wq].view(H, D).add_(torch.outer(sumE, rec["mu_d"]))
+            packed[o_sc] = energy
+            packed[o_sc + 1] = sum_v + ecoef * sum_x2
+            packed[o_sc + 2] = float(my_N)
+            if learn_mu:
+                self._call("xe_colsum", "pm_col_sum_ordered_f64", _ptr(Y), ldy, my_N, D, _ptr(cwork), _ptr(packed[n_stats:]), st)
+        # the exchange of the step
+        self.comm.allreduce_device(packed)
+        return self._finalize(packed, model_params, 1.0, 1.0, None, None, None, slot="xe_mstep")
+
     def _det_quanta(self, res, W_DH, mu, P, N):
         """Deterministic mode: bounds no partial sum of the M-step's statistics can exceed on this shard with these
         parameters -> the quanta of the kernels about to run (pm_common.h, PM_Q).  Energies: |y - mu - sum_{h in s} W_h|^2
@@ -1135,7 +1290,7 @@ class BSC_ET(DeviceCAModel):
         sigma_new = np.sqrt(my_sigma / D / N_use) if 'sigma' in self.to_learn else sigma
         return mus_h, my_sigma, Fs, N_use, pi_new, sigma_new
 
-    def _finalize(self, packed, model_params, A_pi_gamma, E_pi_gamma, res=None, pre=None, anneal=None):
+    def _finalize(self, packed, model_params, A_pi_gamma, E_pi_gamma, res=None, pre=None, anneal=None, slot="mstep"):
         """Parameter updates from the all-reduced statistics (bsc_et.py:264-267, 369-438).
         Everything is enqueued on the device first (Wq assembly, Cholesky solve, reductions) and
         fetched with ONE device->host copy, so an EM step synchronises with the GPU exactly once.
@@ -1210,7 +1365,7 @@ class BSC_ET(DeviceCAModel):
                     _, _, _, _, pi_e, sigma_e = self._scalar_updates(early[0], pies, sigma, E_pi_gamma)
                     self._speculate_estep(res, spec[0], self._next_anneal, pi_e, sigma_e)
             # (under speculation the head has already travelled: `body` then starts behind it)
-            body = self._download(flat if early is None else flat[n_head:], slot="mstep", then=then if seed is not None else None)
+            body = self._download(flat if early is None else flat[n_head:], slot=slot, then=then if seed is not None else None)
             base = 0 if early is None else n_head
             host = body if early is None else early[0]
         else:

@@ -137,6 +137,8 @@ class MixtureModel(Model):
     @tracing.traced
     def step(self, anneal, model_params, data):
         """noisify -> check -> partial data -> E_step -> M_step, logging as __init__.py:126-149."""
+        if self.exact:
+            return self.exact_step(anneal, model_params, data)
         self._refuse_training_mask(data)
         model_params = self.noisify_params(model_params, anneal)
         model_params = self.check_params(model_params)
