@@ -3,6 +3,7 @@ workspace reuse, asynchronous parameter upload, the one device->host copy per M-
 launch bookkeeping and the NumPy-compatible handles (``DeviceArray``) results are returned in.
 PyTorch supplies memory, streams and process groups; every computation on the hot path is a call
 into libprosper_hip.so (include/prosper_hip.h)."""
+import contextlib
 import ctypes
 import os
 
@@ -996,6 +997,42 @@ class DeviceCAModel(CAModel):
         self._eval_slot = slot
         self._data_gen = gen             # (shard keys stay unique across both slots)
 
+    @contextlib.contextmanager
+    def _evaluation(self, rows_gemm=True):
+        """The scope every read-out runs in: ``_eval_begin`` / ``_eval_end`` around the body."""
+        saved = self._eval_begin()
+        try:
+            if rows_gemm:
+                # every product of the pass through the one-kernel GEMM, on parameter products of its own: a row of the result
+                # is a function of that row of the data and of the parameters alone (attributes of the evaluation only).
+                # ``log_likelihood`` without a mask or weight (plain and exact) passes False on purpose: it scores the data
+                # with the training step's own products, as it did before these attributes existed, and its bits stay those.
+                self._par, self._rows_gemm = {}, True
+            yield
+        finally:
+            if rows_gemm:
+                self._par = {}
+            self._eval_end(saved)
+
+    def _f64_dev(self, x):
+        """``x`` as a C-contiguous float64 tensor on the device."""
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(self.device)
+
+    def _mu_dev(self, mu):
+        """The (D,) device copy of a mean, None for None."""
+        return None if mu is None else self._f64_dev(mu).reshape(-1)
+
+    @staticmethod
+    def _nonzero_mu(mu):
+        """``mu``, or None for a mean that is absent or all zeros (the kernels then skip it)."""
+        return mu if mu is not None and np.any(np.asarray(mu)) else None
+
+    @staticmethod
+    def _row_stride(X, K):
+        """Leading dimension of the (N, K) rows of ``X``: a single row may carry any stride, so at least K."""
+        N = X.shape[0]
+        return X.stride(0) if N > 1 else max(int(X.stride(0)), K)
+
     def _loglik_terms(self, model_params, my_data):
         """Per model: ``(logpj, a, c)`` -- the (N, K) device log-joints of the T = 1 E-step over exactly the states it scores
         for each datapoint (any row stride), the scale a of the row log-sum-exp and the per-datapoint constant c(Theta) the
@@ -1057,23 +1094,24 @@ class DeviceCAModel(CAModel):
             return self._log_likelihood_masked(model_params, my_data, per_datapoint, exact)
         if exact:
             return self._log_likelihood_exact(model_params, my_data, per_datapoint)
-        saved = self._eval_begin()
-        try:
+        with self._evaluation(rows_gemm=False):
             logpj, a, c = self._loglik_terms(dict(model_params), {'y': my_data['y']})
-            N, K = logpj.shape
-            lib = _lib.load(self.deterministic)
-            work = torch.empty(int(lib.pm_rows_lse_work_len(N)), dtype=torch.float64, device=self.device)
-            total = torch.empty(1, dtype=torch.float64, device=self.device)
-            rows = torch.empty(N, dtype=torch.float64, device=self.device) if per_datapoint else None
-            ld = logpj.stride(0) if N > 1 else max(int(logpj.stride(0)), K)
-            self._call("loglik_rows", "pm_rows_lse_f64", _ptr(logpj), ld, N, K, ctypes.c_double(a), None, _ptr(rows),
-                       _ptr(work), _ptr(total), self._stream())
+            rows, total = self._rows_lse(logpj, a, per_datapoint)
             if per_datapoint:
                 return rows.cpu().numpy() + c
-            local = float(total.cpu()[0]) + N * c
-        finally:
-            self._eval_end(saved)
+            local = float(total.cpu()[0]) + logpj.shape[0] * c
         return self._sum_over_ranks(local)
+
+    def _rows_lse(self, logpj, a, per_datapoint):
+        """pm_rows_lse_f64 on the (N, K) log-joints: (rows (N,) or None, total (1,)) of log sum_k exp(a logpj[n, k])."""
+        N, K = logpj.shape
+        lib = _lib.load(self.deterministic)
+        work = torch.empty(int(lib.pm_rows_lse_work_len(N)), dtype=torch.float64, device=self.device)
+        total = torch.empty(1, dtype=torch.float64, device=self.device)
+        rows = torch.empty(N, dtype=torch.float64, device=self.device) if per_datapoint else None
+        self._call("loglik_rows", "pm_rows_lse_f64", _ptr(logpj), self._row_stride(logpj, K), N, K, ctypes.c_double(a), None,
+                   _ptr(rows), _ptr(work), _ptr(total), self._stream())
+        return rows, total
 
     def _sum_over_ranks(self, local):
         """The ranks' values added in rank order: every rank returns the same bits."""
@@ -1093,62 +1131,69 @@ class DeviceCAModel(CAModel):
         multi-cause states' mean is the rho-combination instead (pm_recon_mca_f64)."""
         raise NotImplementedError("%s has no reconstruct" % type(self).__name__)
 
-    def _recon_expect(self, X, K, N, a=1.0, lse=None, off=None, cand=None, table=None, blocks=(1.0,), soff=0, moff=0,
-                      ones=False):
+    def _layout_dev(self, table, blocks):
+        """A state layout as the kernels take it: (S, the (S, Hprime) table on the device or None, the 8-double vector of
+        ``blocks``)."""
+        S = 0 if table is None else int(table.shape[0])
+        bv = (ctypes.c_double * 8)(*([float(v) for v in blocks] + [0.0] * (8 - len(blocks))))
+        return S, (self._f64_dev(table) if S else None), bv
+
+    def _layout_call(self, label, entry, lp, cand, lay, table, *out):
+        """pm_recon_expect_f64, pm_recon_moments2_f64 or pm_encode_f64: the arguments they share -- the log-joints ``lp`` with
+        their own log-sum-exp, scale 1 and no offsets, the candidates and the layout ``lay`` with ``table`` --, then ``out``."""
+        N, K = lp.shape
+        S, tab_d, bv = self._layout_dev(table, lay["blocks"])
+        self._call(label, entry, _ptr(lp), self._row_stride(lp, K), None, ctypes.c_double(1.0), None, _ptr(cand) if S else None,
+                   _ptr(tab_d), bv, N, self.H, self.Hprime if S else 0, K, lay["soff"], len(lay["blocks"]), lay["moff"], S,
+                   *out, self._stream())
+
+    def _recon_expect(self, lp, cand, lay, ones=False):
         """pm_recon_expect_f64 into an (N, Kp) workspace, Kp = H (+ 1 for the column of ones) padded to a multiple of 8 with
         zero columns: the K range of the product that follows."""
         H = self.H
         Kp = (H + (1 if ones else 0) + 7) // 8 * 8
-        es = self._buf("recon_es", (N, Kp))
-        S = 0 if table is None else int(table.shape[0])
-        tab_d = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float64)).to(self.device) if S else None
-        if lse is not None and not (torch.is_tensor(lse) and lse.dtype == torch.float64 and tuple(lse.shape) == (N,)
-                                    and lse.is_contiguous() and a == 1.0 and off is None):
-            lse = None
-        bv = (ctypes.c_double * 8)(*([float(v) for v in blocks] + [0.0] * (8 - len(blocks))))
-        ld = X.stride(0) if N > 1 else max(int(X.stride(0)), K)
-        self._call("recon_expect", "pm_recon_expect_f64", _ptr(X), ld, _ptr(lse), ctypes.c_double(a), _ptr(off),
-                   _ptr(cand) if S else None, _ptr(tab_d), bv, N, H, self.Hprime if S else 0, K, soff, len(blocks), moff, S,
-                   _ptr(es), Kp, Kp, H if ones else -1, self._stream())
+        es = self._buf("recon_es", (lp.shape[0], Kp))
+        self._layout_call("recon_expect", "pm_recon_expect_f64", lp, cand, lay, lay.get("table"), _ptr(es), Kp, Kp,
+                          H if ones else -1)
         return es
 
-    def _recon_product(self, es, ld, cols, W, mu=None):
-        """Yhat (N, D) = es[:, :cols] . [W | mu | 0]^T through pm_gemm_nt_rows_f64 (``es`` carries a column of ones at H when
-        ``mu`` is given)."""
-        N, D, H = es.shape[0], self.D, self.H
+    def _recon_product(self, es, W, mu=None):
+        """Yhat (N, D) = es . [W | mu | 0]^T through pm_gemm_nt_rows_f64 (``es`` carries a column of ones at H when ``mu`` is
+        given)."""
+        (N, cols), D, H = es.shape, self.D, self.H
         Wp = np.zeros((D, cols))
         Wp[:, :H] = np.asarray(W, dtype=np.float64)
         if mu is not None:
             Wp[:, H] = np.asarray(mu, dtype=np.float64).reshape(-1)
         Wd = torch.from_numpy(Wp).to(self.device)
         out = torch.empty((N, D), dtype=torch.float64, device=self.device)
-        self._call("recon_gemm", "pm_gemm_nt_rows_f64", _ptr(es), ld, _ptr(Wd), cols, _ptr(out), D, N, D, cols,
+        self._call("recon_gemm", "pm_gemm_nt_rows_f64", _ptr(es), cols, _ptr(Wd), cols, _ptr(out), D, N, D, cols,
                    self._stream())
         return out
 
-    def _recon_variance(self, lp, K, N, cand, lay, Yhat, mu, par=None):
+    def _recon_variance(self, lp, cand, lay, Yhat, mu, par=None):
         """The (N, D) device tensor V of ``reconstruct(variance=True)`` from the log-joints, candidates and
         layout ``Yhat`` was formed from: m2 and p by pm_recon_moments2_f64, sum_h m2 W_dh^2 as one pm_gemm_nt_rows_f64
         against W o W, MCA / MMCA's multi-cause squares by pm_recon_mca_var_f64, then pm_recon_var_finish_f64."""
-        H, D, Hp = self.H, self.D, self.Hprime
-        table, blocks = lay.get("table"), lay["blocks"]
-        S = 0 if table is None else int(table.shape[0])
-        npair = Hp * (Hp - 1) // 2 if S else 0
+        H, Hp, N = self.H, self.Hprime, lp.shape[0]
+        table = lay.get("table")
+        npair = Hp * (Hp - 1) // 2 if table is not None and table.shape[0] else 0
         Kp = (H + 7) // 8 * 8
         m2 = self._buf("recon_m2", (N, Kp))
         p2 = self._buf("recon_p2", (N, npair)) if npair else None
-        tab_d = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float64)).to(self.device) if S else None
-        bv = (ctypes.c_double * 8)(*([float(v) for v in blocks] + [0.0] * (8 - len(blocks))))
-        ld = lp.stride(0) if N > 1 else max(int(lp.stride(0)), K)
-        self._call("recon_var", "pm_recon_moments2_f64", _ptr(lp), ld, None, ctypes.c_double(1.0), None,
-                   _ptr(cand) if S else None, _ptr(tab_d), bv, N, H, Hp if S else 0, K, lay["soff"], len(blocks), lay["moff"],
-                   S, _ptr(m2), Kp, Kp, _ptr(p2), max(npair, 1), self._stream())
+        self._layout_call("recon_var", "pm_recon_moments2_f64", lp, cand, lay, table, _ptr(m2), Kp, Kp, _ptr(p2),
+                          max(npair, 1))
         mca = None
         if lay.get("mca") and self.no_states:
-            mca = lambda V: self._call("recon_var", "pm_recon_mca_var_f64", _ptr(lp), ld, None, _ptr(cand), _ptr(self._masks()),
-                                       _ptr(par["Wrho"]), ctypes.c_double(1. / par["rho"]), int(bool(self.signed_w)), N, H, D,
-                                       Hp, self.no_states, _ptr(V), D, self._stream())
+            mca = lambda V: self._recon_mca("recon_var", "pm_recon_mca_var_f64", lp, cand, par, V)
         return self._recon_var_product(m2, p2, cand, lay["W"], mu, Yhat, more=mca)
+
+    def _recon_mca(self, label, entry, lp, cand, par, out):
+        """pm_recon_mca_f64 / pm_recon_mca_var_f64: the multi-cause states' rho-combinations (their squares) added to ``out``."""
+        N, K = lp.shape
+        self._call(label, entry, _ptr(lp), self._row_stride(lp, K), None, _ptr(cand), _ptr(self._masks()), _ptr(par["Wrho"]),
+                   ctypes.c_double(1. / par["rho"]), int(bool(self.signed_w)), N, self.H, self.D, self.Hprime, self.no_states,
+                   _ptr(out), self.D, self._stream())
 
     def _recon_var_product(self, m2, p2, cand, W, mu, Yhat, more=None):
         """V (N, D) from the second moments: sum_h m2 W_dh^2 as one pm_gemm_nt_rows_f64 of ``m2`` (N, Kp; zero past H) against
@@ -1165,43 +1210,47 @@ class DeviceCAModel(CAModel):
         self._call("recon_var", "pm_gemm_nt_rows_f64", _ptr(m2), Kp, _ptr(W2d), Kp, _ptr(V), D, N, D, Kp, self._stream())
         if more is not None:
             more(V)
-        Wt = torch.from_numpy(np.ascontiguousarray(W.T)).to(self.device) if npair else None
-        mu_d = torch.from_numpy(np.ascontiguousarray(mu, dtype=np.float64).reshape(-1)).to(self.device) if mu is not None \
-            else None
+        Wt = self._f64_dev(W.T) if npair else None
+        mu_d = self._mu_dev(mu)
         self._call("recon_var", "pm_recon_var_finish_f64", _ptr(V), D, _ptr(Yhat), D, _ptr(mu_d), _ptr(p2), max(npair, 1),
                    _ptr(cand) if npair else None, _ptr(Wt), D, N, H, D, Hp if npair else 0, self._stream())
         return V
 
-    def _reconstruct(self, model_params, my_data, N, variance=False):
-        """The (N, D) device tensor of ``reconstruct`` for the models whose E-step leaves (N, K) log-joints; with
-        ``variance`` the pair (Yhat, V)."""
+    def _logjoints(self, model_params, y, obs):
+        """What every read-out consumes, in the dict of ``_obs_estep``: ``logpj`` (N, K) and ``cand`` (N, Hprime), the device
+        log-joints and candidates of the selection and T = 1 E-step, and ``lay`` (``_recon_layout``) -- from the model's
+        ``_obs_estep`` when ``obs`` (what ``_observation`` returned) is given, which keeps the plain layout and for MCA adds
+        ``par``, else from the plain selection and E-step.  The caller holds the dict, and with it every tensor of the E-step,
+        for as long as it works on them."""
+        if obs is not None:
+            return self._obs_estep(model_params, y, obs)
         lay = self._recon_layout(model_params)
         mp = lay["params"]
-        data = self.select_Hprimes(mp, my_data)
-        out = self.E_step(LoglikPoint(), mp, data)['logpj']
-        cand = self._device_candidates(data['candidates'], N)
-        lp = out.tensor
-        K = lp.shape[1]
-        mca = bool(lay.get("mca"))
+        data = self.select_Hprimes(mp, {'y': y})
+        lp = self.E_step(LoglikPoint(), mp, data)['logpj'].tensor
+        return {"logpj": lp, "cand": self._device_candidates(data['candidates'], lp.shape[0]), "lay": lay}
+
+    def _mca_tables(self, out, y):
+        """MCA / MMCA's power tables at T = 1: those ``_logjoints`` handed out, or the ones its plain E-step built."""
+        par = out.get("par")
+        return par if par is not None else self._tables_for(out["lay"]["params"]['W'], 1.0, self._resident(y))
+
+    def _reconstruct(self, model_params, y, obs, N, variance=False):
+        """The (N, D) device tensor of ``reconstruct`` for the models whose E-step leaves (N, K) log-joints (``obs``: None or
+        what ``_observation`` returned -- the expectation and product kernels are the same, so the estimate covers all D
+        dimensions); with ``variance`` the pair (Yhat, V)."""
+        out = self._logjoints(model_params, y, obs)
+        lp, cand, lay, par = out["logpj"], out["cand"], out["lay"], out.get("par")
         # (the rows' log-sum-exp is formed again by the kernels, not taken from the E-step: the fused E-step kernels reduce a
         # row in an order that depends on the tile shape its position in the shard gets, so their ``lse`` differs in the last
         # bit between a row of a whole array and the same row of a shard -- and a row of Yhat must not)
-        lse = None
-        mu = lay.get("mu")
-        if mu is not None and not np.any(np.asarray(mu)):
-            mu = None
-        es = self._recon_expect(lp, K, N, lse=lse, cand=cand, table=lay.get("table"), blocks=lay["blocks"],
-                                soff=lay["soff"], moff=lay["moff"], ones=mu is not None)
-        Yhat = self._recon_product(es, es.shape[1], es.shape[1], lay["W"], mu)
-        par = None
-        if mca and self.no_states:
-            par = self._tables_for(mp['W'], 1.0, self._resident(my_data['y']))
-            ld = lp.stride(0) if N > 1 else max(int(lp.stride(0)), K)
-            self._call("recon_mca", "pm_recon_mca_f64", _ptr(lp), ld, None, _ptr(cand), _ptr(self._masks()),
-                       _ptr(par["Wrho"]), ctypes.c_double(1. / par["rho"]), int(bool(self.signed_w)), N, self.H, self.D,
-                       self.Hprime, self.no_states, _ptr(Yhat), self.D, self._stream())
+        mu = self._nonzero_mu(lay.get("mu"))
+        Yhat = self._recon_product(self._recon_expect(lp, cand, lay, ones=mu is not None), lay["W"], mu)
+        if lay.get("mca") and self.no_states:
+            par = self._mca_tables(out, y)
+            self._recon_mca("recon_mca", "pm_recon_mca_f64", lp, cand, par, Yhat)
         if variance:
-            return Yhat, self._recon_variance(lp, K, N, cand, lay, Yhat, mu, par)
+            return Yhat, self._recon_variance(lp, cand, lay, Yhat, mu, par)
         return Yhat
 
     def reconstruct(self, model_params, my_data, device=False, exact=False, variance=False):
@@ -1268,24 +1317,14 @@ class DeviceCAModel(CAModel):
             empty = lambda: DeviceArray(torch.empty((0, self.D), dtype=torch.float64, device=self.device)) if device \
                 else np.empty((0, self.D))
             return (empty(), empty()) if variance else empty()
-        saved = self._eval_begin()
-        try:
-            # every product of the pass through the one-kernel GEMM, on parameter products of its own: a row of the result
-            # is a function of that row of the data and of the parameters alone (attributes of the evaluation only)
-            self._par, self._rows_gemm = {}, True
-            kw = {"variance": True} if variance else {}
-            if obs is not None:
-                Yhat = self._reconstruct_masked(dict(model_params), y, obs, N, **kw)
-            elif exact:
+        with self._evaluation():
+            if exact:
                 Yhat = self._reconstruct_exact(dict(model_params), y, N)
             else:
-                Yhat = self._reconstruct(dict(model_params), {'y': y}, N, **kw)
+                Yhat = self._reconstruct(dict(model_params), y, obs, N, variance)
             if variance:
                 return tuple(DeviceArray(t) if device else t.cpu().numpy() for t in Yhat)
             return DeviceArray(Yhat) if device else Yhat.cpu().numpy()
-        finally:
-            self._par = {}
-            self._eval_end(saved)
 
     # ---- latent codes -------------------------------------------------------------------------------------
     _binary_latents = False           # BSC, MCA, MMCA: s_h in {0, 1} -- prob is min(mean, 1), and ``encode(exact=True)`` is built
@@ -1295,61 +1334,24 @@ class DeviceCAModel(CAModel):
         (``_recon_layout``) that ``reconstruct`` reads; ``lay['encode_table']`` is the table of a model whose reconstruction
         needs none (MCA / MMCA)."""
         H = self.H
-        K = lp.shape[1]
-        table = lay.get("encode_table", lay.get("table"))
-        blocks = lay["blocks"]
-        S = 0 if table is None else int(table.shape[0])
-        tab_d = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float64)).to(self.device) if S else None
-        bv = (ctypes.c_double * 8)(*([float(v) for v in blocks] + [0.0] * (8 - len(blocks))))
-        ld = lp.stride(0) if N > 1 else max(int(lp.stride(0)), K)
         mean = torch.empty((N, H), dtype=torch.float64, device=self.device)
         prob = torch.empty((N, H), dtype=torch.float64, device=self.device)
-        self._call("encode", "pm_encode_f64", _ptr(lp), ld, None, ctypes.c_double(1.0), None, _ptr(cand) if S else None,
-                   _ptr(tab_d), bv, N, H, self.Hprime if S else 0, K, lay["soff"], len(blocks), lay["moff"], S, _ptr(mean), H,
-                   _ptr(prob), H, self._stream())
+        self._layout_call("encode", "pm_encode_f64", lp, cand, lay, lay.get("encode_table", lay.get("table")), _ptr(mean), H,
+                          _ptr(prob), H)
         return mean, prob
 
-    def _encode(self, model_params, my_data, N):
-        """``encode`` for the models whose E-step leaves (N, K) log-joints: the selection and T = 1 E-step of
-        ``_reconstruct``, then ``_encode_from``."""
-        lay = self._recon_layout(model_params)
-        mp = lay["params"]
-        data = self.select_Hprimes(mp, my_data)
-        lp = self.E_step(LoglikPoint(), mp, data)['logpj'].tensor
-        cand = self._device_candidates(data['candidates'], N)
-        return self._encode_from(lp, N, cand, lay)
-
-    def _encode_masked(self, model_params, y, obs, N):
-        """``_encode`` from the masked or weighted E-step's log-joints, which keep the unmasked layout."""
-        out = self._obs_estep(model_params, y, obs)
+    def _encode(self, model_params, y, obs, N):
+        """``encode`` for the models whose E-step leaves (N, K) log-joints: the log-joints of ``_reconstruct``, then
+        ``_encode_from``."""
+        out = self._logjoints(model_params, y, obs)
         return self._encode_from(out["logpj"], N, out["cand"], out["lay"])
 
     def _encode_exact(self, model_params, y, N):
         """``encode(exact=True)`` of the binary models from the ``_loglik_exact`` hook: E[s] over all 2^H states by
         pm_recon_exact_lin_f64 (BSC) or pm_encode_exact_mca_f64 (MCA / MMCA); prob = min(E[s], 1)."""
-        D, H = self.D, self.H
-        kind, arrays, sc = self._loglik_exact(model_params)
-        dev = {k: (torch.from_numpy(np.array(v, dtype=np.float64, order="C")).to(self.device) if v is not None else None)
-               for k, v in arrays.items()}
-        dbl = ctypes.c_double
-
-        def entry(call, Yp, ld, n, out, work):
-            if kind == "lin":
-                call("pm_recon_exact_lin_f64", Yp, ld, _ptr(dev.get("mu")), _ptr(dev["P"]), _ptr(dev["G"]), _ptr(dev["logp"]),
-                     _ptr(dev["values"]), int(arrays["values"].shape[0]), n, D, H, out, H, work, self._stream())
-            else:
-                call("pm_encode_exact_mca_f64", Yp, ld, _ptr(dev["Wrho"]), dbl(sc["inv_rho"]), int(sc["signed"]),
-                     dbl(sc["lp1"]), dbl(sc["lp0"]), dbl(sc["inv_s2"]), n, D, H, out, H, work, self._stream())
-
-        # (the limits first, as ``_reconstruct_exact``: with no rows the entry checks its arguments and returns)
-        probe = torch.empty(1, dtype=torch.float64, device=self.device)
-        entry(lambda name, *a: _lib.call(name, *a, det=self.deterministic), None, D, 0, None, _ptr(probe))
-        Y = self._resident(y)["Y"]
-        lib = _lib.load(self.deterministic)
-        work = torch.empty(max(int(lib.pm_recon_exact_work_len(N, H, D)), 1), dtype=torch.float64, device=self.device)
-        mean = torch.empty((N, H), dtype=torch.float64, device=self.device)
-        entry(lambda name, *a: self._call("encode_exact", name, *a), _ptr(Y), max(int(Y.stride(0)), D), N, _ptr(mean),
-              _ptr(work))
+        _, _, entry = self._exact_entry(model_params, "encode")
+        self._exact_limits(entry, self.H)
+        mean = self._exact_rows("encode_exact", entry, y, torch.empty((N, self.H), dtype=torch.float64, device=self.device))
         return mean, torch.clamp(mean, max=1.0)
 
     def _encode_admit(self, exact):
@@ -1398,19 +1400,12 @@ class DeviceCAModel(CAModel):
             empty = lambda: DeviceArray(torch.empty((0, self.H), dtype=torch.float64, device=self.device)) if device \
                 else np.empty((0, self.H))
             return empty(), empty()
-        saved = self._eval_begin()
-        try:
-            self._par, self._rows_gemm = {}, True
-            if obs is not None:
-                pair = self._encode_masked(dict(model_params), y, obs, N)
-            elif exact:
+        with self._evaluation():
+            if exact:
                 pair = self._encode_exact(dict(model_params), y, N)
             else:
-                pair = self._encode(dict(model_params), {'y': y}, N)
+                pair = self._encode(dict(model_params), y, obs, N)
             return tuple(DeviceArray(t) if device else t.cpu().numpy() for t in pair)
-        finally:
-            self._par = {}
-            self._eval_end(saved)
 
     # ---- posterior draws ----------------------------------------------------------------------------------
     sample_chunk_bytes = 1 << 26      # bound of the workspace beside the result (indices and active lists of one row chunk)
@@ -1449,7 +1444,7 @@ class DeviceCAModel(CAModel):
         def given(arr):
             t = getattr(arr, "tensor", arr)
             if not torch.is_tensor(t):
-                t = torch.from_numpy(np.ascontiguousarray(np.asarray(t), dtype=np.float64))
+                t = self._f64_dev(np.asarray(t))
             return t.to(device=self.device, dtype=torch.float64).contiguous()
         U = given(uniforms) if uniforms is not None else \
             torch.rand((N, M), generator=g, device=self.device, dtype=torch.float64)
@@ -1467,22 +1462,23 @@ class DeviceCAModel(CAModel):
             return max(1, int(self.sample_chunk_rows))
         return max(1, min(N, int(self.sample_chunk_bytes) // (M * (4 + 12 * A))))
 
-    def _sample_states(self, X, K, n0, n, U, M, a=1.0, off=None, floor=0.0, null_col=-1):
+    def _sample_states(self, X, K, n0, n, U, M):
         """pm_sample_states_f64 on rows [n0, n0 + n) of the log-joints ``X`` and of ``U``: idx (n, M) int32."""
         idx = self._buf("sample_idx", (n, M), torch.int32)
-        ld = X.stride(0) if X.shape[0] > 1 else max(int(X.stride(0)), K)
+        ld = self._row_stride(X, K)
         self._call("sample_states", "pm_sample_states_f64", ctypes.c_void_p(X.data_ptr() + 8 * n0 * ld), ld, None,
-                   ctypes.c_double(a), _ptr(off), ctypes.c_double(floor), null_col,
+                   ctypes.c_double(1.0), None, ctypes.c_double(0.0), -1,
                    ctypes.c_void_p(U.data_ptr() + 8 * n0 * M), M, n, K, M, _ptr(idx), self._stream())
         return idx
 
-    def _sample_active(self, idx, cand_rows, n, M, K, A, table_d, S, blocks, soff, moff):
-        """pm_sample_active_f64: (act_idx (n, M, A) int32, act_val (n, M, A))."""
+    def _sample_active(self, idx, cand_rows, n, M, K, A, layout, lay):
+        """pm_sample_active_f64 with ``layout`` (what ``_layout_dev`` returned): (act_idx (n, M, A) int32, act_val (n, M, A))."""
         ai = self._buf("sample_act_idx", (n, M, A), torch.int32)
         av = self._buf("sample_act_val", (n, M, A))
-        bv = (ctypes.c_double * 8)(*([float(v) for v in blocks] + [0.0] * (8 - len(blocks))))
-        self._call("sample_active", "pm_sample_active_f64", _ptr(idx), cand_rows if S else None, _ptr(table_d) if S else None, bv,
-                   n, M, self.H, self.Hprime if S else 0, K, soff, len(blocks), moff, S, A, _ptr(ai), _ptr(av), self._stream())
+        S, table_d, bv = layout
+        self._call("sample_active", "pm_sample_active_f64", _ptr(idx), cand_rows if S else None, _ptr(table_d), bv, n, M, self.H,
+                   self.Hprime if S else 0, K, lay["soff"], len(lay["blocks"]), lay["moff"], S, A, _ptr(ai), _ptr(av),
+                   self._stream())
         return ai, av
 
     @staticmethod
@@ -1503,31 +1499,18 @@ class DeviceCAModel(CAModel):
         E-step leaves (N, K) log-joints: the E-step of ``reconstruct`` (``obs``: None or what ``_observation`` returned),
         then per row chunk pm_sample_states_f64, the active list and the decode kernel, written in place."""
         H, D, Hp = self.H, self.D, self.Hprime
-        par = None
-        if obs is not None:
-            out = self._obs_estep(model_params, y, obs)
-            lay, lp, cand, par = out["lay"], out["logpj"], out["cand"], out.get("par")
-        else:
-            lay = self._recon_layout(model_params)
-            mp = lay["params"]
-            data = self.select_Hprimes(mp, {'y': y})
-            lp = self.E_step(LoglikPoint(), mp, data)['logpj'].tensor
-            cand = self._device_candidates(data['candidates'], N)
+        out = self._logjoints(model_params, y, obs)
+        lp, cand, lay = out["logpj"], out["cand"], out["lay"]
         K = lp.shape[1]
         mca = bool(lay.get("mca"))
-        table, blocks = lay.get("table"), lay["blocks"]
+        table = lay.get("table")
         if mca:
-            if par is None:
-                par = self._tables_for(lay["params"]['W'], 1.0, self._resident(y))
+            par = self._mca_tables(out, y)
             table = self.state_matrix if self.no_states else None
-        S = 0 if table is None else int(table.shape[0])
-        A = max(1, int((np.asarray(table) != 0).sum(axis=1).max())) if S else 1
-        table_d = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float64)).to(self.device) if S else None
-        mu = lay.get("mu")
-        mu_d = torch.from_numpy(np.ascontiguousarray(mu, dtype=np.float64).reshape(-1)).to(self.device) \
-            if (mu is not None and np.any(np.asarray(mu))) else None
-        Wt = par["Wt"] if mca else \
-            torch.from_numpy(np.ascontiguousarray(np.asarray(lay["W"], dtype=np.float64).T)).to(self.device)
+        layout = self._layout_dev(table, lay["blocks"])
+        A = max(1, int((np.asarray(table) != 0).sum(axis=1).max())) if layout[0] else 1
+        mu_d = self._mu_dev(self._nonzero_mu(lay.get("mu")))
+        Wt = par["Wt"] if mca else self._f64_dev(np.asarray(lay["W"], dtype=np.float64).T)
         Ys = torch.empty((M, N, D), dtype=torch.float64, device=self.device)
         Sl = torch.empty((M, N, H), dtype=torch.float64, device=self.device) if latents else None
         rows = self._sample_rows(N, M, A)
@@ -1541,7 +1524,7 @@ class DeviceCAModel(CAModel):
                            _ptr(par["Wrho"]), ctypes.c_double(1. / par["rho"]), int(bool(self.signed_w)), n, M, H, D, Hp,
                            self.no_states, out_p, D, N * D, self._stream())
             if latents or not mca:
-                ai, av = self._sample_active(idx, cand_rows, n, M, K, A, table_d, S, blocks, lay["soff"], lay["moff"])
+                ai, av = self._sample_active(idx, cand_rows, n, M, K, A, layout, lay)
                 if not mca:
                     self._call("sample_decode", "pm_sample_decode_lin_f64", _ptr(ai), _ptr(av), A, _ptr(Wt), D, _ptr(mu_d), n,
                                M, H, D, out_p, D, N * D, self._stream())
@@ -1602,31 +1585,26 @@ class DeviceCAModel(CAModel):
             z = lambda c: DeviceArray(torch.empty((M, 0, c), dtype=torch.float64, device=self.device)) if device \
                 else np.empty((M, 0, c))
             return (z(self.D), z(self.H)) if latents else z(self.D)
-        saved = self._eval_begin()
-        try:
-            self._par, self._rows_gemm = {}, True
+        with self._evaluation():
             U, E = self._sample_randoms(N, M, seed, uniforms, normals, nn)
             Ys, Sl = self._sample(dict(model_params), y, obs, N, M, U, latents, E)
             return (wrap(Ys), wrap(Sl)) if latents else wrap(Ys)
-        finally:
-            self._par = {}
-            self._eval_end(saved)
 
     # ---- missing values -----------------------------------------------------------------------------------
-    def _masked_estep(self, model_params, y, mask):
-        """Per model: selection and T = 1 E-step of ``y`` over the dimensions its ``mask`` marks as observed (non-zero), run
-        inside an evaluation with ``_rows_gemm`` set.  Returns a dict: ``logpj`` (N, K) device log-joints in the layout of the
-        unmasked E-step, ``cand`` (N, Hprime) int32, ``dn`` (N,) int32 observed dimensions per row, ``c0`` / ``c1`` with
-        log p(s, y_obs) = logpj + c0 + D_n c1, ``lay`` (``_recon_layout``) and, for MCA, ``par`` (the power tables)."""
-        raise NotImplementedError("%s: missing values (my_data['mask']) are not built for this model; BSC_ET, MCA_ET and "
-                                  "MMCA_ET have the masked E-step" % type(self).__name__)
+    _OBS_KIND = {'mask': "masked", 'weight': "weighted"}      # (the word in entry names, launch labels and messages)
 
-    def _weighted_estep(self, model_params, y, weight):
-        """Per model: ``_masked_estep`` for ``y`` observed with the per-entry noise variances sigma^2 / weight
-        (0 = not observed).  Returns the same dict -- log p(s, y | weight) = logpj + c0 + D_n c1 + logw -- plus ``logw`` (N,),
-        the per-row 1/2 sum_{weight > 0} log weight, left on the device."""
-        raise NotImplementedError("%s: per-entry noise weights (my_data['weight']) are not built for this model; BSC_ET, MCA_ET "
-                                  "and MMCA_ET have the weighted E-step" % type(self).__name__)
+    def _obs_estep(self, model_params, y, obs):
+        """Per model: selection and T = 1 E-step of ``y`` under the observation record ``obs`` (what ``_observation``
+        returned), run inside an evaluation with ``_rows_gemm`` set.  ``('mask', mask)``: over the dimensions the mask marks
+        as observed (non-zero).  Returns a dict: ``logpj`` (N, K) device log-joints in the layout of the unmasked E-step,
+        ``cand`` (N, Hprime) int32, ``dn`` (N,) int32 observed dimensions per row, ``c0`` / ``c1`` with log p(s, y_obs) = logpj
+        + c0 + D_n c1, ``lay`` (``_recon_layout``), for MCA ``par`` (the power tables), and ``logw`` = None.  ``('weight',
+        weight)``: ``y`` observed with the per-entry noise variances sigma^2 / weight (0 = not observed) -- the
+        same dict with log p(s, y | weight) = logpj + c0 + D_n c1 + logw, ``logw`` (N,) the per-row 1/2 sum_{weight > 0} log
+        weight, left on the device."""
+        what = "per-entry noise weights" if obs[0] == 'weight' else "missing values"
+        raise NotImplementedError("%s: %s (my_data['%s']) are not built for this model; BSC_ET, MCA_ET and MMCA_ET have the %s "
+                                  "E-step" % (type(self).__name__, what, obs[0], self._OBS_KIND[obs[0]]))
 
     @staticmethod
     def _observation(my_data):
@@ -1640,18 +1618,11 @@ class DeviceCAModel(CAModel):
                              "(weight = 0 where mask == 0)")
         return ('weight', weight)
 
-    def _obs_estep(self, model_params, y, obs):
-        """``_masked_estep`` or ``_weighted_estep``, by the kind of observation record."""
-        return (self._weighted_estep if obs[0] == 'weight' else self._masked_estep)(model_params, y, obs[1])
-
     def _masked_admit(self, y, mask, exact=False, what="log_likelihood", key='mask'):
         """Everything that refuses a masked (``key='mask'``) or weighted (``key='weight'``, ``mask`` the weight) call, before
         any launch: the model, ``exact=True``, the record's shape, a weight's values, H'."""
-        if key == 'weight':
-            if type(self)._weighted_estep is DeviceCAModel._weighted_estep:
-                self._weighted_estep(None, None, None)
-        elif type(self)._masked_estep is DeviceCAModel._masked_estep:
-            self._masked_estep(None, None, None)
+        if type(self)._obs_estep is DeviceCAModel._obs_estep:
+            self._obs_estep(None, None, (key, None))
         if exact:
             raise NotImplementedError("%s.%s: exact=True with a %s is not built (the enumeration kernels "
                                       "read every dimension)" % (type(self).__name__, what, key))
@@ -1676,7 +1647,7 @@ class DeviceCAModel(CAModel):
                                  "never clamped")
         if self.Hprime > 16:
             raise _lib.HipError("%s: the %s E-step holds H' <= 16 candidates, got %d"
-                                % (type(self).__name__, "weighted" if key == 'weight' else "masked", self.Hprime))
+                                % (type(self).__name__, self._OBS_KIND[key], self.Hprime))
 
     def _weight_resident(self, weight):
         """``weight`` (NumPy, torch or DeviceArray of any real numeric type) as a float64 device tensor with unit column
@@ -1684,12 +1655,16 @@ class DeviceCAModel(CAModel):
         converted once."""
         t = getattr(weight, "tensor", weight)
         if not torch.is_tensor(t):
-            t = torch.from_numpy(np.ascontiguousarray(np.asarray(t), dtype=np.float64))
-        t = t.to(device=self.device, dtype=torch.float64)
-        N, D = t.shape
+            t = self._f64_dev(np.asarray(t))
+        return self._record_rows(t.to(device=self.device, dtype=torch.float64))
+
+    def _record_rows(self, t):
+        """An (N, D) observation record on the device with unit column stride (copied if it has another), and its leading
+        dimension."""
+        D = t.shape[1]
         if t.stride(1) != 1 or t.stride(0) < D:
             t = t.contiguous()
-        return t, int(t.stride(0)) if N > 1 else max(int(t.stride(0)), D)
+        return t, int(self._row_stride(t, D))
 
     def _weighted_prepare(self, Y, Wg, ldo, mu=None, x0=False):
         """pm_weighted_prepare_f64: (Xw = omega x, Om = omega, X0 = x or None, sum omega x^2, D_n, 1/2 sum log omega per row), x =
@@ -1700,7 +1675,7 @@ class DeviceCAModel(CAModel):
         xn2 = self._buf("wgt_xn2", (N,))
         dn = torch.empty(N, dtype=torch.int32, device=self.device)
         logw = torch.empty(N, dtype=torch.float64, device=self.device)
-        mu_d = torch.from_numpy(np.ascontiguousarray(mu, dtype=np.float64).reshape(-1)).to(self.device) if mu is not None else None
+        mu_d = self._mu_dev(mu)
         self._call("weighted_prepare", "pm_weighted_prepare_f64", _ptr(Y), max(int(Y.stride(0)), D), _ptr(Wg), ldo, _ptr(mu_d),
                    N, D, _ptr(Xw), D, _ptr(Om), D, _ptr(X0), D, _ptr(xn2), _ptr(dn), _ptr(logw), self._stream())
         return Xw, Om, X0, xn2, dn, logw * 0.5
@@ -1716,10 +1691,7 @@ class DeviceCAModel(CAModel):
             t = t.view(torch.uint8)
         elif t.dtype != torch.uint8:
             t = (t != 0).view(torch.uint8)
-        N, D = t.shape
-        if t.stride(1) != 1 or t.stride(0) < D:
-            t = t.contiguous()
-        return t, int(t.stride(0)) if N > 1 else max(int(t.stride(0)), D)
+        return self._record_rows(t)
 
     def _masked_prepare(self, Y, M, ldm, mu=None):
         """pm_masked_prepare_f64: (X0 = m ? y - mu : 0, Mf = m ? 1 : 0, |X0|^2 per row, D_n per row)."""
@@ -1727,7 +1699,7 @@ class DeviceCAModel(CAModel):
         X0, Mf = self._buf("mask_x0", (N, D)), self._buf("mask_mf", (N, D))
         xn2 = self._buf("mask_xn2", (N,))
         dn = torch.empty(N, dtype=torch.int32, device=self.device)
-        mu_d = torch.from_numpy(np.ascontiguousarray(mu, dtype=np.float64).reshape(-1)).to(self.device) if mu is not None else None
+        mu_d = self._mu_dev(mu)
         self._call("masked_prepare", "pm_masked_prepare_f64", _ptr(Y), max(int(Y.stride(0)), D), _ptr(M), ldm, _ptr(mu_d), N, D,
                    _ptr(X0), D, _ptr(Mf), D, _ptr(xn2), _ptr(dn), self._stream())
         return X0, Mf, xn2, dn
@@ -1739,28 +1711,17 @@ class DeviceCAModel(CAModel):
         g = self._gemm_nt(Mf, (Wt * Wt).contiguous(), self._buf("mask_g", (N, H)), "masked_gemm")
         return b, g
 
-    def _reconstruct_masked(self, model_params, y, obs, N, variance=False):
-        """``_reconstruct`` from the masked or weighted E-step's log-joints (``obs``: what ``_observation`` returned): the
-        expectation and product kernels are the unmasked ones, so the estimate (and with ``variance`` its variance given the
-        observed dimensions) covers all D dimensions."""
-        out = self._obs_estep(model_params, y, obs)
-        lay, lp, cand = out["lay"], out["logpj"], out["cand"]
-        K = lp.shape[1]
-        mu = lay.get("mu")
-        if mu is not None and not np.any(np.asarray(mu)):
-            mu = None
-        es = self._recon_expect(lp, K, N, cand=cand, table=lay.get("table"), blocks=lay["blocks"], soff=lay["soff"],
-                                moff=lay["moff"], ones=mu is not None)
-        Yhat = self._recon_product(es, es.shape[1], es.shape[1], lay["W"], mu)
-        if lay.get("mca") and self.no_states:
-            par = out["par"]
-            ld = lp.stride(0) if N > 1 else max(int(lp.stride(0)), K)
-            self._call("recon_mca", "pm_recon_mca_f64", _ptr(lp), ld, None, _ptr(cand), _ptr(self._masks()),
-                       _ptr(par["Wrho"]), ctypes.c_double(1. / par["rho"]), int(bool(self.signed_w)), N, self.H, self.D,
-                       self.Hprime, self.no_states, _ptr(Yhat), self.D, self._stream())
-        if variance:
-            return Yhat, self._recon_variance(lp, K, N, cand, lay, Yhat, mu, out.get("par"))
-        return Yhat
+    def _obs_prepare(self, Y, obs, mu=None, x0=False):
+        """The record of ``obs`` on the device and the prepare kernel of its kind: ``(R, ldr, Xa, Xb, X0, xn2, dn, logw)`` -- the
+        record and its leading dimension; the two operands of ``_masked_dense`` (mask: x and m, weight: omega x and omega);
+        x itself (weight: only with ``x0``); |x|^2 (omega-weighted) and D_n per row; weight: 1/2 sum log omega per row, else
+        None."""
+        if obs[0] == 'weight':
+            R, ldr = self._weight_resident(obs[1])
+            return (R, ldr) + self._weighted_prepare(Y, R, ldr, mu, x0)
+        R, ldr = self._mask_resident(obs[1])
+        X0, Mf, xn2, dn = self._masked_prepare(Y, R, ldr, mu)
+        return R, ldr, X0, Mf, X0, xn2, dn, None
 
     def _log_likelihood_masked(self, model_params, my_data, per_datapoint, exact):
         """``log_likelihood`` with ``my_data['mask']``: log sum_{s in K_n} p(s, y_obs,n), the per-row constant c0 + D_n c1; with
@@ -1770,20 +1731,11 @@ class DeviceCAModel(CAModel):
         N = int(y.shape[0])
         if N == 0:
             return np.empty(0) if per_datapoint else self._sum_over_ranks(0.0)
-        saved = self._eval_begin()
-        try:
-            self._par, self._rows_gemm = {}, True
+        with self._evaluation():
             out = self._obs_estep(dict(model_params), y, obs)
-            logpj, dn, c0, c1 = out["logpj"], out["dn"], out["c0"], out["c1"]
+            dn, c0, c1 = out["dn"], out["c0"], out["c1"]
             logw = out["logw"].cpu().numpy() if out.get("logw") is not None else None      # (weights: 1/2 sum log omega)
-            K = logpj.shape[1]
-            lib = _lib.load(self.deterministic)
-            work = torch.empty(int(lib.pm_rows_lse_work_len(N)), dtype=torch.float64, device=self.device)
-            total = torch.empty(1, dtype=torch.float64, device=self.device)
-            rows = torch.empty(N, dtype=torch.float64, device=self.device) if per_datapoint else None
-            ld = logpj.stride(0) if N > 1 else max(int(logpj.stride(0)), K)
-            self._call("loglik_rows", "pm_rows_lse_f64", _ptr(logpj), ld, N, K, ctypes.c_double(1.0), None, _ptr(rows),
-                       _ptr(work), _ptr(total), self._stream())
+            rows, total = self._rows_lse(out["logpj"], 1.0, per_datapoint)
             if per_datapoint:
                 rows = rows.cpu().numpy() + (c0 + dn.cpu().numpy().astype(np.float64) * c1)
                 return rows if logw is None else rows + logw
@@ -1791,46 +1743,69 @@ class DeviceCAModel(CAModel):
             local = float(total.cpu()[0]) + N * c0 + int(dn.sum(dtype=torch.int64)) * c1
             if logw is not None:
                 local += float(np.sum(logw))
-        finally:
-            self._par = {}
-            self._eval_end(saved)
         return self._sum_over_ranks(local)
 
+    # ---- the enumeration entries --------------------------------------------------------------
+    def _exact_upload(self, arrays):
+        """The arrays of the ``_loglik_exact`` hook (or of ``_exact_linear``) as float64 device tensors, None kept."""
+        return {k: (torch.from_numpy(np.array(v, dtype=np.float64, order="C")).to(self.device) if v is not None else None)
+                for k, v in arrays.items()}
+
+    def _exact_entry(self, model_params, what):
+        """The ``_loglik_exact`` hook as a call: ``(kind, arrays, entry)``.  ``entry(call, Yp, ld, n, *out)`` runs
+        ``call(name, Yp, ld, <parameters>, n, D, H, *out, stream)`` with the entry name and the parameter arguments of the
+        hook's kind for ``what`` -- 'loglik' (pm_loglik_exact_*), 'recon' (pm_recon_exact_*) or 'encode' (E[s]: the linear
+        kind's reconstruction entry, pm_encode_exact_mca_f64)."""
+        kind, arrays, sc = self._loglik_exact(model_params)
+        dev = self._exact_upload(arrays)
+        p, dbl, ll = (lambda k: _ptr(dev.get(k))), ctypes.c_double, what == "loglik"
+        name = "pm_encode_exact_mca_f64" if (what == "encode" and kind == "mca") else \
+            "pm_%s_exact_%s_f64" % ("loglik" if ll else "recon", kind)
+
+        if kind == "lin":
+            args = [p("mu"), p("P"), p("G"), p("logp"), p("values"), int(arrays["values"].shape[0])] \
+                + ([dbl(sc["cst"]), dbl(sc["qcoef"])] if ll else [])
+        elif kind == "mca":
+            args = [p("Wrho"), dbl(sc["inv_rho"]), int(sc["signed"]), dbl(sc["lp1"]), dbl(sc["lp0"]), dbl(sc["inv_s2"])]
+        else:
+            args = [p("P")] + ([p("wdiag"), p("Lw")] if ll else []) + [p("M"), p("Psi"), p("mu"), p("logp")]
+        if ll and kind != "lin":
+            args.append(dbl(sc["cst"]))
+
+        def entry(call, Yp, ld, n, *out, dev=dev):         # (``dev`` keeps the uploads behind ``args`` alive)
+            call(name, Yp, ld, *args, n, self.D, self.H, *out, self._stream())
+        return kind, arrays, entry
+
+    def _exact_limits(self, entry, ldo):
+        """The limits first, before the data reaches the device or anything is launched: with no rows the entry checks its
+        arguments (PM_ERANGE past a limit -> HipError) and returns.  Not a launch: it does not go through the timer."""
+        probe = torch.empty(1, dtype=torch.float64, device=self.device)
+        entry(lambda name, *a: _lib.call(name, *a, det=self.deterministic), None, self.D, 0, None, ldo, _ptr(probe))
+
+    def _exact_rows(self, label, entry, y, out):
+        """The reconstruction or encode ``entry`` over the resident rows of ``y`` into ``out`` (N, ldo), which it returns."""
+        Y = self._resident(y)["Y"]
+        N, D = Y.shape
+        lib = _lib.load(self.deterministic)
+        work = torch.empty(max(int(lib.pm_recon_exact_work_len(N, self.H, D)), 1), dtype=torch.float64, device=self.device)
+        entry(lambda name, *a: self._call(label, name, *a), _ptr(Y), max(int(Y.stride(0)), D), N, _ptr(out), out.shape[1],
+              _ptr(work))
+        return out
+
     def _log_likelihood_exact(self, model_params, my_data, per_datapoint):
-        saved = self._eval_begin()
-        try:
-            res = self._resident(my_data['y'])
-            Y = res["Y"]
-            N, D, H = Y.shape[0], self.D, self.H
-            kind, arrays, sc = self._loglik_exact(dict(model_params))
-            dev = {k: (torch.from_numpy(np.array(v, dtype=np.float64, order="C")).to(self.device) if v is not None else None)
-                   for k, v in arrays.items()}
+        with self._evaluation(rows_gemm=False):
+            Y = self._resident(my_data['y'])["Y"]
+            N, D = Y.shape[0], self.D
+            _, _, entry = self._exact_entry(dict(model_params), "loglik")
             lib = _lib.load(self.deterministic)
-            wl = int(lib.pm_loglik_exact_work_len(N, H))
-            work = torch.empty(max(wl, 1), dtype=torch.float64, device=self.device)
+            work = torch.empty(max(int(lib.pm_loglik_exact_work_len(N, self.H)), 1), dtype=torch.float64, device=self.device)
             total = torch.empty(1, dtype=torch.float64, device=self.device)
             rows = torch.empty(N, dtype=torch.float64, device=self.device) if per_datapoint else None
-            Yp = _ptr(Y) if N else None
-            ld = max(int(Y.stride(0)), D) if N else D
-            out = (_ptr(rows), _ptr(work), _ptr(total), self._stream())
-            dbl = ctypes.c_double
-            if kind == "lin":
-                self._call("loglik_exact", "pm_loglik_exact_lin_f64", Yp, ld, _ptr(dev.get("mu")), _ptr(dev["P"]),
-                           _ptr(dev["G"]), _ptr(dev["logp"]), _ptr(dev["values"]), int(arrays["values"].shape[0]),
-                           dbl(sc["cst"]), dbl(sc["qcoef"]), N, D, H, *out)
-            elif kind == "mca":
-                self._call("loglik_exact", "pm_loglik_exact_mca_f64", Yp, ld, _ptr(dev["Wrho"]), dbl(sc["inv_rho"]),
-                           int(sc["signed"]), dbl(sc["lp1"]), dbl(sc["lp0"]), dbl(sc["inv_s2"]), dbl(sc["cst"]), N, D, H,
-                           *out)
-            else:
-                self._call("loglik_exact", "pm_loglik_exact_gsc_f64", Yp, ld, _ptr(dev["P"]), _ptr(dev.get("wdiag")),
-                           _ptr(dev.get("Lw")), _ptr(dev["M"]), _ptr(dev["Psi"]), _ptr(dev["mu"]), _ptr(dev["logp"]),
-                           dbl(sc["cst"]), N, D, H, *out)
+            entry(lambda name, *a: self._call("loglik_exact", name, *a), _ptr(Y) if N else None,
+                  max(int(Y.stride(0)), D) if N else D, N, _ptr(rows), _ptr(work), _ptr(total))
             if per_datapoint:
                 return rows.cpu().numpy()
             local = float(total.cpu()[0])
-        finally:
-            self._eval_end(saved)
         return self._sum_over_ranks(local)
 
     def _reconstruct_exact(self, model_params, y, N):
@@ -1838,42 +1813,13 @@ class DeviceCAModel(CAModel):
         arrays, scalars)``: 'lin' -- E[s] by pm_recon_exact_lin_f64, then mu + E[s] W^T through ``_recon_product``; 'gsc' --
         E[s o z] by pm_recon_exact_gsc_f64 and the same product with W; 'mca' -- Yhat itself by pm_recon_exact_mca_f64."""
         D, H = self.D, self.H
-        kind, arrays, sc = self._loglik_exact(model_params)
-        dev = {k: (torch.from_numpy(np.array(v, dtype=np.float64, order="C")).to(self.device) if v is not None else None)
-               for k, v in arrays.items()}
-        dbl = ctypes.c_double
-        mu = arrays.get("mu") if kind == "lin" else None
-        if mu is not None and not np.any(mu):
-            mu = None
+        kind, arrays, entry = self._exact_entry(model_params, "recon")
+        mu = self._nonzero_mu(arrays.get("mu")) if kind == "lin" else None
         Kp = D if kind == "mca" else (H + (1 if mu is not None else 0) + 7) // 8 * 8
-
-        def entry(call, Yp, ld, n, out, work):
-            if kind == "lin":
-                call("pm_recon_exact_lin_f64", Yp, ld, _ptr(dev.get("mu")), _ptr(dev["P"]), _ptr(dev["G"]), _ptr(dev["logp"]),
-                     _ptr(dev["values"]), int(arrays["values"].shape[0]), n, D, H, out, Kp, work, self._stream())
-            elif kind == "mca":
-                call("pm_recon_exact_mca_f64", Yp, ld, _ptr(dev["Wrho"]), dbl(sc["inv_rho"]), int(sc["signed"]), dbl(sc["lp1"]),
-                     dbl(sc["lp0"]), dbl(sc["inv_s2"]), n, D, H, out, Kp, work, self._stream())
-            else:
-                call("pm_recon_exact_gsc_f64", Yp, ld, _ptr(dev["P"]), _ptr(dev["M"]), _ptr(dev["Psi"]), _ptr(dev["mu"]),
-                     _ptr(dev["logp"]), n, D, H, out, Kp, work, self._stream())
-
-        # the limits first, before the data reaches the device or anything is launched: with no rows the entry checks its
-        # arguments (PM_ERANGE past a limit -> HipError) and returns
-        probe = torch.empty(1, dtype=torch.float64, device=self.device)
-        entry(lambda name, *a: _lib.call(name, *a, det=self.deterministic), None, D, 0, None, _ptr(probe))
-        res = self._resident(y)
-        Y = res["Y"]
-        lib = _lib.load(self.deterministic)
-        work = torch.empty(max(int(lib.pm_recon_exact_work_len(N, H, D)), 1), dtype=torch.float64, device=self.device)
-        ld = max(int(Y.stride(0)), D)
-        launch = lambda name, *a: self._call("recon_exact", name, *a)
+        self._exact_limits(entry, Kp)
         if kind == "mca":
-            Yhat = torch.empty((N, D), dtype=torch.float64, device=self.device)
-            entry(launch, _ptr(Y), ld, N, _ptr(Yhat), _ptr(work))
-            return Yhat
+            return self._exact_rows("recon_exact", entry, y, torch.empty((N, D), dtype=torch.float64, device=self.device))
         es = torch.zeros((N, Kp), dtype=torch.float64, device=self.device)
         if mu is not None:
             es[:, H] = 1.0
-        entry(launch, _ptr(Y), ld, N, _ptr(es), _ptr(work))
-        return self._recon_product(es, Kp, Kp, model_params['W'], mu)
+        return self._recon_product(self._exact_rows("recon_exact", entry, y, es), model_params['W'], mu)

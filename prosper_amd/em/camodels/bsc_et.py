@@ -649,53 +649,26 @@ class BSC_ET(DeviceCAModel):
                 "table": self.state_matrix if self.no_states else None, "W": model_params['W'],
                 "mu": model_params.get('mu')}
 
-    def _masked_estep(self, model_params, y, mask):
+    def _obs_estep(self, model_params, y, obs):
         """Missing values: x = y - mu over the observed dimensions, b = W^T diag(m) x and diag G_n = diag(W^T
         diag(m) W) as two one-kernel GEMMs, then pm_bsc_masked_estep_f64 -- candidates by b_h / sqrt(G_n[h,h]), the
-        candidates' masked pair products, log-joints in the unmasked layout.  c0 = H log(1 - pi), c1 = -1/2 log(2 pi sigma^2)."""
+        candidates' masked pair products, log-joints in the unmasked layout.  c0 = H log(1 - pi), c1 = -1/2 log(2 pi sigma^2).
+        Per-entry noise weights: the same with b = W^T diag(omega) x and diag G_n = diag(W^T diag(omega) W) from
+        pm_weighted_prepare_f64's Xw = omega x and Om = omega, then pm_bsc_weighted_estep_f64 -- the same selection rule, the
+        candidates' weighted pair products.  ``logw``: 1/2 sum log omega per row."""
         lay = self._recon_layout(model_params)
-        res = self._resident(y)
-        Y = res["Y"]
+        Y = self._resident(y)["Y"]
         N, D = Y.shape
         H, Hp, S = self.H, self.Hprime, self.no_states
-        M, ldm = self._mask_resident(mask)
-        mu = model_params.get('mu')
-        if mu is not None and not np.any(np.asarray(mu)):
-            mu = None
-        X0, Mf, xn2, dn = self._masked_prepare(Y, M, ldm, mu)
-        Wt = torch.from_numpy(np.ascontiguousarray(np.asarray(model_params['W'], dtype=np.float64).T)).to(self.device)
-        b, g = self._masked_dense(X0, Mf, Wt)
+        R, ldr, Xa, Xb, _, xn2, dn, logw = self._obs_prepare(Y, obs, self._nonzero_mu(model_params.get('mu')))
+        Wt = self._f64_dev(np.asarray(model_params['W'], dtype=np.float64).T)
+        b, g = self._masked_dense(Xa, Xb, Wt)
         pies, sigma = float(model_params['pi']), float(model_params['sigma'])
         P = self._estep_params(LoglikPoint(), pies, sigma, np.zeros(1))
         cand = torch.empty((N, Hp), dtype=torch.int32, device=self.device)
         logpj, _ = self._estep_outputs(N)
-        self._call("masked_estep", "pm_bsc_masked_estep_f64", _ptr(b), H, _ptr(g), H, _ptr(xn2), _ptr(M), ldm, _ptr(Wt), D,
-                   _ptr(self._state_tables()["masks"]), S, ctypes.byref(P), N, H, D, Hp, _ptr(cand), _ptr(logpj),
-                   logpj.stride(0), self._stream())
-        return {"logpj": logpj, "cand": cand, "dn": dn, "c0": H * np.log(1. - pies),
-                "c1": -0.5 * np.log(2 * _PI * sigma ** 2), "lay": lay}
-
-    def _weighted_estep(self, model_params, y, weight):
-        """Per-entry noise weights: ``_masked_estep`` with b = W^T diag(omega) x and diag G_n = diag(W^T diag(omega)
-        W) from pm_weighted_prepare_f64's Xw = omega x and Om = omega, then pm_bsc_weighted_estep_f64 -- the same selection
-        rule, the candidates' weighted pair products, log-joints in the unmasked layout.  ``logw``: 1/2 sum log omega per row."""
-        lay = self._recon_layout(model_params)
-        res = self._resident(y)
-        Y = res["Y"]
-        N, D = Y.shape
-        H, Hp, S = self.H, self.Hprime, self.no_states
-        Wg, ldo = self._weight_resident(weight)
-        mu = model_params.get('mu')
-        if mu is not None and not np.any(np.asarray(mu)):
-            mu = None
-        Xw, Om, _, xn2, dn, logw = self._weighted_prepare(Y, Wg, ldo, mu)
-        Wt = torch.from_numpy(np.ascontiguousarray(np.asarray(model_params['W'], dtype=np.float64).T)).to(self.device)
-        b, g = self._masked_dense(Xw, Om, Wt)
-        pies, sigma = float(model_params['pi']), float(model_params['sigma'])
-        P = self._estep_params(LoglikPoint(), pies, sigma, np.zeros(1))
-        cand = torch.empty((N, Hp), dtype=torch.int32, device=self.device)
-        logpj, _ = self._estep_outputs(N)
-        self._call("weighted_estep", "pm_bsc_weighted_estep_f64", _ptr(b), H, _ptr(g), H, _ptr(xn2), _ptr(Wg), ldo, _ptr(Wt), D,
+        kind = self._OBS_KIND[obs[0]]
+        self._call(kind + "_estep", "pm_bsc_%s_estep_f64" % kind, _ptr(b), H, _ptr(g), H, _ptr(xn2), _ptr(R), ldr, _ptr(Wt), D,
                    _ptr(self._state_tables()["masks"]), S, ctypes.byref(P), N, H, D, Hp, _ptr(cand), _ptr(logpj),
                    logpj.stride(0), self._stream())
         return {"logpj": logpj, "cand": cand, "dn": dn, "c0": H * np.log(1. - pies),
@@ -1211,8 +1184,8 @@ class BSC_ET(DeviceCAModel):
             ecoef = -0.5 * beta / sigma / sigma
             odds = float((beta if anneal['anneal_prior'] else 1.0) * np.log(pies / (1. - pies)))
             _, arrays, _ = self._exact_linear(W, sigma / np.sqrt(beta), [0., 1.], np.tile([0., odds], (H, 1)))
-            up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)
-            P, G, logp, values = up(arrays["P"]), up(arrays["G"]), up(arrays["logp"]), up(arrays["values"])
+            up = self._exact_upload(arrays)
+            P, G, logp, values = up["P"], up["G"], up["logp"], up["values"]
             npair = H * (H + 1) // 2
             rows = min(my_N, self.XE_ROWS)
             E = self._buf("xe_E", (my_N, H))
@@ -1248,8 +1221,8 @@ class BSC_ET(DeviceCAModel):
             sumE, sum_v, sum_x2 = tot[:H], tot[H + npair], tot[H + npair + 1]
             packed[o_mus:o_sc] = sumE
             # the expected energy from the moments: sum_n (|x_n|^2 - 2 x_n^T W E[s]_n + tr(W^T W E[s s^T]_n))
-            Wt = up(W.T)
-            WtW = up(W.T @ W)
+            Wt = self._f64_dev(W.T)
+            WtW = self._f64_dev(W.T @ W)
             energy = sum_x2 - 2.0 * (Wt * Wpx).sum() + (WtW * Wq).sum()
             packed[:o_wq].view(H, D).copy_(Wpx)
             if rec["mu_d"] is not None:            # (_finalize takes Wp against y and subtracts sum E[s] mu^T itself)

@@ -520,6 +520,13 @@ class GSC(DeviceCAModel):
         cand, _, _, _ = self._run(1.0, model_params, res, None, logpj=logpj)
         return DeviceArray(logpj), DeviceArray(cand, np.int64)
 
+    @staticmethod
+    def _sigma_ok(model_params):
+        """Whether the noise covariance (scalar, diagonal or full) is positive definite; where it is not, every read-out
+        returns NaN rows."""
+        sig = np.asarray(model_params['sigma_sq'], dtype=np.float64)
+        return not (np.linalg.eigvalsh(0.5 * (sig + sig.T)).min() <= 0) if sig.ndim == 2 else bool(np.all(sig > 0))
+
     def _loglik_terms(self, model_params, my_data):
         """log_likelihood.  Given s, y is Gaussian: N(y; W_s mu_s, C_s), C_s = Sigma + W_s Psi_s W_s^T, Sigma the
         noise covariance (scalar, diagonal or full).  By the determinant lemma and Woodbury, log det C_s = log det Sigma +
@@ -530,7 +537,7 @@ class GSC(DeviceCAModel):
         hence c = sum_h log(1 - pi_h) - D/2 log(2 pi) - 1/2 log det Sigma."""
         pi = np.broadcast_to(np.asarray(model_params['pi'], dtype=np.float64), (self.H,))
         sig = np.asarray(model_params['sigma_sq'], dtype=np.float64)
-        if (np.linalg.eigvalsh(0.5 * (sig + sig.T)).min() <= 0) if sig.ndim == 2 else not np.all(sig > 0):
+        if not self._sigma_ok(model_params):
             # a noise covariance that is not positive definite: every row NaN (nothing raises, no datapoint is dropped)
             N = self._resident(my_data['y'])["Y"].shape[0]
             return torch.full((N, 1), float("nan"), dtype=torch.float64, device=self.device), 1.0, float("nan")
@@ -546,7 +553,7 @@ class GSC(DeviceCAModel):
         c = float(np.log(1. - pi).sum()) - 0.5 * self.D * np.log(2 * np.pi) - 0.5 * logdet
         return logpj.tensor, 0.5, c
 
-    def _reconstruct(self, model_params, my_data, N, variance=False):
+    def _reconstruct(self, model_params, y, obs, N, variance=False):
         """reconstruct: yhat_n = W E[s z | y_n] = sum_s q_n(s) W_s kappa_s(y_n), kappa_s = mu_s + Lambda_s^-1
         W_s^T Sigma^-1 (y_n - W_s mu_s) = E[z_s | s, y_n].  The E-step pass returns xpt_sz = sum_s w_n(s) kappa_s with the
         reference's weights exp(beta (lp + prior)), lp carrying the Gaussian terms WITHOUT the 1/2 (gsc_et.py:341-354): at
@@ -554,15 +561,14 @@ class GSC(DeviceCAModel):
         generative model's, and kappa_s does not depend on beta.  Then Yhat = xpt_sz W^T.  The pass floors every state's
         weight at DBL_MIN as the reference does (:355-356): visible only in a row whose weights all underflow.  A noise
         covariance that is not positive definite: every row NaN.  ``variance``: the pair (Yhat, V), ``_recon_variance_gsc``."""
-        sig = np.asarray(model_params['sigma_sq'], dtype=np.float64)
-        if (np.linalg.eigvalsh(0.5 * (sig + sig.T)).min() <= 0) if sig.ndim == 2 else not np.all(sig > 0):
+        if not self._sigma_ok(model_params):
             nan = lambda: torch.full((N, self.D), float("nan"), dtype=torch.float64, device=self.device)
             return (nan(), nan()) if variance else nan()
         self._lpi_scale = 2.0          # (an attribute of the evaluation only: _eval_end restores the model's)
         self._require_scalar()
-        res = self._resident(my_data['y'])
+        res = self._resident(y)
         cand, _, xsz, _ = self._run(2.0, model_params, res, None)
-        W = torch.from_numpy(np.ascontiguousarray(model_params['W'], dtype=np.float64)).to(self.device)
+        W = self._f64_dev(model_params['W'])
         out = torch.empty((N, self.D), dtype=torch.float64, device=self.device)
         self._call("recon_gemm", "pm_gemm_nt_rows_f64", _ptr(xsz), max(int(xsz.stride(0)), self.H), _ptr(W), self.H,
                    _ptr(out), self.D, N, self.D, self.H, self._stream())
@@ -570,18 +576,17 @@ class GSC(DeviceCAModel):
             return out, self._recon_variance_gsc(model_params, res, cand, out, N)
         return out
 
-    def _encode(self, model_params, my_data, N):
+    def _encode(self, model_params, y, obs, N):
         """encode: mean = E[s_h z_h | y_n] (xpt_sz) and prob = E[s_h | y_n] (xpt_s) of the pass ``_reconstruct``
         runs -- beta = 1/2, every logit doubled, every state's weight floored at DBL_MIN as there --, returned as copies: the
         pass's two output buffers alternate.  prob is clamped at 1 (rounding).  A noise covariance that is not positive
         definite: every row NaN."""
-        sig = np.asarray(model_params['sigma_sq'], dtype=np.float64)
-        if (np.linalg.eigvalsh(0.5 * (sig + sig.T)).min() <= 0) if sig.ndim == 2 else not np.all(sig > 0):
+        if not self._sigma_ok(model_params):
             nan = lambda: torch.full((N, self.H), float("nan"), dtype=torch.float64, device=self.device)
             return nan(), nan()
         self._lpi_scale = 2.0          # (an attribute of the evaluation only: _eval_end restores the model's)
         self._require_scalar()
-        res = self._resident(my_data['y'])
+        res = self._resident(y)
         _, xs, xsz, _ = self._run(2.0, model_params, res, None)
         return xsz.clone(memory_format=torch.contiguous_format), torch.clamp(xs, max=1.0).contiguous()
 
@@ -628,8 +633,7 @@ class GSC(DeviceCAModel):
         dev = self.device
         Ys = torch.empty((M, N, D), dtype=torch.float64, device=dev)
         Sl = torch.empty((M, N, H), dtype=torch.float64, device=dev) if latents else None
-        sig = np.asarray(model_params['sigma_sq'], dtype=np.float64)
-        if (np.linalg.eigvalsh(0.5 * (sig + sig.T)).min() <= 0) if sig.ndim == 2 else not np.all(sig > 0):
+        if not self._sigma_ok(model_params):
             Ys.fill_(float("nan"))
             if latents:
                 Sl.fill_(float("nan"))
@@ -641,7 +645,7 @@ class GSC(DeviceCAModel):
         cand, _, _, _ = self._run(2.0, model_params, res, None, logpj=lp)
         par = self._tables_for(model_params, res)
         scores = self._scores_used
-        Wt = torch.from_numpy(np.ascontiguousarray(np.asarray(model_params['W'], dtype=np.float64).T)).to(dev)
+        Wt = self._f64_dev(np.asarray(model_params['W'], dtype=np.float64).T)
         zeros = torch.zeros(N, dtype=torch.float64, device=dev)
         A = max(gamma, 1)
         rows = self._sample_rows(N, M, A)
@@ -669,8 +673,7 @@ class GSC(DeviceCAModel):
         """reconstruct(exact=True): yhat_n = W E_n[s o z] over all 2^H supports, E_n[s o z] = sum_s q_n(s)
         kappa_s(y_n) by pm_recon_exact_gsc_f64 from the whitened products of ``_loglik_exact`` (scalar, diagonal or full
         Sigma).  A noise covariance that is not positive definite: every row NaN, as ``_reconstruct``."""
-        sig = np.asarray(model_params['sigma_sq'], dtype=np.float64)
-        if (np.linalg.eigvalsh(0.5 * (sig + sig.T)).min() <= 0) if sig.ndim == 2 else not np.all(sig > 0):
+        if not self._sigma_ok(model_params):
             return torch.full((N, self.D), float("nan"), dtype=torch.float64, device=self.device)
         return super()._reconstruct_exact(model_params, y, N)
 
@@ -687,7 +690,7 @@ class GSC(DeviceCAModel):
         Psi = 0.5 * (Psi + Psi.T) if Psi.ndim == 2 else np.diag(np.broadcast_to(Psi, (H,)))
         sig = np.asarray(model_params['sigma_sq'], dtype=np.float64)
         arrays = {"Psi": Psi, "mu": mu}
-        if (np.linalg.eigvalsh(0.5 * (sig + sig.T)).min() <= 0) if sig.ndim == 2 else not np.all(sig > 0):
+        if not self._sigma_ok(model_params):
             # (as _loglik_terms: every row NaN -- the kernel runs on neutral products, the constant carries the NaN)
             arrays.update(P=np.zeros((D, H)), M=np.zeros((H, H)), wdiag=np.ones(D))
             logdet = float("nan")

@@ -276,15 +276,16 @@ class MCA_ET(DeviceCAModel):
                 # (encode, DESIGN 4.23: which candidate positions a multi-cause state holds -- the mean above has no use for it)
                 "encode_table": self.state_matrix if self.no_states else None}
 
-    def _masked_select(self, res, M, ldm, par, A, wn, xn2):
-        """Masked selection: the H' smallest R[n,h] = sum_d m_d max(W_hd - y_d, 0), ranked as ``_select_on_device`` does."""
+    def _obs_select(self, res, kind, R, ldr, par, A, wn, xn2):
+        """Masked or weighted selection (``kind``): the H' smallest sum_d m_d max(W_hd - y_d, 0), with a
+        weight sum_d omega_d max(W_hd - y_d, 0), ranked as ``_select_on_device`` does."""
         Y = res["Y"]
         N, D = Y.shape
         H = self.H
-        R = self._buf("mca_sim", (N, H))
-        self._call("select_scores", "pm_mca_masked_select_scores_f64", _ptr(Y), D, _ptr(M), ldm, _ptr(par["Wt"]), D, _ptr(R),
-                   H, N, H, D, self._stream())
-        return self._rank_smallest(R, res)
+        sim = self._buf("mca_sim", (N, H))
+        self._call("select_scores", "pm_mca_%s_select_scores_f64" % kind, _ptr(Y), D, _ptr(R), ldr, _ptr(par["Wt"]), D,
+                   _ptr(sim), H, N, H, D, self._stream())
+        return self._rank_smallest(sim, res)
 
     def _rank_smallest(self, R, res):
         """The H' smallest entries of each row of R (N, H), ascending: the selection kernel in raw mode."""
@@ -295,68 +296,32 @@ class MCA_ET(DeviceCAModel):
                    None, None, None, 0, self.gamma, None, N, H, Hp, 1 | 4 | 8, _ptr(cand), None, 0, None, self._stream())
         return cand
 
-    def _masked_estep(self, model_params, y, mask):
+    def _obs_estep(self, model_params, y, obs):
         """Missing values: the model of ``_loglik_terms`` over the observed dimensions.  One-cause energies
         from |W_h|^2_obs - 2 <W_h, y>_obs + |y|^2_obs (two one-kernel GEMMs on pm_masked_prepare_f64's outputs), multi-cause
-        energies sum_d m_d (y_d - Wbar_d(s))^2 in pm_mca_masked_estep_f64.  c0 = H log(1 - pi), c1 = -1/2 log(2 pi sigma^2)."""
+        energies sum_d m_d (y_d - Wbar_d(s))^2 in pm_mca_masked_estep_f64.  c0 = H log(1 - pi), c1 = -1/2 log(2 pi sigma^2).
+        Per-entry noise weights: the one-cause energies from sum omega W_hd^2 - 2 sum omega W_hd y_d + sum omega
+        y_d^2 (pm_weighted_prepare_f64's outputs) and the multi-cause energies sum_d omega_d (y_d - Wbar_d(s))^2 in
+        pm_mca_weighted_estep_f64.  ``logw``: 1/2 sum log omega per row."""
         lay = self._recon_layout(model_params)
         mp = lay["params"]
         res = self._resident(y)
         Y = res["Y"]
         N, D = Y.shape
         H, Hp, S = self.H, self.Hprime, self.no_states
-        M, ldm = self._mask_resident(mask)
+        kind = self._OBS_KIND[obs[0]]
         masks = self._masks()
-        X0, Mf, xn2, dn = self._masked_prepare(Y, M, ldm)
+        R, ldr, Xa, Xb, X0, xn2, dn, logw = self._obs_prepare(Y, obs, x0=True)
         par = self._tables_for(mp['W'], 1.0, res)
-        A, wn = self._masked_dense(X0, Mf, par["Wt"])
-        cand = self._masked_select(res, M, ldm, par, A, wn, xn2)
+        A, wn = self._masked_dense(Xa, Xb, par["Wt"])
+        cand = self._obs_select(res, kind, R, ldr, par, A, wn, xn2)
         pies, sigma = float(mp['pi']), float(mp['sigma'])
         P = self._params(LoglikPoint(), pies, sigma, par["rho"])
         K = 1 + H + S
         logpj = torch.empty((N, K), dtype=torch.float64, device=self.device)
         lse1 = torch.empty((N,), dtype=torch.float64, device=self.device)
         lseb = torch.empty((N,), dtype=torch.float64, device=self.device)
-        self._call("masked_estep", "pm_mca_masked_estep_f64", _ptr(A), H, _ptr(wn), H, _ptr(xn2), _ptr(X0), D, _ptr(M), ldm,
-                   _ptr(par["Wrho"]), _ptr(cand), _ptr(masks), S, ctypes.byref(P), N, H, D, Hp, _ptr(logpj), K, _ptr(lse1),
-                   _ptr(lseb), self._stream())
-        return {"logpj": logpj, "cand": cand, "dn": dn, "c0": H * np.log(1. - pies),
-                "c1": -0.5 * np.log(2 * _PI * sigma ** 2), "lay": lay, "par": par}
-
-    def _weighted_select(self, res, Wg, ldo, par, A, wn, xn2):
-        """Weighted selection: the H' smallest R[n,h] = sum_d omega_d max(W_hd - y_d, 0), ranked as
-        ``_select_on_device`` does."""
-        Y = res["Y"]
-        N, D = Y.shape
-        H = self.H
-        R = self._buf("mca_sim", (N, H))
-        self._call("select_scores", "pm_mca_weighted_select_scores_f64", _ptr(Y), D, _ptr(Wg), ldo, _ptr(par["Wt"]), D, _ptr(R),
-                   H, N, H, D, self._stream())
-        return self._rank_smallest(R, res)
-
-    def _weighted_estep(self, model_params, y, weight):
-        """Per-entry noise weights: ``_masked_estep`` with the one-cause energies from sum omega W_hd^2 - 2 sum
-        omega W_hd y_d + sum omega y_d^2 (two one-kernel GEMMs on pm_weighted_prepare_f64's outputs) and the multi-cause
-        energies sum_d omega_d (y_d - Wbar_d(s))^2 in pm_mca_weighted_estep_f64.  ``logw``: 1/2 sum log omega per row."""
-        lay = self._recon_layout(model_params)
-        mp = lay["params"]
-        res = self._resident(y)
-        Y = res["Y"]
-        N, D = Y.shape
-        H, Hp, S = self.H, self.Hprime, self.no_states
-        Wg, ldo = self._weight_resident(weight)
-        masks = self._masks()
-        Xw, Om, X0, xn2, dn, logw = self._weighted_prepare(Y, Wg, ldo, x0=True)
-        par = self._tables_for(mp['W'], 1.0, res)
-        A, wn = self._masked_dense(Xw, Om, par["Wt"])
-        cand = self._weighted_select(res, Wg, ldo, par, A, wn, xn2)
-        pies, sigma = float(mp['pi']), float(mp['sigma'])
-        P = self._params(LoglikPoint(), pies, sigma, par["rho"])
-        K = 1 + H + S
-        logpj = torch.empty((N, K), dtype=torch.float64, device=self.device)
-        lse1 = torch.empty((N,), dtype=torch.float64, device=self.device)
-        lseb = torch.empty((N,), dtype=torch.float64, device=self.device)
-        self._call("weighted_estep", "pm_mca_weighted_estep_f64", _ptr(A), H, _ptr(wn), H, _ptr(xn2), _ptr(X0), D, _ptr(Wg), ldo,
+        self._call(kind + "_estep", "pm_mca_%s_estep_f64" % kind, _ptr(A), H, _ptr(wn), H, _ptr(xn2), _ptr(X0), D, _ptr(R), ldr,
                    _ptr(par["Wrho"]), _ptr(cand), _ptr(masks), S, ctypes.byref(P), N, H, D, Hp, _ptr(logpj), K, _ptr(lse1),
                    _ptr(lseb), self._stream())
         return {"logpj": logpj, "cand": cand, "dn": dn, "c0": H * np.log(1. - pies),

@@ -112,16 +112,12 @@ class MMCA_ET(MCA_ET):
         data['candidates'] = DeviceArray(cand, np.int64)
         return data
 
-    def _masked_select(self, res, M, ldm, par, A, wn, xn2):
+    def _obs_select(self, res, kind, R, ldr, par, A, wn, xn2):
         """Masked selection: this model ranks by distance, so the mask goes into its own expression -- the H'
-        smallest sum_d m_d (W_hd - y_d)^2 = |W_h|^2_obs - 2 <W_h, y>_obs + |y|^2_obs, from the E-step's three terms."""
-        R = (wn - 2.0 * A + xn2[:, None]).contiguous()
-        return self._rank_smallest(R, res)
-
-    def _weighted_select(self, res, Wg, ldo, par, A, wn, xn2):
-        """Weighted selection: the H' smallest sum_d omega_d (W_hd - y_d)^2, from the E-step's three weighted
-        terms -- ``_masked_select``'s expression on them."""
-        return self._masked_select(res, Wg, ldo, par, A, wn, xn2)
+        smallest sum_d m_d (W_hd - y_d)^2 = |W_h|^2_obs - 2 <W_h, y>_obs + |y|^2_obs, from the E-step's three terms.
+        Weighted selection: the H' smallest sum_d omega_d (W_hd - y_d)^2, the same expression on the E-step's
+        three weighted terms."""
+        return self._rank_smallest((wn - 2.0 * A + xn2[:, None]).contiguous(), res)
 
     def _finalize(self, stats, model_params, par, A_pi_gamma, B_pi_gamma):
         """W update with inertia and the scalars (mmca_et.py:365-427), one device->host copy."""

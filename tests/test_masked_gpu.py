@@ -86,12 +86,12 @@ def _check_ll(tag, got, want, M, p, H):
 def _capture(m):
     """The model's masked-evaluation hook, wrapped to keep what it returned."""
     kept = {}
-    orig = m._masked_estep
+    orig = m._obs_estep
 
     def hook(*a):
         kept["out"] = orig(*a)
         return kept["out"]
-    m._masked_estep = hook
+    m._obs_estep = hook
     return kept
 
 

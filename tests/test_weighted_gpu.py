@@ -82,12 +82,12 @@ def _check_ll(tag, got, want, Om, p, H, full):
 def _capture(m):
     """The model's weighted-evaluation hook, wrapped to keep what it returned."""
     kept = {}
-    orig = m._weighted_estep
+    orig = m._obs_estep
 
     def hook(*a):
         kept["out"] = orig(*a)
         return kept["out"]
-    m._weighted_estep = hook
+    m._obs_estep = hook
     return kept
 
 
