@@ -2,6 +2,7 @@
 """The reference's bars test (examples/barstests/bars-learning.py + param-bars-*.py) on the MI355X path.
 
     python examples/bars_learning.py [bsc|mca|mmca|dsc|tsc|gsc|mog|mop] [--steps 50] [--N 2000] [--h5]
+    python examples/bars_learning.py bsc|mca|mmca --heldout 500 --infer --exact      (MAP states: truncated against exact)
 
 Generates bars data from ground-truth parameters, runs the annealed EM loop through the drop-in classes and
 reports how well the learned dictionary matches the bars (mean absolute error after the best permutation).
@@ -111,6 +112,11 @@ def main():
                     help="with --heldout: the codes of the held-out datapoints under the learned parameters (encode, DESIGN "
                     "4.23): the mean number of active latents per datapoint, sum_h P(s_h != 0 | y_n), beside the generating "
                     "pi H; with --exact (BSC, MCA, MMCA, the mixtures) also the largest |prob_truncated - prob_exact|")
+    ap.add_argument("--infer", action="store_true",
+                    help="bsc, mca, mmca with --heldout: the MAP state of every held-out datapoint under the learned parameters "
+                    "(inference, H' = 5, gamma = 3) with and without the adaptive re-runs; with --exact (DESIGN 4.26) the share "
+                    "of datapoints whose truncated MAP state is the exact one over all 2^H states, for both settings, and "
+                    "the mean posterior probability of the exact MAP state")
     ap.add_argument("--exact-em", action="store_true",
                     help="bsc: train the same start parameters twice on the same data and schedule -- truncated (H' = 5, gamma = "
                     "3) and with the posterior over all 2^H states (model.exact = True, DESIGN 4.25) -- and print the bars "
@@ -118,6 +124,8 @@ def main():
     a = ap.parse_args()
     if a.exact_em and a.model != "bsc":
         ap.error("--exact-em is built for bsc")
+    if a.infer and (a.model not in ("bsc", "mca", "mmca") or a.heldout <= 0):
+        ap.error("--infer is built for bsc, mca and mmca and needs --heldout N")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         import torch
         import torch.distributed as dist
@@ -220,6 +228,24 @@ def main():
                 worst = max(comm.allgather(float(np.abs(prob - exact_prob).max()) if prob.size else 0.0))
                 if comm.rank == 0:
                     print("held-out codes: largest |prob_truncated - prob_exact| %.3e" % worst)
+        if a.infer:
+            # how often the truncated MAP state is the true one: the selection function proposes H' latents, the adaptive loop
+            # re-runs only the datapoints whose MAP state fills gamma -- a MAP latent that was never proposed goes unnoticed
+            from prosper_amd.em.camodels._device import LoglikPoint
+            maps = {ad: model.inference(LoglikPoint(), dict(em.lparams), heldout, topK=1, adaptive=ad)['s'][:, 0]
+                    for ad in (True, False)}
+            moved = comm.allreduce(np.array([float((maps[True] != maps[False]).any(axis=1).sum())]))[0]
+            if comm.rank == 0:
+                print("held-out MAP states (%d datapoints, H' = %d, gamma = %d): the adaptive re-runs change %.4f of them"
+                      % (a.heldout, model.Hprime, model.gamma, moved / a.heldout))
+            if a.exact:
+                ex = model.inference(LoglikPoint(), dict(em.lparams), heldout, topK=1, logprob=True, exact=True)
+                hit = [float((maps[ad] == ex['s'][:, 0]).all(axis=1).sum()) for ad in (True, False)]
+                tot = comm.allreduce(np.array(hit + [float(np.exp(ex['p'][:, 0]).sum())]))
+                if comm.rank == 0:
+                    print("held-out MAP states: the truncated MAP state is the exact one (all 2^%d states) for %.4f of the "
+                          "datapoints with adaptive=True, %.4f with adaptive=False; mean posterior probability of the exact MAP "
+                          "state %.4f" % (H, tot[0] / a.heldout, tot[1] / a.heldout, tot[2] / a.heldout))
         if a.reconstruct:
             y = np.asarray(heldout['y'], dtype=np.float64)
             sq = lambda x: float(((np.asarray(x) - clean) ** 2).sum())

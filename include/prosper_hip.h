@@ -1164,6 +1164,63 @@ int pm_recon_exact_gsc_f64(const double *Y, int64_t ldy, const double *P, const 
                            double *work, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Exact top-K posterior states (infer_exact.hip)
+ * ---------------------------------------------------------------------------------------
+ * Per datapoint the topK states of largest log-joint l_n(s) over the model's WHOLE state space by enumeration on the device,
+ * and v_n = log sum_{all s} exp l_n(s), with the models, operands and log-joints of pm_recon_exact_* (row constants are not
+ * taken).  A state ranks before another if its log-joint is larger, or if the two are equal and its state index is smaller:
+ * the order is a function of (value, index) alone.  The state index is sum_h k_h K^h (linear models) or the bit mask of s (MCA
+ * / MMCA).  Outputs, per row n:
+ *   top_idx (N x cols, int64, row stride ldi)   the state indices, best first
+ *   top_l   (N x cols, row stride ldl)          their log-joints l_n(s), without the row constants
+ *   v       (N)                                 v_n
+ * with cols = min(topK, states); columns past cols are not written.  A state of zero prior has l = -inf and ranks after every
+ * finite one, by index.  A row that holds a NaN log-joint gets index -1 and NaN in its cols columns and NaN in v; no other row
+ * is affected.
+ *
+ * One sweep over the states: every thread keeps a running (max, sum exp) and its PM_INFER_EXACT_MAX_TOPK best (value, index)
+ * pairs in registers, a workgroup -- one (row, state range) -- reduces both into one partial, and one wavefront per row merges
+ * the row's R partials.  The contract is that of pm_recon_exact_*: no atomics and nothing depends on PM_DETERMINISTIC; the
+ * split of the state space into R ranges, the assignment of states to threads and every merge are functions of the state count
+ * (and H, K, D, topK) alone, never of N; l_n(s) comes from the single definitions of pm_exact.h.  A row of the result is a
+ * function of that row of Y and of the parameters alone: the same bits on every run, in both builds, under a row permutation
+ * and in any shard.
+ *
+ * topK: 1 .. PM_INFER_EXACT_MAX_TOPK (the length of a thread's list), else PM_EINVAL (< 1) / PM_ERANGE (above).  `work`:
+ * pm_infer_exact_work_len(N, H, topK) doubles, enough for either entry: the entries walk N in row blocks (256 rows; MCA 64), so
+ * the length is bounded in N: min(N, 256) (H + 256 (2 + 2 topK)) or min(N, 64) 64 (2 + 2 topK), whichever is larger (-1 for N <
+ * 0, H < 1 or a topK outside its limits).  Every entry checks its arguments before it touches a device: PM_EINVAL for a null
+ * pointer, N < 0, D < 1, H < 1, ldy < D, ldi or ldl < cols or a bad K; PM_ERANGE past the limits of pm_recon_exact_lin_f64
+ * (K^H <= 2^32, H <= 32, K <= 8) and pm_recon_exact_mca_f64 (H <= 32, D <= 1024).  N == 0 launches nothing. */
+#define PM_INFER_EXACT_MAX_TOPK 16
+int64_t pm_infer_exact_work_len(int64_t N, int64_t H, int64_t topK);
+/* What pm_infer_exact_{lin,mca}_f64 do for (N, D, K, H, topK), from the host function the entries themselves take it from;
+ * nothing is launched and no device is needed.  `kind`: PM_EXACT_LIN (K is read) or PM_EXACT_MCA.  out[PM_INFER_PLAN_LEN]:
+ *   0 rows      rows per block of the host walk: 256, MCA 64            1 blocks   ceil(N / rows)
+ *   2 L, 3 CH   as in pm_loglik_exact_plan (MCA: 0, 1)
+ *   4 space     what the ranges cut: lin the chunks, MCA the states; range r is [space r / R, space (r + 1) / R)
+ *   5 R         lin min(256, max(1, chunks / 2)), MCA min(64, max(1, states / 64)): pm_recon_exact_plan's, 1 <= R <= space
+ *   6 cols      min(topK, states): the columns written, and the length of a partial list
+ *   7, 8        offset and length (doubles) of the (max, sum exp) partials inside `work` for the largest block, nb =
+ *               min(N, rows) rows: nb H (MCA 0) and 2 nb R
+ *   9, 10       offsets of the partial lists' values and of their indices (int64, one per double's place)
+ *   11          length of either: nb R cols
+ * Returns PM_OK, PM_EINVAL (null `out`, unknown kind -- PM_EXACT_GSC has no entry --, N < 0, D < 1, H < 1, topK < 1, lin: K
+ * outside 2..8) or PM_ERANGE exactly where the entry of the kind returns it. */
+#define PM_INFER_PLAN_LEN 12
+int pm_infer_exact_plan(int kind, int64_t N, int64_t D, int64_t K, int64_t H, int64_t topK, int64_t *out);
+/* The linear models (K-ary: BSC, TSC, DSC); Y, ymu, P, G, logp, values and K as for pm_recon_exact_lin_f64. */
+int pm_infer_exact_lin_f64(const double *Y, int64_t ldy, const double *ymu, const double *P, const double *G,
+                           const double *logp, const double *values, int64_t K, int64_t N, int64_t D, int64_t H,
+                           int64_t topK, int64_t *top_idx, int64_t ldi, double *top_l, int64_t ldl, double *v, double *work,
+                           void *stream);
+/* MCA (signed_w = 0) and MMCA (signed_w = 1); Wrho, inv_rho, lp1, lp0 and inv_s2 as for pm_recon_exact_mca_f64.  One wavefront
+ * per state, lanes over the dimensions. */
+int pm_infer_exact_mca_f64(const double *Y, int64_t ldy, const double *Wrho, double inv_rho, int signed_w, double lp1,
+                           double lp0, double inv_s2, int64_t N, int64_t D, int64_t H, int64_t topK, int64_t *top_idx,
+                           int64_t ldi, double *top_l, int64_t ldl, double *v, double *work, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Posterior-mean reconstruction (reconstruct_kernels.hip)
  * ---------------------------------------------------------------------------------------
  * yhat_n = sum_{s in K_n} q_n(s) ybar(s), q_n(s) = exp(a logpj[n,s] + o_s - lse_n), over exactly the states whose log-joints

@@ -1,8 +1,11 @@
-// What the two exact-enumeration units share: loglik_exact.hip sums exp l_n(s) over every latent state s,
-// recon_exact.hip weights f(s) by exp(l_n(s) - v_n) over the same states.  The log-joint l_n(s) and everything it is built
+// What the exact-enumeration units share: loglik_exact.hip sums exp l_n(s) over every latent state s,
+// recon_exact.hip weights f(s) by exp(l_n(s) - v_n) over the same states, infer_exact.hip ranks them by l_n(s).  The log-joint
+// l_n(s) and everything it is built
 // from -- the online log-sum-exp, the bounds, the state space and its split into digits, the prep product, MCA's Wbar(s), GSC's staging and
-// per-support factorisation -- are defined ONCE, here; the kernels of the two units keep their own ranges, tile shapes,
-// partial layouts and merge trees.  Every device routine is inlined into its callers.
+// per-support factorisation -- are defined ONCE, here; so is the walk of one datapoint's states that recon_exact.hip and
+// infer_exact.hip both make (the linear kernels' lo states, chunk terms and odometer; MCA's prior and wavefront energy; the
+// ranges; the block's log-sum-exp tree).  The units keep their own tile shapes, partial layouts and merges.  Every device
+// routine is inlined into its callers.
 #ifndef PM_EXACT_H
 #define PM_EXACT_H
 
@@ -87,14 +90,160 @@ __device__ __forceinline__ double pmx_prep_dot(const double *y, const double *ym
     return acc;
 }
 
+// ... as a kernel, one thread per output of B (N x H): recon_exact.hip and infer_exact.hip launch it per row block
+static __global__ void __launch_bounds__(PMX_THREADS) pmx_prep_kernel(const double *__restrict__ Y, int64_t ldy,
+                                                                      const double *__restrict__ ymu, int64_t N, int64_t D,
+                                                                      const double *__restrict__ P, int64_t H,
+                                                                      double *__restrict__ B) {
+    const int64_t i = (int64_t)blockIdx.x * PMX_THREADS + threadIdx.x;
+    if (i >= N * H) return;
+    const int64_t n = i / H, h = i % H;
+    const double *y = Y + n * ldy;
+    B[i] = pmx_prep_dot(y, ymu, D, P, H, h);
+}
+
 // The linear models' log-joint, for both units' kernels: log p(s, y_n) = sum_h logp[h, k_h] - 1/2 s^T G s + s^T B_n + (row
 // constant), s_h = values[k_h], G = W^T W / sigma^2, B_n = W^T y_n / sigma^2.  With s = s_lo + s_hi:
 //   l(s) = [prior_lo - 1/2 s_lo^T G_ll s_lo]          (per lo, once per workgroup, in registers: plo)
 //        + [prior_hi - 1/2 s_hi^T G_hh s_hi]          (per chunk, shared: the sum of sHv)
 //        - s_lo^T (G_lh s_hi)                          (per chunk a table sGv[h][k] = -values[k] (G_lh s_hi)_h, L lookups)
 //   s^T B_n = s_lo^T B_n,lo (per lo and datapoint, registers: blo) + s_hi^T B_n,hi (per chunk and datapoint, shared: sBh)
-// so a (state, datapoint) costs two adds and one exp.  ex_lin_kernel<TN> and rx_lin_kernel<SWEEP> each hold the device code of
-// these terms (lo-state setup, per-chunk terms, digit odometer), and the MCA kernels their one-line prior term: DESIGN 4.13.
+// so a (state, datapoint) costs two adds and one exp.
+//
+// The walk of ONE datapoint's states by one workgroup -- what rx_lin_kernel<SWEEP> (recon_exact.hip) and ix_lin_kernel
+// (infer_exact.hip) share: lo-state setup, per-chunk terms, digit odometer -- is the set of routines below over the kernel's
+// own LDS arrays, named by a PmxLin.  ex_lin_kernel<TN> (loglik_exact.hip) walks TN datapoints at once and holds its own
+// statement of the same terms, as ex_mca_kernel does of the one-line prior term.
+struct PmxLin {
+    double *G, *logp, *val, *B;   // H x H, H x K, K, H: the operands and the datapoint's row of B
+    double *Gv;                   // PMX_MAX_H x PMX_LIN_MAX_K: -values[k] (G_lh s_hi)_h of the chunk
+    double *Hv, *Sv;              // PMX_MAX_H each: prior_hi - 1/2 s_i (G_hh s_hi)_i and s_i per hi latent of the chunk
+    double *Bh;                   // 1: s_hi^T B_n,hi of the chunk
+    int *dig;                     // PMX_MAX_H: the chunk's hi digits
+    int H, K, L, CH, NH;
+};
+
+// the operands into LDS; the caller syncs
+__device__ __forceinline__ void pmx_lin_stage(const PmxLin &w, const double *G, const double *logp, const double *values,
+                                              const double *Brow) {
+    for (int i = threadIdx.x; i < w.H * w.H; i += PMX_THREADS) w.G[i] = G[i];
+    for (int i = threadIdx.x; i < w.H * w.K; i += PMX_THREADS) w.logp[i] = logp[i];
+    if ((int)threadIdx.x < w.K) w.val[threadIdx.x] = values[threadIdx.x];
+    if ((int)threadIdx.x < w.H) w.B[threadIdx.x] = Brow[threadIdx.x];
+}
+
+// the hi digits of chunk c (thread 0); the caller syncs
+__device__ __forceinline__ void pmx_lin_seek(const PmxLin &w, uint64_t c) {
+    if (threadIdx.x == 0) {
+        for (int i = 0; i < w.NH; ++i) {
+            w.dig[i] = (int)(c % (uint64_t)w.K);
+            c /= (uint64_t)w.K;
+        }
+    }
+}
+
+// odometer: the next chunk's hi digits (thread 0); the caller syncs
+__device__ __forceinline__ void pmx_lin_next_chunk(const PmxLin &w) {
+    if (threadIdx.x == 0) {
+        for (int i = 0; i < w.NH; ++i) {
+            if (++w.dig[i] < w.K) break;
+            w.dig[i] = 0;
+        }
+    }
+}
+
+// the lo state `lo` of a thread: its packed digits (3 bits each), prior_lo - 1/2 s_lo^T G_ll s_lo and s_lo^T B_n,lo; a lo state
+// past CH gets (0, -inf, 0)
+__device__ __forceinline__ void pmx_lin_lo_state(const PmxLin &w, int lo, uint32_t &code, double &plo, double &blo) {
+    const int H = w.H, K = w.K, L = w.L;
+    code = 0;
+    plo = -INFINITY;
+    blo = 0.0;
+    if (lo >= w.CH) return;
+    int x = lo;
+    double pr = 0.0, quad = 0.0, bl = 0.0;
+    for (int h = 0; h < L; ++h) {
+        const int k = x % K;
+        x /= K;
+        code |= (uint32_t)k << (3 * h);
+        pr += w.logp[h * K + k];
+    }
+    for (int h = 0; h < L; ++h) {
+        const double sh = w.val[(code >> (3 * h)) & 7];
+        if (sh == 0.0) continue;
+        double gs = 0.0;
+        for (int l = 0; l < L; ++l) gs = fma(w.G[h * H + l], w.val[(code >> (3 * l)) & 7], gs);
+        quad = fma(sh, gs, quad);
+        bl = fma(sh, w.B[h], bl);
+    }
+    plo = pr - 0.5 * quad;
+    blo = bl;
+}
+
+// the shared per-chunk terms from the hi digits, by the threads 0 .. PMX_MAX_H; the caller syncs
+__device__ __forceinline__ void pmx_lin_chunk_terms(const PmxLin &w) {
+    const int H = w.H, K = w.K, L = w.L, NH = w.NH;
+    const int t = threadIdx.x;
+    if (t < L) {                                        // g_t = (G_lh s_hi)_t, times every value
+        double g = 0.0;
+        for (int i = 0; i < NH; ++i) g = fma(w.G[t * H + L + i], w.val[w.dig[i]], g);
+        for (int k = 0; k < K; ++k) w.Gv[t * K + k] = -w.val[k] * g;
+    } else if (t < H) {                                 // hi latent i: prior - 1/2 s_i (G_hh s_hi)_i
+        const int i = t - L;
+        const double si = w.val[w.dig[i]];
+        double g = 0.0;
+        if (si != 0.0)
+            for (int l = 0; l < NH; ++l) g = fma(w.G[t * H + L + l], w.val[w.dig[l]], g);
+        w.Hv[i] = w.logp[t * K + w.dig[i]] - 0.5 * si * g;
+        w.Sv[i] = si;
+    } else if (t == PMX_MAX_H) {                         // s_hi^T B_n,hi
+        double b = 0.0;
+        for (int l = 0; l < NH; ++l) b = fma(w.val[w.dig[l]], w.B[L + l], b);
+        w.Bh[0] = b;
+    }
+}
+
+// prior_hi - 1/2 s_hi^T G_hh s_hi of the chunk, after pmx_lin_chunk_terms and the sync
+__device__ __forceinline__ double pmx_lin_chunk_prior(const PmxLin &w) {
+    double lhi = 0.0;
+    for (int i = 0; i < w.NH; ++i) lhi += w.Hv[i];
+    return lhi;
+}
+
+// l_n(s) of the state (lo state of `code`, plo, blo; the current chunk, lhi = pmx_lin_chunk_prior, bh = Bh[0])
+__device__ __forceinline__ double pmx_lin_logjoint(const PmxLin &w, uint32_t code, double plo, double blo, double lhi,
+                                                   double bh) {
+    double cross = 0.0;
+    for (int h = 0; h < w.L; ++h) cross += w.Gv[h * w.K + ((code >> (3 * h)) & 7)];
+    return ((plo + lhi) + cross) + (blo + bh);
+}
+
+// ---- what recon_exact.hip and infer_exact.hip share beyond l_n(s) -----------------------------------------------------------
+constexpr int PMX_WAVES = PMX_THREADS / 64;
+
+// ranges of a space of `units`, at least `per` units each, at most `cap`: a function of the state count alone
+static int64_t pmx_ranges(uint64_t units, uint64_t per, int64_t cap) {
+    uint64_t r = units / per;
+    if (r < 1) r = 1;
+    return r > (uint64_t)cap ? cap : (int64_t)r;
+}
+
+// The 256 threads' (max, sum exp) pairs merged in a fixed order: lane l takes lane l + o for o = 32, 16, ..., 1, then the
+// wavefronts 1, 2, 3 are merged into 0 in order.  Every thread calls it; thread 0 holds the result.  `red`: 2 PMX_WAVES doubles.
+__device__ __forceinline__ void pmx_block_lse(double &m, double &s, double *red) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const double m2 = __shfl_down(m, o), s2 = __shfl_down(s, o);
+        if ((int)(threadIdx.x & 63) < o) pmx_lse_merge(m, s, m2, s2);
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        red[2 * (threadIdx.x >> 6)] = m;
+        red[2 * (threadIdx.x >> 6) + 1] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < PMX_WAVES; ++w) pmx_lse_merge(m, s, red[2 * w], red[2 * w + 1]);
+}
 
 // ---- MCA / MMCA ---------------------------------------------------------------------------------------------------------------
 // log p(s, y_n) = |s| lp1 + (H - |s|) lp0 + inv_s2 sum_d (y_nd Wbar_d(s) - 1/2 Wbar_d(s)^2) + (row constant), Wbar_d(s) =
@@ -106,6 +255,37 @@ __device__ __forceinline__ double pmx_mca_wbar(const double *Wrho, int64_t D, in
     double t = 0.0;
     for (uint64_t b = st; b; b &= b - 1) t += Wrho[(int64_t)__builtin_ctzll(b) * D + d];
     return signed_w ? copysign(pow(fabs(t), inv_rho), t) : pow(t, inv_rho);
+}
+
+// One wavefront per state with its lanes over the dimensions d = lane + 64 i (rx_mca_kernel, ix_mca_kernel): D <= 1024.
+constexpr int PMX_MCA_MAX_D = 1024;
+constexpr int PMX_MCA_SLABS = PMX_MCA_MAX_D / 64;
+
+// log prior of a state with k of H causes active (a zero count never meets an infinite log-probability)
+__device__ __forceinline__ double pmx_mca_prior(int k, int H, double lp1, double lp0) {
+    return (k ? k * lp1 : 0.0) + (H - k ? (H - k) * lp0 : 0.0);
+}
+
+// sum_d (y_d Wbar_d(st) - 1/2 Wbar_d(st)^2) by one wavefront: lane `lane` forms Wbar of its dimensions of the first nsl slabs
+// into wv (0 past D and for st = 0; y holds the lane's entries of the row, 0 past D), a butterfly adds the lanes: every lane
+// returns the same bits
+__device__ __forceinline__ double pmx_mca_wave_energy(const double *Wrho, int64_t D, int nsl, uint64_t st, double inv_rho,
+                                                      int signed_w, int lane, const double (&y)[PMX_MCA_SLABS],
+                                                      double (&wv)[PMX_MCA_SLABS]) {
+    double e = 0.0;
+#pragma unroll
+    for (int i = 0; i < PMX_MCA_SLABS; ++i) {
+        wv[i] = 0.0;
+        if (i < nsl) {
+            const int64_t d = lane + 64 * i;
+            if (d < D && st) {
+                wv[i] = pmx_mca_wbar(Wrho, D, d, st, inv_rho, signed_w);
+            }
+            e = fma(wv[i], y[i] - 0.5 * wv[i], e);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
+    return e;
 }
 
 // ---- GSC ----------------------------------------------------------------------------------------------------------------------

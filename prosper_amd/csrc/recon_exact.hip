@@ -3,7 +3,7 @@
 // v_n = log sum_{all s} exp l_n(s), for the six component-analysis models, with no state table and no (N, states) buffer.
 //
 // Every entry walks N in row blocks of a fixed size and runs, per block:
-//   rx_prep          B = (Y - ymu) P (rows x H), one thread per output, fixed order (linear models and GSC);
+//   pmx_prep         B = (Y - ymu) P (rows x H), one thread per output, fixed order (linear models and GSC);
 //   sweep 1          the model's enumeration kernel: a workgroup owns one (row or 64-row tile, state range), every thread
 //                    keeps a running (max, sum exp) over the states it owns, a fixed tree merges them into ONE partial;
 //   rx_combine_lse   v_n from the R partials of the row, merged in range order;
@@ -29,8 +29,8 @@ namespace {
 
 constexpr int RX_THREADS = PMX_THREADS;
 constexpr int RX_WAVES = RX_THREADS / 64;
-constexpr int RX_MCA_MAX_D = 1024;
-constexpr int RX_MCA_SLABS = RX_MCA_MAX_D / 64;
+constexpr int RX_MCA_MAX_D = PMX_MCA_MAX_D;
+constexpr int RX_MCA_SLABS = PMX_MCA_SLABS;
 constexpr int64_t RX_ROWS = 256;              // rows per block of the host walk: linear models, GSC
 constexpr int64_t RX_MAX_RANGES = 256;
 constexpr int64_t RX_MCA_ROWS = 64;           // ... MCA / MMCA (a partial is D wide)
@@ -39,13 +39,6 @@ constexpr uint64_t RX_LIN_MIN_CHUNKS = 2;     // chunks per range at least (wher
 constexpr uint64_t RX_PAIR_MIN_CHUNKS = 16;   // ... of the moments entry's pair sweeps, whose epilogue is longer
 constexpr uint64_t RX_MCA_MIN_STATES = 64;    // states per range at least: 16 per wavefront
 constexpr uint64_t RX_GSC_MIN_STATES = 32;    // supports per range at least: 8 per wavefront
-
-// ranges of a space of `units`, at least `per` units each, at most `cap`: a function of the state count alone
-int64_t rx_ranges(uint64_t units, uint64_t per, int64_t cap) {
-    uint64_t r = units / per;
-    if (r < 1) r = 1;
-    return r > (uint64_t)cap ? cap : (int64_t)r;
-}
 
 // The 256 threads' values added in a fixed order: lane l takes lane l + o for o = 32, 16, ..., 1, then the four wavefronts'
 // sums as (0 + 1) + (2 + 3).  Every thread calls it; thread 0 holds the result.  `red`: RX_WAVES doubles.
@@ -57,33 +50,7 @@ __device__ double block_sum(double v, double *red) {
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// ... and their (max, sum exp) pairs: the same lane tree, then wavefronts 1, 2, 3 merged into 0 in order.  `red`: 2 RX_WAVES.
-__device__ void block_lse(double &m, double &s, double *red) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const double m2 = __shfl_down(m, o), s2 = __shfl_down(s, o);
-        if ((int)(threadIdx.x & 63) < o) pmx_lse_merge(m, s, m2, s2);
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-        red[2 * (threadIdx.x >> 6)] = m;
-        red[2 * (threadIdx.x >> 6) + 1] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < RX_WAVES; ++w) pmx_lse_merge(m, s, red[2 * w], red[2 * w + 1]);
-}
-
-// B[n,h] = sum_d (y_nd - ymu_d) P[d,h] (ymu NULL: 0), one thread per output
-__global__ void __launch_bounds__(RX_THREADS) rx_prep_kernel(const double *__restrict__ Y, int64_t ldy,
-                                                             const double *__restrict__ ymu, int64_t N, int64_t D,
-                                                             const double *__restrict__ P, int64_t H,
-                                                             double *__restrict__ B) {
-    const int64_t i = (int64_t)blockIdx.x * RX_THREADS + threadIdx.x;
-    if (i >= N * H) return;
-    const int64_t n = i / H, h = i % H;
-    const double *y = Y + n * ldy;
-    B[i] = pmx_prep_dot(y, ymu, D, P, H, h);
-}
+// ... and their (max, sum exp) pairs: pmx_block_lse (pm_exact.h), the same lane tree.
 
 // v[n] = log sum exp of the row's R partials part[2 (r nb + n)], merged in range order: one thread per row
 __global__ void __launch_bounds__(RX_THREADS) rx_combine_lse_kernel(const double *__restrict__ part, int64_t nb, int64_t R,
@@ -146,10 +113,8 @@ __global__ void __launch_bounds__(RX_THREADS) rx_lin_kernel(LinArgs a) {
     __shared__ double sOut[SWEEP == 3 ? RX_WAVES * LIN_OUT3 : 1];   // sweep 3: the wavefronts' sums of every output
     const int H = a.H, K = a.K, L = a.L, CH = a.CH, NH = H - L;
     const int64_t R = a.R, n = blockIdx.x / R, r = blockIdx.x % R;
-    for (int i = threadIdx.x; i < H * H; i += RX_THREADS) sG[i] = a.G[i];
-    for (int i = threadIdx.x; i < H * K; i += RX_THREADS) sLogp[i] = a.logp[i];
-    if ((int)threadIdx.x < K) sVal[threadIdx.x] = a.values[threadIdx.x];
-    if ((int)threadIdx.x < H) sB[threadIdx.x] = a.B[n * H + threadIdx.x];
+    const PmxLin w = {sG, sLogp, sVal, sB, sGv, sHv, sSv, sBh, sDig, H, K, L, CH, NH};
+    pmx_lin_stage(w, a.G, a.logp, a.values, a.B + n * H);
     const uint64_t c0 = a.nchunks * (uint64_t)r / (uint64_t)R, c1 = a.nchunks * (uint64_t)(r + 1) / (uint64_t)R;
     if (SWEEP == 3 && a.pin >= 0) {
         // a range none of whose chunks carries weight (the pinned digit moves every pdiv chunks and shows every value within
@@ -165,44 +130,14 @@ __global__ void __launch_bounds__(RX_THREADS) rx_lin_kernel(LinArgs a) {
             return;
         }
     }
-    if (threadIdx.x == 0) {                    // the hi digits of chunk c0
-        uint64_t c = c0;
-        for (int i = 0; i < NH; ++i) {
-            sDig[i] = (int)(c % (uint64_t)K);
-            c /= (uint64_t)K;
-        }
-    }
+    pmx_lin_seek(w, c0);                       // the hi digits of chunk c0
     __syncthreads();
 
     // per lo state of this thread: its packed digits (3 bits each), prior_lo - 1/2 s_lo^T G_ll s_lo and s_lo^T B_n,lo
     uint32_t code[PMX_LIN_MAX_J];
     double plo[PMX_LIN_MAX_J], blo[PMX_LIN_MAX_J];
 #pragma unroll
-    for (int j = 0; j < PMX_LIN_MAX_J; ++j) {
-        const int lo = threadIdx.x + j * RX_THREADS;
-        code[j] = 0;
-        plo[j] = -INFINITY;
-        blo[j] = 0.0;
-        if (lo >= CH) continue;
-        int x = lo;
-        double pr = 0.0, quad = 0.0, bl = 0.0;
-        for (int h = 0; h < L; ++h) {
-            const int k = x % K;
-            x /= K;
-            code[j] |= (uint32_t)k << (3 * h);
-            pr += sLogp[h * K + k];
-        }
-        for (int h = 0; h < L; ++h) {
-            const double sh = sVal[(code[j] >> (3 * h)) & 7];
-            if (sh == 0.0) continue;
-            double gs = 0.0;
-            for (int l = 0; l < L; ++l) gs = fma(sG[h * H + l], sVal[(code[j] >> (3 * l)) & 7], gs);
-            quad = fma(sh, gs, quad);
-            bl = fma(sh, sB[h], bl);
-        }
-        plo[j] = pr - 0.5 * quad;
-        blo[j] = bl;
-    }
+    for (int j = 0; j < PMX_LIN_MAX_J; ++j) pmx_lin_lo_state(w, threadIdx.x + j * RX_THREADS, code[j], plo[j], blo[j]);
 
     const double vn = SWEEP >= 2 ? a.v[n] : 0.0;
     double m = -INFINITY, s = 0.0;             // sweep 1
@@ -216,46 +151,20 @@ __global__ void __launch_bounds__(RX_THREADS) rx_lin_kernel(LinArgs a) {
         if (SWEEP == 3 && a.pin >= 0) {
             wpin = sVal[(int)((c / a.pdiv) % (uint64_t)K)];
             if (wpin == 0.0) {                              // no state of the chunk carries weight: on to the next one
-                if (threadIdx.x == 0) {
-                    for (int i = 0; i < NH; ++i) {
-                        if (++sDig[i] < K) break;
-                        sDig[i] = 0;
-                    }
-                }
+                pmx_lin_next_chunk(w);
                 __syncthreads();
                 continue;
             }
         }
-        // shared per-chunk terms from the hi digits
-        const int t = threadIdx.x;
-        if (t < L) {                                        // g_t = (G_lh s_hi)_t, times every value
-            double g = 0.0;
-            for (int i = 0; i < NH; ++i) g = fma(sG[t * H + L + i], sVal[sDig[i]], g);
-            for (int k = 0; k < K; ++k) sGv[t * K + k] = -sVal[k] * g;
-        } else if (t < H) {                                 // hi latent i: prior - 1/2 s_i (G_hh s_hi)_i
-            const int i = t - L;
-            const double si = sVal[sDig[i]];
-            double g = 0.0;
-            if (si != 0.0)
-                for (int l = 0; l < NH; ++l) g = fma(sG[t * H + L + l], sVal[sDig[l]], g);
-            sHv[i] = sLogp[t * K + sDig[i]] - 0.5 * si * g;
-            sSv[i] = si;
-        } else if (t == PMX_MAX_H) {                         // s_hi^T B_n,hi
-            double b = 0.0;
-            for (int l = 0; l < NH; ++l) b = fma(sVal[sDig[l]], sB[L + l], b);
-            sBh[0] = b;
-        }
+        pmx_lin_chunk_terms(w);                             // shared per-chunk terms from the hi digits
         __syncthreads();
-        double lhi = 0.0;
-        for (int i = 0; i < NH; ++i) lhi += sHv[i];
+        const double lhi = pmx_lin_chunk_prior(w);
         const double bh = sBh[0];
         double cm = 0.0;
 #pragma unroll
         for (int j = 0; j < PMX_LIN_MAX_J; ++j) {
             if (threadIdx.x + j * RX_THREADS >= (unsigned)CH) break;
-            double cross = 0.0;
-            for (int h = 0; h < L; ++h) cross += sGv[h * K + ((code[j] >> (3 * h)) & 7)];
-            const double l = ((plo[j] + lhi) + cross) + (blo[j] + bh);
+            const double l = pmx_lin_logjoint(w, code[j], plo[j], blo[j], lhi, bh);
             if (SWEEP == 1) {
                 pmx_lse_add(m, s, l);
             } else {
@@ -270,16 +179,11 @@ __global__ void __launch_bounds__(RX_THREADS) rx_lin_kernel(LinArgs a) {
             for (int i = 0; i < LIN_MAX_NH; ++i)
                 if (i < NH) ehi[i] = fma(sSv[i], cm, ehi[i]);
         }
-        if (threadIdx.x == 0) {                           // odometer: the next chunk's hi digits
-            for (int i = 0; i < NH; ++i) {
-                if (++sDig[i] < K) break;
-                sDig[i] = 0;
-            }
-        }
+        pmx_lin_next_chunk(w);                            // odometer: the next chunk's hi digits
         __syncthreads();
     }
     if (SWEEP == 1) {
-        block_lse(m, s, red);
+        pmx_block_lse(m, s, red);
         if (threadIdx.x == 0) {
             a.part[2 * (r * a.nb + n)] = m;
             a.part[2 * (r * a.nb + n) + 1] = s;
@@ -419,21 +323,10 @@ __global__ void __launch_bounds__(RX_THREADS) rx_mca_kernel(McaArgs a) {
     double m = -INFINITY, s = 0.0;
     for (uint64_t st = s0 + w; st < s1; st += RX_WAVES) {   // (st is uniform over the wavefront)
         const int k = __popcll(st);
-        const double lp = (k ? k * a.lp1 : 0.0) + (a.H - k ? (a.H - k) * a.lp0 : 0.0);
+        const double lp = pmx_mca_prior(k, a.H, a.lp1, a.lp0);
         if (lp == -INFINITY) continue;
-        double wv[RX_MCA_SLABS], e = 0.0;
-#pragma unroll
-        for (int i = 0; i < RX_MCA_SLABS; ++i) {
-            wv[i] = 0.0;
-            if (i < nsl) {
-                const int64_t d = lane + 64 * i;
-                if (d < D && st) {
-                    wv[i] = pmx_mca_wbar(a.Wrho, D, d, st, a.inv_rho, a.signed_w);
-                }
-                e = fma(wv[i], y[i] - 0.5 * wv[i], e);
-            }
-        }
-        for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
+        double wv[RX_MCA_SLABS];
+        const double e = pmx_mca_wave_energy(a.Wrho, D, nsl, st, a.inv_rho, a.signed_w, lane, y, wv);
         const double l = lp + a.inv_s2 * e;
         if (SWEEP == 1) {
             pmx_lse_add(m, s, l);
@@ -636,7 +529,7 @@ int rx_plan(int kind, int64_t N, int64_t D, int64_t K, int64_t H, RxPlan &p) {
         pmx_lin_split(K, H, p.L, p.CH);
         if (H - p.L > LIN_MAX_NH) return PM_ERANGE;
         p.space = S / (uint64_t)p.CH;
-        p.R = rx_ranges(p.space, RX_LIN_MIN_CHUNKS, RX_MAX_RANGES);
+        p.R = pmx_ranges(p.space, RX_LIN_MIN_CHUNKS, RX_MAX_RANGES);
     } else if (kind == PM_EXACT_MCA) {
         if (H > PMX_MAX_H || D > RX_MCA_MAX_D) return PM_ERANGE;
         p.rows = RX_MCA_ROWS;
@@ -644,11 +537,11 @@ int rx_plan(int kind, int64_t N, int64_t D, int64_t K, int64_t H, RxPlan &p) {
         p.has_b = 0;
         p.slabs = (int)((D + 63) / 64);
         p.space = 1ull << H;
-        p.R = rx_ranges(p.space, RX_MCA_MIN_STATES, RX_MCA_MAX_RANGES);
+        p.R = pmx_ranges(p.space, RX_MCA_MIN_STATES, RX_MCA_MAX_RANGES);
     } else if (kind == PM_EXACT_GSC) {
         if (H > PMX_GSC_MAX_H) return PM_ERANGE;
         p.space = 1ull << H;
-        p.R = rx_ranges(p.space, RX_GSC_MIN_STATES, RX_MAX_RANGES);
+        p.R = pmx_ranges(p.space, RX_GSC_MIN_STATES, RX_MAX_RANGES);
     } else {
         return PM_EINVAL;
     }
@@ -723,7 +616,7 @@ extern "C" int pm_recon_exact_lin_f64(const double *Y, int64_t ldy, const double
         const int64_t nb = rx_min(pl.rows, N - n0);
         const RxWork w = rx_work(work, nb, H, pl);
         double *B = w.B, *v = w.v, *part = w.part;
-        hipLaunchKernelGGL(rx_prep_kernel, dim3(rx_blocks(nb * H)), dim3(RX_THREADS), 0, st, Y + n0 * ldy, ldy, ymu, nb, D, P,
+        hipLaunchKernelGGL(pmx_prep_kernel, dim3(rx_blocks(nb * H)), dim3(RX_THREADS), 0, st, Y + n0 * ldy, ldy, ymu, nb, D, P,
                            H, B);
         int err = (int)hipGetLastError();
         if (err) return err;
@@ -748,7 +641,7 @@ extern "C" int pm_recon_exact_lin_f64(const double *Y, int64_t ldy, const double
 // epilogue is paid per 64 states of a thread and not per 8: sweep 3 with pin = -1 for the lo-lo pairs, then one pinned sweep per
 // hi digit over the chunks where that digit's value is not 0: sum_s q(s) s_p s_h for every h, which gives the lo-hi and hi-hi
 // pairs.  3 + (H - L) (K - 1) / K sweeps.
-int64_t rx_pair_ranges(const RxPlan &p) { return rx_ranges(p.space, RX_PAIR_MIN_CHUNKS, RX_MAX_RANGES); }
+int64_t rx_pair_ranges(const RxPlan &p) { return pmx_ranges(p.space, RX_PAIR_MIN_CHUNKS, RX_MAX_RANGES); }
 
 
 extern "C" int64_t pm_moments_exact_work_len(int64_t N, int64_t H) {
@@ -802,7 +695,7 @@ extern "C" int pm_moments_exact_lin_f64(const double *Y, int64_t ldy, const doub
     for (int64_t n0 = 0; n0 < N; n0 += pl.rows) {
         const int64_t nb = rx_min(pl.rows, N - n0);
         const RxWork w = rx_work(work, nb, H, pl);
-        hipLaunchKernelGGL(rx_prep_kernel, dim3(rx_blocks(nb * H)), dim3(RX_THREADS), 0, st, Y + n0 * ldy, ldy, ymu, nb, D, P,
+        hipLaunchKernelGGL(pmx_prep_kernel, dim3(rx_blocks(nb * H)), dim3(RX_THREADS), 0, st, Y + n0 * ldy, ldy, ymu, nb, D, P,
                            H, w.B);
         int err = (int)hipGetLastError();
         if (err) return err;
@@ -897,7 +790,7 @@ extern "C" int pm_recon_exact_gsc_f64(const double *Y, int64_t ldy, const double
         const int64_t nb = rx_min(pl.rows, N - n0);
         const RxWork w = rx_work(work, nb, H, pl);
         double *B = w.B, *v = w.v, *part = w.part;
-        hipLaunchKernelGGL(rx_prep_kernel, dim3(rx_blocks(nb * H)), dim3(RX_THREADS), 0, st, Y + n0 * ldy, ldy,
+        hipLaunchKernelGGL(pmx_prep_kernel, dim3(rx_blocks(nb * H)), dim3(RX_THREADS), 0, st, Y + n0 * ldy, ldy,
                            (const double *)nullptr, nb, D, P, H, B);
         int err = (int)hipGetLastError();
         if (err) return err;

@@ -909,14 +909,32 @@ class DeviceCAModel(CAModel):
                 'gamma': buf['gamma'].cpu().numpy(), 'Hprime': buf['Hprime'].cpu().numpy()}
 
     def inference(self, anneal, model_params, test_data, topK=10, logprob=False, adaptive=True,
-                  Hprime_max=None, gamma_max=None):
+                  Hprime_max=None, gamma_max=None, exact=False):
         """Top-K posterior states and marginals per datapoint (camodels/__init__.py:256-375).
 
         Same return dict as the reference: ``s`` (N,topK,H) int8, ``m`` (N,H), ``p`` (N,topK),
         ``gamma`` / ``Hprime`` (N,).  With ``adaptive`` the datapoints whose MAP state has exactly
         gamma active units are re-run with Hprime+1 / gamma+1 (the state table is regenerated) until
         none remain or the caps are reached.  The log-joints come from the HIP E-step; the
-        normalisation, top-K and marginals run on the device too."""
+        normalisation, top-K and marginals run on the device too.
+
+        ``exact=True`` (BSC, MCA, MMCA): the same dict over the model's WHOLE state space {0,1}^H by
+        enumeration on the device (pm_infer_exact_*), for the model and parameters of ``log_likelihood(exact=True)`` (T = 1):
+        no candidates, no state table, nothing truncated.  ``s``: the topK states of largest log-joint, best first; of two
+        states with equal log-joints the one with the smaller state index sum_h s_h 2^h comes first (a function of (value,
+        index) alone, unlike the reference's argsort).  ``p``: with ``logprob`` the normalised log posterior l_n(s) - v_n, v_n
+        the log-sum-exp over all 2^H states; without it exp(l_n(s) - l_n(s_best)) as in the truncated call (column 0 is 1).
+        ``m``: P(s_h = 1 | y_n) over all states -- the bits of ``encode(exact=True)[1]`` -- or its log.  ``gamma`` and
+        ``Hprime`` hold H.  With topK above 2^H the first 2^H entries of ``s`` and ``p`` are written and the rest stay zero.
+        ``adaptive`` has nothing to act on and is ignored.  A row's results depend on that row and the parameters alone: the
+        same bits from both libraries, under a row permutation, in a shard and on a second call; the training state is left
+        as it was.  Refused before any launch: ``NotImplementedError`` for DSC, TSC and GSC, for ``anneal['T'] != 1`` and for
+        a ``'mask'`` or ``'weight'`` in ``test_data``; ``ValueError`` for ``Hprime_max`` / ``gamma_max`` (nothing to grow) and
+        for topK = -1, topK < 1 or topK > 16 (``EXACT_MAX_TOPK``, the length of a thread's list in the kernel); ``HipError``
+        past the limits of ``reconstruct(exact=True)`` (H > 32; MCA / MMCA D > 1024).  A NaN log-joint raises ``HipError``
+        as in the truncated call."""
+        if exact:
+            return self._inference_exact(anneal, model_params, test_data, topK, logprob, Hprime_max, gamma_max)
         from . import generate_state_matrix
         assert 'y' in test_data, "Key 'y' in test_data dict not defined."
         model_params = self.check_params(model_params)
@@ -969,6 +987,74 @@ class DeviceCAModel(CAModel):
 
         return self._inference_result(self._adaptive_inference(anneal, model_params, test_data, topK, adaptive, Hprime_max,
                                                                gamma_max, run_pass, regenerate, restore), logprob)
+
+    # ---- exact inference ------------------------------------------------------------------------------------
+    EXACT_MAX_TOPK = 16               # PM_INFER_EXACT_MAX_TOPK: the entries a thread of the enumeration kernel keeps
+
+    def _inference_exact_admit(self, anneal, model_params, test_data, topK, Hprime_max, gamma_max):
+        """Everything that refuses ``inference(exact=True)``, before anything reaches the device: the model, the annealing
+        point, the caps, topK, a mask or weight, and the kernels' limits (from pm_infer_exact_plan, which needs no device).
+        Returns topK as an int."""
+        name = type(self).__name__
+        if not self._binary_latents:
+            raise NotImplementedError("%s.inference: exact=True is not built for this model (the reference defines the "
+                                      "marginals of DSC, TSC and GSC on the truncated table); BSC_ET, MCA_ET and MMCA_ET "
+                                      "have it" % name)
+        if float(anneal['T']) != 1.0:
+            raise NotImplementedError("%s.inference: exact=True is the T = 1 model, got T = %r" % (name, anneal['T']))
+        if Hprime_max is not None or gamma_max is not None:
+            raise ValueError("%s.inference: exact=True with Hprime_max / gamma_max: nothing is truncated, so there is "
+                             "nothing to grow" % name)
+        if topK != int(topK) or topK < 1 or topK > self.EXACT_MAX_TOPK:
+            raise ValueError("%s.inference: exact=True needs 1 <= topK <= %d (the length of a thread's list in the "
+                             "enumeration kernel; topK = -1 is not built), got %r" % (name, self.EXACT_MAX_TOPK, topK))
+        for key in ('mask', 'weight'):
+            if test_data.get(key) is not None:
+                raise NotImplementedError("%s.inference: exact=True with a %s is not built (the enumeration kernels "
+                                          "read every dimension)" % (name, key))
+        kind, arrays, _ = self._loglik_exact(dict(model_params))
+        K = int(arrays["values"].shape[0]) if kind == "lin" else 0
+        plan = (ctypes.c_int64 * 12)()
+        rc = _lib.load(self.deterministic).pm_infer_exact_plan({"lin": 0, "mca": 1}[kind], 0, self.D, K, self.H, int(topK),
+                                                               plan)
+        if rc:
+            raise _lib.HipError("%s.inference: exact=True holds H <= 32 latents%s (pm_infer_exact_%s_f64 returned %d), got "
+                                "H = %d, D = %d" % (name, " and D <= 1024" if kind == "mca" else "", kind, rc, self.H, self.D))
+        return int(topK)
+
+    def _inference_exact(self, anneal, model_params, test_data, topK, logprob, Hprime_max, gamma_max):
+        """``inference(exact=True)``: state indices, log-joints and v_n by pm_infer_exact_lin_f64 (BSC) or
+        pm_infer_exact_mca_f64 (MCA / MMCA) from the ``_loglik_exact`` hook, the states decoded from their indices on the
+        device, the marginals from ``_encode_exact``; one download, of the dict's arrays."""
+        assert 'y' in test_data, "Key 'y' in test_data dict not defined."
+        topK = self._inference_exact_admit(anneal, model_params, test_data, topK, Hprime_max, gamma_max)
+        y, H = test_data['y'], self.H
+        N = int(y.shape[0])
+        if N == 0:
+            return {'s': np.zeros((0, topK, H), dtype=np.int8), 'm': np.zeros((0, H)), 'p': np.zeros((0, topK)),
+                    'gamma': np.zeros(0), 'Hprime': np.zeros(0)}
+        with self._evaluation():
+            dev = self.device
+            _, _, entry = self._exact_entry(dict(model_params), "infer")
+            Y = self._resident(y)["Y"]
+            D = Y.shape[1]
+            cols = min(topK, 1 << H)
+            top_idx = torch.empty((N, cols), dtype=torch.int64, device=dev)
+            top_l = torch.empty((N, cols), dtype=torch.float64, device=dev)
+            v = torch.empty(N, dtype=torch.float64, device=dev)
+            lib = _lib.load(self.deterministic)
+            work = torch.empty(max(int(lib.pm_infer_exact_work_len(N, H, topK)), 1), dtype=torch.float64, device=dev)
+            entry(lambda name, *a: self._call("infer_exact", name, *a), _ptr(Y), max(int(Y.stride(0)), D), N, topK,
+                  _ptr(top_idx), cols, _ptr(top_l), cols, _ptr(v), _ptr(work))
+            self._refuse_nan(top_idx)
+            s = torch.zeros((N, topK, H), dtype=torch.int8, device=dev)
+            s[:, :cols] = ((top_idx[:, :, None] >> torch.arange(H, device=dev)) & 1).to(torch.int8)
+            p = torch.zeros((N, topK), dtype=torch.float64, device=dev)
+            p[:, :cols] = (top_l - v[:, None]) if logprob else torch.exp(top_l - top_l[:, :1])
+            prob = self._encode_exact(dict(model_params), y, N)[1]
+            m = torch.log(prob) if logprob else prob
+            full = np.full(N, float(H))
+            return {'s': s.cpu().numpy(), 'm': m.cpu().numpy(), 'p': p.cpu().numpy(), 'gamma': full, 'Hprime': full.copy()}
 
     # ---- held-out log-likelihood (DESIGN 4.12) --------------------------------------------------------------------------
     # What a log_likelihood call swaps out: the resident shard, the parameter products computed on it, the workspaces and
@@ -1754,13 +1840,13 @@ class DeviceCAModel(CAModel):
     def _exact_entry(self, model_params, what):
         """The ``_loglik_exact`` hook as a call: ``(kind, arrays, entry)``.  ``entry(call, Yp, ld, n, *out)`` runs
         ``call(name, Yp, ld, <parameters>, n, D, H, *out, stream)`` with the entry name and the parameter arguments of the
-        hook's kind for ``what`` -- 'loglik' (pm_loglik_exact_*), 'recon' (pm_recon_exact_*) or 'encode' (E[s]: the linear
-        kind's reconstruction entry, pm_encode_exact_mca_f64)."""
+        hook's kind for ``what`` -- 'loglik' (pm_loglik_exact_*), 'recon' (pm_recon_exact_*), 'encode' (E[s]: the linear
+        kind's reconstruction entry, pm_encode_exact_mca_f64) or 'infer' (pm_infer_exact_*: the arguments of 'recon')."""
         kind, arrays, sc = self._loglik_exact(model_params)
         dev = self._exact_upload(arrays)
         p, dbl, ll = (lambda k: _ptr(dev.get(k))), ctypes.c_double, what == "loglik"
         name = "pm_encode_exact_mca_f64" if (what == "encode" and kind == "mca") else \
-            "pm_%s_exact_%s_f64" % ("loglik" if ll else "recon", kind)
+            "pm_%s_exact_%s_f64" % ({"loglik": "loglik", "infer": "infer"}.get(what, "recon"), kind)
 
         if kind == "lin":
             args = [p("mu"), p("P"), p("G"), p("logp"), p("values"), int(arrays["values"].shape[0])] \

@@ -413,7 +413,7 @@ class DSC_ET(TableCAModel):
         return {'W': W_out, 'pi': pi_new, 'sigma': sigma_new, 'Q': 0.}
 
     def inference(self, anneal, model_params, test_data, topK=10, logprob=False, adaptive=True,
-                  Hprime_max=None, gamma_max=None):
+                  Hprime_max=None, gamma_max=None, exact=False):
         """Top-K posterior states and marginals per datapoint (dsc_et.py:927-1059); same return dict
         (``s`` (N,topK,H) int8 with the latent VALUES, ``m`` (N,H), ``p`` (N,topK), ``gamma``, ``Hprime``).
 
@@ -423,6 +423,8 @@ class DSC_ET(TableCAModel):
         (:1010-1016); and in the adaptive re-runs ``state_abs`` is the 1-D count of non-zeros
         (``generate_state_matrix``, :1048), so every multi-cause state gets the same prior there.  Unlike
         upstream the proper (K, S) ``state_abs`` is restored afterwards (upstream leaves the 1-D one behind)."""
+        if exact:           # (refused by name, before any launch: DeviceCAModel._inference_exact_admit)
+            self._inference_exact_admit(anneal, model_params, test_data, topK, Hprime_max, gamma_max)
         assert 'y' in test_data, "Key 'y' in test_data dict not defined."
         model_params = self.check_params(model_params)
         H, dev = self.H, self.device

@@ -91,12 +91,14 @@ class TSC_ET(TableCAModel):
         return {'y': y, 's': s}
 
     def inference(self, anneal, model_params, test_data, topK=10, logprob=False, abs_marginal=True,
-                  adaptive=True, Hprime_max=None, gamma_max=None):
+                  adaptive=True, Hprime_max=None, gamma_max=None, exact=False):
         """Top-K posterior states, signed marginal ``m`` and absolute marginal ``am`` per datapoint
         (tsc_et.py:546-680); same return dict.  As upstream: ``p`` is the normalised probability (its log with
         ``logprob``), a repeated candidate's LAST position wins the writes into ``s`` / ``m`` / ``am``, re-run
         datapoints keep earlier entries, and datapoints whose best state has exactly gamma non-zeros are re-run
         with Hprime+1 / gamma+1."""
+        if exact:           # (refused by name, before any launch: DeviceCAModel._inference_exact_admit)
+            self._inference_exact_admit(anneal, model_params, test_data, topK, Hprime_max, gamma_max)
         assert 'y' in test_data, "Key 'y' in test_data dict not defined."
         H, dev = self.H, self.device
         res_am = torch.zeros((test_data['y'].shape[0], H), dtype=torch.float64, device=dev)
