@@ -42,19 +42,9 @@ __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// Diagnostic builds only (scratch/f8_bench.hip, scratch/f8_variants.sh), never in the shipped library:
+// Diagnostic build only (scratch/f8_bench.hip, scratch/f8_variants.sh), never in the shipped library:
 //   -DPM_F8_STAMPS   per-workgroup timeline (s_memrealtime, 100 MHz) and shader clock over the K-loop
-//   -DPM_F8_ABL=1    K-loop only (no row passes)          =2  row passes behind a K-loop of 8 steps
-//               =3   K-loop without its hand-over barrier (wrong results; what the barrier costs)
-#ifndef PM_F8_ABL
-#define PM_F8_ABL 0
-#endif
-//   -DPM_F8_SKIP=mask  timing-only ablations of the lean row passes (wrong results): 1 no ranking (keys, sort, pop
-//               rounds), 2 no multi-cause states, 4 no log-joint stores, 8 no log-sum-exp, 16 no barriers in the passes,
-//               32 (M-statistics) no E[s] row stores, 64 no Wq / mus atomics
-#ifndef PM_F8_SKIP
-#define PM_F8_SKIP 0
-#endif
+// (The timing-only ablations of the K-loop and of the row passes are measured and gone: profiles/r03_f8_ablations.txt.)
 #define F8_STORE(p, v) (*reinterpret_cast<double *>(p) = (v))
 #ifdef PM_F8_STAMPS
 __device__ unsigned long long pm_f8_stamps[8192][8];
@@ -167,11 +157,7 @@ __device__ __forceinline__ void tile16_scores(d4 (&acc)[NJ], double *sm, const d
 #pragma unroll
     for (int i = 0; i < NJ; ++i) acc[i] = d4{0.0, 0.0, 0.0, 0.0};
 
-#if PM_F8_ABL == 2
-    const int nk = 8;
-#else
     const int nk = D / DK;   // host guarantees D % DK == 0, D >= DK
-#endif
     auto kloop = [&](auto withA) {
         constexpr bool WA = decltype(withA)::value;
         constexpr int L = WA ? 2 : 1;          // DMA instructions per K-step of this wavefront
@@ -211,9 +197,7 @@ __device__ __forceinline__ void tile16_scores(d4 (&acc)[NJ], double *sm, const d
                     if (ahead >= 2) wait_vmcnt<2 * L>();
                     else if (ahead == 1) wait_vmcnt<L>();
                     else wait_vmcnt<0>();
-#if PM_F8_ABL != 3
                     __builtin_amdgcn_s_barrier();
-#endif
                     const d2 an = read_a(nstage);
                     if (par) fa[0] = an;
                     else fa[1] = an;
@@ -459,15 +443,6 @@ __global__ __launch_bounds__(TAIL ? THREADS : 1024, TAIL ? 2 : 4) void bsc_estep
 #ifdef PM_F8_STAMPS
     if (tid == 0 && blockIdx.x < 8192) pm_f8_stamps[blockIdx.x][6] = __builtin_amdgcn_s_memtime() - clk0;
 #endif
-#if PM_F8_ABL == 1
-    {
-        double s = 0.0;
-#pragma unroll
-        for (int i = 0; i < NJ; ++i) s += (acc[i][0] + acc[i][1]) + (acc[i][2] + acc[i][3]);
-        if (s == 1.2345e300) lse[0] = s;
-        return;
-    }
-#endif
     lds_barrier();                       // every wavefront is done with the ring (TAIL: with the reduction scratch)
     unsigned char *smem = reinterpret_cast<unsigned char *>(sm);
     const double ppil = P.prior_scale * P.pil_bar, ecoef = P.ecoef;
@@ -597,7 +572,7 @@ __global__ __launch_bounds__(TAIL ? THREADS : 1024, TAIL ? 2 : 4) void bsc_estep
         double yn = *reinterpret_cast<const double *>(yn_t + (uint32_t)lrow * 8u);
         if (ymu_t) yn = yn - 2.0 * *reinterpret_cast<const double *>(ymu_t + (uint32_t)lrow * 8u) + P.mu_sqnorm;
         F8_ESTAMP(r * 8 + 0);
-        if (!(PM_F8_SKIP & 16) || r == 0) lds_barrier();      // the scores of pass r (and, r = 0, the tables) are in LDS
+        lds_barrier();      // the scores of pass r (and, r = 0, the tables) are in LDS
         F8_ESTAMP(r * 8 + 1);
         double a[NJ];
 #pragma unroll
@@ -605,9 +580,7 @@ __global__ __launch_bounds__(TAIL ? THREADS : 1024, TAIL ? 2 : 4) void bsc_estep
 
         // ---------------- select_Hprimes (bsc_et.py:98-115) ---------------------------------------------------------
         int myc = 0;
-        if (PM_F8_SKIP & 1) {
-            myc = (j32 * 29 + (int)a[0]) & 255;
-        } else if (sel) {
+        if (sel) {
             double key[NJ];
             // scores are finite unless the datapoint or W is not
             bool odd = !(yn < 1.0e150);
@@ -678,7 +651,7 @@ __global__ __launch_bounds__(TAIL ? THREADS : 1024, TAIL ? 2 : 4) void bsc_estep
             G0 = *reinterpret_cast<const double *>(gram_b + (ci0 * H8 + ck8));
             G1 = *reinterpret_cast<const double *>(gram_b + (ci1 * H8 + ck8));
         }
-        if (!TAIL && !(PM_F8_SKIP & 16)) lds_barrier();
+        if (!TAIL) lds_barrier();
         F8_ESTAMP(r * 8 + 3);
         if (!TAIL && r + 1 < 4) {
 #pragma unroll
@@ -690,11 +663,7 @@ __global__ __launch_bounds__(TAIL ? THREADS : 1024, TAIL ? 2 : 4) void bsc_estep
         double wmuc = 0.0;
         if (wmu && j32 < HP) wmuc = wmu[myc];
         // singleton log-joints meanwhile: f_h = prior + ecoef (|W_h|^2 - 2 a_h + |y|^2)
-#if PM_F8_SKIP & 128
-        char *out = out_t + ((uint32_t)(lrow & 1) * ldl8 + (uint32_t)j32 * 8u);  // (timing only: every row into rows 0/1)
-#else
         char *out = out_t + ((uint32_t)lrow * ldl8 + (uint32_t)j32 * 8u);        // &logpj[n, j32]
-#endif
         const double f0 = ecoef * yn;
         double mx = f0;
 #pragma unroll
@@ -705,12 +674,10 @@ __global__ __launch_bounds__(TAIL ? THREADS : 1024, TAIL ? 2 : 4) void bsc_estep
             a[i] = f;
             mx = vmax64(mx, f);
         }
-        if (!(PM_F8_SKIP & 4)) {
 #pragma unroll
-            for (int i = 0; i < NJ; ++i)
-                if (FULL || j32 + 32 * i < H) F8_STORE(out + 8 * (1 + 32 * i), a[i]);
-            if (j32 == 0) F8_STORE(out, f0);
-        }
+        for (int i = 0; i < NJ; ++i)
+            if (FULL || j32 + 32 * i < H) F8_STORE(out + 8 * (1 + 32 * i), a[i]);
+        if (j32 == 0) F8_STORE(out, f0);
         Pm[9 + j32] = G0;
         Pm[9 + 32 + j32] = G1;
         wave_lds_sync16();
@@ -729,7 +696,7 @@ __global__ __launch_bounds__(TAIL ? THREADS : 1024, TAIL ? 2 : 4) void bsc_estep
             for (int k = 0; k < SS::iters(g); ++k) {
                 const int s0 = SS::off(g) + 32 * k;                     // + j32 = this lane's state
                 double f = -1.0e300;
-                if (!(PM_F8_SKIP & 2) && (32 * (k + 1) <= SS::cnt(g) || j32 < SS::cnt(g) - 32 * k)) {
+                if (32 * (k + 1) <= SS::cnt(g) || j32 < SS::cnt(g) - 32 * k) {
                     const uint32_t *t = stA + 4 * s0;
                     const uint32_t t01 = t[0], t23 = t[1], t4 = t[2];
                     const double e = (*reinterpret_cast<const double *>(Pb + (t01 & 0xFFFFu)) +
@@ -739,7 +706,7 @@ __global__ __launch_bounds__(TAIL ? THREADS : 1024, TAIL ? 2 : 4) void bsc_estep
                                             *reinterpret_cast<const double *>(Pb + t4));
                     PeA[s0] = e;
                     f = fma(ecoef, yn + e, pg);
-                    if (!(PM_F8_SKIP & 4)) F8_STORE(outS + 8 * s0, f);
+                    F8_STORE(outS + 8 * s0, f);
                 }
                 fs[nf++] = f;
                 mx = vmax64(mx, f);
@@ -747,10 +714,6 @@ __global__ __launch_bounds__(TAIL ? THREADS : 1024, TAIL ? 2 : 4) void bsc_estep
             wave_lds_sync16();
         }
         if (!lse) continue;
-        if (PM_F8_SKIP & 8) {
-            if (mx == 1.2345e300) lse[0] = mx;
-            continue;
-        }
         F8_ESTAMP(r * 8 + 5);
         // ---------------- log-sum-exp: only terms within exp(-37) of the largest are evaluated ----------------------
         mx = half_max_f64(mx);
@@ -848,7 +811,7 @@ __global__ __launch_bounds__(TAIL ? THREADS : 1024, TAIL ? 2 : 4) void bsc_estep
                                             mk &= mk - 1;
                                             atomicAdd(&Bp[kk * (kk + 1) / 2 + i], w);
                                         }
-                                    } else if (!(PM_F8_SKIP & (64 | 256)) && live) {
+                                    } else if (live) {
                                         unsigned mk = mi;
                                         while (mk) {
                                             const int kk = __builtin_ctz(mk);
@@ -877,12 +840,12 @@ __global__ __launch_bounds__(TAIL ? THREADS : 1024, TAIL ? 2 : 4) void bsc_estep
                 } else {
                     const int ci = cl[pair_i], ck = cl[pair_k];
                     const int lo = ci < ck ? ci : ck, hi = ci < ck ? ck : ci;
-                    if (!(PM_F8_SKIP & (64 | 256)) && live && v != 0.0) pm_atomic_add(wq + (int64_t)lo * H + hi, PM_Q(v, 0));
+                    if (live && v != 0.0) pm_atomic_add(wq + (int64_t)lo * H + hi, PM_Q(v, 0));
                     if (j32 < PAIR_ENTRIES - 32) {
                         const double v2 = Bp[32 + j32];
                         const int c2 = cl[4 + j32], c7 = cl[7];
                         const int lo2 = c2 < c7 ? c2 : c7, hi2 = c2 < c7 ? c7 : c2;
-                        if (!(PM_F8_SKIP & (64 | 256)) && live && v2 != 0.0) pm_atomic_add(wq + (int64_t)lo2 * H + hi2, PM_Q(v2, 0));
+                        if (live && v2 != 0.0) pm_atomic_add(wq + (int64_t)lo2 * H + hi2, PM_Q(v2, 0));
                     }
                 }
             }
@@ -904,8 +867,8 @@ __global__ __launch_bounds__(TAIL ? THREADS : 1024, TAIL ? 2 : 4) void bsc_estep
                 double v = 0.0;
                 if (FULL || h < H) {
                     v = (a[i] + Pm[h]) * inv;
-                    if (!(PM_F8_SKIP & 32) && !lists) *reinterpret_cast<double *>(erow + 256 * i) = v;
-                    if (!(PM_F8_SKIP & 64) && live && !dfr && __any(v != 0.0)) {
+                    if (!lists) *reinterpret_cast<double *>(erow + 256 * i) = v;
+                    if (live && !dfr && __any(v != 0.0)) {
                         if (v != 0.0) atomicAdd(&t_mus[h], PM_Q(v, 0));       // (the one LDS accumulator all wavefronts share)
                     }
                 }
@@ -922,7 +885,7 @@ __global__ __launch_bounds__(TAIL ? THREADS : 1024, TAIL ? 2 : 4) void bsc_estep
                     }
                 }
             }
-            if (lists && nzn > PM_BSC_NZ_MAX && !(PM_F8_SKIP & 32)) {      // (uniform over the datapoint's 32 lanes)
+            if (lists && nzn > PM_BSC_NZ_MAX) {      // (uniform over the datapoint's 32 lanes)
 #pragma unroll
                 for (int i = 0; i < NJ; ++i) {
                     const int h = j32 + 32 * i;

@@ -27,10 +27,7 @@ namespace {
 
 constexpr int SP_DC = 64;          // columns per workgroup
 constexpr int SP_WAVES = 16;
-#ifndef PM_SP_UNROLL
-#define PM_SP_UNROLL 8
-#endif
-constexpr int SP_UNROLL = PM_SP_UNROLL;   // datapoints per batch; two batches in flight per wavefront (16 x 512 B of Y)
+constexpr int SP_UNROLL = 8;       // datapoints per batch; two batches in flight per wavefront (16 x 512 B of Y)
 
 __device__ __forceinline__ double readlane_f64(double v, int l) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
@@ -119,13 +116,8 @@ __global__ __launch_bounds__(SP_WAVES * 64) __attribute__((amdgpu_waves_per_eu(6
         const int nb = in ? n0 : lo;                           // (past the end: any valid batch, its lists are not used)
         b.n0 = in ? n0 : -1;
 #pragma unroll
-        for (int u = 0; u < SP_UNROLL; ++u) {
-#ifdef PM_SP_NO_NT
-            b.y[u] = (Y + (int64_t)(nb + u) * ldy)[col];
-#else
+        for (int u = 0; u < SP_UNROLL; ++u)
             b.y[u] = __builtin_nontemporal_load((Y + (int64_t)(nb + u) * ldy) + col);   // read once: leave L2 to the lists
-#endif
-        }
         const uint16_t *pi = nz_idx + (int64_t)nb * PM_BSC_NZ_MAX;
         const double *pv = nz_val + (int64_t)nb * PM_BSC_NZ_MAX;
         b.ix[0] = pi[lane];

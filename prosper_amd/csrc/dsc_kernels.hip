@@ -25,10 +25,8 @@
 namespace {
 
 constexpr int WAVES = 4;
-#ifndef PM_DSC_M16_WPE
-#define PM_DSC_M16_WPE 4     // wavefronts per SIMD dsc_mstep_rows16_kernel<8, 8> is compiled for: 4 costs 28 spilled registers and
-                             // still wins (0.170 ms; 3 per SIMD, no spill: 0.200; scratch/dsc_ab.sh)
-#endif
+constexpr int DSC_M16_WPE = 4;   // wavefronts per SIMD dsc_mstep_rows16_kernel<8, 8> is compiled for: 4 costs 28 spilled
+                                 // registers and still wins (0.170 ms; 3 per SIMD, no spill: 0.200)
 
 __global__ __launch_bounds__(256) void dsc_select_scores_kernel(const double *__restrict__ scores, int64_t lds,
                                                                  const double *__restrict__ gram, pm_dsc_params P,
@@ -598,11 +596,9 @@ __global__ __launch_bounds__(256, MAXHP <= 8 ? 4 : 2) void dsc_estep16_kernel(
 // LDS: the layout of dsc_estep16_kernel, then [ qdiag (H) cnt (8) scal (4) | per row: m (H') B (H'^2) ]; the E[s] row of a
 // datapoint stays in its lanes' registers.
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef PM_DSC_MS_WPE
-#define PM_DSC_MS_WPE 3        // wavefronts per SIMD the kernel is compiled for (register budget 512 / WPE)
-#endif
+constexpr int DSC_MS_WPE = 3;  // wavefronts per SIMD the kernel is compiled for (register budget 512 / WPE)
 template <int MAXHP, int VPL, int KM>      // KM >= K: latent values the per-lane counters are sized for (4 or 8)
-__global__ __launch_bounds__(256, (MAXHP <= 8 && VPL <= 8) ? PM_DSC_MS_WPE : 2) void dsc_estep16_ms_kernel(
+__global__ __launch_bounds__(256, (MAXHP <= 8 && VPL <= 8) ? DSC_MS_WPE : 2) void dsc_estep16_ms_kernel(
     const double *__restrict__ scores, int64_t lds, const double *__restrict__ gram,
     const double *__restrict__ ynorm2, const int32_t *__restrict__ cand, const uint8_t *__restrict__ state_idx, int S,
     const double *__restrict__ prior_g, pm_dsc_params P, int64_t N, int H, int D, int Hp, double *__restrict__ logpj,
@@ -934,7 +930,7 @@ __global__ __launch_bounds__(64 * WAVES, MAXHP <= 8 ? 4 : 3) void dsc_mstep_rows
 // LDS: [ qdiag (H) cnt (8) scal (4) | state table | prior (K, when staged) | per row: E[s] row (H) m (H') B (H'^2) ]
 // ---------------------------------------------------------------------------------------------------------------
 template <int MAXHP, int VPL>
-__global__ __launch_bounds__(256, (MAXHP <= 8 && VPL <= 8) ? PM_DSC_M16_WPE : 2) void dsc_mstep_rows16_kernel(
+__global__ __launch_bounds__(256, (MAXHP <= 8 && VPL <= 8) ? DSC_M16_WPE : 2) void dsc_mstep_rows16_kernel(
     const double *__restrict__ logpj, int64_t ldl, const double *__restrict__ lse, double lse_cut,
     const int32_t *__restrict__ cand, const uint8_t *__restrict__ state_idx, int S, const double *__restrict__ prior_g,
     pm_dsc_params P, int64_t N, int H, int D, int Hp, double *__restrict__ expect, int64_t lde,
@@ -1116,9 +1112,6 @@ inline int64_t dsc_term_entries(int64_t Hprime, int64_t Kn, int64_t S) {
 // False where neither fits or the kernels do not apply (H > 256: the scores row is held in registers); *stage is then
 // not meaningful (it may have been written).
 static bool dsc_fit_lay16(int64_t H, int64_t Hprime, int64_t S, int64_t Kt, int64_t NT, Lay16 *L, int *stage) {
-#ifdef PM_DSC_WAVE64
-    return false;
-#else
     if (!(H <= 256 && S * Hprime < (1 << 20) && Kt < (1 << 20))) return false;
     *stage = 1;
     *L = dsc_lay16((int)H, (int)Hprime, (int)S, (int)Kt, (int)NT, 1);
@@ -1127,7 +1120,6 @@ static bool dsc_fit_lay16(int64_t H, int64_t Hprime, int64_t S, int64_t Kt, int6
         *L = dsc_lay16((int)H, (int)Hprime, (int)S, (int)Kt, (int)NT, 0);
     }
     return L->bytes <= 40 * 1024;
-#endif
 }
 
 // E-step + M-step row statistics in one pass (dsc_estep16_ms_kernel): its LDS layout, or 0 where it does not apply
@@ -1143,9 +1135,6 @@ static size_t dsc_estep_ms_lds(int64_t H, int64_t Hprime, int64_t S, int64_t Kt,
 
 // the launch geometry of dsc_mstep_rows16_kernel, or 0 bytes where it does not apply
 static size_t dsc_rows16_lds(int64_t H, int64_t Hprime, int64_t S, int64_t Kt, int *stage16) {
-#ifdef PM_DSC_WAVE64
-    return 0;
-#else
     if (!(H <= 256 && S * Hprime < (1 << 20) && Kt < (1 << 20))) return 0;
     const size_t fixed = sizeof(double) * (H + PM_DSC_MAX_K + 4) + align8((size_t)S * Hprime);
     const size_t rows16 = sizeof(double) * 16 * (size_t)(H + Hprime + Hprime * Hprime);
@@ -1156,7 +1145,6 @@ static size_t dsc_rows16_lds(int64_t H, int64_t Hprime, int64_t S, int64_t Kt, i
         sh16 = fixed + rows16;
     }
     return sh16 <= 40 * 1024 ? sh16 : 0;
-#endif
 }
 
 // Every launch decision of pm_dsc_estep_f64, pm_dsc_estep_mstats_f64 and pm_dsc_mstep_rows_cutp_f64: the launchers switch on
@@ -1180,7 +1168,7 @@ static int dsc_plan(int which, int64_t H, int64_t Hprime, int64_t S, int64_t K, 
     if (which == PM_DSC_PLAN_ESTEP_MSTATS) {
         p->lds = dsc_estep_ms_lds(H, Hprime, S, Kt, Kn, &p->stage, &p->nt);
         if (!p->lds) return PM_ERANGE;
-        const int per_cu = (Hprime <= 8 && H <= 128) ? PM_DSC_MS_WPE : 2;
+        const int per_cu = (Hprime <= 8 && H <= 128) ? DSC_MS_WPE : 2;
         p->family = PM_DSC_PLAN_LANES16;
         p->vpl = H <= 128 ? 8 : 16;
         p->km = K <= 4 ? 4 : PM_DSC_MAX_K;

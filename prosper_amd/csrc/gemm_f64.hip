@@ -756,9 +756,8 @@ int resident_slots() {  // workgroups of these kernels resident at once: 2 per C
     return slots;
 }
 
-// (The two-launch form -- main rounds, then the split-K remainder -- and a forced split factor were environment
-// switches in round 2; measured, settled, removed: the library reads no environment.)
-constexpr bool fuse_remainder() { return true; }
+// (The split-K remainder always shares the main rounds' launch: the two-launch form and a forced split factor were
+// round-2 switches; measured, settled, removed.)
 
 template <int MT>
 void launch_nt_mt(bool al, const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int M,
@@ -870,7 +869,7 @@ NtPlan nt_plan(int64_t M, int64_t N, int64_t K, bool aligned) {
             return p;
         }
 #endif
-        if (main_panels > 0 && rest_rows > 0 && nsplit > 1 && fuse_remainder()) {
+        if (main_panels > 0 && rest_rows > 0 && nsplit > 1) {
             nt_slices(nk, (int)nsplit, p.kps, p.nsplit);
             p.mask |= PM_NT_PLAN_DMA_FUSED;
             return p;
@@ -1045,10 +1044,7 @@ extern "C" int pm_gemm_tn_acc_rows_f64(const double *A, int64_t lda, const doubl
     const int tiles_m = (int)(M / TN_BM), tiles_n = (int)(N / BN);
     const int64_t tiles = (int64_t)tiles_m * tiles_n;
     const int slots = resident_slots();
-#ifndef PM_TN_ROWS_DIV
-#define PM_TN_ROWS_DIV 1
-#endif
-    int64_t nsplit = slots / tiles / PM_TN_ROWS_DIV;    // ONE round of resident workgroups, whatever *count turns out to be
+    int64_t nsplit = slots / tiles;    // ONE round of resident workgroups, whatever *count turns out to be
     const int64_t max_split = (max_rows + 8 * DK - 1) / (8 * DK);
     if (nsplit > max_split) nsplit = max_split;
     if (nsplit < 1) nsplit = 1;

@@ -152,12 +152,6 @@ struct GscTables {
 // LACC: the column sums of xpt_s / xpt_sz and the singletons' diagonal of sum xpt_szsz are accumulated in LDS -- [3][4
 // wavefronts][H] accumulators, ds_add_f64 per lane and datapoint row, a copy per wavefront so that the four never contend --
 // and folded at the end: no second pass over the N x H moments (gsc_colsum_kernel read 410 MB again at config 4: 0.09 ms).
-#ifndef PM_GSC_LAUNDER
-#define PM_GSC_LAUNDER 1
-#endif
-#ifndef PM_GSC_ABL
-#define PM_GSC_ABL 0      // timing-only ablation builds (scratch/gsc_abl.sh): bits switch phases off, results are wrong
-#endif
 // -DPM_GSC_STAMPS (scratch/gsc_stamps.py, never in the shipped library): wavefront 0 of every 37th workgroup writes s_memrealtime
 // (100 MHz) at the phase boundaries of its first datapoints into pm_gsc_stamps[workgroup / 37][datapoint][phase]
 #ifdef PM_GSC_STAMPS
@@ -170,9 +164,7 @@ __device__ unsigned long long pm_gsc_stamps[32][12][10];
 #else
 #define GSC_STAMP(ph)
 #endif
-#ifndef PM_GSC_WPE
-#define PM_GSC_WPE 3        // wavefronts per SIMD the common instantiations are compiled for (register budget 512 / WPE)
-#endif
+constexpr int GSC_WPE = 3;    // wavefronts per SIMD the common instantiations are compiled for (register budget 512 / WPE)
 // LIST (with LACC): the M-step's contraction [Y | xpt_s | xpt_sz]^T . xpt_sz (gsc_et.py:592-625) as a sparse + a dense part.
 // A row of xpt_sz whose entries above `thr` number at most PM_BSC_NZ_MAX leaves them as a list (format of the BSC / DSC
 // statistics passes: nz_idx uint16 x 16 with 0xFFFF behind the last, nz_val f64 x 16) for pm_wp_sparse_t_f64; any other row
@@ -183,7 +175,7 @@ __device__ unsigned long long pm_gsc_stamps[32][12][10];
 // themselves; thr = 0 (first step, a dead latent's column) keeps everything: every row is dense then, correct and slow.
 constexpr int GSC_DENSE_CAP = 512;          // datapoints per workgroup in LIST mode at most (the launcher sizes the grid)
 template <int VPL, int GMAX, bool LPJ, bool LACC, bool LIST = false>
-__global__ __launch_bounds__(256, (VPL <= 8 && GMAX <= 3) ? PM_GSC_WPE : 1) void gsc_estep_kernel(const double *__restrict__ scores, int64_t lds,
+__global__ __launch_bounds__(256, (VPL <= 8 && GMAX <= 3) ? GSC_WPE : 1) void gsc_estep_kernel(const double *__restrict__ scores, int64_t lds,
                                                          const double *__restrict__ gram,
                                                          const double *__restrict__ psi,
                                                          const double *__restrict__ ynorm2, GscTables T,
@@ -278,7 +270,7 @@ __global__ __launch_bounds__(256, (VPL <= 8 && GMAX <= 3) ? PM_GSC_WPE : 1) void
             const int ci = __builtin_amdgcn_ds_bpermute((rowbase + i) << 2, myc_prev);
             const int ck = __builtin_amdgcn_ds_bpermute((rowbase + k) << 2, myc_prev);
             if (ok) {
-                if (pend && !(PM_GSC_ABL & 16)) {
+                if (pend) {
                     // xpt_ss is symmetric: upper triangle only; xpt_szsz = kappa kappa^T + Lambda^-1 is NOT once psi_sq has
                     // been through an M-step (gsc_et.py:660-675 leaves it non-symmetric): both triangles, as they are
                     // The diagonals stay at home: diag(sum xpt_ss) IS the column sum of xpt_s (s_h^2 = s_h; nobody reads the
@@ -347,7 +339,7 @@ __global__ __launch_bounds__(256, (VPL <= 8 && GMAX <= 3) ? PM_GSC_WPE : 1) void
                 key[i] = kx;
             }
             uint64_t mine = 0;                                // this lane's own selected latents, bit i
-            for (int r = 0; r < ((PM_GSC_ABL & 32) ? 1 : Hp); ++r) {
+            for (int r = 0; r < Hp; ++r) {
                 double m = key[0];
 #pragma unroll
                 for (int i = 1; i < VPL; ++i) m = __builtin_fmax(m, key[i]);
@@ -370,17 +362,12 @@ __global__ __launch_bounds__(256, (VPL <= 8 && GMAX <= 3) ? PM_GSC_WPE : 1) void
                 before_slot += __builtin_popcount(rowbits);
             }
             g_sync();
-#if PM_GSC_LAUNDER
             {
                 int jq = j;
                 asm volatile("" : "+v"(jq));      // (see below: no spilled LDS address, no scratch reload here)
                 if (jq < Hp) myc = (int)s_as[jq];
             }
-#else
-            if (j < Hp) myc = (int)s_as[j];
-#endif
             g_sync();
-#if PM_GSC_LAUNDER
             {   // (the lane's slot, opaque to the optimiser here: `cand + j` is otherwise a loop-invariant 64-bit address
                 // that gets SPILLED at three wavefronts per SIMD -- and a scratch reload is a vector-memory operation:
                 // its `s_waitcnt vmcnt(0)` drains the previous datapoint's stores before the candidate store may issue)
@@ -388,9 +375,6 @@ __global__ __launch_bounds__(256, (VPL <= 8 && GMAX <= 3) ? PM_GSC_WPE : 1) void
                 asm volatile("" : "+v"(jq));
                 if (live && jq < Hp) cand[n * Hp + jq] = myc;
             }
-#else
-            if (live && j < Hp) cand[n * Hp + j] = myc;
-#endif
         } else {
             if (j < Hp) myc = cand[nn * Hp + j];
         }
@@ -398,7 +382,6 @@ __global__ __launch_bounds__(256, (VPL <= 8 && GMAX <= 3) ? PM_GSC_WPE : 1) void
         // ---- candidate blocks -> LDS, accumulators cleared.  Candidate k of this datapoint sits in lane
         // rowbase + k: ds_bpermute fetches it (uniform trip counts: every source lane stays active)
         GSC_STAMP(1);
-#if PM_GSC_LAUNDER
         {
             int jq = j;
             asm volatile("" : "+v"(jq));
@@ -408,13 +391,6 @@ __global__ __launch_bounds__(256, (VPL <= 8 && GMAX <= 3) ? PM_GSC_WPE : 1) void
                 s_asz[jq] = 0.0;
             }
         }
-#else
-        if (j < Hp) {
-            s_ac[j] = arow[myc];
-            s_as[j] = 0.0;
-            s_asz[j] = 0.0;
-        }
-#endif
         for (int p0 = 0; p0 < HH; p0 += 16) {
             const int p = p0 + j;
             const bool ok = p < HH;
@@ -422,8 +398,8 @@ __global__ __launch_bounds__(256, (VPL <= 8 && GMAX <= 3) ? PM_GSC_WPE : 1) void
             const int ci = __builtin_amdgcn_ds_bpermute((rowbase + i) << 2, myc);
             const int ck = __builtin_amdgcn_ds_bpermute((rowbase + k) << 2, myc);
             if (ok) {
-                s_Gc[p] = (PM_GSC_ABL & 128) ? (ci == ck ? 250.0 : 1.0) : gram[(int64_t)ci * H + ck];
-                s_Pc[p] = (PM_GSC_ABL & 128) ? (ci == ck ? 1.1 : 0.0) : psi[(int64_t)ci * H + ck];
+                s_Gc[p] = gram[(int64_t)ci * H + ck];
+                s_Pc[p] = psi[(int64_t)ci * H + ck];
             }
         }
         // every load of this datapoint has landed before the atomics below are issued -- said explicitly, so that
@@ -439,7 +415,7 @@ __global__ __launch_bounds__(256, (VPL <= 8 && GMAX <= 3) ? PM_GSC_WPE : 1) void
         double Z = (j == 0) ? exp(-yn * inv_s2 * beta) : 0.0;       // null state (not clamped upstream: libm)
         double Zm = 0.0;                                            // (LPJ + blocks: the multi-cause states' weights alone)
         if (LPJ && live && j == 0) logpj[n * ldl] = -yn * inv_s2;
-        for (int s0 = 0; s0 < ((PM_GSC_ABL & 1) ? 0 : S); s0 += 16) {
+        for (int s0 = 0; s0 < S; s0 += 16) {
             const int s = s0 + j;
             const bool valid = s < S;
             const unsigned mask = valid ? s_masks[s] : 0u;
@@ -556,7 +532,7 @@ __global__ __launch_bounds__(256, (VPL <= 8 && GMAX <= 3) ? PM_GSC_WPE : 1) void
                 const double bb = ai - s_gm[h];
                 const double lp = s_c0[h] - yn * inv_s2 + s_c1[h] * ai + bb * bb * s_il[h] + s_lpi[h];
                 if (LPJ && live) logpj[n * ldl + 1 + h] = lp;
-                p = (PM_GSC_ABL & 2) ? lp : gsc_weight(lp * beta, etab);
+                p = gsc_weight(lp * beta, etab);
                 Z += p;
             }
             xs[i] = p;
@@ -607,11 +583,9 @@ __global__ __launch_bounds__(256, (VPL <= 8 && GMAX <= 3) ? PM_GSC_WPE : 1) void
             bool sig = false;
             if (live && h < H) {
                 const double vs = xs[i] * nf, vz = xsz[i] * nf;
-                if (!(PM_GSC_ABL & 4)) {
-                    xpt_s[n * ldx + h] = vs;
-                    xpt_sz[n * ldx + h] = vz;
-                }
-                if (LACC && !(PM_GSC_ABL & 8)) {
+                xpt_s[n * ldx + h] = vs;
+                xpt_sz[n * ldx + h] = vz;
+                if (LACC) {
                     atomicAdd(&acc_mine[16 * i], vs);
                     atomicAdd(&acc_mine[4 * H + 16 * i], vz);
                 }
@@ -623,7 +597,7 @@ __global__ __launch_bounds__(256, (VPL <= 8 && GMAX <= 3) ? PM_GSC_WPE : 1) void
             }
         }
         GSC_STAMP(7);
-        if (LIST && live && !(PM_GSC_ABL & 64)) {
+        if (LIST && live) {
             const bool sparse = nsig <= PM_BSC_NZ_MAX;
             uint16_t *li = nz_idx + n * PM_BSC_NZ_MAX;
             if (sparse) {
@@ -773,9 +747,7 @@ extern "C" int pm_gsc_supported(int64_t H, int64_t Hprime, int64_t gamma) {
     return gsc_shmem(H, Hprime, gsc_full_states(Hprime, gamma)) <= 64 * 1024 ? 1 : 0;
 }
 
-#ifndef PM_PAIRS_WGS
-#define PM_PAIRS_WGS 256
-#endif
+constexpr int PAIRS_WGS = 256;      // workgroups a pm_gsc_list_pairs_f64 launch aims at: 2 products x row chunks x datapoint groups
 // Every launch decision of gsc_estep_launch (pm_gsc_estep_f64, _lists_f64, _lpj_f64, _lpj_blocks_f64), pm_gsc_list_pairs_f64,
 // pm_gsc_pack_stats_f64 and pm_gsc_component_scores_f64: the launchers switch on this struct and pm_gsc_plan exports it, so a
 // test that asks for the plan sees the instantiation the launch takes.
@@ -801,7 +773,7 @@ static int gsc_plan(int which, int64_t H, int64_t Hprime, int64_t S, int64_t gam
         while (H % rows_c != 0) --rows_c;
         p->rows_c = rows_c;
         p->nchunks = (int)(H / rows_c);
-        int64_t groups = PM_PAIRS_WGS / (2 * p->nchunks);
+        int64_t groups = PAIRS_WGS / (2 * p->nchunks);
         if (groups < 1) groups = 1;
         int64_t rpg = (N + groups - 1) / groups;
         rpg = (rpg + 63) / 64 * 64;

@@ -27,30 +27,8 @@
 // documented part of the statistics buffer; the per-XCD copies of [Wp | Wq] follow it (pm_common.h)
 __host__ __device__ static inline int64_t mca_stats_base(int64_t H, int64_t D) { return 3 * H * D + H + PM_MCA_NSCALARS; }
 
-#ifndef PM_MCA_TSUM
-#define PM_MCA_TSUM 0   // the states' row sums in the fused pass: 1 prefix in registers + the new row a trip ahead, 0 the same without the read-ahead, 2 two rows per state
-#endif
-#ifndef PM_MCA_VDEFER
-#define PM_MCA_VDEFER 0 // a state's V update (and the rare rescaling) at the top of the next trip: one straight-line block for both stages
-#endif
-#ifndef PM_MCA_PAIR
-#define PM_MCA_PAIR -1  // two states per trip of the fused pass's state loop: -1 where one wavefront per SIMD runs anyway, 0 never, 1 always
-#endif
-#ifndef PM_MCA_NS
-#define PM_MCA_NS 2     // states per trip of that form
-#endif
-#ifndef PM_MCA_ABL
-#define PM_MCA_ABL 0   // timing ablations (scratch/mca_abl.sh): 1 no global atomics, 2 no powers, 3 no V updates, 4 T sums from candidate 0 only, 5 no wave reduction, 6 no exponential, 7 no states at all (S = 0)
-#endif
-
-#ifndef PM_SCATTER_LDS_DOUBLES
-#define PM_SCATTER_LDS_DOUBLES 16384  // LDS of a mca_defer_scatter_kernel workgroup, in doubles: 128 KB, one workgroup per CU (8192 = two per CU: 0.68 against 0.46 ms -- twice the latent ranges, every datapoint scanned and its y row read by twice as many workgroups)
-#endif
-#ifndef PM_SCATTER_ABL
-#define PM_SCATTER_ABL 0          // timing-only ablations of mca_defer_scatter_kernel (wrong results): 1 no LDS atomics, 2 no record loads
-#endif
-// the fused pass's root / power table area: pm_load_root21 / pm_load_root6 (A/B builds) or pm_load_upow (any rho)
-#define PM_FUSED_RT_LEN (PM_ROOT21_LEN + 1)      // (>= PM_UPOW_AB_LEN; NOT larger: four workgroups of two wavefronts fill a CU's LDS to within 1.6 KB at config 5)
+// the fused pass's second power table area (pm_load_upow's `ab`), at the size of the table-seeded roots' tables it once also held
+#define PM_FUSED_RT_LEN (256 + 21 + 1)      // (>= PM_UPOW_AB_LEN; NOT larger: four workgroups of two wavefronts fill a CU's LDS to within 1.6 KB at config 5)
 
 namespace {
 
@@ -59,10 +37,8 @@ namespace {
 // an inline function the E-step and M-step kernels compile to other branches than the expression written out in them;
 // its argument is a plain double wherever it is used.
 #define MCA_RHO_IS(inv_rho, rho) ((inv_rho) > 0.0 && fabs(1.0 / (inv_rho) - (rho)) < 1e-9)
-// the fused pass walks its states two per trip (see PAIRED in mca_estep_fused_body)
-__host__ __device__ constexpr bool mca_fused_paired(int dpl, int hp, bool sgn) {
-    return (PM_MCA_PAIR == 1) || (PM_MCA_PAIR < 0 && sgn && dpl <= 4 && hp * dpl >= 24);
-}
+// the fused pass walks its states two per trip (see PAIRED in mca_estep_fused_body): where one wavefront per SIMD runs anyway
+__host__ __device__ constexpr bool mca_fused_paired(int dpl, int hp, bool sgn) { return sgn && dpl <= 4 && hp * dpl >= 24; }
 
 // ---------------------------------------------------------------------------------------------
 // sim[n,h] = sum_d max(W[h,d] - Y[n,d], 0): 64 x 64 output tile per 256-thread workgroup, 4 x 4 per
@@ -121,27 +97,19 @@ __global__ __launch_bounds__(256) void mca_select_scores_kernel(const double *__
             for (int a = 0; a < 4; ++a)
 #pragma unroll
                 for (int b = 0; b < 4; ++b) {
-#ifndef PM_MCA_SEL3
                     // sum_d max(W - y, 0) = sum_d max(W, y) - sum_d y: two f64 instructions per (n, h, d) instead of three
                     // (one raw v_max_f64 -- fmax() canonicalises operands it cannot prove quiet -- and one add; the row
                     // sums of y ride along, one add per datapoint and d): 0.343 -> 0.283 ms at config 5 once the slabs are
                     // prefetched (before that the pass was latency-bound and this form measured no faster).  The difference
                     // of two sums of ~500 rounds at ~1e-13 absolute; the ranking it feeds separates candidates by O(1).
-                    // -DPM_MCA_SEL3 builds the three-instruction form.
                     double m0, m1;
                     asm("v_max_f64 %0, %1, %2" : "=v"(m0) : "v"(wv[b].x), "v"(yv[a].x));
                     asm("v_max_f64 %0, %1, %2" : "=v"(m1) : "v"(wv[b].y), "v"(yv[a].y));
                     acc[a][b] += m0;
                     acc[a][b] += m1;
-#else
-                    acc[a][b] += fmax(wv[b].x - yv[a].x, 0.0);
-                    acc[a][b] += fmax(wv[b].y - yv[a].y, 0.0);
-#endif
                 }
-#ifndef PM_MCA_SEL3
 #pragma unroll
             for (int a = 0; a < 4; ++a) ysum[a] += yv[a].x + yv[a].y;
-#endif
         }
         __syncthreads();
     }
@@ -152,12 +120,7 @@ __global__ __launch_bounds__(256) void mca_select_scores_kernel(const double *__
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             const int h = h0 + tc + 16 * b;
-#ifndef PM_MCA_SEL3
             if (h < H) R[n * ldr + h] = acc[a][b] - ysum[a];
-#else
-            (void)ysum;
-            if (h < H) R[n * ldr + h] = acc[a][b];
-#endif
         }
     }
 }
@@ -182,11 +145,8 @@ __global__ __launch_bounds__(256) void mca_estep_kernel(const double *__restrict
     double *s_e = s_wr + Hp * DS;
     pm_load_powtab(s_tab, tid, blockDim.x);
     // rho = 21 (every temperature T <= 1.05), unsigned W: the log / exp-free power (pm_pow_m20_21)
-    __shared__ __attribute__((aligned(16))) double s_rt[PM_ROOT21_LEN + 1];
     const bool r21 = P.signed_w == 0.0 && MCA_RHO_IS(P.inv_rho, 21.0);
     const bool r6 = MCA_RHO_IS(P.inv_rho, 6.0);       // (MMCA's steady rho; either sign of W)
-    if (!PM_POW_HWSEED && r21) pm_load_root21(s_rt, pm_powtab_dev, tid, blockDim.x);       // (the table seed's tables: A/B builds)
-    else if (!PM_POW_HWSEED && r6) pm_load_root6(s_rt, pm_powtab_dev, tid, blockDim.x);
     __syncthreads();
 
     const int64_t wave0 = (int64_t)blockIdx.x * waves + wave;
@@ -251,8 +211,8 @@ __global__ __launch_bounds__(256) void mca_estep_kernel(const double *__restrict
                 for (int i = 0; i < DPL; ++i) {
                     // MMCA: T may be negative or 0 (mmca_et.py:191: sign(t) exp(log|t| / rho)); for MCA T > 0
                     const double aT = fabs(T[i]);
-                    const double wbar = (aT > 0.0) ? (ROOT == 21 ? aT * pm_pow_m20_21(aT, s_rt)
-                                                      : ROOT == 6 ? copysign(aT * pm_pow_m5_6(aT, s_rt), T[i])
+                    const double wbar = (aT > 0.0) ? (ROOT == 21 ? aT * pm_pow_m20_21(aT)
+                                                      : ROOT == 6 ? copysign(aT * pm_pow_m5_6(aT), T[i])
                                                                   : copysign(pm_pow_tab(aT, P.inv_rho, s_tab), T[i]))
                                                    : 0.0;
                     const double df = wbar - y[i];
@@ -302,12 +262,12 @@ __global__ __launch_bounds__(256) void mca_estep_kernel(const double *__restrict
 // smaller than its final value, so nothing underflows that would survive in the two-pass form.
 // ---------------------------------------------------------------------------------------------
 
-// ROOT = 21: rho = 21 (every temperature T <= 1.05, unsigned W): the states' power through pm_pow_m20_21 (no log / exp);
-// ROOT = 6: rho = 6 (MMCA at every T <= 1.2): pm_pow_m5_6; ROOT = 0: any rho, the table power
+// ROOT = 6: rho = 6 (MMCA at every T <= 1.2): the states' power through pm_pow_m5_6 (no log / exp); ROOT = 0: any rho, the
+// uniform-exponent power (pm_pow_uni) -- unsigned W at every rho, rho = 21 included (see mca_plan)
 // (The body is a device function shared by two kernels: mca_estep_fused_kernel keeps the argument list it had before the
 // deferred form existed -- two more pointer arguments alone moved the rho = 21 instantiation from 202 to 235 registers and
 // from 6.6 to 7.7 ms --, mca_estep_fused_defer_kernel adds the record pointers.)
-template <int DPL, int HP, bool SIGNED, int ROOT, bool DEFER>      // ROOT: 21 / 6 = the log / exp-free powers of those rho, 0 = the uniform-exponent power; DEFER: statistics as per-datapoint records
+template <int DPL, int HP, bool SIGNED, int ROOT, bool DEFER>      // ROOT: 6 = the log / exp-free power of that rho, 0 = the uniform-exponent power; DEFER: statistics as per-datapoint records
 __device__ __forceinline__ void mca_estep_fused_body(const double *__restrict__ scores, int64_t lds,
                                        const double *__restrict__ wnorm2, const double *__restrict__ ynorm2,
                                        const double *__restrict__ Y, int64_t ldy, const double *__restrict__ Wrho,
@@ -322,24 +282,22 @@ __device__ __forceinline__ void mca_estep_fused_body(const double *__restrict__ 
     // with the largest log-denominator, known only once every rank's E-step is through -- the pass then ACCUMULATES NOTHING:
     // it leaves each datapoint's Aid block (Hp x D, what it would have scattered into Wq; times y into Wp) in defer_rec, its
     // three scalars in defer_sc, its singleton posteriors in q1 as always, and mca_defer_apply_kernel adds the kept ones.
-    // [ power tables (PM_POWTAB_LEN) | root table (PM_ROOT21_LEN) | q1sum (H) | red (4 * waves) | per wave: wr (HP*DS)
+    // [ power tables (PM_POWTAB_LEN) | second power table (PM_FUSED_RT_LEN) | q1sum (H) | red (4 * waves) | per wave: wr (HP*DS)
     //   [wm (HP*DS)] e (S) ]
     constexpr int DS = 64 * DPL;
     const int waves = blockDim.x >> 6;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double *s_tab = reinterpret_cast<double *>(smem);
-    double *s_rt = s_tab + PM_POWTAB_LEN;
-    double *s_q1sum = s_rt + PM_FUSED_RT_LEN;            // (an even number of doubles: 16-byte alignment of what follows)
+    double *s_ab = s_tab + PM_POWTAB_LEN;
+    double *s_q1sum = s_ab + PM_FUSED_RT_LEN;            // (an even number of doubles: 16-byte alignment of what follows)
     if (ROOT == 0) {
         // any other rho (every step of an annealing ramp): the tables of THIS launch's exponent 1 / rho - 1 (pm_pow_uni) --
         // its (r_i, r_i^-c) pairs take the place of pm_pow_tab's (r_i, L_i) in the power table, pm_exp_tab's E_j stay
         for (int i = 256 + tid; i < PM_POWTAB_LEN; i += blockDim.x) s_tab[i] = pm_powtab_dev[i];
-        pm_load_upow(s_tab, s_rt, pm_powtab_dev, P.inv_rho - 1.0, tid, blockDim.x);
+        pm_load_upow(s_tab, s_ab, pm_powtab_dev, P.inv_rho - 1.0, tid, blockDim.x);
     } else {
         pm_load_powtab(s_tab, tid, blockDim.x);
     }
-    if (!PM_POW_HWSEED && ROOT == 21) pm_load_root21(s_rt, pm_powtab_dev, tid, blockDim.x);  // (the table seed's tables: A/B builds)
-    if (!PM_POW_HWSEED && ROOT == 6) pm_load_root6(s_rt, pm_powtab_dev, tid, blockDim.x);
     double *s_red = s_q1sum + H;
     const size_t per_wave = (size_t)(SIGNED ? 2 : 1) * HP * DS + S;
     double *s_wr = s_red + 4 * waves + (size_t)wave * per_wave;
@@ -399,9 +357,10 @@ __device__ __forceinline__ void mca_estep_fused_body(const double *__restrict__ 
         // T of a state = the sum of its candidates' rows in ascending order = (the sum over all but its highest candidate)
         // + that candidate's row.  The states arrive as itertools.combinations lists them: consecutive ones share that
         // prefix (56 of config 5's 84), so the prefix sum stays in registers (Pf, its mask in a scalar) and a state costs ONE
-        // row read -- requested a trip ahead, its LDS latency under the previous state's work -- and DPL additions, with
-        // no branch in the common case; the bits are those of the straight sum (0 + x = x).  [round 5; before: eight bit
-        // tests and up to gamma read -> wait -> add blocks per state, 1.0 of the pass's 7.4 ms]
+        // row read and DPL additions, with no branch in the common case; the bits are those of the straight sum (0 + x = x).
+        // [round 5; before: eight bit tests and up to gamma read -> wait -> add blocks per state, 1.0 of the pass's 7.4 ms.
+        // Reading the row a trip ahead measured no better (6.63-6.74 against 6.62-6.64 ms), two rows per state over a cached
+        // rest slower (6.78-6.82): profiles/r05_mca_rowsums.txt]
         double Pf[DPL];
         unsigned pfx = 0xFFFFFFFFu;
         auto sum_rows = [&](unsigned mm, double (&out)[DPL]) {      // the straight sum (uniform bit tests)
@@ -414,32 +373,7 @@ __device__ __forceinline__ void mca_estep_fused_body(const double *__restrict__ 
                     for (int i = 0; i < DPL; ++i) out[i] += s_wr[j * DS + lane + 64 * i];
                 }
         };
-        auto row_of = [&](unsigned m, double (&row)[DPL]) {
-            const int hb = 31 - __builtin_clz(m | 1u);
-#pragma unroll
-            for (int i = 0; i < DPL; ++i) row[i] = s_wr[hb * DS + lane + 64 * i];
-        };
-#if PM_MCA_TSUM == 2
-        // two rows per state (its two highest candidates), the sum of the others cached: no branch for 77 of 84 states
-        auto state_T = [&](unsigned m, const double (&)[DPL], double (&T)[DPL]) {
-            const int hb = 31 - __builtin_clz(m | 1u);
-            const unsigned pm = m & ~(1u << hb);
-            const int hb2 = 31 - __builtin_clz(pm | 1u);
-            const unsigned pm2 = pm & ~(1u << hb2);
-            if (pm == 0u) {                       // fewer than two candidates: never among the multi-cause states
-                asm volatile("" ::: "memory");
-                sum_rows(m, T);
-                return;
-            }
-            if (pm2 != pfx) {
-                sum_rows(pm2, Pf);
-                pfx = pm2;
-            }
-#pragma unroll
-            for (int i = 0; i < DPL; ++i) T[i] = (Pf[i] + s_wr[hb2 * DS + lane + 64 * i]) + s_wr[hb * DS + lane + 64 * i];
-        };
-#else
-        auto state_T = [&](unsigned m, const double (&row)[DPL], double (&T)[DPL]) {
+        auto state_T = [&](unsigned m, double (&T)[DPL]) {
             const int hb = 31 - __builtin_clz(m | 1u);
             const unsigned pm = m & ~(1u << hb);
             if (pm != pfx) {                      // uniform: the prefix changed (28 of 84 states)
@@ -447,47 +381,37 @@ __device__ __forceinline__ void mca_estep_fused_body(const double *__restrict__ 
                 pfx = pm;
             }
 #pragma unroll
-            for (int i = 0; i < DPL; ++i) T[i] = Pf[i] + (PM_MCA_TSUM == 0 ? s_wr[hb * DS + lane + 64 * i] : row[i]);
+            for (int i = 0; i < DPL; ++i) T[i] = Pf[i] + s_wr[hb * DS + lane + 64 * i];
             if (m == 0u) {                        // (no candidate at all: never among the multi-cause states)
                 asm volatile("" ::: "memory");    // (a real branch, not eight selects per state)
 #pragma unroll
                 for (int i = 0; i < DPL; ++i) T[i] = 0.0;
             }
         };
-#endif
         auto state_pow = [&](const double (&T)[DPL], double (&wb_out)[DPL], double &part) {
 #pragma unroll
             for (int i = 0; i < DPL; ++i) {
                 // ONE power per element: r = |T|^(1/rho - 1) gives |Wbar| = |T| r here and Wbar / T = r for the
                 // M-step weights (no division).  Padding dimensions have T = 0: Wbar = 0, never scattered.
                 const double aT = SIGNED ? fabs(T[i]) : T[i];      // (unsigned W: T is a sum of W^rho >= 0)
-                const double r = (PM_MCA_ABL == 2) ? aT * 0.37
-                                 : (ROOT == 21 ? pm_pow_m20_21(aT, s_rt) : ROOT == 6 ? pm_pow_m5_6(aT, s_rt)
-                                                                                 : pm_pow_uni(aT, s_tab, s_rt));
+                const double r = ROOT == 6 ? pm_pow_m5_6(aT) : pm_pow_uni(aT, s_tab, s_ab);
                 const double wb = (aT > 0.0) ? aT * r : 0.0;
                 const double df = (SIGNED ? copysign(wb, T[i]) : wb) - y[i];
                 part = fma(df, df, part);
                 wb_out[i] = (aT > 0.0) ? r : (SIGNED ? INFINITY : 0.0);
             }
         };
-        // state s's V update: w |T|^(1/rho - 1) into the rows of its own candidates [signed W: times W^(rho - 1)'s row]
-        double vD[DPL], wD = 0.0, scD = 0.0;
+        // state s's V update: w |T|^(1/rho - 1) into the rows of its own candidates [signed W: times W^(rho - 1)'s row].
+        // (Deferred to the top of the next trip, one straight-line block for both stages: 6.77-6.86 against 6.62-6.64 ms,
+        // profiles/r05_mca_rowsums.txt.)
+        double vD[DPL], wD = 0.0;
         unsigned maskD = 0u;
-        bool rescD = false;
 #pragma unroll
         for (int i = 0; i < DPL; ++i) vD[i] = 0.0;
         auto v_update = [&]() {
-            if (PM_MCA_VDEFER && rescD) {
-                const double sc = exp(scD);
-#pragma unroll
-                for (int j = 0; j < HP; ++j)
-#pragma unroll
-                    for (int i = 0; i < DPL; ++i) V[j][i] *= sc;
-            }
             if (!SIGNED) {
-#ifndef PM_MCA_VPRED
                 // (round 3: uniform branches instead of 0/1 factors over all H' candidates -- 2.7 of 8 rows per state at
-                // config 5: 8.15 -> 7.82 ms; -DPM_MCA_VPRED restores the predicated form)
+                // config 5: 8.15 -> 7.82 ms)
 #pragma unroll
                 for (int j = 0; j < HP; ++j) {
                     if ((maskD >> j) & 1u) {      // uniform (scalar) branch: only the state's own candidates are touched
@@ -495,14 +419,6 @@ __device__ __forceinline__ void mca_estep_fused_body(const double *__restrict__ 
                         for (int i = 0; i < DPL; ++i) V[j][i] += vD[i];
                     }
                 }
-#else
-#pragma unroll
-                for (int j = 0; j < HP; ++j) {
-                    const double sel = (((maskD >> j) & 1u) && (PM_MCA_ABL != 3 || wD == 1.2345e-300)) ? 1.0 : 0.0;   // uniform
-#pragma unroll
-                    for (int i = 0; i < DPL; ++i) V[j][i] = fma(sel, vD[i], V[j][i]);
-                }
-#endif
             } else {
 #pragma unroll
                 for (int j = 0; j < HP; ++j)
@@ -520,10 +436,10 @@ __device__ __forceinline__ void mca_estep_fused_body(const double *__restrict__ 
         // 10.67 -> 9.72 ms.  (At two wavefronts per SIMD the pair form needs 272 registers -- one wavefront, 9.0 against 6.65 ms.)
         constexpr bool PAIRED = mca_fused_paired(DPL, HP, SIGNED);
         if constexpr (PAIRED) {
-        constexpr int NS = PM_MCA_NS;                 // states per trip
+        constexpr int NS = 2;                         // states per trip
         auto mask_at = [&](int s) { return masks[s < S ? s : S - 1]; };
         unsigned mP[NS], ld[NS];
-        double wbQ[NS][DPL], partQ[NS], rowX[DPL];
+        double wbQ[NS][DPL], partQ[NS];
 #pragma unroll
         for (int u = 0; u < NS; ++u) {
             mP[u] = S > 0 ? (unsigned)__builtin_amdgcn_readfirstlane((int)mask_at(u)) : 0u;
@@ -533,7 +449,7 @@ __device__ __forceinline__ void mca_estep_fused_body(const double *__restrict__ 
 #pragma unroll
         for (int u = 0; u < NS; ++u) {
             double T[DPL];
-            state_T(mP[u], rowX, T);
+            state_T(mP[u], T);
             state_pow(T, wbQ[u], partQ[u]);
         }
         auto weigh = [&](unsigned m, double bf, const double (&wb)[DPL]) {      // one state, the reference level may move
@@ -553,7 +469,7 @@ __device__ __forceinline__ void mca_estep_fused_body(const double *__restrict__ 
             for (int i = 0; i < DPL; ++i) vD[i] = SIGNED ? wb[i] : w * wb[i];
             v_update();
         };
-        for (int s = 0; s < ((PM_MCA_ABL == 7) ? 0 : S); s += NS) {
+        for (int s = 0; s < S; s += NS) {
             unsigned mN[NS];
 #pragma unroll
             for (int u = 0; u < NS; ++u) {
@@ -565,7 +481,7 @@ __device__ __forceinline__ void mca_estep_fused_body(const double *__restrict__ 
 #pragma unroll
             for (int u = 0; u < NS; ++u) {
                 partN[u] = 0.0;
-                state_T(mN[u], rowX, TN[u]);
+                state_T(mN[u], TN[u]);
             }
 #pragma unroll
             for (int u = 0; u < NS; ++u) state_pow(TN[u], wbN[u], partN[u]);
@@ -610,48 +526,24 @@ __device__ __forceinline__ void mca_estep_fused_body(const double *__restrict__ 
         unsigned maskP = S > 0 ? (unsigned)__builtin_amdgcn_readfirstlane((int)masks[0]) : 0u;      // (scalar registers)
         unsigned maskN = S > 0 ? (unsigned)__builtin_amdgcn_readfirstlane((int)masks[S > 1 ? 1 : 0]) : 0u;
         unsigned mask_load = S > 0 ? masks[S > 2 ? 2 : S - 1] : 0u;
-        double rowN[DPL];
         {
-            double T[DPL], row0[DPL];
-            if (PM_MCA_TSUM == 1) row_of(maskP, row0);
-            state_T(maskP, row0, T);
-            if (PM_MCA_TSUM == 1) row_of(maskN, rowN);
+            double T[DPL];
+            state_T(maskP, T);
             state_pow(T, wbP, partP);
         }
-        for (int s = 0; s < ((PM_MCA_ABL == 7) ? 0 : S); ++s) {
-            // wave-uniform masks; the one three states on is requested now (vector-memory latency under this trip's
-            // work), the row of the state after next as soon as its mask is here
+        for (int s = 0; s < S; ++s) {
+            // wave-uniform masks; the one three states on is requested now (vector-memory latency under this trip's work)
             const unsigned maskNN = (unsigned)__builtin_amdgcn_readfirstlane((int)mask_load);
             mask_load = masks[s + 3 < S ? s + 3 : S - 1];
-            if (PM_MCA_VDEFER) v_update();         // state s - 1 (nothing in the first trip: maskD = 0)
-            double rowNN[DPL];
-            if (PM_MCA_TSUM == 1) row_of(maskNN, rowNN);
             // ---- stage A, state s + 1 (the last trip computes a dummy) ----
             double T[DPL], wbN[DPL], partN = 0.0;
-            if (PM_MCA_ABL == 4) {
-#pragma unroll
-                for (int i = 0; i < DPL; ++i) T[i] = s_wr[lane + 64 * i];
-            } else {
-                state_T(maskN, rowN, T);
-            }
+            state_T(maskN, T);
             state_pow(T, wbN, partN);
             // ---- stage B, state s ----
-            const double part = (PM_MCA_ABL == 5) ? partP * 64.0 : pm_wave_sum_dpp(partP);   // wave-uniform
+            const double part = pm_wave_sum_dpp(partP);   // wave-uniform
             if (lane == 0) s_e[s] = part;
             const double bf = P.beta * (P.pil_bar * (double)__builtin_popcount(maskP) + P.pre1 * part);
-            double w = (PM_MCA_ABL == 6) ? (bf - M) * 0.001 + 1.0 : pm_exp_tab(bf - M, s_tab);   // (meaningless if the reference level moves)
-#if PM_MCA_VDEFER
-            // the reference level moves (uniform; the first state, then hardly ever): selects here, the rescaling of V and
-            // this state's V update at the top of the next trip -- nothing branches between the two stages' chains
-            rescD = bf > M + 50.0;
-            scD = M - bf;
-            M = rescD ? bf : M;
-            w = rescD ? 1.0 : w;
-            maskD = maskP;
-            wD = w;
-#pragma unroll
-            for (int i = 0; i < DPL; ++i) vD[i] = SIGNED ? wbP[i] : w * wbP[i];
-#else
+            double w = pm_exp_tab(bf - M, s_tab);   // (meaningless if the reference level moves)
             if (bf > M + 50.0) {                                        // uniform; the first state, then hardly ever
                 const double sc = exp(M - bf);
 #pragma unroll
@@ -666,17 +558,12 @@ __device__ __forceinline__ void mca_estep_fused_body(const double *__restrict__ 
 #pragma unroll
             for (int i = 0; i < DPL; ++i) vD[i] = SIGNED ? wbP[i] : w * wbP[i];
             v_update();
-#endif
             partP = partN;
             maskP = maskN;
             maskN = maskNN;
 #pragma unroll
-            for (int i = 0; i < DPL; ++i) {
-                wbP[i] = wbN[i];
-                if (PM_MCA_TSUM == 1) rowN[i] = rowNN[i];
-            }
+            for (int i = 0; i < DPL; ++i) wbP[i] = wbN[i];
         }
-        if (PM_MCA_VDEFER) v_update();             // the last state
         }
         pm_wave_lds_sync();
 
@@ -809,7 +696,7 @@ __device__ __forceinline__ void mca_estep_fused_body(const double *__restrict__ 
                         const int d = lane + 64 * i;
                         if (d < D) {
                             const double aid = SIGNED ? V[j][i] * g : V[j][i] * g * Wrm1[base + d];
-                            if (aid != 0.0 && (PM_MCA_ABL != 1 || aid == 1.2345e-300)) {
+                            if (aid != 0.0) {
                                 pm_atomic_add(Wp + base + d, PM_Q(aid * y[i], 1));
                                 pm_atomic_add(Wq + base + d, PM_Q(aid, 0));
                             }
@@ -881,11 +768,8 @@ __global__ __launch_bounds__(256) void mca_mstep_rows_kernel(const double *__res
     double *s_wr = s_red + 4 * waves + (size_t)wave * ((SIGNED ? 2 : 1) * HP * DS);
     double *s_wm = s_wr + HP * DS;   // SIGNED only: |W|^(rho-1)[cand]
     for (int h = tid; h < H; h += blockDim.x) s_q1sum[h] = 0.0;
-    __shared__ __attribute__((aligned(16))) double s_rt[PM_ROOT21_LEN + 1];       // (see mca_estep_kernel)
     const bool r21 = !SIGNED && MCA_RHO_IS(P.inv_rho, 21.0);
     const bool r6 = SIGNED && MCA_RHO_IS(P.inv_rho, 6.0);
-    if (!PM_POW_HWSEED && r21) pm_load_root21(s_rt, pm_powtab_dev, tid, blockDim.x);       // (the table seed's tables: A/B builds)
-    else if (!PM_POW_HWSEED && r6) pm_load_root6(s_rt, pm_powtab_dev, tid, blockDim.x);
     __syncthreads();
 
     // multi-cause numerator / denominator (stats[0 .. H*D) = Q1^T Y by the GEMM): this XCD's copy, folded by
@@ -973,12 +857,12 @@ __global__ __launch_bounds__(256) void mca_mstep_rows_kernel(const double *__res
             for (int i = 0; i < DPL; ++i) {
                 if (!SIGNED) {
                     // q_s Wbar_sd / T_sd = q_s T^(1/rho - 1); padding: T = 0
-                    v[i] = (T[i] > 0.0) ? q * (r21 ? pm_pow_m20_21(T[i], s_rt) : pm_pow_tab(T[i], P.inv_rho - 1.0, s_tab)) : 0.0;
+                    v[i] = (T[i] > 0.0) ? q * (r21 ? pm_pow_m20_21(T[i]) : pm_pow_tab(T[i], P.inv_rho - 1.0, s_tab)) : 0.0;
                 } else {
                     // q_s min(1, (|W_jd| / |Wbar_sd|)^(rho-1)), (.)^(rho-1) = |W_jd|^(rho-1) |Wbar_sd| / |t_sd|;
                     // t = 0 gives Wbar = 0 and the factor 1 (mmca_et.py:316-324: max(-inf - Wl, 0) = 0)
                     const double aT = fabs(T[i]);
-                    v[i] = (aT > 0.0) ? q * (r6 ? pm_pow_m5_6(aT, s_rt) : pm_pow_tab(aT, P.inv_rho - 1.0, s_tab)) : INFINITY;
+                    v[i] = (aT > 0.0) ? q * (r6 ? pm_pow_m5_6(aT) : pm_pow_tab(aT, P.inv_rho - 1.0, s_tab)) : INFINITY;
                 }
             }
         };
@@ -1075,6 +959,9 @@ __global__ __launch_bounds__(256) void mca_mstep_rows_kernel(const double *__res
     MCA_STATS_EPILOGUE();
 }
 
+// LDS of a mca_defer_scatter_kernel workgroup, in doubles: 128 KB, one workgroup per CU (8192 = two per CU: 0.68 against 0.46 ms
+// -- twice the latent ranges, every datapoint scanned and its y row read by twice as many workgroups)
+constexpr int SCATTER_LDS_DOUBLES = 16384;
 constexpr int DEFER_GROUPS = 64;      // datapoint groups of the scatter kernel (workspace: one [Wp | Wq] partial per group)
 
 // Every launch decision of pm_mca_estep_f64, pm_mca_mstep_rows_f64, pm_mca_estep_mstats[_defer]_f64 and
@@ -1135,16 +1022,11 @@ static int mca_plan(int which, int64_t H, int64_t D, int64_t Hprime, int64_t S, 
         p->hp = Hprime <= 4 ? 4 : Hprime <= 8 ? 8 : 12;
         if ((int64_t)p->dpl * p->hp > 48) return PM_ERANGE;  // V[HP][DPL] register tile
         // Round 6: unsigned W takes the uniform-exponent power (pm_pow_uni, ROOT = 0) at EVERY rho -- 6.45 ms against 6.74 for the
-        // log / exp-free rho = 21 power at config 5 (scratch/mca_T_sweep.py; -DPM_MCA_ROOT21 brings that one back for A/B builds).
+        // log / exp-free rho = 21 power at config 5 (scratch/mca_T_sweep.py), so the fused pass has no rho = 21 form.
         // Signed W (MMCA) keeps its rho = 6 power (pm_pow_m5_6: 9.65 against 10.48 ms, scratch/mmca_time.py -- that pass runs one
-        // wavefront per SIMD, where the uniform power's three LDS lookups are not hidden; -DPM_MCA_NO_ROOT6: A/B) and takes the
-        // uniform power at every other rho.
-#ifdef PM_MCA_ROOT21
-        if (!sgn && MCA_RHO_IS(inv_rho, 21.0)) p->root = 21;
-#endif
-#ifndef PM_MCA_NO_ROOT6
+        // wavefront per SIMD, where the uniform power's three LDS lookups are not hidden) and takes the uniform power at every
+        // other rho.
         if (sgn && MCA_RHO_IS(inv_rho, 6.0)) p->root = 6;
-#endif
         p->paired = mca_fused_paired(p->dpl, p->hp, sgn) ? 1 : 0;
         const size_t per_wave = sizeof(double) * ((size_t)p->hp * 64 * p->dpl * (sgn ? 2 : 1) + S);
         const size_t shared = sizeof(double) * (PM_POWTAB_LEN + PM_FUSED_RT_LEN + H + 16);
@@ -1157,7 +1039,7 @@ static int mca_plan(int which, int64_t H, int64_t D, int64_t Hprime, int64_t S, 
     if (H > 512 || D > 512 || Hprime > 12) return PM_ERANGE;
     p->hp = (int)Hprime;
     p->dpl = D <= 64 ? 1 : D <= 128 ? 2 : D <= 256 ? 4 : 8;
-    p->hr = PM_SCATTER_LDS_DOUBLES / (2 * 64 * p->dpl);          // rows of Wp and Wq per workgroup: 32 at D <= 256
+    p->hr = SCATTER_LDS_DOUBLES / (2 * 64 * p->dpl);          // rows of Wp and Wq per workgroup: 32 at D <= 256
     if (p->hr > H) p->hr = (int)H;
     p->nranges = (int)((H + p->hr - 1) / p->hr);
     int64_t groups = DEFER_GROUPS;
@@ -1332,7 +1214,7 @@ int launch_fused_hp(int hp, int root, int Hp, dim3 grid, dim3 block, size_t shme
                     int H, int D, double *logpj, int64_t ldl, double *lse1, double *lseb, double *q1, int64_t ldq,
                     double *stats, double *defer_rec, double *defer_sc) {
     // hp, root: the register tile and the power of the plan (mca_plan); Hp: the candidates
-    const bool rho21 = !SIGNED && root == 21, rho6 = SIGNED && root == 6;
+    const bool rho6 = SIGNED && root == 6;
 #define PM_LAUNCH_F(HPV, SG, RT, DF)                                                                                  \
     do {                                                                                                              \
         if (DF) {                                                                                                     \
@@ -1350,28 +1232,12 @@ int launch_fused_hp(int hp, int root, int Hp, dim3 grid, dim3 block, size_t shme
         }                                                                                                             \
         return (int)hipGetLastError();                                                                                \
     } while (0)
-#ifdef PM_MCA_ROOT21
-#define PM_CASE21(HPV)                                                \
-    if (rho21) {                                                      \
-        if (defer_rec) PM_LAUNCH_F(HPV, false, 21, true);             \
-        PM_LAUNCH_F(HPV, false, 21, false);                           \
-    }
-#else
-#define PM_CASE21(HPV)
-#endif
-#ifndef PM_MCA_NO_ROOT6
-#define PM_CASE6(HPV)                                                 \
-    if (rho6) {                                                       \
-        if (defer_rec) PM_LAUNCH_F(HPV, true, 6, true);               \
-        PM_LAUNCH_F(HPV, true, 6, false);                             \
-    }
-#else
-#define PM_CASE6(HPV)
-#endif
 #define PM_CASE(HPV)                                                  \
     case HPV: {                                                       \
-        PM_CASE21(HPV)                                                \
-        PM_CASE6(HPV)                                                 \
+        if (rho6) {                                                   \
+            if (defer_rec) PM_LAUNCH_F(HPV, true, 6, true);           \
+            PM_LAUNCH_F(HPV, true, 6, false);                         \
+        }                                                             \
         if (defer_rec) PM_LAUNCH_F(HPV, SIGNED, 0, true);             \
         PM_LAUNCH_F(HPV, SIGNED, 0, false);                           \
     }
@@ -1380,11 +1246,7 @@ int launch_fused_hp(int hp, int root, int Hp, dim3 grid, dim3 block, size_t shme
         default: return PM_ERANGE;
     }
 #undef PM_CASE
-#undef PM_CASE21
-#undef PM_CASE6
 #undef PM_LAUNCH_F
-    (void)rho21;
-    (void)rho6;
 }
 }  // namespace
 
@@ -1536,11 +1398,11 @@ __global__ __launch_bounds__(1024) void mca_defer_scatter_kernel(const double *_
                 }
 #pragma unroll
                 for (int i = 0; i < DPL; ++i) {
-                    if (v0[i] != 0.0 && (PM_SCATTER_ABL != 1 || v0[i] == 1.2345e-300)) {
+                    if (v0[i] != 0.0) {
                         atomicAdd(&s_wq[r0 * DS + lane + 64 * i], PM_Q(v0[i], 0));
                         atomicAdd(&s_wp[r0 * DS + lane + 64 * i], PM_Q(v0[i] * y[i], 1));
                     }
-                    if (v1[i] != 0.0 && (PM_SCATTER_ABL != 1 || v1[i] == 1.2345e-300)) {
+                    if (v1[i] != 0.0) {
                         atomicAdd(&s_wq[r1 * DS + lane + 64 * i], PM_Q(v1[i], 0));
                         atomicAdd(&s_wp[r1 * DS + lane + 64 * i], PM_Q(v1[i] * y[i], 1));
                     }

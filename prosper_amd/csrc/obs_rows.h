@@ -247,11 +247,8 @@ __global__ __launch_bounds__(256) void mca_obs_estep_kernel(const double *__rest
     double *s_wr = s_tab + PM_POWTAB_LEN + (size_t)wave * (Hp * DS + S);
     double *s_e = s_wr + Hp * DS;
     pm_load_powtab(s_tab, tid, blockDim.x);
-    __shared__ __attribute__((aligned(16))) double s_rt[PM_ROOT21_LEN + 1];
     const bool r21 = P.signed_w == 0.0 && P.inv_rho > 0.0 && fabs(1.0 / P.inv_rho - 21.0) < 1e-9;
     const bool r6 = P.inv_rho > 0.0 && fabs(1.0 / P.inv_rho - 6.0) < 1e-9;
-    if (!PM_POW_HWSEED && r21) pm_load_root21(s_rt, pm_powtab_dev, tid, blockDim.x);
-    else if (!PM_POW_HWSEED && r6) pm_load_root6(s_rt, pm_powtab_dev, tid, blockDim.x);
     __syncthreads();
 
     const int64_t wave0 = (int64_t)blockIdx.x * waves + wave;
@@ -295,8 +292,8 @@ __global__ __launch_bounds__(256) void mca_obs_estep_kernel(const double *__rest
 #pragma unroll
                 for (int i = 0; i < DPL; ++i) {
                     const double aT = fabs(T[i]);
-                    const double wbar = (aT > 0.0) ? (ROOT == 21 ? aT * pm_pow_m20_21(aT, s_rt)
-                                                      : ROOT == 6 ? copysign(aT * pm_pow_m5_6(aT, s_rt), T[i])
+                    const double wbar = (aT > 0.0) ? (ROOT == 21 ? aT * pm_pow_m20_21(aT)
+                                                      : ROOT == 6 ? copysign(aT * pm_pow_m5_6(aT), T[i])
                                                                   : copysign(pm_pow_tab(aT, P.inv_rho, s_tab), T[i]))
                                                    : 0.0;
                     const double df = wbar - y[i];

@@ -289,30 +289,14 @@ __device__ __forceinline__ double pm_pow_tab(double x, double c, const double *t
 
 // x^(1/21 - 1) = x^(-20/21) for NORMAL x > 0 -- the power of MCA's multi-cause states at rho = 21, i.e. at every annealing
 // temperature T <= 1.05 (mca_et.py:142-175: rho = 1 / (1 - 1 / max(T, 1.05))), the steady state of a run -- without a
-// logarithm or an exponential:  x = 2^(21 q + r) m,  x' = 2^r m,  y = x'^(-1/21) from a table seed
-//   y0 = 2^(-r/21) r_i^(1/21) (1 - d / 21),  d = m r_i - 1 < 2^-7   (r_i: pm_pow_tab's reciprocal table; error 1.5e-6)
-// then  x'^(-20/21) = y0^20 (1 - res)^(-20/21),  res = 1 - x' y0^21  (|res| < 4e-5: three series terms, the fourth is 1e-18)
-// with y0^20, y0^21 by repeated squaring: 15 f64 + 11 integer instructions and two LDS lookups against pm_pow_tab's 36 + 2,
-// and a dependent chain of 14 instead of ~20.  The rounding errors of the power chain cancel between y0^20 and the
-// residual: relative error <= 3e-16 against an 80-bit reference over [e^-190, e^40] (pm_pow_tab: 2.3e-16).
-// `rt`: the workgroup's LDS table from pm_load_root21 -- 128 pairs (r_i, r_i^(1/21)), then 2^(-r/21), r = 0 .. 20.
-#define PM_ROOT21_LEN (256 + 21)
-__device__ __forceinline__ void pm_load_root21(double *rt, const double *powtab, int tid, int nthreads) {
-    for (int i = tid; i < 128; i += nthreads) {
-        const double ri = powtab[2 * i];
-        rt[2 * i] = ri;
-        rt[2 * i + 1] = pow(ri, 1.0 / 21.0);
-    }
-    for (int r = tid; r < 21; r += nthreads) rt[256 + r] = exp2(-(double)r / 21.0);
-}
-#ifndef PM_POW_HWSEED
-#define PM_POW_HWSEED 1     // the roots' seed from v_log_f32 / v_exp_f32 (round 5: no LDS lookup in the chain, 27 fewer registers in the MCA
-                            // pass: 7.0-7.17 -> 6.69 ms, 2.5e-16); 0: the round-4 table seed (two LDS lookups), kept for A/B builds
-#endif
-__device__ __forceinline__ double pm_pow_m20_21(double x, const double *rt) {
-#if PM_POW_HWSEED
-    // seed y0 ~ x'^(-1/21) = exp2(-log2(x') / 21) in f32 (x' = 2^r m in [1, 2^21): relative error ~1e-7, res = 1 - x' y0^21
-    // ~2e-6 -- inside the three series terms' reach); no table, no LDS access in the chain
+// f64 logarithm or exponential:  x = 2^(21 q + r) m,  x' = 2^r m in [1, 2^21),  y = x'^(-1/21) from the f32 seed
+//   y0 = exp2(-log2(x') / 21)  (v_log_f32 / v_exp_f32: relative error ~1e-7; no table, no LDS access in the chain)
+// then  x'^(-20/21) = y0^20 (1 - res)^(-20/21),  res = 1 - x' y0^21  (~2e-6: three series terms, the fourth is below 1e-18)
+// with y0^20, y0^21 by repeated squaring, against pm_pow_tab's 36 instructions + 2 lookups and its dependent chain of ~20.
+// The rounding errors of the power chain cancel between y0^20 and the residual: relative error 2.5e-16 against an 80-bit
+// reference over [e^-190, e^40] (pm_pow_tab: 2.3e-16; scratch/pow_hwseed_check.hip).  Round 4's seed came from two LDS
+// tables; this one took the MCA pass from 7.0-7.17 to 6.69 ms with 27 fewer registers (round 5, profiles/r05_mca_rowsums.txt).
+__device__ __forceinline__ double pm_pow_m20_21(double x) {
     const unsigned hi = (unsigned)__double2hiint(x), lo = (unsigned)__double2loint(x);
     const unsigned eu = (hi >> 20) + 27u;
     const unsigned q = (eu * 3121u) >> 16;
@@ -326,46 +310,13 @@ __device__ __forceinline__ double pm_pow_m20_21(double x, const double *rt) {
     double t = fma(res, 20.0 * 41.0 * 62.0 / (6.0 * 9261.0), 20.0 * 41.0 / (2.0 * 441.0));
     t = fma(t, res, 20.0 / 21.0);
     const double v = fma(y20, t * res, y20);
-    (void)rt;
     return __hiloint2double(__double2hiint(v) + (int)((1000u - 20u * q) << 20), __double2loint(v));
-#else
-    typedef double pm_d2 __attribute__((ext_vector_type(2)));
-    const unsigned hi = (unsigned)__double2hiint(x), lo = (unsigned)__double2loint(x);
-    const unsigned idx = (hi >> 13) & 127u;
-    const pm_d2 rs = reinterpret_cast<const pm_d2 *>(rt)[idx];
-    const unsigned eu = (hi >> 20) + 27u;                    // biased exponent - 1023 + 1050 in [28, 2073]
-    const unsigned q = (eu * 3121u) >> 16;                   // eu / 21 (exact on that range)
-    const unsigned r = eu - 21u * q;
-    const unsigned mant = hi & 0x000FFFFFu;
-    const double m = __hiloint2double((int)(mant | 0x3FF00000u), (int)lo);             // [1, 2)
-    const double xp = __hiloint2double((int)(mant | ((1023u + r) << 20)), (int)lo);    // 2^r m
-    const double d = fma(m, rs.x, -1.0);
-    const double y0 = (rs.y * rt[256 + r]) * fma(d, -1.0 / 21.0, 1.0);
-    const double y2 = y0 * y0, y4 = y2 * y2, y8 = y4 * y4, y16 = y8 * y8;
-    const double y20 = y16 * y4;
-    const double res = fma(-xp, y20 * y0, 1.0);
-    double t = fma(res, 20.0 * 41.0 * 62.0 / (6.0 * 9261.0), 20.0 * 41.0 / (2.0 * 441.0));
-    t = fma(t, res, 20.0 / 21.0);
-    const double v = fma(y20, t * res, y20);
-    // * 2^(-20 (q - 50))
-    return __hiloint2double(__double2hiint(v) + (int)((1000u - 20u * q) << 20), __double2loint(v));
-#endif
 }
 
 // x^(1/6 - 1) = x^(-5/6) for NORMAL x > 0: the same construction for rho = 6 -- MMCA's power at every temperature T <= 1.2
 // (mmca_et.py:37, 127-199: rho = 1 / (1 - 1 / max(T, 1.2))), the steady state of its runs.  x = 2^(6 q + r) m, x' = 2^r m,
-// y0 = 2^(-r/6) r_i^(1/6) (1 - d / 6) (error 7 d^2 / 72 < 6e-6), x'^(-5/6) = y0^5 (1 - res)^(-5/6), res = 1 - x' y0^6 (|res| < 4e-5:
-// three series terms, the fourth is 1e-18).  12 f64 + 11 integer instructions.  `rt` from pm_load_root6 (layout of pm_load_root21).
-__device__ __forceinline__ void pm_load_root6(double *rt, const double *powtab, int tid, int nthreads) {
-    for (int i = tid; i < 128; i += nthreads) {
-        const double ri = powtab[2 * i];
-        rt[2 * i] = ri;
-        rt[2 * i + 1] = pow(ri, 1.0 / 6.0);
-    }
-    for (int r = tid; r < 6; r += nthreads) rt[256 + r] = exp2(-(double)r / 6.0);
-}
-__device__ __forceinline__ double pm_pow_m5_6(double x, const double *rt) {
-#if PM_POW_HWSEED
+// y0 = exp2(-log2(x') / 6) in f32, x'^(-5/6) = y0^5 (1 - res)^(-5/6), res = 1 - x' y0^6 (three series terms).
+__device__ __forceinline__ double pm_pow_m5_6(double x) {
     const unsigned hi = (unsigned)__double2hiint(x), lo = (unsigned)__double2loint(x);
     const unsigned eu = (hi >> 20) + 27u;
     const unsigned q = (eu * 10923u) >> 16;
@@ -379,51 +330,25 @@ __device__ __forceinline__ double pm_pow_m5_6(double x, const double *rt) {
     double t = fma(res, 5.0 * 11.0 * 17.0 / (6.0 * 216.0), 5.0 * 11.0 / (2.0 * 36.0));
     t = fma(t, res, 5.0 / 6.0);
     const double v = fma(y5, t * res, y5);
-    (void)rt;
     return __hiloint2double(__double2hiint(v) + (int)((875u - 5u * q) << 20), __double2loint(v));
-#else
-    typedef double pm_d2 __attribute__((ext_vector_type(2)));
-    const unsigned hi = (unsigned)__double2hiint(x), lo = (unsigned)__double2loint(x);
-    const unsigned idx = (hi >> 13) & 127u;
-    const pm_d2 rs = reinterpret_cast<const pm_d2 *>(rt)[idx];
-    const unsigned eu = (hi >> 20) + 27u;                    // biased exponent - 1023 + 1050 (= 6 * 175) in [28, 2073]
-    const unsigned q = (eu * 10923u) >> 16;                  // eu / 6 (exact on that range)
-    const unsigned r = eu - 6u * q;
-    const unsigned mant = hi & 0x000FFFFFu;
-    const double m = __hiloint2double((int)(mant | 0x3FF00000u), (int)lo);             // [1, 2)
-    const double xp = __hiloint2double((int)(mant | ((1023u + r) << 20)), (int)lo);    // 2^r m
-    const double d = fma(m, rs.x, -1.0);
-    const double y0 = (rs.y * rt[256 + r]) * fma(d, -1.0 / 6.0, 1.0);
-    const double y2 = y0 * y0, y4 = y2 * y2;
-    const double y5 = y4 * y0;
-    const double res = fma(-xp, y5 * y0, 1.0);
-    double t = fma(res, 5.0 * 11.0 * 17.0 / (6.0 * 216.0), 5.0 * 11.0 / (2.0 * 36.0));
-    t = fma(t, res, 5.0 / 6.0);
-    const double v = fma(y5, t * res, y5);
-    // * 2^(-5 (q - 175))
-    return __hiloint2double(__double2hiint(v) + (int)((875u - 5u * q) << 20), __double2loint(v));
-#endif
 }
 
 // The MCA / MMCA read-outs (reconstruct(), its variance, sample_posterior()) form Wbar_d(s) = sign(T) |T|^(1/rho), T the sum
-// of the state's rows of W^rho, with the power functions above.  pm_mca_pow_setup fills the workgroup's tables (s_tab:
-// PM_POWTAB_LEN doubles, s_rt: PM_ROOT21_LEN + 1) and picks the path for this rho -- r21: rho = 21 (MCA, unsigned), r6: rho = 6,
+// of the state's rows of W^rho, with the power functions above.  pm_mca_pow_setup fills the workgroup's table (s_tab:
+// PM_POWTAB_LEN doubles) and picks the path for this rho -- r21: rho = 21 (MCA, unsigned), r6: rho = 6,
 // the root functions; neither: pm_pow_tab.  The caller's __syncthreads() follows it.
-__device__ __forceinline__ void pm_mca_pow_setup(double *s_tab, double *s_rt, double inv_rho, int signed_w, int tid,
+__device__ __forceinline__ void pm_mca_pow_setup(double *s_tab, double inv_rho, int signed_w, int tid,
                                                  int nthreads, bool &r21, bool &r6) {
     pm_load_powtab(s_tab, tid, nthreads);
     r21 = !signed_w && inv_rho > 0.0 && fabs(1.0 / inv_rho - 21.0) < 1e-9;
     r6 = inv_rho > 0.0 && fabs(1.0 / inv_rho - 6.0) < 1e-9;
-    if (!PM_POW_HWSEED && r21) pm_load_root21(s_rt, pm_powtab_dev, tid, nthreads);
-    else if (!PM_POW_HWSEED && r6) pm_load_root6(s_rt, pm_powtab_dev, tid, nthreads);
 }
-__device__ __forceinline__ double pm_mca_wbar(double T, double inv_rho, bool r21, bool r6, const double *s_tab,
-                                              const double *s_rt) {
+__device__ __forceinline__ double pm_mca_wbar(double T, double inv_rho, bool r21, bool r6, const double *s_tab) {
     const double aT = fabs(T);
     double wbar = 0.0;
     if (aT > 0.0)
-        wbar = r21 ? aT * pm_pow_m20_21(aT, s_rt)
-                   : r6 ? copysign(aT * pm_pow_m5_6(aT, s_rt), T) : copysign(pm_pow_tab(aT, inv_rho, s_tab), T);
+        wbar = r21 ? aT * pm_pow_m20_21(aT)
+                   : r6 ? copysign(aT * pm_pow_m5_6(aT), T) : copysign(pm_pow_tab(aT, inv_rho, s_tab), T);
     return wbar;
 }
 

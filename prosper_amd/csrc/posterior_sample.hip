@@ -312,10 +312,9 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_decode_mca_kernel(const in
                                                                         int S, double *__restrict__ out, int64_t ldn,
                                                                         int64_t ldm) {
     __shared__ __attribute__((aligned(16))) double s_tab[PM_POWTAB_LEN];
-    __shared__ __attribute__((aligned(16))) double s_rt[PM_ROOT21_LEN + 1];
     const int tid = threadIdx.x, lane = tid & 63;
     bool r21, r6;
-    pm_mca_pow_setup(s_tab, s_rt, inv_rho, signed_w, tid, blockDim.x, r21, r6);
+    pm_mca_pow_setup(s_tab, inv_rho, signed_w, tid, blockDim.x, r21, r6);
     __syncthreads();
     const int64_t total = N * (int64_t)M;
     const int64_t wave0 = (int64_t)blockIdx.x * (SMP_THREADS / 64) + (tid >> 6);
@@ -345,7 +344,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_decode_mca_kernel(const in
 #pragma unroll
                 for (int j = 0; j < PM_MAX_HPRIME; ++j)
                     if ((mk >> j) & 1u) T += Wrho[coff[j] + d];   // uniform
-                orow[d] = pm_mca_wbar(T, inv_rho, r21, r6, s_tab, s_rt);
+                orow[d] = pm_mca_wbar(T, inv_rho, r21, r6, s_tab);
             }
         }
     }

@@ -23,10 +23,9 @@ static __global__ __launch_bounds__(RMCA_THREADS) void recon_mca_kernel(const do
                                                                         int signed_w, int64_t N, int H, int D, int Hp, int S,
                                                                         double *__restrict__ out, int64_t ldo) {
     __shared__ __attribute__((aligned(16))) double s_tab[PM_POWTAB_LEN];
-    __shared__ __attribute__((aligned(16))) double s_rt[PM_ROOT21_LEN + 1];
     const int tid = threadIdx.x, lane = tid & 63;
     bool r21, r6;
-    pm_mca_pow_setup(s_tab, s_rt, inv_rho, signed_w, tid, blockDim.x, r21, r6);
+    pm_mca_pow_setup(s_tab, inv_rho, signed_w, tid, blockDim.x, r21, r6);
     __syncthreads();
     const int K = 1 + H + S;
     const int64_t wave0 = (int64_t)blockIdx.x * RMCA_WAVES + (tid >> 6), nwaves = (int64_t)gridDim.x * RMCA_WAVES;
@@ -62,7 +61,7 @@ static __global__ __launch_bounds__(RMCA_THREADS) void recon_mca_kernel(const do
             }
 #pragma unroll
             for (int i = 0; i < DPL; ++i) {
-                const double wbar = pm_mca_wbar(T[i], inv_rho, r21, r6, s_tab, s_rt);
+                const double wbar = pm_mca_wbar(T[i], inv_rho, r21, r6, s_tab);
                 acc[i] = fma(q, SQUARE ? wbar * wbar : wbar, acc[i]);
             }
         }

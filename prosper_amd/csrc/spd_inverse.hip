@@ -12,10 +12,6 @@
 
 #include "prosper_hip.h"
 
-#ifndef PM_SPD_ABL
-#define PM_SPD_ABL 0   // timing ablations for scratch/spd_bench.hip; 0 = the real kernel
-#endif
-
 namespace {
 
 constexpr int TS = 32, EL = 8, NMAX = TS * EL;  // 256
@@ -90,26 +86,26 @@ __global__ __launch_bounds__(1024) void spd_inverse_kernel(const double *__restr
             double *cb = s_c[k & 1];
             // publish column k: c[i] = A[min(i,k)][max(i,k)].  For i in block-row x <= kx the element sits at
             // block (x, kx) of the threads with tj == km; for x > kx at block (kx, x) of the threads with ti == km.
-            if (PM_SPD_ABL != 3 && tj == km) {
+            if (tj == km) {
 #pragma unroll
                 for (int x = 0; x <= kx; ++x) cb[ti + TS * x] = a[x][kx];
             }
-            if (PM_SPD_ABL != 3 && ti == km) {
+            if (ti == km) {
 #pragma unroll
                 for (int y = kx + 1; y < EL; ++y) cb[tj + TS * y] = a[kx][y];
             }
-            if (PM_SPD_ABL != 4) __syncthreads();
+            __syncthreads();
             const double p = cb[k];
-            const double ip = (PM_SPD_ABL == 1) ? p * 0.5 : 1.0 / p;
+            const double ip = 1.0 / p;
             pmin = fmin(pmin, p);
             pmax = fmax(pmax, p);
             double ci[EL];
 #pragma unroll
-            for (int x = 0; x < EL; ++x) ci[x] = (PM_SPD_ABL == 2) ? p + x : cb[ti + TS * x];
+            for (int x = 0; x < EL; ++x) ci[x] = cb[ti + TS * x];
             // rank-1 update of everything, then the few threads holding row / column k overwrite those entries
 #pragma unroll
             for (int y = 0; y < EL; ++y) {
-                const double cjy = ((PM_SPD_ABL == 2) ? p - y : cb[tj + TS * y]) * ip;
+                const double cjy = cb[tj + TS * y] * ip;
 #pragma unroll
                 for (int x = 0; x <= y; ++x) a[x][y] = fma(-ci[x], cjy, a[x][y]);
                 asm volatile("" ::: "memory");             // keep the LDS reads of later columns from being hoisted

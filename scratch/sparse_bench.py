@@ -8,7 +8,7 @@ from prosper_amd import _lib
 import os
 N, H, D = int(os.environ.get("SP_N", 200000)), 256, 1024
 nnz = float(sys.argv[1]) if len(sys.argv) > 1 else 3.7
-variants = sys.argv[2:]        # standalone builds of bsc_wp_sparse.hip (scratch/sparse_variants.sh); default: the library
+variants = sys.argv[2:]        # paths of standalone shared-library builds of bsc_wp_sparse.hip; default: the library
 dev = torch.device("cuda", 0)
 lib = _lib.load()
 rng = np.random.RandomState(0)

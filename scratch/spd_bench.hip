@@ -1,5 +1,4 @@
-// Timing + residual check of the one-workgroup SPD inverse (prosper_amd/csrc/spd_inverse.hip is #included;
-// -DPM_SPD_ABL=1..4 are its timing ablations).
+// Timing + residual check of the one-workgroup SPD inverse (prosper_amd/csrc/spd_inverse.hip is #included).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
