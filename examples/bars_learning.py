@@ -2,6 +2,7 @@
 """The reference's bars test (examples/barstests/bars-learning.py + param-bars-*.py) on the MI355X path.
 
     python examples/bars_learning.py [bsc|mca|mmca|dsc|tsc|gsc|mog|mop] [--steps 50] [--N 2000] [--h5]
+    python examples/bars_learning.py mog|mop --init kmeans++ [--seed 1]               (both inits side by side)
     python examples/bars_learning.py bsc|mca|mmca --heldout 500 --infer --exact      (MAP states: truncated against exact)
 
 Generates bars data from ground-truth parameters, runs the annealed EM loop through the drop-in classes and
@@ -121,7 +122,15 @@ def main():
                     help="bsc: train the same start parameters twice on the same data and schedule -- truncated (H' = 5, gamma = "
                     "3) and with the posterior over all 2^H states (model.exact = True, DESIGN 4.25) -- and print the bars "
                     "error and log_likelihood(exact=True) per datapoint of both end points side by side")
+    ap.add_argument("--init", choices=["standard", "kmeans++"], default="standard",
+                    help="mog, mop with kmeans++: train the same data twice on the same schedule -- from standard_init (H "
+                    "components at the data mean) and from kmeanspp_init (H datapoints by D^2 sampling on the device, DESIGN "
+                    "4.27) -- and print the bars error and log_likelihood per datapoint of both end points, and the seeding "
+                    "potential beside the potential of H uniformly drawn rows")
+    ap.add_argument("--seed", type=int, default=1, help="seed of NumPy's generator (data, standard_init) and of the seeding")
     a = ap.parse_args()
+    if a.init != "standard" and a.model not in ("mog", "mop"):
+        ap.error("--init kmeans++ is built for mog and mop")
     if a.exact_em and a.model != "bsc":
         ap.error("--exact-em is built for bsc")
     if a.infer and (a.model not in ("bsc", "mca", "mmca") or a.heldout <= 0):
@@ -132,7 +141,7 @@ def main():
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
         dist.init_process_group("nccl")
     comm = parallel.Comm()
-    np.random.seed(1 + comm.rank)
+    np.random.seed(a.seed + comm.rank)
 
     model, gt = build(a.model, a.size, 5, 3, comm)
     H = 2 * a.size
@@ -170,6 +179,28 @@ def main():
             print("  %-28s %14s %14s" % ("", "truncated 5/3", "exact 2^H"))
             for i, what in enumerate(("bars mean abs error", "exact log-likelihood / N", "pi", "sigma")):
                 print("  %-28s %14.6f %14.6f" % (what, ends[False][i], ends[True][i]))
+        return
+
+    if a.init == "kmeans++":
+        seeded = model.kmeanspp_init(my_data, seed=a.seed)
+        all_y = np.concatenate(comm.allgather(np.asarray(my_data['y'], dtype=np.float64)))
+        rows = all_y[np.random.RandomState(a.seed).choice(len(all_y), size=H, replace=False)]
+        uniform = float(((all_y[:, None, :] - rows[None, :, :]) ** 2).sum(2).min(1).sum())
+        ends = {}
+        for what, start in (("standard", init), ("kmeans++", seeded)):
+            start = {k: np.array(v, copy=True) for k, v in start.items()}
+            em = EM(model=model, anneal=schedule(), data={'y': my_data['y']}, lparams=start)
+            em.run()
+            _, mae = find_permutation(np.asarray(em.lparams['W']), np.asarray(gt['W']))
+            ends[what] = (mae, model.log_likelihood(dict(em.lparams), {'y': my_data['y']}) / a.N)
+        if comm.rank == 0:
+            print("%s on %d bars datapoints (%d ranks), %d EM steps, seed %d, H = %d:" % (a.model.upper(), a.N, comm.size,
+                                                                                       a.steps, a.seed, H))
+            print("  %-28s %14s %14s" % ("", "standard_init", "kmeanspp_init"))
+            for i, what in enumerate(("bars mean abs error", "log-likelihood / N")):
+                print("  %-28s %14.6f %14.6f" % (what, ends["standard"][i], ends["kmeans++"][i]))
+            print("  seeding potential %.6g (D^2 sampling) against %.6g (H uniformly drawn rows)" % (
+                float(model.seed_potential[-1]), uniform))
         return
 
     anneal = schedule()

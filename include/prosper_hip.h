@@ -1621,6 +1621,55 @@ int pm_sample_decode_mca_f64(const int32_t *idx, const int32_t *cand, const uint
                              const double *Wrho, double inv_rho, int signed_w, int64_t N, int64_t M, int64_t H, int64_t D,
                              int64_t Hprime, int64_t S, double *out, int64_t ld_row, int64_t ld_sample, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * k-means++ seeding of the mixture models (seed_kernels.hip)
+ * ---------------------------------------------------------------------------------------
+ * D^2 sampling over a shard Y (N, ldy >= D): H rounds of [update the distance of every row to its nearest chosen centre,
+ * draw the next centre with probability proportional to it].  Every sum is a chain of plain IEEE additions of rounded terms
+ * in a pinned order -- no fused multiply-add, no atomics, no branch on the build: both libraries return the same bits, and
+ * tests/seeding_reference.py restates them in NumPy.
+ *
+ * Distance of row n to a centre c: with g the smallest power of two >= min(D, 64), partial sum l (l < g) adds t t, t =
+ * Y[n,d] - c[d] (difference rounded, product rounded), for d = l, l + g, l + 2g, ... in ascending order starting from +0; the
+ * g partial sums are combined by butterflies v_l <- v_l + v_(l xor o) for o = g/2, ..., 1.  A row's distance depends on that
+ * row and the centre alone.
+ *
+ * Blocks: rpb = ceil(N / min(1024, ceil(N / 16))) rows per block, nb = ceil(N / rpb) blocks -- a function of N alone.  B_b
+ * adds the distances of block b in ascending n starting from +0; Q_b = ((B_0 + B_1) + ...) + B_b; S = Q_(nb-1) is the
+ * shard's potential.  `work` holds [B (nb) | Q (nb)]: pm_seed_work_len(N) = 2 max(nb, 1) doubles (-1 for N < 0 or N > 2^40).
+ *
+ * Every entry checks its arguments before it touches a device: PM_EINVAL for a null pointer (where not allowed below), a
+ * non-positive D or nc, a negative N or H, a leading dimension shorter than D; PM_ERANGE for N > 2^40 and, in the entries
+ * that keep the centre in LDS (update, plan), D > 6144.  N == 0 launches nothing.
+ *
+ * pm_seed_plan: host-only query, N >= 1.  out[0..PM_SEED_PLAN_LEN): 0 rpb, 1 nb, 2 g, 3 rows per wavefront (64 / max(g/2, 1):
+ * a row belongs to max(g/2, 1) lanes, each holding two neighbouring partial sums, so that 16-byte loads keep the order),
+ * 4 grid of the update kernel (one workgroup per block), 5 wavefronts per workgroup, 6 dynamic LDS bytes, 7 trips of a lane
+ * over a row's pairs of elements.  Rows of Y that all start at a 16-byte boundary (Y aligned, ldy even) are read with 16-byte
+ * loads, the last element of an odd row and every other shard with 8-byte loads; the bits are the same. */
+#define PM_SEED_PLAN_LEN 8
+int64_t pm_seed_work_len(int64_t N);
+int pm_seed_plan(int64_t N, int64_t D, int32_t *out);
+/* One round's pass over the shard.  The centre is row *idx_dev of centre_src (nc rows, ldc >= D; idx_dev NULL: row 0), read on
+ * the device.  first != 0: dist[n] <- d(n, c); else dist[n] <- d(n, c) < dist[n] ? d(n, c) : dist[n], an explicit compare (a row
+ * that is a centre keeps exactly 0; a NaN distance never replaces a number).  Then B, Q into `work` and S into
+ * *potential_out (NULL: not written).  *idx_dev < 0 or >= nc (an exhausted shard: no row left to draw) leaves dist as it is and
+ * writes B = Q = 0 and S = 0.  Two launches. */
+int pm_seed_update_f64(const double *Y, int64_t ldy, int64_t N, int64_t D, const double *centre_src, int64_t ldc, int64_t nc,
+                       const int64_t *idx_dev, int first, double *dist, double *work, double *potential_out, void *stream);
+/* The draw from dist (N) and the `work` the update left: t = u S' + t_offset (product rounded, sum rounded), S' = *S (device) or,
+ * S NULL, the shard's own S; a one-rank caller passes S NULL and t_offset 0, so that t is formed on the device.  b* = the
+ * smallest block with Q_b* > t; r = Q_(b*-1) (+0 for block 0), then r <- r + dist[n] over the block's rows in ascending n: the
+ * drawn row is the first with r > t.  If the block ends before that (the two chains differ in rounding), the last row of the
+ * block with dist > 0; if no block has Q_b > t (t rounded up to S), the last block with B_b > 0 is walked in the same way.  A
+ * row of distance 0 is never drawn.  *idx_out receives the row, or -1 where the shard's S == 0 or no row has a positive
+ * distance.  One workgroup. */
+int pm_seed_pick_f64(const double *dist, int64_t N, const double *work, const double *S, double t_offset, double u,
+                     int64_t *idx_out, void *stream);
+/* centres[h, :] = Y[idx[h], :] for h < H (ldc >= D); a row with idx[h] outside [0, N) is left as it is. */
+int pm_seed_gather_f64(const double *Y, int64_t ldy, int64_t N, int64_t D, const int64_t *idx, int64_t H, double *centres,
+                       int64_t ldc, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

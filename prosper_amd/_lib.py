@@ -266,6 +266,11 @@ SIGNATURES = {
     "pm_sample_decode_lin_f64": (C.c_int, [c_dp, c_dp, i64, c_dp, i64, c_dp, i64, i64, i64, i64, c_dp, i64, i64, c_dp]),
     "pm_sample_decode_mca_f64": (C.c_int, [c_dp, c_dp, c_dp, c_dp, c_dp, C.c_double, C.c_int, i64, i64, i64, i64, i64, i64,
                                            c_dp, i64, i64, c_dp]),
+    "pm_seed_work_len": (i64, [i64]),
+    "pm_seed_plan": (C.c_int, [i64, i64, C.POINTER(C.c_int32)]),
+    "pm_seed_update_f64": (C.c_int, [c_dp, i64, i64, i64, c_dp, i64, i64, c_dp, C.c_int, c_dp, c_dp, c_dp, c_dp]),
+    "pm_seed_pick_f64": (C.c_int, [c_dp, i64, c_dp, c_dp, C.c_double, C.c_double, c_dp, c_dp]),
+    "pm_seed_gather_f64": (C.c_int, [c_dp, i64, i64, i64, c_dp, i64, c_dp, i64, c_dp]),
 }
 
 
@@ -273,7 +278,7 @@ class HipError(RuntimeError):
     pass
 
 
-MIN_VERSION = 1035
+MIN_VERSION = 1036
 _lib = None
 _lib_det = None
 LIB_PATH_DET = os.path.join(os.path.dirname(LIB_PATH), "libprosper_hip_det.so")

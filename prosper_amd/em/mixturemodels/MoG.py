@@ -23,11 +23,16 @@ class MoG(DeviceMixture, MixtureModel):
         """MixtureModel.standard_init, then every component's covariance = rank 0's LOCAL data covariance, broadcast
         (MoG.py:23-60): ``np.cov(y.T) + 0.001 I`` (ddof 1) for 'full', ``np.var(y, 0) + 0.001`` (ddof 0) for 'diagonal'.
         The collective min / max of the data the reference computes there (unused) are computed as well."""
+        my_y = _host(my_data['y'])
+        model_params = MixtureModel.standard_init(self, {'y': my_y})
+        return self.comm.bcast(self._init_noise(model_params, {'y': my_y}))
+
+    def _init_noise(self, model_params, my_data):
+        """sigmas_sq of ``standard_init`` (MoG.py:41-58), for ``kmeanspp_init`` too."""
         comm = self.comm
         H = self.H
         my_y = _host(my_data['y'])
         N, D = my_y.shape
-        model_params = MixtureModel.standard_init(self, {'y': my_y})
         if 'sigmas_sq' in self.to_learn:
             if self.sigmas_sq_type == 'full':
                 sigma = comm.bcast(np.cov(my_y.T) + (0.001 * np.eye(D)))
@@ -39,7 +44,7 @@ class MoG(DeviceMixture, MixtureModel):
             for h in range(H):
                 sigmas_sq[h] = sigma
             model_params['sigmas_sq'] = sigmas_sq
-        return comm.bcast(model_params)
+        return model_params
 
     @tracing.traced
     def resume_init(self, h5_output):

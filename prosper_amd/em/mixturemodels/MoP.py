@@ -28,6 +28,12 @@ class MoP(DeviceMixture, MixtureModel):
         model_params = MixtureModel.standard_init(self, my_data)
         return self.comm.bcast(model_params)
 
+    def _seed_rates(self, W):
+        """``kmeanspp_init``: a datapoint with a zero count is not a rate (log 0 in the E-step, 0 * -inf = NaN against a zero
+        count): W = max(W, eps), the floor the M-step's "+ eps" keeps every rate above (MoP.py:130-160).  Positive counts keep
+        their bits."""
+        return np.maximum(W, np.finfo(np.float64).eps)
+
     @tracing.traced
     def resume_init(self, h5_output):
         """W and pies of the last logged step of a ``result.h5`` (MoP.py:42-63, which calls the undefined ``openFile``;

@@ -50,6 +50,45 @@ class MixtureModel(Model):
             model_params['pies'] = np.ones(H) * 1. / H
         return model_params
 
+    @tracing.traced
+    def kmeanspp_init(self, data, seed=None, uniforms=None):
+        """k-means++ seeding in place of ``standard_init``'s H coincident components: W (D, H) holds H
+        datapoints drawn by D^2 sampling on the device (``utils.seeding.kmeanspp``: squared Euclidean distance for every
+        model; ``seed`` / ``uniforms`` as there and as in ``sample_posterior``), pies = 1/H when learned, and every other entry
+        is what ``standard_init`` puts there, from the same code (MoG: the shared covariance) -- the two inits differ in W
+        alone.  No NumPy random number is drawn.  The dict goes through ``check_params`` and is broadcast like
+        ``standard_init``'s.  ``self.seed_indices`` (H,) are the global row numbers of the chosen datapoints and
+        ``self.seed_potential`` (H,) the seeding potential after each of them.  MoP: W = max(datapoint, eps) -- a zero count
+        would be a zero rate, whose logarithm the E-step cannot weigh; eps is the floor its M-step keeps W above.
+
+        Collective.  ``ValueError`` as ``kmeanspp`` raises them, and for data whose second axis is not D -- before any
+        launch; fewer than H distinct rows and non-finite data after the rounds."""
+        from ...utils.seeding import kmeanspp
+        y = data['y']
+        shape = tuple(getattr(y, "tensor", y).shape)
+        if len(shape) != 2 or shape[1] != self.D:
+            raise ValueError("%s.kmeanspp_init: data['y'] must be (my_N, %d), got %r" % (type(self).__name__, self.D, shape))
+        import contextlib
+        import torch
+        # (a model bound to a device runs there; otherwise the current device, looked up after kmeanspp's refusals)
+        with torch.cuda.device(self._device) if self._device is not None else contextlib.nullcontext():
+            centres, indices, potential = kmeanspp(y, self.H, seed=seed, uniforms=uniforms, comm=self.comm,
+                                                   deterministic=bool(getattr(self, "deterministic", False)))
+        self.seed_indices, self.seed_potential = indices, potential
+        model_params = {'W': self._seed_rates(np.ascontiguousarray(centres.T))}
+        if 'pies' in self.to_learn:
+            model_params['pies'] = np.ones(self.H) * 1. / self.H
+        model_params = self._init_noise(model_params, data)
+        return self.comm.bcast(self.check_params(model_params))
+
+    def _seed_rates(self, W):
+        """What a model makes of the chosen datapoints before they become W (MoP: rates are positive)."""
+        return W
+
+    def _init_noise(self, model_params, data):
+        """The entries of an initial parameter dict beside W and pies (MoG: sigmas_sq); shared by both inits."""
+        return model_params
+
     def check_params(self, model_params):
         raise NotImplementedError
 
